@@ -10,6 +10,12 @@ i.e. two streams over the rank's whole 2-bit genotype shard.  `value` = algorith
 step (2 x (Mt*ceil(N/4) + 24*Mt + 32*ceil(N/4))) x steps / wall time, inputs resident in HBM.
 
 One process per GPU:  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, roofline of the timed kernels from HIP events
+inside the timed region, decompositions).  Everything measured beside it -- host-pointer rates, read / copy bandwidth, the VAMP
+iterations/s legs, the LD leg, the CPU baseline, the step on the other resident layout and the mid-size rows -- runs only with
+--full.  --dump-outputs DIR writes the timed step's output d = tau A^T (A p) + gam2 p of the last step as DIR/lmmse_mult.npy
+(float64, all Mt markers; a fixed, seeded sample of them past 64 MB); the inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -52,6 +58,11 @@ def parse():
                          "2 = also z1 rides in a free slot and A x2_hat / A^T A invQ u come out of the CG recurrences, "
                          "3 = also the warm start's initial residual comes from the previous solve (no Ax + ATx for it), "
                          "4 = also the Onsager solve's first step comes from A^T A u of the probe, computed once")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (host-pointer and bandwidth figures, VAMP and LD legs, CPU "
+                         "baseline, the other resident layout, the mid-size rows); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed step computed in its last step to DIR/lmmse_mult.npy (float64)")
     return ap.parse_args()
 
 
@@ -213,6 +224,29 @@ def run_rows(a, device):
     return rows
 
 
+DUMP_MAX_VALUES = 8000000       # 64 MB of float64, less room for the .npy header
+
+
+def dump_outputs(path, d_local, S, Mt, world, rank):
+    """DIR/lmmse_mult.npy: the step's output over all Mt markers in marker order (sharded runs gather the ranks' slices on rank 0),
+    or the values at a fixed, seeded, sorted sample of markers when all of them would pass 64 MB."""
+    import torch.distributed as dist
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (S, d_local))
+        if rank != 0:
+            return
+        out = np.empty(Mt)
+        for s, v in parts:
+            out[s:s + len(v)] = v
+    else:
+        out = d_local
+    if out.size > DUMP_MAX_VALUES:
+        out = out[np.sort(np.random.default_rng(0).choice(out.size, DUMP_MAX_VALUES, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "lmmse_mult.npy"), np.ascontiguousarray(out, dtype=np.float64))
+
+
 def spawn_ranks(a):
     """`python bench.py --gpus N` with no launcher: start the N per-GPU ranks ourselves, as plain child processes, BEFORE
     anything in this process touches the GPU (torch.cuda.device_count() does not initialise it on this image), and leave
@@ -310,7 +344,8 @@ def main():
         sh.set_kernel_mode(0)
     assert sh.get_kernel_mode() == a.mode
     # what this run is about to do with the shard (gv_set_expected_passes, as the drivers announce iterations x 12): the timed steps
-    # and the VAMP legs (levels 4 / 0 / 3, then the LD genotypes at 4 / 0), ~12 ATx passes per iteration
+    # and the VAMP legs (levels 4 / 0 / 3, then the LD genotypes at 4 / 0), ~12 ATx passes per iteration.  A plain run announces the
+    # same count as --full, so that both time the same resident layout
     planned_passes = a.warmup + a.steps + a.vamp_iterations * 12 * (3 + (2 if a.ld_block > 0 else 0))
     sh.set_expected_passes(planned_passes)
     t0 = time.time()
@@ -364,21 +399,24 @@ def main():
     cnt = sh.counters()
     sh.set_timing(0)
     d_host = d.download()            # (after the timed region) the operator's output, compared with the tile-layout leg below
-    # PCIe-inclusive rate through the host-pointer entry points gv_ax / gv_atx (data::Ax / data::ATx as the reference's vamp.cpp
-    # calls them: the M- or N-vector crosses PCIe each way).  Outside the timed region; never `value`.
-    hx = np.ascontiguousarray(rng_p)
-    hp = np.zeros(4 * ((N + 3) // 4))
-    hp[:N] = np.random.default_rng(8).standard_normal(N)
-    sh.Ax(hx); sh.ATx(hp)
-    t1 = time.perf_counter()
-    for _ in range(5):
-        sh.Ax(hx)
-    t_hax = (time.perf_counter() - t1) / 5
-    t1 = time.perf_counter()
-    for _ in range(5):
-        sh.ATx(hp)
-    t_hatx = (time.perf_counter() - t1) / 5
-    sh.counters(reset=True)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, d_host, S, Mt, world, rank)
+    if a.full:
+        # PCIe-inclusive rate through the host-pointer entry points gv_ax / gv_atx (data::Ax / data::ATx as the reference's vamp.cpp
+        # calls them: the M- or N-vector crosses PCIe each way).  Outside the timed region; never `value`.
+        hx = np.ascontiguousarray(rng_p)
+        hp = np.zeros(4 * ((N + 3) // 4))
+        hp[:N] = np.random.default_rng(8).standard_normal(N)
+        sh.Ax(hx); sh.ATx(hp)
+        t1 = time.perf_counter()
+        for _ in range(5):
+            sh.Ax(hx)
+        t_hax = (time.perf_counter() - t1) / 5
+        t1 = time.perf_counter()
+        for _ in range(5):
+            sh.ATx(hp)
+        t_hatx = (time.perf_counter() - t1) / 5
+        sh.counters(reset=True)
 
     job_bytes = 2 * alg_bytes(N, Mt)
     value = job_bytes * a.steps / dt / 1e9
@@ -421,8 +459,9 @@ def main():
                    "markers_per_gpu": M, "kernel_mode": a.mode, "parallelism": "marker-sharded x%d" % world,
                    "resident_layout": ("fp64 raw rows" if a.mode == 0 else "two stripe sets, 2 x M*N/4 bytes" if layout == 1
                                        else "one tile layout, M*N/4 bytes"),
-                   "engine": ("library defaults (no gv_set_kernel_mode / gv_set_layout call; gv_set_expected_passes(%d) = what this "
-                              "run makes)" % planned_passes if engine_defaults else "--mode %d --layout %d" % (a.mode, a.layout)),
+                   "engine": ("library defaults (no gv_set_kernel_mode / gv_set_layout call; gv_set_expected_passes(%d) = what %s "
+                              "run makes)" % (planned_passes, "this" if a.full else "the --full")
+                              if engine_defaults else "--mode %d --layout %d" % (a.mode, a.layout)),
                    "ingest_s": round(t_ingest, 2), "ingest_alloc_s": round(t_alloc, 2), "ingest_fill_s": round(t_fill, 2),
                    "tune_s": round(tune_s, 3), "tune_source": tune_src},
         "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(ax_gbps, 1), "peak": 8000.0, "unit": "GB/s",
@@ -431,19 +470,20 @@ def main():
                      # how avg_kernel_ms is measured: gv_set_timing(2) = HIP events recorded on the context's stream around EVERY
                      # streaming-kernel launch of the timed region (the events stay inside `value`'s clock: conservative by their
                      # ~2 us per launch); the rocprofv3 --kernel-trace --stats average of the same command is in profiles/
-                     "timing": "HIP events around every streaming-kernel launch inside the timed region (gv_set_timing(2))",
-                     # context ("also report vs measured copy bandwidth"): what plain streaming kernels reach
-                     # on this box, measured now -- a read-only stream over the same resident stripes, and a copy
-                     "read_stream_GBps": round(sh.read_bandwidth(1 << 30, 3), 1),
-                     "copy_GBps_read_plus_write": round(sh.copy_bandwidth(1 << 30, 10), 1)},
+                     "timing": "HIP events around every streaming-kernel launch inside the timed region (gv_set_timing(2))"},
         "kernels": {"ax": {"avg_ms": round(ms_ax, 4), "GBps": round(ax_gbps, 1), "launches": cnt["n_ax_kernel"]},
                     "atx": {"avg_ms": round(ms_atx, 4), "GBps": round(atx_gbps, 1), "launches": cnt["n_atx_kernel"]}},
+    }
+    if a.full:
+        # context ("also report vs measured copy bandwidth"): what plain streaming kernels reach
+        # on this box, measured now -- a read-only stream over the same resident stripes, and a copy
+        out["roofline"]["read_stream_GBps"] = round(sh.read_bandwidth(1 << 30, 3), 1)
+        out["roofline"]["copy_GBps_read_plus_write"] = round(sh.copy_bandwidth(1 << 30, 10), 1)
         # the same two products through gv_ax / gv_atx on HOST pointers (this rank's shard; pageable numpy buffers, vectors over
         # PCIe both ways, for sharded jobs the all-reduce inside): algorithmic bytes / wall time per call
-        "hostptr_GBps": round(2 * shard_bytes / (t_hax + t_hatx) / 1e9, 1),
-        "hostptr": {"ax_ms": round(t_hax * 1e3, 3), "atx_ms": round(t_hatx * 1e3, 3),
-                    "ax_GBps": round(shard_bytes / t_hax / 1e9, 1), "atx_GBps": round(shard_bytes / t_hatx / 1e9, 1)},
-    }
+        out["hostptr_GBps"] = round(2 * shard_bytes / (t_hax + t_hatx) / 1e9, 1)
+        out["hostptr"] = {"ax_ms": round(t_hax * 1e3, 3), "atx_ms": round(t_hatx * 1e3, 3),
+                          "ax_GBps": round(shard_bytes / t_hax / 1e9, 1), "atx_GBps": round(shard_bytes / t_hatx / 1e9, 1)}
     # what each rank ran: shard, picked decompositions, kernel and exchange times of the timed region (HIP events)
     mine = {"rank": rank, "markers": M, "first_marker": S, "ms_ax_kernel": round(ms_ax, 4), "ms_atx_kernel": round(ms_atx, 4),
             "ms_allreduce_per_ax": round(cnt["ms_allreduce"] / max(cnt["n_allreduce"], 1), 4), "decomposition": dec}
@@ -463,7 +503,7 @@ def main():
         out["forced_multi"] = {"GVAMP_FORCE_MULTI": os.environ["GVAMP_FORCE_MULTI"], "GV_OVERLAP": os.environ.get("GV_OVERLAP", "0"),
                                "ms_allreduce_per_ax": mine["ms_allreduce_per_ax"], "n_allreduce": cnt["n_allreduce"]}
     # ---- second half of the metric: VAMP iterations/s (vamp::infere of the host C++ mirror on the same shard) ----
-    if a.vamp_iterations > 0:
+    if a.full and a.vamp_iterations > 0:
         from gvamp_amd import hostapi
         p.free(); d.free()
         CV = max(1, Mt // 100)
@@ -533,7 +573,7 @@ def main():
                 out["vamp"]["level_3"] = {k: v3[k] for k in ("iters_per_s", "seconds_per_iter", "n_ax_pass", "n_atx_pass")}
                 out["vamp"]["level_3"]["x_hat_rel_l2"] = float(np.sqrt(num3 / den)) if den > 0 else None
     # ---- a harder setting beside it: block-correlated genotypes (LD), where the CG of the LMMSE step runs tens of steps -------
-    if a.vamp_iterations > 0 and a.ld_block > 0:
+    if a.full and a.vamp_iterations > 0 and a.ld_block > 0:
         from gvamp_amd import hostapi
         t1 = time.perf_counter()
         sh.synth_bed(a.seed + 1, 5000, ld_block=a.ld_block, ld_ppm=a.ld_ppm)      # same shapes, same picks
@@ -591,7 +631,7 @@ def main():
                 "iters_per_s": round(len(tail0) / tot0, 4) if tot0 > 0 else None,
                 "n_ax_pass": [t["n_ax_pass"] for t in r0.trace], "n_atx_pass": [t["n_atx_pass"] for t in r0.trace],
                 "cg_iters": [t["cg_iters"] for t in r0.trace], "onsager_iters": [t["onsager_iters"] for t in r0.trace]}
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cb = cpu_baseline(N, a.seed, a.cpu_markers, local_rank)
         if "vamp" in out and len(out["vamp"]["n_ax"]) > 1:
             f = Mt / cb["sample_markers"]       # CPU matvec time is linear in the number of markers at fixed N
@@ -610,7 +650,9 @@ def main():
     # ---- the same operator on the OTHER resident layout (main leg on the one tile layout: two stripe sets, 2 x M*N/4 bytes, announced
     # as a long run would announce itself; main leg on two stripe sets: the tile layout), measured in the same process on the same box,
     # and checked bit for bit against the main leg's result --------------------------------------------------------------------
-    other = 1 if layout_everywhere == 2 else (2 if layout_everywhere == 1 else 0)
+    other = 0
+    if a.full:
+        other = 1 if layout_everywhere == 2 else (2 if layout_everywhere == 1 else 0)
     if other == 1:
         free_b, total_b = torch.cuda.mem_get_info(local_rank)
         if 2.0 * M * ((N + 3) // 4) + 4e9 > 0.92 * free_b:
@@ -684,7 +726,7 @@ def main():
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
-    if rank == 0 and world == 1 and not a.no_rows:
+    if a.full and rank == 0 and world == 1 and not a.no_rows:
         out["rows"] = run_rows(a, local_rank)
     if rank == 0:
         print(json.dumps(out), flush=True)

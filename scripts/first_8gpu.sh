@@ -26,7 +26,7 @@ run_bench() {   # name, gpus, extra env..., then bench flags after --
     [ $# -gt 0 ] && shift
     echo "== $name (gpus $n ${envs[*]:-})"
     if [ "$n" -gt "$NGPU" ]; then echo "{\"skipped\": \"needs $n GPUs, have $NGPU\"}" > "$OUT/$name.json"; return; fi
-    env "${envs[@]}" timeout -k 10 1500 python bench.py --gpus "$n" "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" \
+    env "${envs[@]}" timeout -k 10 1500 python bench.py --full --gpus "$n" "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" \
         || echo "{\"failed\": \"exit $?\"}" > "$OUT/$name.json"
 }
 

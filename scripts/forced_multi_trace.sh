@@ -10,6 +10,6 @@ for leg in plain forced forced_ov4; do
   rm -rf $O/$leg
 done
 for leg in 0 2 3; do
-  GVAMP_FORCE_MULTI=$leg python3 bench.py --N 400000 --Mt 125000 --no-cpu-baseline --no-side-leg --no-rows --ld-block 0 > $O/bench_fm$leg.json 2>$O/bench_fm$leg.err || exit 1
+  GVAMP_FORCE_MULTI=$leg python3 bench.py --full --N 400000 --Mt 125000 --no-cpu-baseline --no-side-leg --no-rows --ld-block 0 > $O/bench_fm$leg.json 2>$O/bench_fm$leg.err || exit 1
 done
-GVAMP_FORCE_MULTI=3 GV_OVERLAP=4 python3 bench.py --N 400000 --Mt 125000 --no-cpu-baseline --no-side-leg --no-rows --ld-block 0 > $O/bench_fm3_ov4.json 2>$O/bench_fm3_ov4.err
+GVAMP_FORCE_MULTI=3 GV_OVERLAP=4 python3 bench.py --full --N 400000 --Mt 125000 --no-cpu-baseline --no-side-leg --no-rows --ld-block 0 > $O/bench_fm3_ov4.json 2>$O/bench_fm3_ov4.err

@@ -136,7 +136,7 @@ def test_synth_bed_is_stable_and_plausible():
 
 
 def test_committed_bench_line_honours_the_contract():
-    """The newest profiles/r<k>_bench_n1.json is the line `python bench.py` printed on an MI355X (library defaults): every key the
+    """The newest profiles/r<k>_bench_n1.json is the line `python bench.py --full` prints on an MI355X (library defaults): every key the
     driver and the judge read must be there, with consistent arithmetic (frac = achieved / peak, value = bytes / time)."""
     import glob
     import json

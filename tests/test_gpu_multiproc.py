@@ -258,7 +258,7 @@ def test_rccl_two_ranks_gvamp_sim_vs_real_reference_np2(tmp_path):
 
 def _bench_cmd(extra):
     return [os.path.join(ROOT, "bench.py"), "--N", "20000", "--Mt", "60000", "--steps", "2", "--warmup", "1",
-            "--vamp-iterations", "2", "--no-cpu-baseline"] + extra
+            "--vamp-iterations", "2", "--no-cpu-baseline", "--full"] + extra
 
 
 @pytest.mark.skipif(_gpu_count() < 2, reason="needs >= 2 GPUs (RCCL with nranks > 1)")
@@ -309,7 +309,7 @@ def test_first_contact_eight_gpus(tmp_path):
     3 % of the committed line, and step time / aggregate rate / VAMP iterations per second / all-reduce time per Ax INSIDE the bands
     DESIGN.md section 6 predicted from one-GPU measurements."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    flags = ["--no-cpu-baseline", "--no-rows", "--no-side-leg", "--ld-block", "0"]
+    flags = ["--full", "--no-cpu-baseline", "--no-rows", "--no-side-leg", "--ld-block", "0"]
     legs = {}
     for n in (1, 8):
         if n == 1:

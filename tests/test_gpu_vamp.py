@@ -278,7 +278,7 @@ def test_bench_prints_exactly_one_json_line():
     import json
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--N", "20000", "--Mt", "60000", "--steps", "2", "--warmup", "1",
-                        "--vamp-iterations", "2", "--cpu-markers", "500"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--vamp-iterations", "2", "--cpu-markers", "500", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[:2000]
@@ -287,6 +287,38 @@ def test_bench_prints_exactly_one_json_line():
               "dtype", "data", "config", "roofline", "cpu_baseline", "vamp"):
         assert k in d, k
     assert d["steps"] == 2 and d["n_gpus"] == 1 and d["roofline"]["traffic"] is None     # no PMC profile for this size
+
+
+def test_plain_bench_times_the_steps_and_dumps_the_step_output(oracle, tmp_path):
+    """A plain bench.py run (no --full) prints the headline line and nothing measured beside it; --steps is the number of timed
+    steps; --dump-outputs writes the last step's d = tau A^T (A p) + gam2 p, equal to the oracle's and the same from run to run."""
+    import json
+    import sys
+    N, Mt, steps = 4000, 6000, 3
+    lines, dumps = [], []
+    for i in range(2):
+        out = tmp_path / ("dump%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--N", str(N), "--Mt", str(Mt), "--steps",
+                            str(steps), "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(got) == 1, r.stdout[:2000]
+        lines.append(json.loads(got[0]))
+        assert sorted(os.listdir(out)) == ["lmmse_mult.npy"]
+        dumps.append(np.load(out / "lmmse_mult.npy"))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline", "kernels"):
+        assert k in d, k
+    for k in ("vamp", "vamp_ld", "cpu_baseline", "rows", "hostptr", "two_stripe_sets", "tile_layout"):
+        assert k not in d, k
+    assert d["steps"] == steps and d["kernels"]["ax"]["launches"] == steps and d["kernels"]["atx"]["launches"] == steps
+    assert abs(d["value"] - 2 * (Mt * (N // 4) + 24 * Mt + 32 * (N // 4)) / (d["ms_per_step"] * 1e-3) / 1e9) < 0.01 * d["value"]
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (Mt,) and np.array_equal(dumps[0], dumps[1])
+    bed = synth.synth_bed(N, Mt, seed=1234, miss_ppm=5000)             # bench.py's defaults: --seed 1234, 5000 ppm missing
+    p = np.random.default_rng(7).standard_normal(Mt)
+    mave, msig = oracle.marker_stats(bed, N, Mt)
+    ref = 2.0 * oracle.atx(bed, N, Mt, mave, msig, oracle.ax(bed, N, Mt, mave, msig, p)) + 1.35 * p
+    assert rel(dumps[0], ref) < 1e-12
 
 
 def test_host_exceptions_stop_at_the_c_boundary():
