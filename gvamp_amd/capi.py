@@ -24,6 +24,7 @@ EXPORTS = [
     "gv_denoise", "gv_prior_estep", "gv_denoise_global", "gv_prior_estep_global",
     "gv_probit_denoise", "gv_probit_denoise_cov", "gv_people_stats", "gv_cg_solve_aat", "gv_cg_solve_aat2", "gv_cg_solve_aat2w", "gv_cg_solve2w", "gv_pvals_loo", "gv_pvals_loco", "gv_pvals_loco_pred", "gv_allreduce_host", "gv_comm_unique_id", "gv_comm_init", "gv_comm_init_local", "gv_comm_init_callback", "gv_comm_share", "gv_set_overlap", "gv_debug_force_multi", "gv_comm_rank", "gv_comm_size", "gv_bind_host_numa", "gv_set_timing",
     "gv_get_counters", "gv_reset_counters", "gv_get_decomp", "gv_set_decomp", "gv_tune_info", "gv_ingest_info", "gv_ingest_info2", "gv_set_expected_passes", "gv_copy_bandwidth", "gv_read_bandwidth",
+    "gv_upload_meth", "gv_upload_meth_file", "gv_synth_meth",
 ]
 
 
@@ -110,6 +111,9 @@ def load():
     L.gv_synth_bed_ld.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
     L.gv_upload_bed_file.argtypes = [vp, C.c_char_p, i64]
     L.gv_download_bed.argtypes = [vp, up, C.c_size_t]
+    L.gv_upload_meth.argtypes = [vp, dp, C.c_size_t]
+    L.gv_upload_meth_file.argtypes = [vp, C.c_char_p, i64]
+    L.gv_synth_meth.argtypes = [vp, C.c_uint64]
     L.gv_set_mask.argtypes = [vp, up, i64]
     L.gv_marker_stats.argtypes = [vp, C.c_double]
     L.gv_get_marker_stats.argtypes = [vp, dp, dp]
@@ -282,6 +286,21 @@ class Shard:
             self._ck(self.L.gv_synth_bed_ld(self.h, seed, miss_ppm, ld_block, ld_ppm))
         else:
             self._ck(self.L.gv_synth_bed(self.h, seed, miss_ppm))
+
+    def upload_meth(self, x):
+        """methylation data (type_data == "meth"): M x N doubles of this shard, marker-major"""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.size == self.M * self.N, (x.size, self.M, self.N)
+        self._ck(self.L.gv_upload_meth(self.h, _dp(x), x.size))
+
+    def upload_meth_file(self, path, offset=None):
+        """M x N doubles at byte offset (default S * N * 8, data.cpp:259) of a file of raw doubles"""
+        off = self.S * self.N * 8 if offset is None else offset
+        self._ck(self.L.gv_upload_meth_file(self.h, path.encode(), off))
+
+    def synth_meth(self, seed):
+        """the device-generated methylation matrix that synth.synth_meth(N, M, seed, S) reproduces on the host"""
+        self._ck(self.L.gv_synth_meth(self.h, seed))
 
     def download_bed(self):
         out = np.empty(self.M * self.mbytes, dtype=np.uint8)

@@ -819,8 +819,80 @@ bool use_overlap(const gv_ctx* c) {   // nothing rank-local in here (have_stripe
     return c->overlap_tiles > 1 && is_multi(c) && c->kernel_mode == 1 && c->have_stripes;
 }
 
+// ---- the dense fp64 design matrix of methylation data (gv_dense.hip).  Dispatched ahead of the kernel mode and the layout;
+// the CG hooks of the device-resident loops never reach it (cgx_usable is false without a re-encoded layout).
+static int dense_ax(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg) {
+    NEED(c, !cg, "Ax: the device-resident CG does not run on methylation data");
+    NEED(c, c->have_stats && c->mask2, "Ax: methylation data, mask and marker statistics must be set first");
+    const double scale = 1.0 / sqrt((double)c->N);
+    const bool multi = is_multi(c);
+    if (c->M == 0) {   // an empty shard contributes zeros through the same collective as its peers
+        gvk::fill(c->stream, outa, c->npad, 0.0);
+        if (nv == 2) gvk::fill(c->stream, outb, c->npad, 0.0);
+        KCHK(c);
+    } else {
+        const gvd::AxShape sh = gvd::ax_shape(c->N, c->M, c->dense_cus);
+        const size_t need = (size_t)2 * sh.segs * c->npad;
+        if (need > c->dense_part_cap) {
+            if (c->dense_part) (void)hipFree(c->dense_part);
+            c->dense_part = nullptr;
+            c->dense_part_cap = 0;
+            HIPCHK(c, hipMalloc(&c->dense_part, sizeof(double) * need));
+            c->dense_part_cap = need;
+        }
+        Timer t(c, &c->cnt.ms_ax);
+        gv_ctx::EvRec* er = ev_next(c, 0);
+        if (er) (void)hipEventRecord(er->a, c->stream);
+        gvd::ax_partial(c->stream, nv, sh, c->dense, c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->mave, c->msig, c->dense_part, c->npad);
+        if (er) (void)hipEventRecord(er->b, c->stream);
+        gvd::ax_reduce(c->stream, nv, sh, c->dense_part, c->N, c->npad, multi ? 1.0 : scale, outa, nv == 2 ? outb : outa);
+        KCHK(c);
+        t.stop();
+    }
+    c->cnt.n_ax += nv;
+    c->cnt.n_ax_pass += 1;
+    if (multi) {   // data.cpp:1034 MPI_Allreduce, then the 1/sqrt(N) of :1036-1037 (pad slots stay exact zeros)
+        Timer t(c, &c->cnt.ms_allreduce);
+        gv_ctx::EvRec* er = ev_next(c, 2);
+        if (er) (void)hipEventRecord(er->a, c->stream);
+        if (nv == 2 && c->w_n && c->w_n2 && outa == c->w_n->d && outb == c->w_n2->d) {   // w_n | w_n2: one message
+            if (comm_allreduce(c, outa, 2 * c->npad)) return 1;
+            gvk::scale_vec(c->stream, outa, 2 * c->npad, scale);
+        } else {
+            if (comm_allreduce(c, outa, c->npad)) return 1;
+            if (nv == 2 && comm_allreduce(c, outb, c->npad)) return 1;
+            gvk::scale_vec(c->stream, outa, c->npad, scale);
+            if (nv == 2) gvk::scale_vec(c->stream, outb, c->npad, scale);
+        }
+        if (er) (void)hipEventRecord(er->b, c->stream);
+        KCHK(c);
+        t.stop();
+        if (c->timing == 1) c->cnt.n_allreduce++;
+    }
+    return 0;
+}
+static int dense_atx(gv_ctx* c, int nv, const double* pa, const double* pb, double* outa, double* outb, const double* addxa,
+                     const double* addxb, double tau, double gam2, const gvm::CgHook* cg) {
+    NEED(c, !cg, "ATx: the device-resident CG does not run on methylation data");
+    NEED(c, c->have_stats, "ATx: methylation data and marker statistics must be set first");
+    if (c->M > 0) {
+        Timer t(c, &c->cnt.ms_atx);
+        gv_ctx::EvRec* er = ev_next(c, 1);
+        if (er) (void)hipEventRecord(er->a, c->stream);
+        gvd::atx(c->stream, nv, c->dense, c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->mave, c->msig, 1.0 / sqrt((double)c->N),
+                 outa, nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2);
+        if (er) (void)hipEventRecord(er->b, c->stream);
+        KCHK(c);
+        t.stop();
+    }
+    c->cnt.n_atx += nv;
+    c->cnt.n_atx_pass += 1;
+    return 0;
+}
+
 // data::Ax on device pointers.  x: M doubles, out: npad doubles.
 int ax_device(gv_ctx* c, const double* x, double* out, const gvm::CgHook* cg) {
+    if (c->have_dense) return dense_ax(c, 1, x, nullptr, out, nullptr, cg);
     NEED(c, c->have_stats && c->mask2, "Ax: bed, mask and marker statistics must be set first");
     const double scale = 1.0 / sqrt((double)c->N);
     const bool multi = is_multi(c);
@@ -877,6 +949,7 @@ int ax_device(gv_ctx* c, const double* x, double* out, const gvm::CgHook* cg) {
 
 // data::ATx on device pointers.  p: npad doubles (zero at NA / pad slots), out: M doubles.
 int atx_device(gv_ctx* c, const double* p, double* out, const double* addx, double tau, double gam2, const gvm::CgHook* cg) {
+    if (c->have_dense) return dense_atx(c, 1, p, nullptr, out, nullptr, addx, nullptr, tau, gam2, cg);
     NEED(c, c->have_stats, "ATx: bed and marker statistics must be set first");
     if (c->M == 0) {   // empty shard: no markers; the <d,p> a CG hook asks for is 0 from this rank (it is all-reduced next)
         if (cg && cg->dot_out[0]) { gvk::fill(c->stream, cg->dot_out[0], 8, 0.0); KCHK(c); }
@@ -914,6 +987,7 @@ int atx_device(gv_ctx* c, const double* p, double* out, const double* addx, doub
 
 // two-vector forms: ONE pass over the shard in kernel mode 1, two single passes otherwise
 int ax2_device(gv_ctx* c, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg) {
+    if (c->have_dense) return dense_ax(c, 2, xa, xb, outa, outb, cg);
     // The collective sequence below must not depend on rank-local state (an empty shard, M == 0, enters the same calls
     // with zeros): it is chosen by the kernel mode -- the same on every rank of a job -- and the output pointers only.
     if (c->kernel_mode != 1) {
@@ -969,6 +1043,7 @@ int ax2_device(gv_ctx* c, const double* xa, const double* xb, double* outa, doub
 }
 int atx2_device(gv_ctx* c, const double* pa, const double* pb, double* outa, double* outb, const double* addxa,
                 const double* addxb, double tau, double gam2, const gvm::CgHook* cg) {
+    if (c->have_dense) return dense_atx(c, 2, pa, pb, outa, outb, addxa, addxb, tau, gam2, cg);
     if (c->M == 0) {   // empty shard: no local markers, no collective in ATx
         for (int k = 0; k < 2 && cg; k++) {
             if (cg->dot_out[k]) gvk::fill(c->stream, cg->dot_out[k], 8, 0.0);
@@ -1010,6 +1085,9 @@ void free_dataset(gv_ctx* c) {
         p = nullptr;
     };
     F(c->bed); F(c->mask2); F(c->mave); F(c->msig); F(c->t3); F(c->ax_partial); F(c->counts);
+    F(c->dense); F(c->dense_part);
+    c->dense_part_cap = 0;
+    c->have_dense = false;
     if (c->stripes_slab) {
         (void)hipFree(c->stripes_slab);
         c->stripes_slab = nullptr;
@@ -1429,6 +1507,11 @@ static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed,
     const int64_t M = c->M, P = c->pitch;
     gvm::Plan& pl = c->plan;
     c->have_raw = c->have_stripes = c->have_stats = false;
+    if (c->dense) {      // uploading either kind replaces the dataset held before
+        (void)hipFree(c->dense);
+        c->dense = nullptr;
+        c->have_dense = false;
+    }
     if (c->want_raw && !c->bed) HIPCHK(c, hipMalloc(&c->bed, (size_t)(M > 0 ? M : 1) * P));
     if (!c->want_raw && c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
     const auto t_in0 = std::chrono::steady_clock::now();
@@ -1672,7 +1755,125 @@ int gv_synth_bed_ld(gv_ctx* c, uint64_t seed, uint32_t miss_ppm, uint32_t ld_blo
     return ingest(c, nullptr, true, seed, thr, nullptr, ld_block, (uint32_t)(lt > 0xFFFFFFFFull ? 0xFFFFFFFFull : lt));
 }
 
+// ---- methylation data (type_data == "meth"): the dense fp64 design matrix of gv_dense.hip ------------------------------------
+// Frees whatever genotype layout is resident (the next bed ingest rebuilds it) and allocates the dense rows, zeroed.
+static int meth_prepare(gv_ctx* c) {
+    NEED(c, c->N > 0, "methylation upload: gv_set_dims must be called first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    gvm::Plan& pl = c->plan;
+    if (c->stripes_slab) { (void)hipFree(c->stripes_slab); c->stripes_slab = nullptr; pl.stripes_m = pl.stripes_n = nullptr; }
+    for (void** q : {&pl.stripes_m, &pl.stripes_n, &pl.tiles, &pl.dig0, &pl.dig1, (void**)&pl.cv, (void**)&pl.ev, (void**)&pl.cv2,
+                     (void**)&pl.ev2, (void**)&pl.scal, (void**)&pl.partial})
+        if (*q) { (void)hipFree(*q); *q = nullptr; }
+    if (c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
+    c->have_raw = c->have_stripes = c->have_stats = c->have_dense = false;
+    c->ingest_bytes = 0;
+    if (!c->dense_cus) {
+        int cus = 0;
+        HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
+        c->dense_cus = cus > 0 ? cus : 256;
+    }
+    c->dpitch = gvd::row_pitch(c->N);
+    const size_t bytes = sizeof(double) * (size_t)(c->M > 0 ? c->M : 1) * (size_t)c->dpitch;
+    if (!c->dense) {
+        const hipError_t e = hipMalloc(&c->dense, bytes);
+        if (e != hipSuccess) {
+            c->dense = nullptr;
+            return fail(c, "methylation upload: no room for %lld x %lld doubles in HBM: %s", (long long)c->M, (long long)c->dpitch,
+                        hipGetErrorString(e));
+        }
+    }
+    HIPCHK(c, hipMemsetAsync(c->dense, 0, bytes, c->stream));
+    return 0;
+}
+static int meth_done(gv_ctx* c, double t_alloc, std::chrono::steady_clock::time_point t0) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ingest_alloc_s = t_alloc;
+    c->ingest_overlap_s = 0.0;
+    c->ingest_fill_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_alloc;
+    c->ingest_bytes = sizeof(double) * (size_t)c->M * (size_t)c->dpitch;
+    c->have_dense = true;
+    return 0;
+}
+
+int gv_upload_meth(gv_ctx* c, const double* x, size_t n) {
+    NEED(c, c->N > 0, "gv_upload_meth: gv_set_dims must be called first");
+    NEED(c, n == (size_t)c->M * (size_t)c->N, "gv_upload_meth: n != M * N");
+    const auto t0 = std::chrono::steady_clock::now();
+    if (meth_prepare(c)) return 1;
+    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const int64_t rows = c->M < 4096 ? c->M : 4096;      // rows per copy: a caller-owned pageable buffer, nothing to overlap
+    for (int64_t m0 = 0; m0 < c->M; m0 += rows) {
+        const int64_t mc = c->M - m0 < rows ? c->M - m0 : rows;
+        HIPCHK(c, hipMemcpy2DAsync(c->dense + m0 * c->dpitch, sizeof(double) * c->dpitch, x + m0 * c->N, sizeof(double) * c->N,
+                                   sizeof(double) * c->N, mc, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return meth_done(c, ta, t0);
+}
+
+// read_methylation_data (data.cpp:241-278): M*N doubles at byte `offset` (= S*N*8, :259), streamed through two bounded pinned
+// buffers as gv_upload_bed_file streams a .bed: reading chunk k + 1 overlaps the copy of chunk k, host memory stays O(chunk).
+int gv_upload_meth_file(gv_ctx* c, const char* path, int64_t offset) {
+    NEED(c, c->N > 0, "gv_upload_meth_file: gv_set_dims must be called first");
+    NEED(c, offset >= 0, "gv_upload_meth_file: negative offset");
+    const int fd = open(path, O_RDONLY);
+    if (fd < 0) return fail(c, "gv_upload_meth_file: could not open methylation file: %s", path);
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = meth_prepare(c);
+    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const size_t rowb = sizeof(double) * (size_t)c->N;
+    int64_t CH = (int64_t)(((size_t)64 << 20) / rowb);
+    if (CH < 1) CH = 1;
+    if (CH > c->M) CH = c->M > 0 ? c->M : 1;
+    void* stage[2] = {nullptr, nullptr};
+    hipEvent_t stage_free[2] = {nullptr, nullptr};
+    for (int b = 0; b < 2 && !rc; b++) {
+        hipError_t e = hipHostMalloc(&stage[b], (size_t)CH * rowb);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&stage_free[b], hipEventDisableTiming);
+        if (e != hipSuccess) rc = fail(c, "gv_upload_meth_file: no pinned staging buffer: %s", hipGetErrorString(e));
+    }
+    int64_t chunk = 0;
+    for (int64_t m0 = 0; m0 < c->M && !rc; m0 += CH, chunk++) {
+        const int64_t mc = c->M - m0 < CH ? c->M - m0 : CH;
+        const int sb = (int)(chunk & 1);
+        hipError_t e = hipSuccess;
+        if (chunk >= 2) e = hipEventSynchronize(stage_free[sb]);      // the copy of chunk - 2 has left this buffer
+        if (e != hipSuccess) { rc = fail(c, "gv_upload_meth_file: %s", hipGetErrorString(e)); break; }
+        const int io = read_slab(fd, offset + m0 * (int64_t)rowb, (uint8_t*)stage[sb], (size_t)mc * rowb);
+        if (io) {
+            rc = io < 0 ? fail(c, "gv_upload_meth_file: %s ends before marker %lld is complete (short file)", path, (long long)(c->S + m0 + mc - 1))
+                        : fail(c, "gv_upload_meth_file: reading %s at marker %lld failed: %s", path, (long long)(c->S + m0), strerror(io));
+            break;
+        }
+        e = hipMemcpy2DAsync(c->dense + m0 * c->dpitch, sizeof(double) * c->dpitch, stage[sb], rowb, rowb, mc,
+                             hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(stage_free[sb], c->stream);
+        if (e != hipSuccess) rc = fail(c, "gv_upload_meth_file: copy at marker %lld failed: %s", (long long)(c->S + m0), hipGetErrorString(e));
+    }
+    (void)hipStreamSynchronize(c->stream);
+    for (int b = 0; b < 2; b++) {
+        if (stage[b]) (void)hipHostFree(stage[b]);
+        if (stage_free[b]) (void)hipEventDestroy(stage_free[b]);
+    }
+    close(fd);
+    if (rc) return rc;
+    return meth_done(c, ta, t0);
+}
+
+int gv_synth_meth(gv_ctx* c, uint64_t seed) {
+    NEED(c, c->N > 0, "gv_synth_meth: gv_set_dims must be called first");
+    const auto t0 = std::chrono::steady_clock::now();
+    if (meth_prepare(c)) return 1;
+    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    gvd::synth(c->stream, c->dense, c->M, c->S, c->N, c->dpitch, seed);
+    KCHK(c);
+    return meth_done(c, ta, t0);
+}
+
 int gv_download_bed(gv_ctx* c, uint8_t* bed, size_t nbytes) {
+    NEED(c, !c->have_dense, "gv_download_bed: the resident dataset is methylation data (a dense fp64 matrix), not PLINK rows");
     NEED(c, c->have_raw, "gv_download_bed: the raw row layout is not resident (not the default: call gv_set_layout(ctx, 1, stripes) before the ingest)");
     NEED(c, nbytes == (size_t)c->M * (size_t)c->mbytes, "gv_download_bed: nbytes != M * ceil(N/4)");
     if (c->M > 0)
@@ -1698,6 +1899,15 @@ int gv_set_mask(gv_ctx* c, const uint8_t* mask4, int64_t nonas) {
 }
 
 int gv_marker_stats(gv_ctx* c, double alpha_scale) {
+    if (c->have_dense) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
+        NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
+        gvd::stats(c->stream, c->dense, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale, c->mave, c->msig);
+        c->alpha_scale = alpha_scale;
+        KCHK(c);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->have_stats = true;
+        return 0;
+    }
     NEED(c, (c->have_raw || c->have_stripes) && c->mask2, "gv_marker_stats: bed and mask must be set first");
     if (c->have_stripes && c->plan.layout == 1 && (c->kernel_mode != 0 || !c->have_raw))
         gvm::stats_from_tiles(c->stream, c->plan.tiles, c->mask2, c->M, c->plan.nrg_m, c->plan.nkb_m, c->pitch / 4,
@@ -1854,8 +2064,10 @@ int gv_atx(gv_ctx* c, const double* p, double* out) {
     // The kernels (like data::dot_product, data.cpp:728-801, which applies no mask) need p = 0 at NA-phenotype and pad
     // slots; the reference's callers hand in filter_pheno()'d vectors.  A caller-owned host vector is not trusted to be
     // filtered -- data::get_phen() carries DBL_MAX at NA individuals (data.cpp:147) -- so the staged copy is masked here:
-    // a no-op for filtered input, a defined result (the NA individuals dropped) otherwise.
-    gvk::mask_copy(c->stream, c->w_n->d, c->w_n->d, c->mask2, c->npad);
+    // a no-op for filtered input, a defined result (the NA individuals dropped) otherwise.  Methylation data: p is used as given at
+    // every individual below N, as the reference's meth dot_product (data.cpp:783-797) uses it -- its Ax leaves NA individuals
+    // unmasked too, and its ATx must see them.
+    if (!c->have_dense) gvk::mask_copy(c->stream, c->w_n->d, c->w_n->d, c->mask2, c->npad);
     KCHK(c);
     if (atx_device(c, c->w_n->d, c->cg_d->d)) return 1;
     return to_host(c, out, c->cg_d->d, sizeof(double) * (c->M > 0 ? c->M : 0));
@@ -1945,6 +2157,8 @@ int gv_probit_denoise(gv_ctx* c, const gv_vec* p1, const gv_vec* y, double tau1,
 // ---- --use-XXT-denoiser 1: LMMSE through CG in N-space (denoiserXXT.cpp), matrix-free ------------------------------
 // data::compute_people_statistics (data.cpp:558-716): three table passes of the fp64 Ax kernel over the raw rows.
 int gv_people_stats(gv_ctx* c, double* mave_people, double* msig_people, double* numb_people) {
+    NEED(c, !c->have_dense, "gv_people_stats: not available for methylation data (the reference's meth branch of "
+                            "compute_people_statistics, data.cpp:633-672, never reduces or finalises its sums)");
     NEED(c, c->have_stats && c->mask2, "gv_people_stats: marker statistics must be computed first");
     const bool from_stripes = c->have_stripes && (c->kernel_mode != 0 || !c->have_raw);
     NEED(c, c->have_raw || from_stripes, "gv_people_stats: no genotype layout resident");
@@ -2006,6 +2220,8 @@ static int marker_sums_p_p2_f64(gv_ctx* c, const double* p, double* p2_scratch, 
 // chrom == NULL: leave-one-out (the marker's own effect is added back analytically); else leave-one-chromosome-out.
 static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
                       double* pvals, double* chrom_pred = nullptr) {
+    NEED(c, !c->have_dense, "gv_pvals: not available for methylation data (the reference's meth branch of pvals_calc, "
+                            "data.cpp:1187-1223, computes and stores nothing)");
     NEED(c, z1->space == GV_SPACE_N && y->space == GV_SPACE_N && x1_hat->space == GV_SPACE_M, "gv_pvals: bad vector spaces");
     NEED(c, c->have_stats, "gv_pvals: marker statistics must be computed first");
     if (ensure_work(c) || ensure_w2(c)) return 1;
@@ -2250,7 +2466,7 @@ int gv_reset_counters(gv_ctx* c) {
     c->cnt = gv_counters{};
     return 0;
 }
-int gv_get_layout(const gv_ctx* c) { return c->have_stripes ? (c->plan.layout == 1 ? 2 : 1) : 0; }
+int gv_get_layout(const gv_ctx* c) { return c->have_dense ? 3 : (c->have_stripes ? (c->plan.layout == 1 ? 2 : 1) : 0); }
 int gv_ingest_info(gv_ctx* c, double* alloc_seconds, double* fill_seconds) {
     if (alloc_seconds) *alloc_seconds = c->ingest_alloc_s;
     if (fill_seconds) *fill_seconds = c->ingest_fill_s;
@@ -2339,6 +2555,7 @@ int gv_get_decomp(gv_ctx* c, gv_decomp_info* out4) {
     return 0;
 }
 int gv_set_decomp(gv_ctx* c, int cls, const gv_decomp_info* in) {
+    NEED(c, !c->have_dense, "gv_set_decomp: methylation data has no tunable decomposition (derived from N, M and the CU count)");
     NEED(c, cls >= 0 && cls <= 3 && in != nullptr, "gv_set_decomp: class 0..3 and a decomposition are required");
     NEED(c, c->have_stripes, "gv_set_decomp: no re-encoded layout resident yet (call it after the ingest)");
     gvm::Decomp d;

@@ -1,0 +1,300 @@
+// gv_dense.hip -- the dense fp64 design matrix of methylation data (type_data == "meth", data.cpp:54-57 / :107-110): marker
+// statistics, data::ATx, data::Ax and their two-vector forms, and the device-side synthetic matrix.
+//
+// Layout: marker-major fp64 rows as the reference holds meth_data (data.cpp:245-266, meth_data[i*N + j]), the row pitch padded to
+// a multiple of 64 doubles with zeros in the padding.  One layout serves both products.  Every offset is 64-bit (the reference's
+// `int` products mloc * N and i * N, data.cpp:785,1022, overflow past 2^31 elements).
+//
+// Decomposition (closed form from N, M and the CU count, no tuning):
+//   statistics / ATx : one wave per marker row, four rows per 256-thread workgroup, 16-byte non-temporal loads four deep per lane;
+//                      a lane sums its pieces in ascending order, the 64 lane sums are combined by a fixed xor butterfly.
+//   Ax               : a workgroup owns 512 individuals (a double2 per lane) and a segment of markers; the per-marker weights
+//                      msig[i] v[i] and mave[i] are uniform across it (scalar loads).  K segments write K partial vectors that
+//                      a second kernel adds in segment order -- no atomics, results are bit-reproducible run to run.
+// The two-vector forms run the one-vector arithmetic per slot in the same order, so each slot is bit-identical to the
+// one-vector kernel on that vector.
+#include "gv_internal.h"
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int AX_COLS = 512;     // individuals per Ax workgroup: 256 lanes x one double2
+
+__device__ inline uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+__device__ inline double2 ntload2(const double* p) {      // one 16-byte non-temporal load (the row is read once per pass)
+    const f64x2 v = __builtin_nontemporal_load(reinterpret_cast<const f64x2*>(p));
+    return make_double2(v.x, v.y);
+}
+
+__device__ inline double wave_sum(double v) {      // fixed order: the same bits on every call
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    return v;
+}
+
+__device__ inline double present(const uint32_t* __restrict__ mask2, int64_t n) {
+    return (double)((mask2[n >> 4] >> (2 * (n & 15))) & 1u);
+}
+
+// ---- synthetic matrix: value(g, n) = c_g 2^-12 + (u0 + u1 + u2 + u3) 2^-19, with c_g an 11-bit per-marker centre and u_k the
+// four 16-bit fields of a per-entry hash (an Irwin-Hall sum).  Every value is a dyadic rational of at most 20 significant bits,
+// exact in fp64, so gvamp_amd/synth.py:synth_meth reproduces the matrix bit for bit.  Pad columns are written as zeros.
+__global__ void k_synth_meth(double* __restrict__ A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed) {
+    for (int64_t m = blockIdx.x; m < M; m += gridDim.x) {
+        const uint64_t g = (uint64_t)(S + m);
+        const uint64_t hm = splitmix64(seed ^ (g * 0xD1342543DE82EF95ull));
+        const uint64_t base = splitmix64(hm + 0x632BE59BD9B4E019ull);
+        const double centre = (double)(hm >> 53) * 0x1p-12;
+        double* row = A + m * pitch;
+        for (int64_t j = threadIdx.x; j < pitch; j += blockDim.x) {
+            double v = 0.0;
+            if (j < N) {
+                const uint64_t r = splitmix64(base + (uint64_t)j);
+                const uint64_t s = (r & 0xFFFFull) + ((r >> 16) & 0xFFFFull) + ((r >> 32) & 0xFFFFull) + (r >> 48);
+                v = centre + (double)s * 0x1p-19;
+            }
+            row[j] = v;
+        }
+    }
+}
+
+// ---- compute_markers_statistics, meth branch (data.cpp:487-540): two passes over the row, as the reference does them
+__global__ __launch_bounds__(256) void k_dense_stats(const double* __restrict__ A, int64_t M, int64_t N, int64_t pitch,
+                                                     const uint32_t* __restrict__ mask2, double nonas, double alpha_scale,
+                                                     double* __restrict__ mave, double* __restrict__ msig) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const double* row = A + m * pitch;
+    double s = 0.0;
+    for (int64_t j = lane; j < N; j += WAVE) s += row[j] * present(mask2, j);
+    const double mu = wave_sum(s) / nonas;
+    double q = 0.0;
+    for (int64_t j = lane; j < N; j += WAVE) {
+        const double d = (row[j] - mu) * present(mask2, j);
+        q = fma(d, d, q);
+    }
+    q = wave_sum(q);
+    if (lane == 0) {
+        mave[m] = mu;
+        double sg = 1.0;      // a constant column
+        if (q != 0.0)
+            sg = alpha_scale == 1.0 ? 1.0 / sqrt(q / (nonas - 1.0)) : 1.0 / pow(sqrt(q / (nonas - 1.0)), alpha_scale);
+        msig[m] = sg;
+    }
+}
+
+// ---- data::ATx, meth branch (dot_product data.cpp:783-797, ATx :814-835): out[m] = msig[m] * sum_j (x[m][j] - mave[m]) p[j]
+// * scale, the difference formed inside the loop (methylation values have large means relative to their spread).  Optional
+// epilogue of lmmse_mult (vamp.cpp:1112-1115): out = tau * out + gam2 * addx.
+template <int NV>
+__global__ __launch_bounds__(256) void k_dense_atx(const double* __restrict__ A, int64_t M, int64_t N, int64_t pitch,
+                                                   const double* __restrict__ pa, const double* __restrict__ pb,
+                                                   const double* __restrict__ mave, const double* __restrict__ msig,
+                                                   double scale, double* __restrict__ outa, double* __restrict__ outb,
+                                                   const double* __restrict__ addxa, const double* __restrict__ addxb,
+                                                   double tau, double gam2) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const double* row = A + m * pitch;
+    const double2* p2a = reinterpret_cast<const double2*>(pa);
+    const double2* p2b = reinterpret_cast<const double2*>(pb);
+    const double mu = mave[m];
+    const int64_t nh = N >> 1;      // whole double2 pieces below N
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[v] = 0.0;
+    int64_t k = lane;
+    for (; k + 3 * WAVE < nh; k += 4 * WAVE) {
+        double2 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) x[u] = ntload2(row + 2 * (k + u * WAVE));
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const double d0 = x[u].x - mu, d1 = x[u].y - mu;
+            const double2 qa = p2a[k + u * WAVE];
+            acc[0] = fma(d0, qa.x, acc[0]);
+            acc[0] = fma(d1, qa.y, acc[0]);
+            if (NV == 2) {
+                const double2 qb = p2b[k + u * WAVE];
+                acc[NV - 1] = fma(d0, qb.x, acc[NV - 1]);
+                acc[NV - 1] = fma(d1, qb.y, acc[NV - 1]);
+            }
+        }
+    }
+    for (; k < nh; k += WAVE) {
+        const double2 x = ntload2(row + 2 * k);
+        const double d0 = x.x - mu, d1 = x.y - mu;
+        const double2 qa = p2a[k];
+        acc[0] = fma(d0, qa.x, acc[0]);
+        acc[0] = fma(d1, qa.y, acc[0]);
+        if (NV == 2) {
+            const double2 qb = p2b[k];
+            acc[NV - 1] = fma(d0, qb.x, acc[NV - 1]);
+            acc[NV - 1] = fma(d1, qb.y, acc[NV - 1]);
+        }
+    }
+    if ((N & 1) && lane == (int)(nh & (WAVE - 1))) {     // odd N: the last individual, after the lane's own pieces
+        const double d = A[m * pitch + N - 1] - mu;
+        acc[0] = fma(d, pa[N - 1], acc[0]);
+        if (NV == 2) acc[NV - 1] = fma(d, pb[N - 1], acc[NV - 1]);
+    }
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[v] = wave_sum(acc[v]);
+    if (lane == 0) {
+        const double sg = msig[m];
+        double r = sg * acc[0] * scale;
+        outa[m] = addxa ? fma(tau, r, gam2 * addxa[m]) : r;
+        if (NV == 2) {
+            r = sg * acc[NV - 1] * scale;
+            outb[m] = addxb ? fma(tau, r, gam2 * addxb[m]) : r;
+        }
+    }
+}
+
+// ---- data::Ax, meth branch (data.cpp:1013-1045), first stage: partial[seg][j] = sum over the segment's markers i of
+// (x[i][j] - mave[i]) * (msig[i] v[i]), markers in ascending order.  Columns N <= j < pitch carry (0 - mave) terms that the
+// reduction discards.
+template <int NV>
+__global__ __launch_bounds__(256) void k_dense_ax(const double* __restrict__ A, int64_t M, int64_t pitch, int64_t seg_len,
+                                                  const double* __restrict__ va, const double* __restrict__ vb,
+                                                  const double* __restrict__ mave, const double* __restrict__ msig,
+                                                  double* __restrict__ part, int64_t part_stride, int64_t npad) {
+    const int64_t col = (int64_t)blockIdx.x * AX_COLS + 2 * threadIdx.x;
+    if (col >= pitch) return;
+    const int64_t i0 = (int64_t)blockIdx.y * seg_len;
+    const int64_t i1 = i0 + seg_len < M ? i0 + seg_len : M;
+    const double* base = A + col;
+    double2 acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; v++) acc[v] = make_double2(0.0, 0.0);
+    int64_t i = i0;
+    for (; i + 3 < i1; i += 4) {
+        double2 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) x[u] = ntload2(base + (i + u) * pitch);
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const double mu = mave[i + u], sg = msig[i + u];
+            const double d0 = x[u].x - mu, d1 = x[u].y - mu;
+            const double wa = sg * va[i + u];
+            acc[0].x = fma(d0, wa, acc[0].x);
+            acc[0].y = fma(d1, wa, acc[0].y);
+            if (NV == 2) {
+                const double wb = sg * vb[i + u];
+                acc[NV - 1].x = fma(d0, wb, acc[NV - 1].x);
+                acc[NV - 1].y = fma(d1, wb, acc[NV - 1].y);
+            }
+        }
+    }
+    for (; i < i1; i++) {
+        const double2 x = ntload2(base + i * pitch);
+        const double mu = mave[i], sg = msig[i];
+        const double d0 = x.x - mu, d1 = x.y - mu;
+        const double wa = sg * va[i];
+        acc[0].x = fma(d0, wa, acc[0].x);
+        acc[0].y = fma(d1, wa, acc[0].y);
+        if (NV == 2) {
+            const double wb = sg * vb[i];
+            acc[NV - 1].x = fma(d0, wb, acc[NV - 1].x);
+            acc[NV - 1].y = fma(d1, wb, acc[NV - 1].y);
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; v++)
+        *reinterpret_cast<double2*>(part + v * part_stride + (int64_t)blockIdx.y * npad + col) = acc[v];
+}
+
+// second stage: out[j] = (sum_seg partial[seg][j]) * scale in segment order for j < N, exact zeros at the pad slots j >= N.
+// The phenotype mask is NOT applied: the reference's meth Ax leaves individuals with a missing phenotype unmasked.
+template <int NV>
+__global__ void k_dense_ax_reduce(const double* __restrict__ part, int64_t part_stride, int K, int64_t N, int64_t npad,
+                                  double scale, double* __restrict__ outa, double* __restrict__ outb) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= npad) return;
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        double s = 0.0;
+        if (j < N)
+            for (int k = 0; k < K; k++) s += part[v * part_stride + (int64_t)k * npad + j];
+        (v == 0 ? outa : outb)[j] = j < N ? s * scale : 0.0;
+    }
+}
+
+inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+}  // namespace
+
+namespace gvd {
+
+int64_t row_pitch(int64_t N) { return (N + 63) / 64 * 64; }
+
+AxShape ax_shape(int64_t N, int64_t M, int cus) {
+    AxShape sh;
+    const int64_t pitch = row_pitch(N);
+    sh.col_tiles = (pitch + AX_COLS - 1) / AX_COLS;
+    // about eight workgroups per CU in all, every segment at least 16 markers long
+    int64_t k = ((int64_t)8 * (cus > 0 ? cus : 256) + sh.col_tiles - 1) / sh.col_tiles;
+    const int64_t kmax = (M + 15) / 16;
+    if (k > kmax) k = kmax;
+    if (k < 1) k = 1;
+    sh.seg_len = M > 0 ? (M + k - 1) / k : 1;
+    sh.segs = M > 0 ? (int)((M + sh.seg_len - 1) / sh.seg_len) : 1;
+    return sh;
+}
+
+void synth(hipStream_t s, double* A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed) {
+    if (M <= 0) return;
+    const int64_t g = M < 16384 ? M : 16384;
+    hipLaunchKernelGGL(k_synth_meth, dim3((unsigned)g), dim3(256), 0, s, A, M, S, N, pitch, seed);
+}
+
+void stats(hipStream_t s, const double* A, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
+           double alpha_scale, double* mave, double* msig) {
+    if (M <= 0) return;
+    hipLaunchKernelGGL(k_dense_stats, dim3(nblk(M, 4)), dim3(256), 0, s, A, M, N, pitch, mask2, nonas, alpha_scale, mave, msig);
+}
+
+void atx(hipStream_t s, int nv, const double* A, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
+         const double* mave, const double* msig, double scale, double* outa, double* outb, const double* addxa,
+         const double* addxb, double tau, double gam2) {
+    if (M <= 0) return;
+    if (nv == 2)
+        hipLaunchKernelGGL(k_dense_atx<2>, dim3(nblk(M, 4)), dim3(256), 0, s, A, M, N, pitch, pa, pb, mave, msig, scale, outa,
+                           outb, addxa, addxb, tau, gam2);
+    else
+        hipLaunchKernelGGL(k_dense_atx<1>, dim3(nblk(M, 4)), dim3(256), 0, s, A, M, N, pitch, pa, pa, mave, msig, scale, outa,
+                           outa, addxa, addxa, tau, gam2);
+}
+
+void ax_partial(hipStream_t s, int nv, const AxShape& sh, const double* A, int64_t M, int64_t pitch, const double* va,
+                const double* vb, const double* mave, const double* msig, double* part, int64_t npad) {
+    if (M <= 0) return;
+    const int64_t stride = (int64_t)sh.segs * npad;
+    const dim3 grid((unsigned)sh.col_tiles, (unsigned)sh.segs);
+    if (nv == 2)
+        hipLaunchKernelGGL(k_dense_ax<2>, grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, vb, mave, msig, part, stride, npad);
+    else
+        hipLaunchKernelGGL(k_dense_ax<1>, grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, va, mave, msig, part, stride, npad);
+}
+
+void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int64_t N, int64_t npad, double scale, double* outa,
+               double* outb) {
+    const int64_t stride = (int64_t)sh.segs * npad;
+    if (nv == 2)
+        hipLaunchKernelGGL(k_dense_ax_reduce<2>, dim3(nblk(npad, 256)), dim3(256), 0, s, part, stride, sh.segs, N, npad, scale,
+                           outa, outb);
+    else
+        hipLaunchKernelGGL(k_dense_ax_reduce<1>, dim3(nblk(npad, 256)), dim3(256), 0, s, part, stride, sh.segs, N, npad, scale,
+                           outa, outa);
+}
+
+}  // namespace gvd

@@ -57,6 +57,14 @@ struct gv_ctx {
     double ingest_overlap_s = 0.0;  // ... of which the allocation ran beside the preparation of the source (helper thread)
     size_t ingest_bytes = 0;        // bytes of genotype layouts resident after the last ingest
     int64_t expected_passes = 0;    // gv_set_expected_passes: 0 = unknown
+    // dense fp64 design matrix of methylation data (gv_upload_meth / gv_upload_meth_file / gv_synth_meth; gv_dense.hip).  When it is
+    // resident no genotype layout is, and every product dispatches on it ahead of the kernel mode and the layout.
+    double* dense = nullptr;        // M * dpitch doubles, marker-major rows, zeros in the padding
+    int64_t dpitch = 0;             // doubles per row: N rounded up to a multiple of 64
+    bool have_dense = false;
+    double* dense_part = nullptr;   // Ax partial vectors: 2 * segs * npad doubles
+    size_t dense_part_cap = 0;
+    int dense_cus = 0;              // CU count of the device (the decomposition's only input beyond N and M)
     double tune_seconds = 0.0;      // wall time the pick cost (0 when it came from the cache)
     int tune_source = 0;            // 0 model's first candidate, 1 measured, 2 cache, 3 fixed by an override / nothing to tune
 
@@ -226,6 +234,29 @@ void pvals_test(hipStream_t s, const uint32_t* cnt, const double* mave, const do
 void copy_bw(hipStream_t s, const double* src, double* dst, int64_t n);
 void read_bw(hipStream_t s, const void* src, int64_t blocks_per_wave, int64_t nwaves, unsigned int* sink, int perm = 0);
 }  // namespace gvk
+
+// ---- dense fp64 design matrix (gv_dense.hip) ----------------------------------------------------------------------------------
+namespace gvd {
+int64_t row_pitch(int64_t N);       // doubles per resident row: N rounded up to 64
+struct AxShape {
+    int64_t col_tiles = 1;          // workgroups across the individuals (512 each)
+    int64_t seg_len = 1;            // markers per segment
+    int segs = 1;                   // marker segments = partial vectors
+};
+AxShape ax_shape(int64_t N, int64_t M, int cus);
+void synth(hipStream_t s, double* A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed);
+void stats(hipStream_t s, const double* A, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
+           double alpha_scale, double* mave, double* msig);
+// out[m] = msig[m] sum_j (x[m][j] - mave[m]) p[j] * scale, then tau * out + gam2 * addx when addx != NULL (nv = 1 or 2 vectors)
+void atx(hipStream_t s, int nv, const double* A, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
+         const double* mave, const double* msig, double scale, double* outa, double* outb, const double* addxa,
+         const double* addxb, double tau, double gam2);
+// partial[v][seg][j] over the segments of sh, then out[j] = scale * sum_seg partial (j < N), 0 at j >= N
+void ax_partial(hipStream_t s, int nv, const AxShape& sh, const double* A, int64_t M, int64_t pitch, const double* va,
+                const double* vb, const double* mave, const double* msig, double* part, int64_t npad);
+void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int64_t N, int64_t npad, double scale, double* outa,
+               double* outb);
+}  // namespace gvd
 
 // ---- internals shared by the translation units of the C ABI (gv_capi.hip, gv_solvers.hip) ------------------------------
 namespace gvi {

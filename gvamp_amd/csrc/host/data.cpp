@@ -119,7 +119,7 @@ void data::push_mask() { ck(ctx, gv_set_mask(ctx, mask4.data(), nonas), "gv_set_
 data::data(std::vector<double> y, std::string genofp, const int N, const int M, const int Mt, const int S,
            const int rank, std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode)
     : bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), phen_data(y), alpha_scale(alpha_scale) {
-    if (type_data != "bed") die("FATAL: only type_data == \"bed\" is supported by this build");
+    if (type_data != "bed" && type_data != "meth") die("FATAL: type_data must be \"bed\" or \"meth\", not \"" + type_data + "\"");
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
     mask4.assign(mbytes, 0x0F);                       // data.cpp:86-89
@@ -130,28 +130,39 @@ data::data(std::vector<double> y, std::string genofp, const int N, const int M, 
     set_nonas(N);
     open_device(device, kernel_mode);
     push_mask();
-    bedfp = genofp;
-    read_genotype_data();
+    if (type_data == "meth") {                        // data.cpp:107-110
+        methfp = genofp;
+        read_methylation_data();
+    } else {
+        bedfp = genofp;
+        read_genotype_data();
+    }
     compute_markers_statistics();
 }
 
 data::data(std::string fp, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
            std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode)
     : phenfp(fp), bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), alpha_scale(alpha_scale) {
-    if (type_data != "bed") die("FATAL: only type_data == \"bed\" is supported by this build");
+    if (type_data != "bed" && type_data != "meth") die("FATAL: type_data must be \"bed\" or \"meth\", not \"" + type_data + "\"");
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
-    bedfp = genofp;
     read_phen();
     open_device(device, kernel_mode);
     push_mask();
-    read_genotype_data();
+    if (type_data == "meth") {                        // data.cpp:54-57
+        methfp = genofp;
+        read_methylation_data();
+    } else {
+        bedfp = genofp;
+        read_genotype_data();
+    }
     compute_markers_statistics();
 }
 
 data::data(gv_ctx* resident, std::vector<double> y, const int N, const int M, const int Mt, const int S, const int rank,
            const std::vector<unsigned char>* m4, int nonas_, double alpha_scale)
     : N(N), M(M), Mt(Mt), S(S), rank(rank), phen_data(y), alpha_scale(alpha_scale), ctx(resident), owns_ctx(false) {
+    if (gv_get_layout(ctx) == 3) type_data = "meth";      // a dense matrix is resident
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
     if (m4) {
@@ -231,6 +242,19 @@ void data::read_genotype_data() {
                       << (st.expected_passes >= 1000 ? ": a long run -- two sets when they fit" : ": not announced as a long run -- one layout")
                       << "; --resident-layout / GVAMP_EXPECTED_PASSES override)" << std::endl;
     }
+}
+
+// data.cpp:241-278: this rank's M x N doubles of the marker-major methylation matrix at byte offset S*N*8, handed to the
+// device in bounded pieces (the reference reads them into host memory; here they go to HBM).
+void data::read_methylation_data() {
+    const size_t size_bytes = size_t(M) * size_t(N) * sizeof(double);
+    if (rank == 0) std::cout << "meth file name = " << methfp << std::endl;
+    printf("INFO   : rank %d streams %zu bytes (%.3f GB) of methylation data to the device.\n", rank, size_bytes, double(size_bytes) / 1.0E9);
+    const auto t0 = std::chrono::steady_clock::now();
+    ck(ctx, gv_upload_meth_file(ctx, methfp.c_str(), (int64_t)(size_t(S) * size_t(N) * sizeof(double))), "gv_upload_meth_file");
+    if (rank == 0)
+        std::cout << "reading methylation data took "
+                  << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " seconds." << std::endl;
 }
 
 std::vector<int> data::read_chromosome_info(std::string bim_file) {

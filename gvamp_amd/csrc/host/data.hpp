@@ -14,7 +14,7 @@ void gv_host_finalize();
 
 class data {
 private:
-    std::string phenfp, bedfp, bimfp, type_data = "bed";
+    std::string phenfp, bedfp, methfp, bimfp, type_data = "bed";
     int N = 0, M = 0, Mt = 0, S = 0, rank = 0;
     int nonas = 0, nas = 0, im4 = 0;
     size_t mbytes = 0;
@@ -67,6 +67,7 @@ public:
 
     void read_phen();                       // data.cpp:128-192
     void read_genotype_data();              // data.cpp:201-234
+    void read_methylation_data();           // data.cpp:241-278 (type_data == "meth")
     std::vector<int> read_chromosome_info(std::string bim_file);   // data.cpp:346-380
     void compute_markers_statistics();      // data.cpp:392-546
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled

@@ -119,6 +119,11 @@ std::vector<double> vamp::infere(data* dataset) {
     for (size_t i = 0; i < vars.size(); i++) vars[i] *= N;   // design matrix is scaled by 1/sqrt(N) (vamp.cpp:154-155)
     if (reverse == 1) {                                       // vamp.cpp:169-170
         ctx = dataset->get_ctx();
+        if (gv_get_layout(ctx) == 3) {
+            std::cout << "FATAL: --use-XXT-denoiser 1 is not available for methylation data (the reference's meth branch of "
+                         "compute_people_statistics never reduces or finalises its sums)" << std::endl;
+            exit(EXIT_FAILURE);
+        }
         ck(gv_people_stats(ctx, nullptr, nullptr, nullptr), "gv_people_stats (--use-XXT-denoiser needs --kernel-mode 0 or both layouts)");
     }
     if (!strcmp(model.c_str(), "linear")) return infere_linear(dataset);
@@ -728,7 +733,9 @@ std::vector<double> vamp::infere_linear(data* dataset) {
         ck(gv_vec_download(ctx, x1_hat, x1_hat_stored.data()), "gv_vec_download");
         for (double& v : x1_hat_stored) v /= sqrtN;
     }
-    if (store_pvals == 1) {                                                 // vamp.cpp:761-776
+    if (store_pvals == 1 && gv_get_layout(ctx) == 3) {
+        if (rank == 0) std::cout << "p-values: skipped for methylation data (the reference's meth branch of pvals_calc stores nothing)" << std::endl;
+    } else if (store_pvals == 1) {                                          // vamp.cpp:761-776
         // z1 / x1_hat of the last completed iteration, y = filtered phenotype (all still resident on the device)
         const double t0 = now_s();
         std::vector<double> pv = dataset->pvals_calc_dev(z1, y, x1_hat, false);

@@ -58,3 +58,24 @@ def write_bed(path, bed_bytes):
     with open(path, "wb") as f:
         f.write(bytes([0x6C, 0x1B, 0x01]))
         f.write(np.ascontiguousarray(bed_bytes, dtype=np.uint8).tobytes())
+
+
+def synth_meth(N, M, seed, S=0):
+    """Host twin of gv_synth_meth (csrc/gv_dense.hip:k_synth_meth): the M x N methylation matrix (marker-major float64) of global
+    markers S..S+M.  value(g, n) = c_g 2^-12 + (u0 + u1 + u2 + u3) 2^-19 -- an 11-bit per-marker centre plus an Irwin-Hall sum of
+    the four 16-bit fields of a per-entry hash; every value is a dyadic rational exact in fp64, so the two agree bit for bit."""
+    out = np.empty((M, N), dtype=np.float64)
+    with np.errstate(over="ignore"):
+        g = np.arange(S, S + M, dtype=np.uint64)
+        hm = _splitmix64(np.uint64(seed) ^ (g * np.uint64(0xD1342543DE82EF95)))
+        base = _splitmix64(hm + np.uint64(0x632BE59BD9B4E019))
+        centre = (hm >> np.uint64(53)).astype(np.float64) * 2.0 ** -12
+        n = np.arange(N, dtype=np.uint64)
+        f = np.uint64(0xFFFF)
+        step = max(1, (1 << 22) // max(N, 1))
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            r = _splitmix64(base[m0:m1, None] + n[None, :])
+            s = (r & f) + ((r >> np.uint64(16)) & f) + ((r >> np.uint64(32)) & f) + (r >> np.uint64(48))
+            out[m0:m1] = centre[m0:m1, None] + s.astype(np.float64) * 2.0 ** -19
+    return out

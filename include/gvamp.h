@@ -62,6 +62,34 @@ int gv_synth_bed(gv_ctx* ctx, uint64_t seed, uint32_t miss_ppm);
  * probability ld_ppm / 1e6, the block's per-individual latent draw instead of its own -- block-correlated columns, as real
  * genotypes have them (the LMMSE CG then needs tens of steps instead of 4-5).  ld_block = 0: gv_synth_bed. */
 int gv_synth_bed_ld(gv_ctx* ctx, uint64_t seed, uint32_t miss_ppm, uint32_t ld_block, uint32_t ld_ppm);
+/* ---- methylation data: `data` with type_data == "meth" (data.cpp:54-57, :107-110) --------------------------------------
+ * A dense fp64 design matrix: M*N doubles, marker-major (meth_data[i*N + j], read_methylation_data data.cpp:241-278), kept resident
+ * in HBM with the row pitch padded to a multiple of 64 doubles (zeros in the padding).  Uploading either kind -- bed or meth --
+ * replaces the dataset held before; gv_get_layout returns 3 while a dense matrix is resident.  The dataset kind is dispatched
+ * ahead of the kernel mode and the layout: gv_set_kernel_mode / gv_set_layout are ignored for dense data (fp64 VALU kernels
+ * of their own, decomposition derived from N, M and the CU count, bit-reproducible), and the solvers take the host-driven CG loops.
+ *   gv_marker_stats : mave = sum x na / nonas, msig = 1 / sqrt(sum ((x - mave) na)^2 / (nonas - 1)) raised to alpha_scale as the
+ *                     reference does (data.cpp:487-540); a constant column gets msig = 1.
+ *   gv_atx          : out[m] = msig[m] sum_{j<N} (x[m][j] - mave[m]) p[j] / sqrt(N) (data.cpp:783-797, :814-835), p used as given
+ *                     at every individual (no phenotype mask, as the meth dot_product; bed data: p is masked on its way in).
+ *   gv_ax           : out[j] = sum_i (x[i][j] - mave[i]) msig[i] v[i] / sqrt(N) (data.cpp:1013-1045), exact zeros at the pad slots
+ *                     j >= N.  The phenotype mask is NOT applied: the reference's meth Ax leaves individuals with a missing
+ *                     phenotype unmasked, and so does this one (bed data: masked, as data.cpp:972 does).
+ *   two-vector forms: one read of the matrix for both vectors; each slot is bit-identical to the one-vector call.
+ * Not available for dense data (non-zero return, the message names the reason): gv_download_bed; gv_people_stats and the N-space
+ * solvers gv_cg_solve_aat* (the reference's meth branch of compute_people_statistics, data.cpp:633-672, never reduces or
+ * finalises its sums); gv_pvals_* (its meth branch of pvals_calc, data.cpp:1187-1223, computes and stores nothing);
+ * gv_set_decomp (nothing to tune). */
+/* x: M*N doubles of this shard, marker-major. */
+int gv_upload_meth(gv_ctx* ctx, const double* x, size_t n);
+/* The same from a file of doubles: M*N of them starting at byte `offset` of `path` -- offset = S*N*8 (data.cpp:259) -- streamed
+ * through bounded pinned buffers (host memory stays O(64 MB) however large the shard). */
+int gv_upload_meth_file(gv_ctx* ctx, const char* path, int64_t offset);
+/* Synthetic methylation matrix generated on the device: value(g, n) = c_g 2^-12 + (u0 + u1 + u2 + u3) 2^-19 for global marker g,
+ * an 11-bit per-marker centre c_g and four 16-bit hash fields u_k (an Irwin-Hall sum): every value is exact in fp64, so
+ * gvamp_amd.synth.synth_meth(N, M, seed, S) reproduces the matrix bit for bit on the host. */
+int gv_synth_meth(gv_ctx* ctx, uint64_t seed);
+
 /* The PLINK rows back from HBM: only when the raw row layout is resident, i.e. gv_set_layout(ctx, 1, ..) was called before
  * the ingest (not the default). */
 int gv_download_bed(gv_ctx* ctx, uint8_t* bed, size_t nbytes);
@@ -88,7 +116,7 @@ int gv_atx(gv_ctx* ctx, const double* p, double* out);
  * section B): the rows stream through a chunk buffer at ingest and only the re-encoded layout stays resident, so a 100 GB
  * shard occupies 100 GB (or 200 GB) of HBM, not 300.  raw_rows = 1 is needed by kernel mode 0 and gv_download_bed only. */
 int gv_set_layout(gv_ctx* ctx, int raw_rows, int stripes);
-int gv_get_layout(const gv_ctx* ctx);   /* the re-encoded layout resident now: 0 none, 1 two stripe sets, 2 tile layout */
+int gv_get_layout(const gv_ctx* ctx);   /* resident now: 0 none, 1 two stripe sets, 2 tile layout, 3 dense fp64 matrix (meth) */
 /* kernel family for Ax/ATx: 1 (default) = i8 MFMA fixed-point kernels on the re-encoded layout (0.8 of the HBM roofline,
  * results within 2e-14 of fp64 sums, bit-reproducible); 0 = fp64 VALU kernels on the raw rows (parity anchor, 4-9 % of the
  * roofline; needs gv_set_layout(ctx, 1, ..) before ingest); 2 = two-level fixed point on the re-encoded layout (below). */
