@@ -25,6 +25,7 @@ EXPORTS = [
     "gv_probit_denoise", "gv_probit_denoise_cov", "gv_people_stats", "gv_cg_solve_aat", "gv_cg_solve_aat2", "gv_cg_solve_aat2w", "gv_cg_solve2w", "gv_pvals_loo", "gv_pvals_loco", "gv_pvals_loco_pred", "gv_allreduce_host", "gv_comm_unique_id", "gv_comm_init", "gv_comm_init_local", "gv_comm_init_callback", "gv_comm_share", "gv_set_overlap", "gv_debug_force_multi", "gv_comm_rank", "gv_comm_size", "gv_bind_host_numa", "gv_set_timing",
     "gv_get_counters", "gv_reset_counters", "gv_get_decomp", "gv_set_decomp", "gv_tune_info", "gv_ingest_info", "gv_ingest_info2", "gv_set_expected_passes", "gv_copy_bandwidth", "gv_read_bandwidth",
     "gv_upload_meth", "gv_upload_meth_file", "gv_synth_meth",
+    "gv_huber_denoise", "gv_huber_delta",
 ]
 
 
@@ -155,6 +156,8 @@ def load():
     L.gv_allreduce_host.argtypes = [vp, dp, C.c_int]
     L.gv_probit_denoise.argtypes = [vp, vp, vp, C.c_double, C.c_double, vp, dp]
     L.gv_probit_denoise_cov.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, vp, dp]
+    L.gv_huber_denoise.argtypes = [vp, vp, vp, C.c_double, C.c_double, vp, dp]
+    L.gv_huber_delta.argtypes = [vp, vp, vp, C.c_double, dp, C.c_int, dp]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
     L.gv_cg_solve_aat.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(CgStats), dp]
     L.gv_cg_solve_aat2.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.POINTER(CgStats),
@@ -466,6 +469,19 @@ class Shard:
         else:
             self._ck(self.L.gv_probit_denoise_cov(self.h, p1.h, y.h, m_cov.h, tau1, probit_var, z1_out.h, _dp(sums)))
         return sums
+
+    def huber_denoise(self, p1, y, tau1, deltaH, z1_out):
+        """g1_Huber over the N individuals (--model robust): z1_out, and [sum dz1/dp1, sum (z1 - p1)^2]"""
+        sums = np.empty(2)
+        self._ck(self.L.gv_huber_denoise(self.h, p1.h, y.h, tau1, deltaH, z1_out.h, _dp(sums)))
+        return sums
+
+    def huber_delta(self, p1, y, tau1, grid):
+        """the delta_H objective per grid value: mean expected Huber loss + log Z (--model robust)"""
+        g = np.ascontiguousarray(grid, dtype=np.float64)
+        obj = np.empty(g.size)
+        self._ck(self.L.gv_huber_delta(self.h, p1.h, y.h, tau1, _dp(g), g.size, _dp(obj)))
+        return obj
 
     def compute_people_statistics(self):
         """data::compute_people_statistics: (mave_people, msig_people, numb_people), 4*mbytes each."""

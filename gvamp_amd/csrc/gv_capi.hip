@@ -2154,6 +2154,41 @@ int gv_probit_denoise(gv_ctx* c, const gv_vec* p1, const gv_vec* y, double tau1,
     return gv_probit_denoise_cov(c, p1, y, nullptr, tau1, probit_var, z1_out, sums2);
 }
 
+// ---- robust: z-side denoiser and delta_H objective of vamp::infere_robust (vamp_Huber.cpp:224-260) ------------------------
+// Every rank holds all N individuals: these run redundantly on each rank, with no collective.
+int gv_huber_denoise(gv_ctx* c, const gv_vec* p1, const gv_vec* y, double tau1, double deltaH, gv_vec* z1_out, double* sums2) {
+    NEED(c, p1 && y && z1_out && p1->space == GV_SPACE_N && y->space == GV_SPACE_N && z1_out->space == GV_SPACE_N,
+         "gv_huber_denoise: N-space vectors required");
+    arm_scalars(c);
+    gvk::huber_denoise(c->stream, p1->d, y->d, c->N, c->npad, tau1, deltaH, z1_out->d, c->red_partial, c->red_out);
+    KCHK(c);
+    return read_scalars(c, 2, sums2);
+}
+
+// log Z(d), Z(d) = int exp(-rho_d(w)) dw = sqrt(2 pi) erf(d / sqrt 2) + (2 / d) exp(-d^2 / 2): the normaliser of the Huber
+// density that M_deltaH_update (vamp_Huber.cpp:554-573) leaves out
+static double huber_log_norm(double d) {
+    return log(sqrt(2 * M_PI) * erf(d * M_SQRT1_2) + 2.0 / d * exp(-0.5 * d * d));
+}
+
+int gv_huber_delta(gv_ctx* c, const gv_vec* p1, const gv_vec* y, double tau1, const double* grid, int G, double* obj_out) {
+    NEED(c, p1 && y && p1->space == GV_SPACE_N && y->space == GV_SPACE_N, "gv_huber_delta: N-space vectors required");
+    NEED(c, grid && obj_out && G >= 1 && G <= gvk::HUBER_GMAX, "gv_huber_delta: 1 <= G <= 16 grid values required");
+    gvk::HuberGrid hg{};
+    for (int g = 0; g < G; g++) {
+        NEED(c, grid[g] > 0 && std::isfinite(grid[g]), "gv_huber_delta: grid values must be positive and finite");
+        hg.v[g] = grid[g];
+    }
+    NEED(c, tau1 > 0 && std::isfinite(tau1), "gv_huber_delta: tau1 must be positive and finite");
+    arm_scalars(c);
+    gvk::huber_delta(c->stream, p1->d, y->d, c->N, tau1, hg, G, c->red_partial, c->red_out);
+    KCHK(c);
+    double sums[gvk::HUBER_GMAX];
+    if (read_scalars(c, G, sums)) return 1;
+    for (int g = 0; g < G; g++) obj_out[g] = sums[g] / (double)c->N + huber_log_norm(grid[g]);
+    return 0;
+}
+
 // ---- --use-XXT-denoiser 1: LMMSE through CG in N-space (denoiserXXT.cpp), matrix-free ------------------------------
 // data::compute_people_statistics (data.cpp:558-716): three table passes of the fp64 Ax kernel over the raw rows.
 int gv_people_stats(gv_ctx* c, double* mave_people, double* msig_people, double* numb_people) {

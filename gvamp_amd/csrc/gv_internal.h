@@ -166,6 +166,13 @@ void cg_step_b_diag(hipStream_t s, double* r, const double* d, double alpha, con
                     double* partial, double* out);   // out = <r,z>, <r,r>
 void probit_denoise(hipStream_t s, const double* p1, const double* y, const double* m_cov, int64_t N, int64_t npad,
                     double tau1, double probit_var, double* z1, double* partial, double* out);   // out = sum g1d, sum (z1-p1)^2
+// --model robust: out = sum dz1/dp1, sum (z1-p1)^2 ; delta_H objective: out[g] = sum_n E[rho_{grid[g]}(y_n - z)], z ~ N(p1_n, 1/tau1)
+constexpr int HUBER_GMAX = 16;
+struct HuberGrid { double v[HUBER_GMAX]; };
+void huber_denoise(hipStream_t s, const double* p1, const double* y, int64_t N, int64_t npad, double tau1, double deltaH,
+                   double* z1, double* partial, double* out);
+void huber_delta(hipStream_t s, const double* p1, const double* y, int64_t N, double tau1, const HuberGrid& grid, int G,
+                 double* partial, double* out);
 void mul(hipStream_t s, double* out, const double* x, const double* y, int64_t n);
 void select_eq(hipStream_t s, double* out, const double* x, const int* key, int value, int64_t n);
 void ax_table(hipStream_t s, const double* x, const double* mave, const double* msig, int64_t M, double* t3);

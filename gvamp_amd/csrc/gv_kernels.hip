@@ -372,6 +372,112 @@ __global__ __launch_bounds__(256) void k_probit_denoise(const double* __restrict
     }
 }
 
+// ---- robust (--model robust): vamp::g1_Huber over the N individuals (vamp_Huber.cpp:224-227, :443-461) in the reference's
+// operation order; z1 = y - prox(w), w = y - p1.  Partials of sum dz1/dp1 (the derivative of g1_Huber: 1/(1+1/tau1) inside the
+// threshold, 1 outside -- not g1d_Huber_der, :485-503) and of sum (z1 - p1)^2 (:257).  Entries n >= N of z1 are zeroed.
+__global__ __launch_bounds__(256) void k_huber_denoise(const double* __restrict__ p1, const double* __restrict__ y, int64_t N,
+                                                       int64_t npad, double tau1, double deltaH, double* __restrict__ z1,
+                                                       double* __restrict__ partial) {
+#pragma clang fp contract(off)   // the reference's roundings, operation by operation (no fused multiply-adds)
+    __shared__ double sh[4];
+    const double var = 1.0 / tau1;
+    const double thr = (1 + var) * deltaH;
+    int64_t stride = (int64_t)gridDim.x * 256;
+    double s0 = 0, s1 = 0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < npad; i += stride) {
+        double out = 0.0;
+        if (i < N) {
+            const double p = p1[i], yy = y[i];
+            const double w = yy - p;
+            double est, der;
+            if (fabs(w) <= thr) {
+                est = w / (1 + var);
+                der = 1.0 / (1 + var);
+            } else if (w > thr) {
+                est = w - var * deltaH;
+                der = 1.0;
+            } else {                       // w < -thr (and a NaN w, which the reference leaves undefined)
+                est = w + var * deltaH;
+                der = 1.0;
+            }
+            out = yy - est;
+            s0 += der;
+            s1 += (out - p) * (out - p);
+        }
+        z1[i] = out;
+    }
+    s0 = block_sum_256(s0, sh);
+    s1 = block_sum_256(s1, sh);
+    if (threadIdx.x == 0) {
+        partial[(int64_t)blockIdx.x * 2] = s0;
+        partial[(int64_t)blockIdx.x * 2 + 1] = s1;
+    }
+}
+
+// E[rho_d(W)], W ~ N(mu, s^2), Huber loss rho_d(w) = w^2/2 (|w| <= d), d |w| - d^2/2 (|w| > d).  With a = (-d-mu)/s, b = (d-mu)/s:
+//   E = 1/2 [(mu^2+s^2)(Phi(b)-Phi(a)) + 2 mu s (phi(a)-phi(b)) + s^2 (a phi(a) - b phi(b))]
+//     + d [(mu - d/2) Phi(-b) + s phi(b)] + d [(-mu - d/2) Phi(a) + s phi(a)]
+// Phi(b) - Phi(a) is formed on the tail side (erfc) when [a, b] lies on one side of 0, and from erf across it, so that it does
+// not cancel.  The first line is the quadratic piece, O(d^3), while each of its terms is O(d): for d <= s/2 it is integrated
+// instead by 20-point Gauss-Legendre over |w| <= d (a polynomial times a Gaussian over at most one s: exact to rounding), where
+// the terms would cancel to 1e-10.  The closed form of the reference's Monte-Carlo estimate E_MC_eval_ind (vamp_Huber.cpp:522-540).
+__constant__ double c_gl_x[10] = {0.076526521133497338, 0.2277858511416451, 0.37370608871541955, 0.51086700195082713,
+                                   0.63605368072651502, 0.7463319064601508, 0.83911697182221878, 0.91223442825132584,
+                                   0.96397192727791381, 0.99312859918509488};
+__constant__ double c_gl_w[10] = {0.15275338713072578, 0.14917298647260366, 0.14209610931838187, 0.13168863844917653,
+                                   0.11819453196151825, 0.10193011981724026, 0.083276741576704671, 0.062672048334109443,
+                                   0.040601429800386217, 0.017614007139153273};
+__device__ __forceinline__ double huber_expect(double mu, double s, double d) {
+    const double inv_sqrt2pi = 0.39894228040143267794;
+    const double a = (-d - mu) / s, b = (d - mu) / s;
+    const double Phi_mb = 0.5 * erfc(b * M_SQRT1_2), Phi_a = 0.5 * erfc(-a * M_SQRT1_2);
+    const double pa = inv_sqrt2pi * exp(-0.5 * a * a), pb = inv_sqrt2pi * exp(-0.5 * b * b);
+    double centre;
+    if (d <= 0.5 * s) {
+        double acc = 0.0;
+        for (int k = 0; k < 10; k++) {
+            const double w = d * c_gl_x[k];
+            const double tp = (w - mu) / s, tm = (-w - mu) / s;
+            acc = acc + c_gl_w[k] * (w * w) * (exp(-0.5 * tp * tp) + exp(-0.5 * tm * tm)) * inv_sqrt2pi;
+        }
+        centre = acc * (0.5 * d / s);
+    } else {
+        double dphi;
+        if (a >= 0)
+            dphi = 0.5 * (erfc(a * M_SQRT1_2) - erfc(b * M_SQRT1_2));
+        else if (b <= 0)
+            dphi = 0.5 * (erfc(-b * M_SQRT1_2) - erfc(-a * M_SQRT1_2));
+        else
+            dphi = 0.5 * (erf(b * M_SQRT1_2) + erf(-a * M_SQRT1_2));
+        centre = 0.5 * ((mu * mu + s * s) * dphi + 2 * mu * s * (pa - pb) + s * s * (a * pa - b * pb));
+    }
+    return centre + d * ((mu - d / 2) * Phi_mb + s * pb) + d * ((-mu - d / 2) * Phi_a + s * pa);
+}
+
+// the delta_H objective (vamp_Huber.cpp:543-551 in closed form): per grid value g < G, block partials of
+// sum_n E[rho_{grid[g]}(W_n)], W_n ~ N(y_n - p1_n, 1/tau1), over the N individuals (pads contribute nothing)
+__global__ __launch_bounds__(256) void k_huber_delta(const double* __restrict__ p1, const double* __restrict__ y, int64_t N,
+                                                     double tau1, gvk::HuberGrid grid, int G, double* __restrict__ partial) {
+    __shared__ double sh[4];
+    const double s = sqrt(1.0 / tau1);
+    int64_t stride = (int64_t)gridDim.x * 256;
+    double acc[gvk::HUBER_GMAX];
+#pragma unroll
+    for (int g = 0; g < gvk::HUBER_GMAX; g++) acc[g] = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += stride) {
+        const double mu = y[i] - p1[i];
+#pragma unroll
+        for (int g = 0; g < gvk::HUBER_GMAX; g++)
+            if (g < G) acc[g] += huber_expect(mu, s, grid.v[g]);
+    }
+#pragma unroll
+    for (int g = 0; g < gvk::HUBER_GMAX; g++)
+        if (g < G) {                       // (G is uniform over the block: every thread reaches the barriers)
+            const double t = block_sum_256(acc[g], sh);
+            if (threadIdx.x == 0) partial[(int64_t)blockIdx.x * G + g] = t;
+        }
+}
+
 // out = x * y (element-wise) and out = a where mask (chrom[i] == ch) else 0 helpers of the p-value passes
 __global__ void k_mul(double* out, const double* x, const double* y, int64_t n) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1162,6 +1268,20 @@ void probit_denoise(hipStream_t s, const double* p1, const double* y, const doub
     int nb = red_blocks(npad, 256);
     hipLaunchKernelGGL(k_probit_denoise, dim3(nb), dim3(256), 0, s, p1, y, m_cov, N, npad, tau1, probit_var, z1, partial);
     launch_finalize(s, partial, nb, 2, out);
+}
+
+void huber_denoise(hipStream_t s, const double* p1, const double* y, int64_t N, int64_t npad, double tau1, double deltaH,
+                   double* z1, double* partial, double* out) {
+    int nb = red_blocks(npad, 256);
+    hipLaunchKernelGGL(k_huber_denoise, dim3(nb), dim3(256), 0, s, p1, y, N, npad, tau1, deltaH, z1, partial);
+    launch_finalize(s, partial, nb, 2, out);
+}
+
+void huber_delta(hipStream_t s, const double* p1, const double* y, int64_t N, double tau1, const HuberGrid& grid, int G,
+                 double* partial, double* out) {
+    int nb = red_blocks(N > 0 ? N : 1, 256);
+    hipLaunchKernelGGL(k_huber_delta, dim3(nb), dim3(256), 0, s, p1, y, N, tau1, grid, G, partial);
+    launch_finalize(s, partial, nb, G, out);
 }
 
 void mul(hipStream_t s, double* out, const double* x, const double* y, int64_t n) {

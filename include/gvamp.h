@@ -278,6 +278,19 @@ int gv_probit_denoise(gv_ctx* ctx, const gv_vec* p1, const gv_vec* y, double tau
 int gv_probit_denoise_cov(gv_ctx* ctx, const gv_vec* p1, const gv_vec* y, const gv_vec* m_cov, double tau1,
                           double probit_var, gv_vec* z1_out, double* sums2);
 
+/* ---- --model robust (vamp_Huber.cpp): the z side of Huber-loss VAMP over the N individuals -----------------------------
+ * gv_huber_denoise: z1 = g1_Huber(p1, tau1, deltaH, y) (vamp_Huber.cpp:443-461); sums2[0] = sum_n dz1/dp1 (1/(1+1/tau1) where
+ * |y - p1| <= (1+1/tau1) deltaH, else 1: the derivative of g1_Huber, which g1d_Huber_der :485-503 is not), sums2[1] =
+ * sum_n (z1 - p1)^2.  Pad slots of z1 are written 0.
+ * gv_huber_delta: obj_out[g] = (1/N) sum_n E[rho_{grid[g]}(y_n - z)], z ~ N(p1_n, 1/tau1), in closed form, + log Z(grid[g]) with
+ * Z(d) = sqrt(2 pi)(2 Phi(d) - 1) + (2/d) exp(-d^2/2): the expected negative log-likelihood of the Huber density, the objective
+ * that M_deltaH_update (:554-573) estimates by Monte Carlo without log Z.  1 <= G <= 16, grid values > 0.
+ * Both take N-space handles (every rank holds all N: no collective) and give the same bits on every call.
+ * Not yet used by vamp::infere: --model robust is still refused; these are its z-side building blocks. */
+int gv_huber_denoise(gv_ctx* ctx, const gv_vec* p1, const gv_vec* y, double tau1, double deltaH, gv_vec* z1_out,
+                     double* sums2);
+int gv_huber_delta(gv_ctx* ctx, const gv_vec* p1, const gv_vec* y, double tau1, const double* grid, int G, double* obj_out);
+
 /* ---- --use-XXT-denoiser 1 (vamp.cpp:169-170, :599-606; denoiserXXT.cpp): LMMSE through CG in N-space, matrix-free --
  * data::compute_people_statistics (data.cpp:558-716): per-individual mean, inverse std and count of the standardised
  * genotypes, all-reduced over ranks; kept on the device for gv_cg_solve_aat.  Host copies (4*mbytes doubles each) are
