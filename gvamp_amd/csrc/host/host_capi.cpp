@@ -82,9 +82,23 @@ int gvh_infere_linear(gv_ctx* ctx, const gvh_opts* o, int N, int M, int Mt, int 
             for (int j = 0; j < o->C; j++) z[i][j] = o->covs[(size_t)i * o->C + j];
         ds.set_covs(std::move(z));
     }
+    std::string model = o->bin_class ? "bin_class" : "linear";
+    if (o->model && o->model[0]) {
+        model = o->model;
+        if (model != "linear" && model != "bin_class" && model != "robust")
+            throw std::invalid_argument("gvh_infere_linear: unknown model \"" + model + "\" (linear, bin_class or robust)");
+        if (o->bin_class && model != "bin_class")
+            throw std::invalid_argument("gvh_infere_linear: bin_class = 1 with model \"" + model + "\"");
+    }
+    if (o->huber_delta_schedule && o->huber_delta_schedule[0]) {
+        const std::string sch = o->huber_delta_schedule;
+        if (sch != "deferred" && sch != "reference")
+            throw std::invalid_argument("gvh_infere_linear: unknown huber_delta_schedule \"" + sch + "\" (deferred or reference)");
+        opt.set_huber_delta_schedule(sch);
+    }
     gv_host_set_quiet(!o->verbose);
     vamp vm(N, M, Mt, o->gam1, o->gamw, o->iterations, o->rho, vars, probs, ts, rank, "",
-            o->out_prefix ? o->out_prefix : "", o->bin_class ? "bin_class" : "linear", opt);
+            o->out_prefix ? o->out_prefix : "", model, opt);
     vm.set_verbose(o->verbose);
     vm.set_keep_history((x1_hist || x2_hist || r1_hist) ? 1 : 0);
     std::vector<double> x = vm.infere(&ds);
@@ -106,6 +120,7 @@ int gvh_infere_linear(gv_ctx* ctx, const gvh_opts* o, int N, int M, int Mt, int 
         t.beta1 = s.beta1; t.tau2 = s.tau2; t.tau1_next = s.tau1_next;
         t.n_ax = s.n_ax; t.n_atx = s.n_atx; t.n_ax_pass = s.n_ax_pass; t.n_atx_pass = s.n_atx_pass; t.seconds = s.seconds; t.seconds_io = s.seconds_io;
         t.probe_product = s.probe_product;
+        t.deltaH = s.deltaH;
     }
     auto dump = [&](const std::vector<std::vector<double>>& h, double* dst) {
         if (!dst) return;

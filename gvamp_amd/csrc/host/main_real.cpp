@@ -67,7 +67,7 @@ int main(int argc, char** argv) {
         const double gam1 = (mode == "restart") ? opt.get_gam1_init() : 1e-6;
         const double gamw = (mode == "restart") ? opt.get_gamw_init() : initial_gamw(opt);
         vamp emvamp(M, gam1, gamw, std::vector<double>(M, 0.0), rank, opt);
-        emvamp.infere(&dataset);
+        infere_or_exit(emvamp, &dataset);
     } else if (mode == "test") {
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);
@@ -117,7 +117,7 @@ int main(int argc, char** argv) {
         {
             data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km);
             vamp emvamp(M, 1e-6, initial_gamw(opt), std::vector<double>(M, 0.0), rank, opt);
-            x_est = emvamp.infere(&dataset);
+            x_est = infere_or_exit(emvamp, &dataset);
             intercept = dataset.get_intercept();
             scale = dataset.get_scale();
         }

@@ -115,7 +115,7 @@ int main(int argc, char** argv) {
     {   // the vamp object owns device vectors of the dataset's context: it must go first
         vamp emvamp((int)N, M, (int)Mt, gam1, gamw_init, opt.get_iterations(), opt.get_rho(), vars_init, probs_init,
                     beta_true, rank, opt.get_out_dir(), opt.get_out_name(), opt.get_model(), opt);
-        std::vector<double> x_est = emvamp.infere(dataset);
+        std::vector<double> x_est = infere_or_exit(emvamp, dataset);
     }
     if (rank == 0) {
         std::cout << "var(y) = " << pow(calc_stdev(y), 2) << std::endl;

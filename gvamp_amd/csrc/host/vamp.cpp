@@ -9,7 +9,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <limits>
 #include <random>
+#include <sstream>
 #include <stdexcept>
 
 #include "utilities.hpp"
@@ -53,6 +55,7 @@ void vamp::common_init(const Options& opt) {
     use_freeze = (int)opt.get_use_freeze();
     freeze_index_file = opt.get_freeze_index_file();
     probit_var = opt.get_probit_var();
+    huber_deferred = opt.get_huber_delta_schedule() != "reference";
     nranks = gv_env_nranks();
     initialize_prior(this->probs, this->vars, N, Mt, rank);
 }
@@ -130,7 +133,19 @@ std::vector<double> vamp::infere(data* dataset) {
     if (!strcmp(model.c_str(), "bin_class")) {
         return infere_bin_class(dataset);
     }
-    throw "invalid model specification!";   // vamp.cpp:180 (bin_class / robust: SURVEY 8f)
+    if (!strcmp(model.c_str(), "robust")) return infere_robust(dataset);
+    throw "invalid model specification!";   // vamp.cpp:180
+}
+
+std::vector<double> infere_or_exit(vamp& v, data* dataset) {
+    try {
+        return v.infere(dataset);
+    } catch (const std::exception& e) {
+        std::cout << "FATAL: " << e.what() << std::endl;
+    } catch (const char* e) {
+        std::cout << "FATAL: " << e << std::endl;
+    }
+    exit(EXIT_FAILURE);
 }
 
 // vamp.cpp:871-889: u in {+-1/sqrt(Mt)}^M from mt19937{seed + S} + bernoulli(0.5) on the host (bit-comparable with the
@@ -756,6 +771,30 @@ std::vector<double> vamp::infere_linear(data* dataset) {
     return x1_hat_stored;   // x1_hat / sqrt(N) of the last iteration (:802)
 }
 
+void vamp::denoise_signal(int it, vamp_iter_stats& st) {
+    ck(gv_vec_copy(ctx, x1_hat_prev, x1_hat), "gv_vec_copy");
+    const double alpha1_prev = alpha1;
+    int it_revar = 1;
+    for (; it_revar <= 50; it_revar++) {                                  // vamp_probit.cpp:117-160
+        double sums[2];
+        ck(gv_denoise_global(ctx, r1, gam1, probs.data(), vars.data(), (int)probs.size(), x1_hat, nullptr, sums), "gv_denoise_global");
+        alpha1 = sums[0] / Mt;
+        eta1 = gam1 / alpha1;
+        if (it <= 1) break;
+        const double prev = gam1;
+        gam1 = std::min(std::max(1 / (1 / eta1 + sums[1] / Mt), gamma_min), gamma_max);
+        if (verbose && rank == 0) std::cout << "it_revar = " << it_revar << ": gam1 = " << gam1 << std::endl;
+        updatePrior(0);
+        if (std::abs(gam1 - prev) < 1e-3) break;
+    }
+    st.gam1_denoise = gam1;
+    st.revar_rounds = std::max(it_revar - 1, 1);
+    if (it > 1) {                                                         // :197-203
+        ck(gv_vec_axpby(ctx, x1_hat, rho, x1_hat, 1 - rho, x1_hat_prev), "gv_vec_axpby");
+        alpha1 = rho * alpha1 + (1 - rho) * alpha1_prev;
+    }
+}
+
 // vamp::infere_bin_class (vamp_probit.cpp:20-658): generalised VAMP for y in {0, 1}, with or without covariates.
 // Signal side shared with the linear model (gv_denoise, updatePrior, gv_cg_solve, g2d_onsager); the z side is
 // gv_probit_denoise over the N individuals.  probit_err_measures and the "true ..." prints of the reference are
@@ -826,27 +865,7 @@ std::vector<double> vamp::infere_bin_class(data* dataset) {
         }
         if (verbose && rank == 0) std::cout << "->DENOISING" << std::endl;
         const double rho_it = 1;                                          // :71
-        ck(gv_vec_copy(ctx, x1_hat_prev, x1_hat), "gv_vec_copy");
-        const double alpha1_prev = alpha1;
-        int it_revar = 1;
-        for (; it_revar <= 50; it_revar++) {                              // :117-160
-            double sums[2];
-            ck(gv_denoise_global(ctx, r1, gam1, probs.data(), vars.data(), (int)probs.size(), x1_hat, nullptr, sums), "gv_denoise_global");
-            alpha1 = sums[0] / Mt;
-            eta1 = gam1 / alpha1;
-            if (it <= 1) break;
-            const double prev = gam1;
-            gam1 = std::min(std::max(1 / (1 / eta1 + sums[1] / Mt), gamma_min), gamma_max);
-            if (verbose && rank == 0) std::cout << "it_revar = " << it_revar << ": gam1 = " << gam1 << std::endl;
-            updatePrior(0);
-            if (std::abs(gam1 - prev) < 1e-3) break;
-        }
-        st.gam1_denoise = gam1;
-        st.revar_rounds = std::max(it_revar - 1, 1);
-        if (it > 1) {                                                     // :197-203
-            ck(gv_vec_axpby(ctx, x1_hat, rho, x1_hat, 1 - rho, x1_hat_prev), "gv_vec_axpby");
-            alpha1 = rho * alpha1 + (1 - rho) * alpha1_prev;
-        }
+        denoise_signal(it, st);                                           // :117-203
         double t0 = now_s();
         {   // :205-224
             ck(gv_vec_download(ctx, x1_hat, x1_host.data()), "gv_vec_download");
@@ -940,6 +959,185 @@ std::vector<double> vamp::infere_bin_class(data* dataset) {
     for (gv_vec* v : {p1, p2, z1_hat, m_cov})
         if (v) gv_vec_free(ctx, v);
     return x1_host;   // unscaled x1_hat (:657)
+}
+
+// vamp::infere_robust (vamp_Huber.cpp:24-441): generalised VAMP with the Huber loss on the z side.  Signal side and LMMSE as in
+// infere_bin_class (the LMMSE solve from zero, :312); the z side is gv_huber_denoise and gv_huber_delta over the N individuals,
+// which every rank holds whole (no collective).  Departures from the reference, DESIGN.md section 12: (a) beta1 sums the
+// derivative of g1_Huber, not g1d_Huber_der (:485-503); (b) delta_H minimises the closed-form expected negative log-likelihood,
+// not the Monte-Carlo expected loss of :522-586; (c) with --huber-delta-schedule deferred (the default) iteration 1 takes no
+// delta_H step, and iteration 2 takes one on the cavity it denoises before g1_Huber.  A run whose 1 - beta1 is not strictly
+// positive, or whose p2 or tau2 is not finite, stops with an error (the guard).  err_measures (:169, :315) and the "true ..."
+// prints are diagnostics against a known signal and are not reproduced.
+std::vector<double> vamp::infere_robust(data* dataset) {
+    ctx = dataset->get_ctx();
+    S = dataset->get_S();
+    warm_chain = false;     // every LMMSE solve of this loop starts from zero (vamp_Huber.cpp:312)
+    auto newM = [&](gv_vec** v) { ck(gv_vec_alloc(ctx, GV_SPACE_M, v), "gv_vec_alloc"); };
+    auto newN = [&](gv_vec** v) { ck(gv_vec_alloc(ctx, GV_SPACE_N, v), "gv_vec_alloc"); };
+    for (gv_vec** v : {&x1_hat, &x1_hat_prev, &x2_hat, &r1, &r2, &bern_vec, &invQ_bern_vec, &vM, &tM}) newM(v);
+    gv_vec *p1 = nullptr, *p2 = nullptr, *z1_hat = nullptr;
+    for (gv_vec** v : {&y, &tN, &tN2, &p1, &p2, &z1_hat}) newN(v);       // p1 = 0 (:48): gv_vec_alloc zero-fills
+    auto release = [&]() {
+        for (gv_vec* v : {p1, p2, z1_hat})
+            if (v) gv_vec_free(ctx, v);
+        p1 = p2 = z1_hat = nullptr;
+    };
+    {   // y = filter_pheno() (:217): NA / pad slots zeroed on the device
+        std::vector<double> yh = dataset->get_phen();
+        yh.resize(N, 0.0);
+        ck(gv_set_phen(ctx, y, yh.data()), "gv_set_phen");
+    }
+    double tau1 = gam1, tau2 = 0;                                         // :36
+    double deltaH = 1e-3;                                                 // :57
+    static const double grid[] = {1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1, 0.2, 0.4, 0.6, 0.8, 1, 1.5, 2, 3};   // :259
+    const int G = (int)(sizeof(grid) / sizeof(grid[0]));
+    // EM_deltaH (:576-586) over M_deltaH_update (:554-573) on the corrected objective, which does not depend on the previous
+    // delta_H: one evaluation is the fixed point.  The first minimum over the grid, strict <.
+    auto delta_step = [&](double tau) {
+        double obj[sizeof(grid) / sizeof(grid[0])];
+        ck(gv_huber_delta(ctx, p1, y, tau, grid, G, obj), "gv_huber_delta");
+        int k = 0;
+        double best = std::numeric_limits<double>::max();
+        for (int g = 0; g < G; g++)
+            if (obj[g] < best) {
+                k = g;
+                best = obj[g];
+            }
+        return grid[k];
+    };
+    alpha1 = 0;                                                           // :50
+    const double sqrtN = sqrt((double)N);
+    const std::string pre = out_dir + out_name;
+    std::vector<double> x1_host(M > 0 ? M : 0, 0.0);
+    bool ran_any = false;
+
+    for (int it = 1; it <= max_iter; it++) {
+        const double t_start = now_s();
+        double t_io = 0;
+        gv_counters c0;
+        gv_get_counters(ctx, &c0);
+        vamp_iter_stats st;
+        memset(&st, 0, sizeof(st));
+        if (verbose && rank == 0)
+            std::cout << std::endl << "********************" << std::endl << "iteration = " << it << std::endl
+                      << "********************" << std::endl << "->DENOISING" << std::endl;
+        denoise_signal(it, st);                                           // :88-138
+        double t0 = now_s();
+        if (store_iterates || keep_history) {                             // :141-158 (otherwise fetched after the loop)
+            ck(gv_vec_download(ctx, x1_hat, x1_host.data()), "gv_vec_download");
+            std::vector<double> stored = x1_host;
+            for (double& v : stored) v /= sqrtN;
+            if (store_iterates) mpi_store_vec_to_file(pre + "_robust_it_" + std::to_string(it) + ".bin", stored, S, M);
+            if (keep_history) x1_hist.push_back(stored);
+        }
+        ran_any = true;
+        store_scaled(pre + "_robust_r1_it_" + std::to_string(it) + ".bin", r1, &r1_hist);
+        t_io += now_s() - t0;
+        if (verbose && rank == 0) std::cout << "alpha1 = " << alpha1 << std::endl;
+
+        gam_before = gam2;
+        gam2 = std::min(std::max(eta1 - gam1, gamma_min), gamma_max);    // :183
+        if (verbose && rank == 0) std::cout << "eta1 = " << eta1 << std::endl << "gam2 = " << gam2 << std::endl;
+        ck(gv_vec_axpby(ctx, r2, eta1 / gam2, x1_hat, -gam1 / gam2, r1), "gv_vec_axpby");   // :191-192
+        st.alpha1 = alpha1; st.eta1 = eta1; st.gam2 = gam2; st.rho = rho;
+
+        // ---- z side (:212-292)
+        if (huber_deferred && it == 2) deltaH = delta_step(tau1);         // (c): iteration 1's step, on this cavity
+        const double deltaH_in = deltaH, tau1_in = tau1;
+        double zs[2];
+        ck(gv_huber_denoise(ctx, p1, y, tau1, deltaH, z1_hat, zs), "gv_huber_denoise");   // :224-227, :242-249 (a)
+        const double beta1 = zs[0] / N;
+        if (verbose && rank == 0) std::cout << "beta1 = " << beta1 << std::endl;
+        const double zeta1 = tau1 / beta1;                                // :254
+        if (it >= 2) tau1 = std::min(std::max(1 / (1 / zeta1 + zs[1] / N), gamma_min), gamma_max);   // :256-257
+        if (!(huber_deferred && it == 1)) deltaH = delta_step(tau1);      // :259-260 (b)
+        if (verbose && rank == 0) std::cout << "deltaH = " << deltaH << std::endl;
+        double p2_norm2 = NAN;
+        if (1 - beta1 > 0) {
+            ck(gv_vec_axpby(ctx, p2, 1.0 / (1 - beta1), z1_hat, -beta1 / (1 - beta1), p1), "gv_vec_axpby");   // :277-278
+            p2_norm2 = dotN(p2, p2);
+        }
+        tau2 = std::min(std::max(tau1 * (1 - beta1) / beta1, gamma_min), gamma_max);   // :287
+        if (!(1 - beta1 > 0) || !std::isfinite(p2_norm2) || !std::isfinite(tau2)) {    // the guard: nothing runs on with NaN
+            std::ostringstream msg;
+            msg.precision(17);
+            msg << "robust VAMP stopped in iteration " << it << ": "
+                << (!(1 - beta1 > 0) ? "1 - beta1 is not strictly positive" : !std::isfinite(tau2) ? "tau2 is not finite"
+                                                                                                    : "p2 is not finite")
+                << " (deltaH = " << deltaH_in << ", tau1 = " << tau1_in << ", beta1 = " << beta1 << ", tau2 = " << tau2 << ")";
+            if (!(1 - beta1 > 0))
+                msg << ": no residual |y - p1| fell inside the Huber threshold (1 + 1/tau1) deltaH"
+                    << (huber_deferred ? "" : "; --huber-delta-schedule deferred picks deltaH on the cavity it is applied to");
+            release();
+            throw std::runtime_error(msg.str());
+        }
+        st.beta1 = beta1;
+        st.deltaH = deltaH_in;
+        if (verbose && rank == 0) std::cout << "tau2 = " << tau2 << std::endl << std::endl << "->LMMMSE" << std::endl;
+
+        ck(gv_atx_dev(ctx, p2, vM), "gv_atx_dev");                         // :306-309
+        ck(gv_vec_axpby(ctx, vM, tau2, vM, gam2, r2), "gv_vec_axpby");
+        if (fuse_solves)                                                   // :312 (always from zero) + :321 in lock-step
+            alpha2 = fused_solves(vM, nullptr, tau2, dataset, &st.cg_iters, &st.onsager_iters);
+        else {
+            cg(vM, nullptr, tau2, 1, x2_hat, &st.cg_iters);
+            alpha2 = g2d_onsager(gam2, tau2, dataset, &st.onsager_iters);
+        }
+        store_scaled("", x2_hat, &x2_hist);
+        st.alpha2 = alpha2;
+        if (verbose && rank == 0) std::cout << "alpha2 = " << alpha2 << std::endl;
+        eta2 = gam2 / alpha2;                                              // :325
+        if (it > 1) {                                                     // :328-333
+            ck(gv_vec_axpby(ctx, tM, 1.0, x2_hat, -1.0, r2), "gv_vec_axpby");
+            gam2 = std::min(std::max(1 / (1 / eta2 + dotM(tM, tM) / Mt), gamma_min), gamma_max);
+        }
+        st.eta2 = eta2; st.gam2_reest = gam2;
+        if (verbose && rank == 0) std::cout << "gam2 after reest = " << gam2 << std::endl;
+        ck(gv_vec_axpby(ctx, r1, 1.0 / (1 - alpha2), x2_hat, -alpha2 / (1 - alpha2), r2), "gv_vec_axpby");   // :338-339
+        gam1 = gam2 * (1 - alpha2) / alpha2;                              // :355
+        st.gam1_next = gam1;
+        if (verbose && rank == 0) std::cout << "gam1 = " << gam1 << std::endl;
+        if (fuse_solves && have_derived)                                   // z2_hat = A x2_hat (:369): a by-product of the solve
+            ck(gv_vec_copy(ctx, tN, ax2_der), "gv_vec_copy");
+        else
+            ck(gv_ax_dev(ctx, x2_hat, tN), "gv_ax_dev");
+        const double beta2 = (double)Mt / N * (1 - alpha2);               // :372
+        const double zeta2 = tau2 / beta2;                                // :382
+        if (it > 1) {                                                     // :376-385 (not clipped)
+            ck(gv_vec_axpby(ctx, tN2, 1.0, tN, -1.0, p2), "gv_vec_axpby");
+            tau2 = 1.0 / (1.0 / zeta2 + dotN(tN2, tN2) / N);
+        }
+        if (verbose && rank == 0) std::cout << "beta2 = " << beta2 << std::endl << "tau2 after reest = " << tau2 << std::endl;
+        ck(gv_vec_axpby(ctx, p1, 1.0 / (1 - beta2), tN, -beta2 / (1 - beta2), p2), "gv_vec_axpby");   // :391-392
+        tau1 = std::min(std::max(tau2 * (1 - beta2) / beta2, gamma_min), gamma_max);                 // :408
+        st.tau2 = tau2; st.tau1_next = tau1;
+        if (verbose && rank == 0) std::cout << "tau1 = " << tau1 << std::endl;
+
+        st.L_after = (int)probs.size();
+        gv_counters c1;
+        gv_get_counters(ctx, &c1);
+        st.n_ax = (long)(c1.n_ax - c0.n_ax);
+        st.n_atx = (long)(c1.n_atx - c0.n_atx);
+        st.n_ax_pass = (long)(c1.n_ax_pass - c0.n_ax_pass);
+        st.n_atx_pass = (long)(c1.n_atx_pass - c0.n_atx_pass);
+        ck(gv_vec_axpby(ctx, tM, 1.0, x1_hat_prev, -1.0, x1_hat), "gv_vec_axpby");   // :415-420
+        const gv_vec* xs[2] = {tM, x1_hat_prev};
+        const gv_vec* ys[2] = {tM, x1_hat_prev};
+        double d2[2];
+        ck(gv_vec_dots(ctx, 2, xs, ys, 1, d2), "gv_vec_dots");
+        st.seconds_io = t_io;
+        st.seconds = now_s() - t_start - t_io;
+        stats.push_back(st);
+        if (it > 1 && sqrt(d2[0] / d2[1]) < stop_criteria_thr) {          // :431-435
+            if (verbose && rank == 0)
+                std::cout << "robustVAMP stopping criteria fulfilled with threshold = " << stop_criteria_thr << "." << std::endl;
+            break;
+        }
+    }
+    if (ran_any && !(store_iterates || keep_history)) ck(gv_vec_download(ctx, x1_hat, x1_host.data()), "gv_vec_download");
+    release();
+    return x1_host;   // unscaled x1_hat (:439)
 }
 
 // ---- covariates of the probit model ----------------------------------------------------------------------------------

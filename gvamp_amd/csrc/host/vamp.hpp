@@ -14,7 +14,8 @@ struct vamp_iter_stats {     // one row per VAMP iteration (what the reference p
     int cg_iters, onsager_iters, revar_rounds, L_after;
     long n_ax, n_atx;                 // vector products
     long n_ax_pass, n_atx_pass;       // passes over the genotype shard (two-vector kernels share a pass)
-    double beta1, tau2, tau1_next;   // bin_class only
+    double beta1, tau2, tau1_next;   // bin_class and robust only
+    double deltaH;                   // robust only: the Huber threshold g1_Huber applied in this iteration
     double seconds, seconds_io;
     // --fuse-solves 4: what happened to A^T A u of the Onsager probe in this iteration: 0 not in play, 1 captured from the solve's
     // first application and kept, 2 captured but not kept (cancellation, vamp::probe_product_is_usable), 3 the kept product used
@@ -46,6 +47,10 @@ private:
     double linearity_max = 100.0; // XXT level 4: A r2 = c1 z1 - c2 A r1 only while both combinations amplify rounding by <= this (development override: GV_LINEARITY_MAX)
     bool reanchor_now() const { return reanchor_every > 0 && cur_it > 1 && cur_it % reanchor_every == 0; }
     double probit_var = 1;   // options.hpp:124
+    bool huber_deferred = true;   // --huber-delta-schedule deferred (the default) or reference
+    // the signal side of one generalised-VAMP iteration (vamp_probit.cpp:117-203 = vamp_Huber.cpp:92-138): x1_hat, alpha1, eta1
+    // and gam1 over at most 50 variance / prior rounds, then the damping of x1_hat and alpha1
+    void denoise_signal(int it, vamp_iter_stats& st);
     // covariates of the probit model (--C > 0, --cov-file): effects fitted once in iteration 1 (vamp_probit.cpp:110-126)
     std::vector<double> cov_eff;                                                          // vamp.hpp:24
     std::vector<double> grad_cov(const std::vector<double>& y, const std::vector<double>& gg, double probit_var,
@@ -84,6 +89,7 @@ public:
     std::vector<double> infere(data* dataset);           // vamp.cpp:149-183
     std::vector<double> infere_linear(data* dataset);    // vamp.cpp:190-803
     std::vector<double> infere_bin_class(data* dataset); // vamp_probit.cpp:20-658
+    std::vector<double> infere_robust(data* dataset);    // vamp_Huber.cpp:24-441
     double g2d_onsager(double gam2, double tau, data* dataset, int* iters);   // vamp.cpp:871-889
     void draw_onsager_probe(data* dataset);
     bool probe_product_is_usable(double tau, double gam2);                    // level 4: is the captured A^T A u accurate enough to keep?                                   // vamp.cpp:875-882 (host RNG)
@@ -126,3 +132,7 @@ public:
     std::vector<double> get_gam2s() const { return gam2s; }
     std::vector<double> get_R2trains() const { return R2trains; }
 };
+
+// vamp::infere for the drivers: an error of the host classes (the robust loop's guard among them) ends the process with a FATAL
+// line and exit code 1 rather than in std::terminate
+std::vector<double> infere_or_exit(vamp& v, data* dataset);

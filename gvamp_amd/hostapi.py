@@ -24,7 +24,8 @@ class Opts(C.Structure):
                 ("verbose", C.c_int), ("diagnostics", C.c_int), ("alpha_scale", C.c_double), ("use_XXT_denoiser", C.c_int),
                 ("bin_class", C.c_int), ("probit_var", C.c_double), ("fuse_solves", C.c_int),
                 ("C", C.c_int), ("covs", C.POINTER(C.c_double)), ("cov_eff_out", C.POINTER(C.c_double)),
-                ("freeze_index_file", C.c_char_p), ("reanchor_every", C.c_int)]
+                ("freeze_index_file", C.c_char_p), ("reanchor_every", C.c_int), ("model", C.c_char_p),
+                ("huber_delta_schedule", C.c_char_p)]
 
 
 class Iter(C.Structure):
@@ -32,10 +33,11 @@ class Iter(C.Structure):
                [("cg_iters", C.c_int), ("onsager_iters", C.c_int), ("revar_rounds", C.c_int), ("L_after", C.c_int),
                 ("n_ax", C.c_long), ("n_atx", C.c_long), ("n_ax_pass", C.c_long), ("n_atx_pass", C.c_long),
                 ("beta1", C.c_double), ("tau2", C.c_double),
-                ("tau1_next", C.c_double), ("seconds", C.c_double), ("seconds_io", C.c_double), ("probe_product", C.c_int)]
+                ("tau1_next", C.c_double), ("seconds", C.c_double), ("seconds_io", C.c_double), ("probe_product", C.c_int),
+                ("deltaH", C.c_double)]
 
 
-HOST_ABI_VERSION = 2     # GVH_ABI_VERSION of include/gvamp_host.h (gvh_opts / gvh_iter below)
+HOST_ABI_VERSION = 3     # GVH_ABI_VERSION of include/gvamp_host.h (gvh_opts / gvh_iter below)
 
 
 def load():
@@ -77,10 +79,12 @@ def infere_linear(shard, y, probs, vars_, *, iterations=1, CG_max_iter=60, EM_ma
                   stop_criteria_thr=1e-4, rho=0.15, learn_vars=1, seed=1, use_lmmse_damp=0, gam1=1e-8, gamw=2.0,
                   true_signal=None, out_prefix=None, verbose=0, diagnostics=0, alpha_scale=1.0, mask4=None,
                   nonas=None, history=True, rank=0, use_XXT_denoiser=0, model="linear", probit_var=1.0, fuse_solves=1,
-                  covs=None, freeze_index_file=None, reanchor_every=-1):
+                  covs=None, freeze_index_file=None, reanchor_every=-1, huber_delta_schedule=None):
     """vamp::infere on the resident shard.  fuse_solves defaults to 1 HERE -- the level whose products are bit-identical to the
     reference's own sequence, which is what most parity tests want to compare against; the drivers (gvamp_sim, gvamp_main_real,
-    options.hpp), the vamp class and bench.py default to 4.  reanchor_every < 0 keeps the drivers' default (10)."""
+    options.hpp), the vamp class and bench.py default to 4.  reanchor_every < 0 keeps the drivers' default (10).
+    model: "linear", "bin_class" or "robust" (x_est is then the unscaled x1_hat, as for bin_class); huber_delta_schedule (robust):
+    None = "deferred", or "reference".  A robust run that its guard stops raises capi.GvError naming the iteration."""
     L = load()
     y = np.ascontiguousarray(y, dtype=np.float64)
     o = Opts()
@@ -98,6 +102,8 @@ def infere_linear(shard, y, probs, vars_, *, iterations=1, CG_max_iter=60, EM_ma
     o.verbose, o.diagnostics, o.alpha_scale = verbose, diagnostics, alpha_scale
     o.use_XXT_denoiser = use_XXT_denoiser
     o.bin_class, o.probit_var = int(model == "bin_class"), probit_var
+    o.model = model.encode() if model else None
+    o.huber_delta_schedule = huber_delta_schedule.encode() if huber_delta_schedule else None
     o.fuse_solves = fuse_solves
     o.reanchor_every = reanchor_every
     o.freeze_index_file = freeze_index_file.encode() if freeze_index_file else None
@@ -128,7 +134,7 @@ def infere_linear(shard, y, probs, vars_, *, iterations=1, CG_max_iter=60, EM_ma
     for i in range(n.value):
         t = {f: getattr(iters[i], f) for f in ITER_FIELDS}
         for f in ("cg_iters", "onsager_iters", "revar_rounds", "L_after", "n_ax", "n_atx", "seconds", "seconds_io",
-                  "beta1", "tau2", "tau1_next", "n_ax_pass", "n_atx_pass", "probe_product"):
+                  "beta1", "tau2", "tau1_next", "n_ax_pass", "n_atx_pass", "probe_product", "deltaH"):
             t[f] = getattr(iters[i], f)
         r.trace.append(t)
     if history:

@@ -286,7 +286,7 @@ int gv_probit_denoise_cov(gv_ctx* ctx, const gv_vec* p1, const gv_vec* y, const 
  * Z(d) = sqrt(2 pi)(2 Phi(d) - 1) + (2/d) exp(-d^2/2): the expected negative log-likelihood of the Huber density, the objective
  * that M_deltaH_update (:554-573) estimates by Monte Carlo without log Z.  1 <= G <= 16, grid values > 0.
  * Both take N-space handles (every rank holds all N: no collective) and give the same bits on every call.
- * Not yet used by vamp::infere: --model robust is still refused; these are its z-side building blocks. */
+ * vamp::infere_robust (--model robust) calls both every iteration. */
 int gv_huber_denoise(gv_ctx* ctx, const gv_vec* p1, const gv_vec* y, double tau1, double deltaH, gv_vec* z1_out,
                      double* sums2);
 int gv_huber_delta(gv_ctx* ctx, const gv_vec* p1, const gv_vec* y, double tau1, const double* grid, int G, double* obj_out);

@@ -10,8 +10,9 @@
 extern "C" {
 #endif
 
-/* libgvamp_host.so has its own version: gvh_opts / gvh_iter grow with the host classes (2: reanchor_every, probe_product). */
-#define GVH_ABI_VERSION 2
+/* libgvamp_host.so has its own version: gvh_opts / gvh_iter grow with the host classes (2: reanchor_every, probe_product;
+ * 3: model, huber_delta_schedule, deltaH). */
+#define GVH_ABI_VERSION 3
 int gvh_abi_version(void);
 
 typedef struct {                 /* the knobs vamp reads from Options (options.hpp:91-142) and its constructor */
@@ -37,6 +38,9 @@ typedef struct {                 /* the knobs vamp reads from Options (options.h
     double* cov_eff_out;          /* C fitted covariate effects (vamp::get_cov_eff), or NULL */
     const char* freeze_index_file; /* --use-freeze 1 --freeze-index-file <text file, one value per global marker>, or NULL */
     int reanchor_every;           /* --reanchor-every K (levels 3 / 4); < 0 = the drivers' default (10), 0 = never */
+    const char* model;            /* --model: "linear", "bin_class" or "robust"; NULL or "" = what bin_class says.  With bin_class = 1
+                                   * any other value is refused.  robust: x_est is the UNSCALED x1_hat, as for bin_class */
+    const char* huber_delta_schedule; /* --huber-delta-schedule (robust): "deferred" (NULL or "": the default) or "reference" */
 } gvh_opts;
 
 typedef struct {
@@ -44,10 +48,11 @@ typedef struct {
     int cg_iters, onsager_iters, revar_rounds, L_after;
     long n_ax, n_atx;              /* vector products */
     long n_ax_pass, n_atx_pass;    /* passes over the genotype shard */
-    double beta1, tau2, tau1_next; /* bin_class only */
+    double beta1, tau2, tau1_next; /* bin_class and robust only */
     double seconds, seconds_io;   /* compute wall time of the iteration, and time spent writing / copying iterates */
     int probe_product;            /* --fuse-solves 4: A^T A u of the Onsager probe this iteration: 0 not in play, 1 captured and kept,
                                    * 2 captured but dropped by the cancellation rule, 3 the kept product used */
+    double deltaH;                /* robust only: the Huber threshold g1_Huber applied in this iteration */
 } gvh_iter;
 
 /* sim.cpp data recipe on a resident shard: beta_out[M] (this rank's slice), y_out[N] (identical on every rank) */
@@ -57,8 +62,9 @@ const char* gvh_last_error(void);
 int gvh_sim_phen(gv_ctx* ctx, int N, int M, int Mt, int S, int rank, double h2, int CV, unsigned long seed,
                  double* beta_out, double* y_out);
 
-/* vamp::infere (vamp.cpp:149) for --model linear on the shard resident in ctx.  y[N]; mask4 NULL = all present.
- * x_est[M] = x1_hat / sqrt(N) of the last iteration.  x1_hist / x2_hist / r1_hist (optional): iters_cap * M doubles. */
+/* vamp::infere (vamp.cpp:149) for the model o selects on the shard resident in ctx.  y[N]; mask4 NULL = all present.
+ * x_est[M] = x1_hat / sqrt(N) of the last iteration (linear).  x1_hist / x2_hist / r1_hist (optional): iters_cap * M doubles.
+ * A robust run that its guard stops returns 1 and gvh_last_error names the iteration. */
 int gvh_infere_linear(gv_ctx* ctx, const gvh_opts* o, int N, int M, int Mt, int S, int rank, const double* y,
                       const unsigned char* mask4, int nonas, const double* true_signal, double* x_est,
                       gvh_iter* iters, int iters_cap, int* n_iters, double* x1_hist, double* x2_hist, double* r1_hist,
