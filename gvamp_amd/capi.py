@@ -26,6 +26,7 @@ EXPORTS = [
     "gv_get_counters", "gv_reset_counters", "gv_get_decomp", "gv_set_decomp", "gv_tune_info", "gv_ingest_info", "gv_ingest_info2", "gv_set_expected_passes", "gv_copy_bandwidth", "gv_read_bandwidth",
     "gv_upload_meth", "gv_upload_meth_file", "gv_synth_meth",
     "gv_huber_denoise", "gv_huber_delta",
+    "gv_set_cg_precond", "gv_precond_info", "gv_precond_window_gram", "gv_precond_apply",
 ]
 
 
@@ -72,6 +73,12 @@ class IngestStats(C.Structure):      # gv_ingest_stats
 class DecompInfo(C.Structure):
     _fields_ = [("ks", C.c_int), ("balanced_cells", C.c_int64), ("prio", C.c_int), ("taper", C.c_float), ("tuned", C.c_int),
                 ("whole_quads", C.c_int64), ("geo", C.c_float), ("wgs_per_cu", C.c_int), ("xcd_skew", C.c_float)]
+
+
+class PrecondStats(C.Structure):     # gv_precond_stats
+    _fields_ = [("kind", C.c_int), ("window", C.c_int), ("windows", C.c_int64 * 2), ("first_window", C.c_int64 * 2),
+                ("resident_bytes", C.c_double), ("build_seconds", C.c_double), ("factorisations", C.c_int64),
+                ("fallback_windows", C.c_int64), ("last_tau", C.c_double), ("last_gam2", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t)
@@ -158,6 +165,10 @@ def load():
     L.gv_probit_denoise_cov.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, vp, dp]
     L.gv_huber_denoise.argtypes = [vp, vp, vp, C.c_double, C.c_double, vp, dp]
     L.gv_huber_delta.argtypes = [vp, vp, vp, C.c_double, dp, C.c_int, dp]
+    L.gv_set_cg_precond.argtypes = [vp, C.c_int, C.c_int]
+    L.gv_precond_info.argtypes = [vp, C.POINTER(PrecondStats)]
+    L.gv_precond_window_gram.argtypes = [vp, C.c_int, i64, dp]
+    L.gv_precond_apply.argtypes = [vp, C.c_double, C.c_double, vp, vp]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
     L.gv_cg_solve_aat.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(CgStats), dp]
     L.gv_cg_solve_aat2.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.POINTER(CgStats),
@@ -414,6 +425,28 @@ class Shard:
         self._ck(self.L.gv_cg_solve(self.h, v.h, mu_start.h if mu_start is not None else None, tau, gam2, denoiser,
                                     max_iter, mu_out.h, C.byref(st), _dp(rr)))
         return st, rr[:st.n_relres].copy()
+
+    def set_cg_precond(self, kind, window=128):
+        """gv_set_cg_precond: 0 / "scalar" (the default) or 1 / "ld" with windows of 32, 64 or 128 markers"""
+        k = {"scalar": 0, "ld": 1}.get(kind, kind)
+        self._ck(self.L.gv_set_cg_precond(self.h, int(k), int(window)))
+
+    def precond_info(self):
+        st = PrecondStats()
+        self._ck(self.L.gv_precond_info(self.h, C.byref(st)))
+        return {"kind": st.kind, "window": st.window, "windows": list(st.windows), "first_window": list(st.first_window),
+                "resident_bytes": st.resident_bytes, "build_seconds": st.build_seconds, "factorisations": st.factorisations,
+                "fallback_windows": st.fallback_windows, "last_tau": st.last_tau, "last_gam2": st.last_gam2}
+
+    def precond_window_gram(self, grid, k):
+        """W x W Gram of window k of grid 0 / 1, clipped to the shard (zero past its clipped length)"""
+        W = self.precond_info()["window"]
+        out = np.empty(W * W)
+        self._ck(self.L.gv_precond_window_gram(self.h, int(grid), int(k), _dp(out)))
+        return out.reshape(W, W)
+
+    def precond_apply(self, tau, gam2, r, z):
+        self._ck(self.L.gv_precond_apply(self.h, tau, gam2, r.h, z.h))
 
     def ax2_dev(self, xa, xb, outa, outb):
         self._ck(self.L.gv_ax2_dev(self.h, xa.h, xb.h, outa.h, outb.h))

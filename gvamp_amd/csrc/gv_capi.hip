@@ -1106,6 +1106,7 @@ void free_dataset(gv_ctx* c) {
     c->spec_hint_passes = 0;
     c->plan = gvm::Plan();
     c->have_raw = c->have_stripes = false;
+    pc_invalidate(c, true);
     for (gv_vec** v : {&c->w_n, &c->cg_r, &c->cg_z, &c->cg_p, &c->cg_d, &c->mave_p, &c->msig_p, &c->numb_p, &c->w_n2,
                       &c->cg2_r, &c->cg2_z, &c->cg2_p, &c->cg2_d})
         if (*v) {
@@ -1895,10 +1896,12 @@ int gv_set_mask(gv_ctx* c, const uint8_t* mask4, int64_t nonas) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->nonas = nonas;
     c->have_stats = false;
+    pc_invalidate(c, false);
     return 0;
 }
 
 int gv_marker_stats(gv_ctx* c, double alpha_scale) {
+    pc_invalidate(c, false);
     if (c->have_dense) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
         NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
         gvd::stats(c->stream, c->dense, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale, c->mave, c->msig);

@@ -111,6 +111,18 @@ struct gv_ctx {
     gv_vec *cg_r = nullptr, *cg_z = nullptr, *cg_p = nullptr, *cg_d = nullptr;  // CG work vectors
     std::unordered_set<gv_vec*> live_vecs;   // every vector of this context (vec_new / vec_del): freed at gv_destroy
 
+    // LD-block preconditioner of the M-space CG solves (gv_set_cg_precond, gv_precond.hip).  Windows u in [pc_u0, pc_u0 + pc_nu)
+    // overlap the shard; each holds a W x W block (zero beyond its clipped length).  Dropped with the data set, the mask and the
+    // marker statistics (pc_invalidate).
+    int pc_kind = 0, pc_W = 128;
+    int64_t pc_u0 = 0, pc_nu = 0;
+    double* pc_gram = nullptr;      // pc_nu * W * W: exact diagonal blocks of A^T A
+    double* pc_inv = nullptr;       // pc_nu * W * W: (tau G + gam2 I)^-1 of the last factorisation
+    int* pc_fail = nullptr;         // pc_nu flags of the last factorisation: 1 = the window fell back to the scalar rule
+    bool pc_have_gram = false, pc_have_inv = false;
+    double pc_tau = 0.0, pc_gam2 = 0.0, pc_build_s = 0.0;
+    int64_t pc_factorisations = 0, pc_fallback = 0;
+
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;
     std::shared_ptr<void> comm_keep;       // owns comm: ncclCommDestroy when the last context sharing it lets go (gv_comm_share)
@@ -265,6 +277,16 @@ void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int
                double* outb);
 }  // namespace gvd
 
+// ---- LD-block preconditioner (gv_precond.hip) --------------------------------------------------------------------------------
+namespace gvp {
+int64_t first_window(int64_t S, int W);             // first half-grid window u overlapping the shard [S, S+M)
+int64_t num_windows(int64_t S, int64_t M, int W);
+void gram(hipStream_t s, const void* lay, int layout, int64_t nkb, const uint32_t* mask2, int64_t P4, int64_t N, int64_t S, int64_t M,
+          int W, const double* mave, const double* msig, double* out);
+int factor(hipStream_t s, const double* gram, int W, int64_t S, int64_t M, double tau, double gam2, double diag, double* inv, int* fail);
+void apply(hipStream_t s, const double* inv, int W, int64_t S, int64_t M, const double* r, double* z);
+}  // namespace gvp
+
 // ---- internals shared by the translation units of the C ABI (gv_capi.hip, gv_solvers.hip) ------------------------------
 namespace gvi {
 int fail(gv_ctx* c, const char* fmt, ...);
@@ -295,6 +317,10 @@ int lmmse_device(gv_ctx* c, const double* v, double tau, double gam2, double* ou
 bool use_overlap(const gv_ctx* c);    // data::Ax cut into chunks whose exchange runs on the side stream (GV_OVERLAP)
 int ax_overlapped(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg);
 int autotune_ks(gv_ctx* c);     // picks the work decompositions of the streaming kernels (once per shard)
+// kind 1 of gv_set_cg_precond: Grams built and (tau, gam2) factorised, ready for pc_apply (error when that cannot be)
+int pc_prepare(gv_ctx* c, double tau, double gam2);
+void pc_apply(gv_ctx* c, const double* r, double* z);
+void pc_invalidate(gv_ctx* c, bool free_mem);
 
 struct Timer {
     gv_ctx* c;

@@ -55,7 +55,8 @@ struct CgSys {
 // d = Q p0 = (tau / diag) A^T A v + gam2 p0 needs no pass; the step itself is the host-driven one (same arithmetic as on the device).
 static int cg_consume_all(gv_ctx* c, CgSys** act, int na, double gam2, double diag, int max_iter, bool multi);
 static int cg_first_step_from_known_product(gv_ctx* c, CgSys& s, double tau, double gam2, double diag, int max_iter, bool multi) {
-    if (!(s.ata_v && s.ata_v_known && s.active && s.phase == 1 && s.iters == 0 && !s.mu0 && max_iter > 0)) return 0;
+    // (not under the LD preconditioner: p0 = M^-1 v is no multiple of v there)
+    if (!(c->pc_kind == 0 && s.ata_v && s.ata_v_known && s.active && s.phase == 1 && s.iters == 0 && !s.mu0 && max_iter > 0)) return 0;
     gvk::axpby(c->stream, s.d, tau / diag, s.ata_v, gam2, s.p, c->M);
     KCHK(c);
     CgSys* one[1] = {&s};
@@ -63,8 +64,16 @@ static int cg_first_step_from_known_product(gv_ctx* c, CgSys& s, double tau, dou
 }
 // ... and where the product is not at hand yet, the first application delivers it: d = tau A^T A (v / diag) + gam2 v / diag
 static void cg_capture_first_product(gv_ctx* c, const CgSys& s, double tau, double gam2, double diag) {
-    if (!(s.ata_v && !s.ata_v_known && tau != 0.0)) return;
+    if (!(c->pc_kind == 0 && s.ata_v && !s.ata_v_known && tau != 0.0)) return;
     gvk::axpby(c->stream, s.ata_v, diag / tau, s.d, -gam2 / tau, s.v, c->M);
+}
+
+// LD preconditioner (gv_set_cg_precond kind 1): after cg_step_b has updated r, z = M^-1 r replaces its z = r / diag and <r,z>
+// replaces out[0]; <r,r> (out[2]) stays.  (out[1] = <z,z> and out[3] = <mu,mu> are read by no M-space rule.)
+static void pc_step_z(gv_ctx* c, const double* r, double* z, double* partial, double* out) {
+    pc_apply(c, r, z);
+    const double *xs[1] = {r}, *ys[1] = {z};
+    gvk::dots(c->stream, 1, xs, ys, c->M, partial, out);
 }
 
 static int cg_finish_init(gv_ctx* c, CgSys& s, double diag, bool multi) {
@@ -72,6 +81,7 @@ static int cg_finish_init(gv_ctx* c, CgSys& s, double diag, bool multi) {
     const int64_t M = c->M;
     double sc[5];
     gvk::cg_step_b(c->stream, s.r, s.d, 0.0, diag, s.z, s.mu, M, c->red_partial, c->red_out);          // red_out[0..3]
+    if (c->pc_kind == 1) pc_step_z(c, s.r, s.z, c->red_partial, c->red_out);                          // z = M^-1 r, <r,z>
     const double* vv[1] = {s.v};
     gvk::dots(c->stream, 1, vv, vv, M, c->red_partial + 4 * RED_BLOCKS, c->red_out + 4);               // red_out[4]
     KCHK(c);
@@ -116,7 +126,7 @@ static int cg_consume_all(gv_ctx* c, CgSys** act, int na, double gam2, double di
     auto part = [&](int j) { return c->red_partial + (size_t)slot[j] * RED_BLOCKS * 8; };
     auto outp = [&](int j) { return c->red_out + 8 * slot[j]; };
     // (one system in slot 0 of an unsharded job: each reduction's finalisation publishes its scalars itself)
-    const bool solo = ns == 1 && slot[0] == 0 && !multi;
+    const bool solo = ns == 1 && slot[0] == 0 && !multi && c->pc_kind == 0;
     // <d, p>
     for (int j = 0; j < ns; j++) {
         const double* xs[1] = {stp[j]->d};
@@ -161,6 +171,7 @@ static int cg_consume_all(gv_ctx* c, CgSys** act, int na, double gam2, double di
         CgSys& s = *stp[j];
         if (solo) arm_scalars(c);
         gvk::cg_step_b(st, s.r, s.d, alpha[j], diag, s.z, s.mu, M, part(j), outp(j));   // :1195-1216
+        if (c->pc_kind == 1) pc_step_z(c, s.r, s.z, part(j), outp(j));
         any = true;
     }
     KCHK(c);
@@ -609,7 +620,9 @@ static int cg_run(gv_ctx* c, CgSys* sys, int nsys, double tau, double gam2, int 
     const int64_t M = c->M;
     const bool multi = is_multi(c);
     const double diag = tau * (double)(c->N - 1) / (double)c->N + gam2;   // :1137-1138
-    const bool device_loop = cgx_usable(c);
+    // the LD preconditioner runs the host-driven loop (its z and <r,z> are not those of k_cgx_ab), factorised once per (tau, gam2)
+    if (c->pc_kind == 1 && pc_prepare(c, tau, gam2)) return 1;
+    const bool device_loop = cgx_usable(c) && c->pc_kind == 0;
     // every system opening without an operator application of its own (zero start, or a warm start whose products are known): the
     // opening runs on the device too (cg_open_device) -- chosen by nothing rank-local (an empty shard takes it with its peers)
     bool dev_open = device_loop && max_iter > 0 && (multi || M > 0);
@@ -746,6 +759,8 @@ int gv_cg_solve2w(gv_ctx* c, const gv_vec* v_a, const gv_vec* mu_start_a, const 
                              wm->ata_v_b != v_a && tau != 0.0),
          "gv_cg_solve2w: ata_v_b is M-space, must not alias the systems' vectors, and needs tau != 0");
     NEED(c, !wm->have_ata_v_b || wm->ata_v_b, "gv_cg_solve2w: have_ata_v_b without ata_v_b");
+    NEED(c, c->pc_kind == 0 || !wm->ata_v_b,
+         "gv_cg_solve2w: ata_v_b (A^T A v_b from the first step) needs the scalar preconditioner: pass NULL under the LD preconditioner");
     if (ensure_work(c)) return 1;
     if (ensure_w2(c)) return 1;
     for (gv_vec** w : {&c->cg2_r, &c->cg2_z, &c->cg2_p, &c->cg2_d})
@@ -861,6 +876,7 @@ int gv_cg_solve_aat(gv_ctx* c, const gv_vec* v, const gv_vec* mu_start, double t
     NEED(c, v->space == GV_SPACE_N && mu_out->space == GV_SPACE_N, "gv_cg_solve_aat: N-space vectors required");
     NEED(c, mu_out != v && mu_out != mu_start, "gv_cg_solve_aat: mu_out must not alias v or mu_start");
     NEED(c, !c->have_dense, "gv_cg_solve_aat: the N-space solver needs people statistics, not available for methylation data");
+    NEED(c, c->pc_kind == 0, "gv_cg_solve_aat: the N-space solver is refused while the LD preconditioner is set (gv_set_cg_precond kind 1)");
     NEED(c, c->mave_p, "gv_cg_solve_aat: gv_people_stats must run first");
     if (ensure_work(c)) return 1;
     hipStream_t s = c->stream;
@@ -987,6 +1003,7 @@ int gv_cg_solve_aat2w(gv_ctx* c, gv_vec* v_a, const gv_vec* mu_start_a, const gv
                       int max_iter, gv_vec* mu_a, gv_vec* at_mu_a, gv_vec* mu_b, gv_cg_stats* st_a, gv_cg_stats* st_b,
                       double* relres_a, double* relres_b, gv_vec* aat_mu_a, gv_vec* ata_mu_b, const gv_aat_warm* wm) {
     NEED(c, !c->have_dense, "gv_cg_solve_aat2w: the N-space solver needs people statistics, not available for methylation data");
+    NEED(c, c->pc_kind == 0, "gv_cg_solve_aat2w: the N-space solver is refused while the LD preconditioner is set (gv_set_cg_precond kind 1)");
     gv_aat_warm nowarm{};
     if (!wm) wm = &nowarm;
     const gv_vec* aat_mu_start_a = wm->aat_mu_start_a;

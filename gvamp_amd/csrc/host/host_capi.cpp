@@ -96,6 +96,15 @@ int gvh_infere_linear(gv_ctx* ctx, const gvh_opts* o, int N, int M, int Mt, int 
             throw std::invalid_argument("gvh_infere_linear: unknown huber_delta_schedule \"" + sch + "\" (deferred or reference)");
         opt.set_huber_delta_schedule(sch);
     }
+    if (o->cg_precond && o->cg_precond[0]) {
+        const std::string pk = o->cg_precond;
+        if (pk != "scalar" && pk != "ld")
+            throw std::invalid_argument("gvh_infere_linear: unknown cg_precond \"" + pk + "\" (scalar or ld)");
+        const int w = o->cg_precond_window > 0 ? o->cg_precond_window : 128;
+        if (w != 32 && w != 64 && w != 128)
+            throw std::invalid_argument("gvh_infere_linear: cg_precond_window must be 32, 64 or 128");
+        opt.set_cg_precond(pk, w);
+    }
     gv_host_set_quiet(!o->verbose);
     vamp vm(N, M, Mt, o->gam1, o->gamw, o->iterations, o->rho, vars, probs, ts, rank, "",
             o->out_prefix ? o->out_prefix : "", model, opt);

@@ -123,6 +123,16 @@ void Options::read_command_line_options(int argc, char** argv) {
             fatal(std::string("FATAL  : option --huber-delta-schedule has to be deferred or reference! (") + a + " was passed)");
         huber_delta_schedule = a;
     };
+    H["--cg-precond"] = [&](const char* a) {
+        if (strcmp(a, "scalar") && strcmp(a, "ld"))
+            fatal(std::string("FATAL  : option --cg-precond has to be scalar or ld! (") + a + " was passed)");
+        cg_precond = a;
+    };
+    H["--cg-precond-window"] = [&](const char* a) {
+        if (strcmp(a, "32") && strcmp(a, "64") && strcmp(a, "128"))
+            fatal(std::string("FATAL  : option --cg-precond-window has to be 32, 64 or 128! (") + a + " was passed)");
+        cg_precond_window = atoi(a);
+    };
     H["--resident-layout"] = [&](const char* a) {      // read by data::open_device (every data object of the run)
         resident_layout = atoi(a);
         setenv("GVAMP_RESIDENT_LAYOUT", a, 1);

@@ -36,10 +36,13 @@
        never): at --fuse-solves 3 / 4 every K-th iteration applies the operator to the warm start explicitly and captures \
        A^T A u afresh, so the products chained from CG residuals never run unanchored for more than K iterations;    \
        --huber-delta-schedule deferred|reference (--model robust): deferred (default) moves       \
-       iteration 1's delta_H step to the start of iteration 2's z side, reference keeps vamp_Huber.cpp's order */     \
+       iteration 1's delta_H step to the start of iteration 2's z side, reference keeps vamp_Huber.cpp's order;       \
+       --cg-precond scalar|ld (default scalar) and --cg-precond-window 32|64|128 (default 128): the preconditioner of   \
+       the M-space CG solves, ld = two grids of LD-block windows */                              \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
-    X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred")
+    X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
+    X(int, cg_precond_window, 128)
 
 class Options {
 public:
@@ -77,6 +80,7 @@ public:
     void set_fuse_solves(int v) { fuse_solves = v; }
     void set_reanchor_every(int v) { reanchor_every = v; }
     void set_huber_delta_schedule(const std::string& v) { huber_delta_schedule = v; }
+    void set_cg_precond(const std::string& v, int window) { cg_precond = v; cg_precond_window = window; }
     void set_C(unsigned int v) { C = v; }
     void set_freeze(const std::string& file) { use_freeze = 1; freeze_index_file = file; }
 

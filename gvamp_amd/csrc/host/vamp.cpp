@@ -56,6 +56,8 @@ void vamp::common_init(const Options& opt) {
     freeze_index_file = opt.get_freeze_index_file();
     probit_var = opt.get_probit_var();
     huber_deferred = opt.get_huber_delta_schedule() != "reference";
+    cg_precond = opt.get_cg_precond() == "ld" ? 1 : 0;
+    cg_precond_window = opt.get_cg_precond_window();
     nranks = gv_env_nranks();
     initialize_prior(this->probs, this->vars, N, Mt, rank);
 }
@@ -120,6 +122,13 @@ std::vector<double> vamp::infere(data* dataset) {
     // products cached from one iteration to the next belong to this run's design matrix and probe
     have_ata_u = have_ata_x2 = have_aat_prev = false;
     for (size_t i = 0; i < vars.size(); i++) vars[i] *= N;   // design matrix is scaled by 1/sqrt(N) (vamp.cpp:154-155)
+    // the preconditioner of the M-space CG solves, on the statistics the data object has computed (refusals end a driver with FATAL)
+    ctx = dataset->get_ctx();
+    if (cg_precond == 1 && reverse == 1)
+        throw std::invalid_argument("--cg-precond ld is not available with --use-XXT-denoiser 1 (the N-space solve has no LD preconditioner)");
+    if (cg_precond == 1 && gv_get_layout(ctx) == 3)
+        throw std::invalid_argument("--cg-precond ld is not available for methylation data (genotype windows only)");
+    if (gv_set_cg_precond(ctx, cg_precond, cg_precond_window)) throw std::runtime_error(gv_last_error(ctx));
     if (reverse == 1) {                                       // vamp.cpp:169-170
         ctx = dataset->get_ctx();
         if (gv_get_layout(ctx) == 3) {
@@ -214,7 +223,8 @@ double vamp::fused_solves(gv_vec* v, gv_vec* mu_start, double tau, data* dataset
             wm.a_mu_start_a = ax2_der;
         }
     }
-    if (fuse_solves >= 4 && CG_max_iter > 0) {
+    if (fuse_solves >= 4 && CG_max_iter > 0 && cg_precond == 0) {
+        // (not under --cg-precond ld: the first step applies the operator to M^-1 u, no multiple of u -- probe_product stays 0)
         // --fuse-solves 4: the Onsager solve starts from zero on the same probe u every iteration: its first operator application is
         // (tau / diag) A^T A u + gam2 u / diag, with A^T A u captured the first time round -- the solve is one pass pair shorter
         if (!ata_u) ck(gv_vec_alloc(ctx, GV_SPACE_M, &ata_u), "gv_vec_alloc");

@@ -47,6 +47,7 @@ private:
     double linearity_max = 100.0; // XXT level 4: A r2 = c1 z1 - c2 A r1 only while both combinations amplify rounding by <= this (development override: GV_LINEARITY_MAX)
     bool reanchor_now() const { return reanchor_every > 0 && cur_it > 1 && cur_it % reanchor_every == 0; }
     double probit_var = 1;   // options.hpp:124
+    int cg_precond = 0, cg_precond_window = 128;   // --cg-precond scalar (0) | ld (1), --cg-precond-window
     bool huber_deferred = true;   // --huber-delta-schedule deferred (the default) or reference
     // the signal side of one generalised-VAMP iteration (vamp_probit.cpp:117-203 = vamp_Huber.cpp:92-138): x1_hat, alpha1, eta1
     // and gam1 over at most 50 variance / prior rounds, then the damping of x1_hat and alpha1

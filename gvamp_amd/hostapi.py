@@ -24,8 +24,9 @@ class Opts(C.Structure):
                 ("verbose", C.c_int), ("diagnostics", C.c_int), ("alpha_scale", C.c_double), ("use_XXT_denoiser", C.c_int),
                 ("bin_class", C.c_int), ("probit_var", C.c_double), ("fuse_solves", C.c_int),
                 ("C", C.c_int), ("covs", C.POINTER(C.c_double)), ("cov_eff_out", C.POINTER(C.c_double)),
-                ("freeze_index_file", C.c_char_p), ("reanchor_every", C.c_int), ("model", C.c_char_p),
-                ("huber_delta_schedule", C.c_char_p)]
+                ("freeze_index_file", C.c_char_p), ("reanchor_every", C.c_int),
+                ("cg_precond", C.c_char_p), ("cg_precond_window", C.c_int),      # ABI 4
+                ("model", C.c_char_p), ("huber_delta_schedule", C.c_char_p)]
 
 
 class Iter(C.Structure):
@@ -37,7 +38,7 @@ class Iter(C.Structure):
                 ("deltaH", C.c_double)]
 
 
-HOST_ABI_VERSION = 3     # GVH_ABI_VERSION of include/gvamp_host.h (gvh_opts / gvh_iter below)
+HOST_ABI_VERSION = 4     # GVH_ABI_VERSION of include/gvamp_host.h (gvh_opts / gvh_iter below)
 
 
 def load():
@@ -79,12 +80,14 @@ def infere_linear(shard, y, probs, vars_, *, iterations=1, CG_max_iter=60, EM_ma
                   stop_criteria_thr=1e-4, rho=0.15, learn_vars=1, seed=1, use_lmmse_damp=0, gam1=1e-8, gamw=2.0,
                   true_signal=None, out_prefix=None, verbose=0, diagnostics=0, alpha_scale=1.0, mask4=None,
                   nonas=None, history=True, rank=0, use_XXT_denoiser=0, model="linear", probit_var=1.0, fuse_solves=1,
-                  covs=None, freeze_index_file=None, reanchor_every=-1, huber_delta_schedule=None):
+                  covs=None, freeze_index_file=None, reanchor_every=-1, huber_delta_schedule=None, cg_precond="scalar",
+                  cg_precond_window=128):
     """vamp::infere on the resident shard.  fuse_solves defaults to 1 HERE -- the level whose products are bit-identical to the
     reference's own sequence, which is what most parity tests want to compare against; the drivers (gvamp_sim, gvamp_main_real,
     options.hpp), the vamp class and bench.py default to 4.  reanchor_every < 0 keeps the drivers' default (10).
     model: "linear", "bin_class" or "robust" (x_est is then the unscaled x1_hat, as for bin_class); huber_delta_schedule (robust):
-    None = "deferred", or "reference".  A robust run that its guard stops raises capi.GvError naming the iteration."""
+    None = "deferred", or "reference".  A robust run that its guard stops raises capi.GvError naming the iteration.
+    cg_precond: "scalar" (the reference's) or "ld" with windows of cg_precond_window markers."""
     L = load()
     y = np.ascontiguousarray(y, dtype=np.float64)
     o = Opts()
@@ -105,6 +108,8 @@ def infere_linear(shard, y, probs, vars_, *, iterations=1, CG_max_iter=60, EM_ma
     o.model = model.encode() if model else None
     o.huber_delta_schedule = huber_delta_schedule.encode() if huber_delta_schedule else None
     o.fuse_solves = fuse_solves
+    o.cg_precond = cg_precond.encode() if cg_precond else None
+    o.cg_precond_window = cg_precond_window
     o.reanchor_every = reanchor_every
     o.freeze_index_file = freeze_index_file.encode() if freeze_index_file else None
     cov_eff = None

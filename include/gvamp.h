@@ -243,7 +243,9 @@ typedef struct gv_cg_warm {
      *   ata_v_b (M-space): with have_ata_v_b == 0 an OUTPUT -- A^T A v_b, taken from solve b's first application (written when
      *                      max_iter > 0); with have_ata_v_b != 0 an INPUT -- that first application becomes
      *                      (tau / diag) * ata_v_b + gam2 * v_b / diag and costs no pass, so solve b is one pass pair shorter.
-     * The caller owns the invariant "same v_b as when ata_v_b was written".  Equal to the explicit product to rounding. */
+     * The caller owns the invariant "same v_b as when ata_v_b was written".  Equal to the explicit product to rounding.
+     * Refused under the LD preconditioner (gv_set_cg_precond kind 1): its first step applies the operator to M^-1 v_b, no multiple
+     * of v_b, so there is nothing to capture or use -- pass NULL there. */
     gv_vec* ata_v_b;
     int have_ata_v_b;
 } gv_cg_warm;
@@ -488,6 +490,31 @@ int gv_copy_bandwidth(gv_ctx* ctx, size_t nbytes, int reps, double* gbps);
  * non-temporal 16-byte loads, nothing else): GB/s over the resident marker-major stripes when there are any, else over a
  * scratch buffer of nbytes.  The ceiling a streaming kernel can be held against on this part. */
 int gv_read_bandwidth(gv_ctx* ctx, size_t nbytes, int reps, double* gbps);
+
+/* LD-block preconditioner of every M-space CG solve (gv_cg_solve, gv_cg_solve2 / 2x / 2w).  New entry points
+ * only: GV_ABI_VERSION stays 4.  kind 0 = the reference's scalar diag = tau (N-1)/N + gam2 (the default, nothing changes); kind 1 =
+ * "ld": windows of `window` (32, 64 or 128) markers on global marker indices in two grids, [kW, kW+W) and [kW-W/2, kW+W/2) for k >= 0
+ * (grid 1's window 0 is [0, W/2): every marker lies in one window of each grid), clipped to the shard; z = 1/2 sum over both grids of blockdiag((tau G + gam2 I)^-1) r with G the window's exact diagonal block of A^T A.  The
+ * Grams come from the resident re-encoded layout (a context with raw rows only is refused, so are dense (meth) data); they are built
+ * at the first solve (or gv_precond_window_gram) and dropped on a new ingest, gv_set_mask and gv_marker_stats; kind 0 releases them.  A window whose pivot is <= 1e-12 x its largest
+ * diagonal, or not finite, takes the scalar rule on its markers.  With kind 1 the M-space solves run the host-driven loop, and the
+ * N-space solvers gv_cg_solve_aat* are refused. */
+int gv_set_cg_precond(gv_ctx* ctx, int kind, int window);
+typedef struct gv_precond_stats {
+    int kind, window;
+    int64_t windows[2];          /* windows of grid 0 / 1 that overlap this shard ... */
+    int64_t first_window[2];     /* ... and the global index k of the first of them */
+    double resident_bytes;       /* Grams + inverses on the device */
+    double build_seconds;        /* wall time of the last Gram build */
+    int64_t factorisations;      /* (tau, gam2) pairs factorised so far */
+    int64_t fallback_windows;    /* windows of the last factorisation on the scalar rule */
+    double last_tau, last_gam2;
+} gv_precond_stats;
+int gv_precond_info(gv_ctx* ctx, gv_precond_stats* info);
+/* W x W doubles, row-major: window k of grid (0 / 1) clipped to the shard, rows and columns past its clipped length are 0 */
+int gv_precond_window_gram(gv_ctx* ctx, int grid, int64_t k, double* out);
+/* z = M^-1 r for (tau, gam2) (factorises when they differ from the last factorisation) */
+int gv_precond_apply(gv_ctx* ctx, double tau, double gam2, const gv_vec* r, gv_vec* z);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,8 @@ extern "C" {
 #endif
 
 /* libgvamp_host.so has its own version: gvh_opts / gvh_iter grow with the host classes (2: reanchor_every, probe_product;
- * 3: model, huber_delta_schedule, deltaH). */
-#define GVH_ABI_VERSION 3
+ * 3: model, huber_delta_schedule, deltaH; 4: cg_precond, cg_precond_window). */
+#define GVH_ABI_VERSION 4
 int gvh_abi_version(void);
 
 typedef struct {                 /* the knobs vamp reads from Options (options.hpp:91-142) and its constructor */
@@ -38,6 +38,8 @@ typedef struct {                 /* the knobs vamp reads from Options (options.h
     double* cov_eff_out;          /* C fitted covariate effects (vamp::get_cov_eff), or NULL */
     const char* freeze_index_file; /* --use-freeze 1 --freeze-index-file <text file, one value per global marker>, or NULL */
     int reanchor_every;           /* --reanchor-every K (levels 3 / 4); < 0 = the drivers' default (10), 0 = never */
+    const char* cg_precond;       /* ABI 4, --cg-precond: "scalar" (NULL or "": the default) or "ld"  */
+    int cg_precond_window;        /* ABI 4, --cg-precond-window: 32, 64 or 128 (<= 0: 128) */
     const char* model;            /* --model: "linear", "bin_class" or "robust"; NULL or "" = what bin_class says.  With bin_class = 1
                                    * any other value is refused.  robust: x_est is the UNSCALED x1_hat, as for bin_class */
     const char* huber_delta_schedule; /* --huber-delta-schedule (robust): "deferred" (NULL or "": the default) or "reference" */
