@@ -455,7 +455,7 @@ gv_ctx::EvRec* ev_next(gv_ctx* c, int kind) {
 // run on a shape pays for the measurement.  One line per key, the last matching line wins; a line is written with one
 // O_APPEND write (ranks of a sharded job may share the file).  Results never depend on the pick (exact integer
 // accumulation), so a stale or foreign line can cost time, never correctness; every loaded pick is range-checked.
-constexpr int GV_TUNE_VERSION = 8;   // bump when the candidate set or the line format changes shape
+constexpr int GV_TUNE_VERSION = 9;   // bump when the candidate set or the line format changes shape (9: tail hybrids, ticket-dealt items)
 #ifndef GV_KERNEL_SRC_HASH
 #error "build with -DGV_KERNEL_SRC_HASH=\"...\" (gvamp_amd/build.py computes it from the streaming-kernel sources)"
 #endif
@@ -476,8 +476,9 @@ static std::string tune_key(gv_ctx* c) {
     char buf[256];
     // GV_KERNEL_SRC_HASH (gvamp_amd/build.py: sha256 of gv_mfma.hip + gv_mfma.h) ties a line to the kernels it was measured on: a
     // pick made for other kernel sources is never read back
-    snprintf(buf, sizeof(buf), "v%d|%s|%s|%d|%lld|%lld|L%d|", GV_TUNE_VERSION, GV_KERNEL_SRC_HASH, pr.gcnArchName,
-             pr.multiProcessorCount, (long long)c->N, (long long)c->M, c->plan.layout);
+    // (D: work items dealt by ticket or taken by block index -- picks measured under one mapping are not read back under the other)
+    snprintf(buf, sizeof(buf), "v%d|%s|%s|%d|%lld|%lld|L%d|D%d|", GV_TUNE_VERSION, GV_KERNEL_SRC_HASH, pr.gcnArchName,
+             pr.multiProcessorCount, (long long)c->N, (long long)c->M, c->plan.layout, c->deal.ctr ? 1 : 0);
     return buf;
 }
 // is decomposition d admissible for side (0: ATx / stripes_m, 1: Ax / stripes_n) of this context?
@@ -559,9 +560,11 @@ static void tune_cache_store(gv_ctx* c) {
     const gvm::Decomp* d[4] = {&c->plan.dm[0], &c->plan.dm[1], &c->plan.dn[0], &c->plan.dn[1]};
     char buf[1024];
     int n = snprintf(buf, sizeof(buf), "%s", key.c_str());
+    // xskew is written as 0: which four XCDs are ahead changes with the box and the allocation (profiles/r6_xcd_skew.txt), so a cached
+    // sign could pin the losing skew for every later process that shares the file
     for (int k = 0; k < 4; k++)
         n += snprintf(buf + n, sizeof(buf) - n, "%d %lld %lld %d %.2f %.2f %d %.3f ", d[k]->ks, (long long)d[k]->skL, (long long)d[k]->piv, d[k]->prio,
-                      d[k]->taper, d[k]->geo, d[k]->occ, d[k]->xskew);
+                      d[k]->taper, d[k]->geo, d[k]->occ, 0.0);
     n += snprintf(buf + n, sizeof(buf) - n, "\n");
     const int fd = open(path.c_str(), O_WRONLY | O_APPEND | O_CREAT, 0644);
     if (fd < 0) return;
@@ -725,7 +728,8 @@ int autotune_ks(gv_ctx* c) {
         // ... then more work for four of the eight XCDs (Decomp::xskew), on a winner whose quads have at least two segments.  WHICH four
         // finish equal shares first belongs to the box and to where the allocation landed (profiles/r6_xcd_skew.txt): both signs are
         // measured on the resident data, and the better one is pushed once more if it beat the equal shares
-        if (best.skL <= 0 && best.ks >= 2) {
+        // (block-index mapping only: dealt launches ignore xskew -- an XCD that is ahead draws more items by itself)
+        if (best.skL <= 0 && best.ks >= 2 && !pl.deal) {
             const gvm::Decomp base = best;
             const double t_base = best_t;
             for (float sk : {0.02f, -0.02f}) {
@@ -1105,6 +1109,7 @@ void free_dataset(gv_ctx* c) {
     c->spec_hint_steps[0] = c->spec_hint_steps[1] = c->spec_hint_steps[2] = 0;
     c->spec_hint_passes = 0;
     c->plan = gvm::Plan();
+    c->plan.deal = c->deal.ctr ? &c->deal : nullptr;
     c->have_raw = c->have_stripes = false;
     pc_invalidate(c, true);
     for (gv_vec** v : {&c->w_n, &c->cg_r, &c->cg_z, &c->cg_p, &c->cg_d, &c->mave_p, &c->msig_p, &c->numb_p, &c->w_n2,
@@ -1126,6 +1131,7 @@ static int plan_decomps(gv_ctx* c) {
     const int64_t N = c->N, M = c->M;
     gvm::Plan& pl = c->plan;
     pl.M = M; pl.N = N;
+    pl.deal = c->deal.ctr ? &c->deal : nullptr;
     pl.nrg_m = (M + 63) / 64;  pl.nkb_m = (N + 255) / 256;
     pl.nrg_n = (N + 63) / 64;  pl.nkb_n = (M + 255) / 256;
     pl.layout = c->want_tile ? 1 : 0;
@@ -1186,13 +1192,13 @@ static int plan_decomps(gv_ctx* c) {
     if (const char* e = getenv("GV_PRIO")) prio_only = atoi(e) ? 1 : 0;
     // piv quads whole (0: as many whole rounds of 768 as the quads allow), the rest balanced over G workgroups; the pieces a row
     // of the remainder is cut into are bounded so that the int32 partial sums stay below 1 GB (4 planes x 32 B per row and piece)
-    auto hybrid_of = [](int64_t nrg, int64_t nkb, int64_t rows, int64_t piv, int64_t G) -> gvm::Decomp {
+    auto hybrid_of = [](int64_t nrg, int64_t nkb, int64_t rows, int64_t piv, int64_t G, double max_bytes = 1.0e9) -> gvm::Decomp {
         gvm::Decomp h;
         const int64_t nq = (nrg + 3) / 4;
         if (piv <= 0) piv = nq / 768 * 768;
         if (piv <= 0 || piv >= nq || nkb < 2 || G <= 0) return h;
         const int64_t cells = (nq - piv) * nkb;
-        int64_t maxp = (int64_t)(1.0e9 / (128.0 * (double)nrg * (double)rows));
+        int64_t maxp = (int64_t)(max_bytes / (128.0 * (double)nrg * (double)rows));
         if (maxp > 60) maxp = 60;
         if (maxp < 3) return h;
         int64_t L = (cells + G - 1) / G;
@@ -1202,6 +1208,7 @@ static int plan_decomps(gv_ctx* c) {
         h.ks = 1; h.skL = L; h.piv = piv; h.prio = 1;
         return h;
     };
+    const bool dealt = c->deal.ctr != nullptr;      // work items dealt by ticket (gv_create)
     auto build = [&](const int* ks3, int64_t nrg, int64_t nkb, int64_t rows, bool balanced_ok, int64_t min_ks_u, bool geo_side, std::vector<gvm::Decomp>& out) {
         out.clear();
         for (int prio = 0; prio < 2; prio++) {
@@ -1247,6 +1254,28 @@ static int plan_decomps(gv_ctx* c) {
                 gvm::Decomp d; d.ks = 1; d.skL = skL_of(nrg, nkb, 768 * r); d.prio = 1;
                 if (d.skL > 0) out.push_back(d);
             }
+            // dealt launches: hybrids whose remainder is a real TAIL -- the last 7 % / 10 % of the quads in ranges of ~80 / ~160 cells
+            // (16 KiB per cell, ~9 GB/s per resident workgroup: 150 / 300 us; never shorter than the partial sums allow: up to 2 GB
+            // here).  The whole quads are drawn first; an XCD that frees its slots early draws tail ranges instead of idling.  Only
+            // where the whole quads fill the chip at least once.
+            if (dealt && (nrg + 3) / 4 >= 768) {
+                const int64_t nq = (nrg + 3) / 4;
+                for (const auto& tl : {std::pair<double, int64_t>{0.07, 80}, {0.10, 160}}) {
+                    int64_t tq = (int64_t)(tl.first * (double)nq + 0.5);
+                    if (tq < 1) tq = 1;
+                    const int64_t G = (tq * nkb + tl.second - 1) / tl.second;
+                    gvm::Decomp t = hybrid_of(nrg, nkb, rows, nq - tq, G, 2.0e9);
+                    bool dup = t.skL <= 0 || t.skL > nkb;
+                    for (const gvm::Decomp& o : out) dup |= o.skL == t.skL && o.piv == t.piv;
+                    if (!dup) out.push_back(t);
+                }
+            }
+        }
+        // dealt launches, Ax side: a few long segments followed by a longer geometric tail (the last of 12 segments is ~1 / 50 of the first)
+        if (dealt && geo_side && prio_only != 0 && 12 >= min_ks_u) {
+            double tot = 0.0, wlast = 1.0;
+            for (int j = 0; j < 12; j++) { tot += wlast; if (j + 1 < 12) wlast *= 0.7; }
+            if ((double)nkb * wlast / tot >= 8.0) { gvm::Decomp d; d.ks = 12; d.skL = 0; d.prio = 1; d.geo = 0.7f; out.push_back(d); }
         }
     };
     build(ks3_m, pl.nrg_m, pl.nkb_m, 64, true, 1, false, c->dec_cand_m);
@@ -1356,6 +1385,19 @@ int gv_create(int device, gv_ctx** out) {
             if (hp) (void)hipHostFree(hp);
         }
     }
+    // work items of the streaming kernels dealt by ticket (gv_mfma.h).  GV_DEAL=0 (development, read per context so that one process can
+    // hold both kinds): the block-index mapping.  GV_DEAL_SPARE=<d> (development): spare workgroups = items / d instead of items / 8
+    {
+        const char* dl = getenv("GV_DEAL");
+        if (!dl || atoi(dl) != 0) {
+            if ((e = hipMalloc(&c->deal.ctr, sizeof(uint32_t))) != hipSuccess) return bail("hipMalloc", e);
+            if ((e = hipMemset(c->deal.ctr, 0, sizeof(uint32_t))) != hipSuccess) return bail("hipMemset", e);
+            c->deal.stream = c->stream;
+            c->deal.base = 0;
+            if (const char* sp = getenv("GV_DEAL_SPARE")) c->deal.spare_div = atoi(sp) < 0 ? 0 : atoi(sp);
+            c->plan.deal = &c->deal;
+        }
+    }
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)
@@ -1404,6 +1446,7 @@ static void gv_destroy_locked(gv_ctx* c) {
     if (c->host_pin) (void)hipHostFree(c->host_pin);
     if (c->mbox) (void)hipHostFree(c->mbox);
     if (c->pub_counter) (void)hipFree(c->pub_counter);
+    if (c->deal.ctr) (void)hipFree(c->deal.ctr);
     for (double* q : c->loop_buf) if (q) (void)hipFree(q);
     if (c->xfer_pin) (void)hipHostFree(c->xfer_pin);
     for (hipEvent_t e : c->xfer_ev) if (e) (void)hipEventDestroy(e);

@@ -48,6 +48,9 @@ struct gv_ctx {
     bool want_tile = false;                      // the MFMA family's layout: false = two stripe sets, true = one tile layout
     bool have_raw = false, have_stripes = false;
     gvm::Plan plan;
+    // ticket counter of the streaming kernels (gv_mfma.h, gvm::Deal): allocated by gv_create unless GV_DEAL=0 (development: the
+    // block-index mapping from the same binary), handed to the plan by plan_decomps; every streaming launch goes to `stream`
+    gvm::Deal deal;
     // candidate work decompositions of the ATx-side / Ax-side streaming kernels (default first) and whether the on-device
     // pick among them has been made (autotune_ks)
     std::vector<gvm::Decomp> dec_cand_m, dec_cand_n;

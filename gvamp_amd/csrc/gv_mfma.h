@@ -20,14 +20,17 @@ struct Decomp {
                          // LDS to that end).  Fewer resident workgroups keep fewer K ranges and rows open at a time: the two-vector
                          // Ax of the 8-GPU shard on the tile layout streams 4 % faster with 512 than with 768 (profiles/r6_launch_dist_shard.txt),
                          // the 100 GB headline kernels 2-6 % slower -- one more thing the tuner measures
-    float xskew = 0.f;   // uniform split, ks >= 2: workgroups are dealt to the eight XCDs round-robin by block index and four of the XCDs
-                         // of an MI355X -- those that get the ODD block indices (hardware XCC ids 0, 2, 4, 6) -- finish equal shares
-                         // 4-6 % earlier than the other four (per-workgroup clocks, every box and round: profiles/r6_shard_wgtime.txt),
-                         // then idle for the rest of the launch.  The segments of a quad alternate between the two kinds; those with an
-                         // odd block index are made 1 + xskew, the others 1 - xskew times their nominal length.  Headline Ax: 15.09 ->
-                         // 14.90 ms at 0.025 (profiles/r6_xcd_skew.txt); the opposite sign loses as much.
+    float xskew = 0.f;   // uniform split, ks >= 2, block-index mapping only (GV_DEAL=0): workgroups are dealt to the eight XCDs round-robin by
+                         // block index and four of the XCDs of an MI355X finish equal shares 4-6 % earlier than the other four (per-workgroup
+                         // clocks: profiles/r6_shard_wgtime.txt), then idle for the rest of the launch.  On the boxes measured the early ones got
+                         // the ODD block indices; WHICH hardware XCC ids those are changes with the box and the allocation (profiles/r6_xcd_skew.txt).
+                         // The segments of a quad alternate between the two kinds; those with an odd block index are made 1 + xskew, the others
+                         // 1 - xskew times their nominal length.  Headline Ax: 15.09 -> 14.90 ms at 0.025 on one box; the opposite sign loses as
+                         // much.  Ignored when work items are dealt by ticket (Deal below): an XCD that is ahead then simply draws more items.
 };
-// dynamic LDS bytes that cap a CU at d.occ workgroups of the streaming kernels (160 KiB per CU, <= 8 KiB static per workgroup)
+// dynamic LDS bytes that cap a CU at d.occ workgroups of the streaming kernels (160 KiB of LDS per CU; static LDS per workgroup: 8 KiB, or
+// 4 KiB on the Ax side of the tile layout, 16 KiB in k_mfma_matvec MODE 3 / 6, plus 16 bytes for the ticket slot:
+// 2 x (60000 + 16400) <= 163840 < 3 x (60000 + 4112).  A part with less LDS per CU could not launch occ = 2 at all.)
 inline unsigned lds_pad_of(const Decomp& d) { return d.occ == 2 ? 60000u : 0u; }
 
 // workgroups of a launch over nq quads x nkb K-blocks, and pieces (int32 partial sums per row) the epilogues add up at most
@@ -38,6 +41,121 @@ inline int64_t grid_of(const Decomp& d, int64_t nq, int64_t nkb) {
     return piv + ((nq - piv) * nkb + d.skL - 1) / d.skL;
 }
 inline int64_t pieces_max(const Decomp& d, int64_t nkb) { return d.skL > 0 ? (nkb + d.skL - 1) / d.skL + 1 : d.ks; }
+
+// ---- work items and how they are handed out ---------------------------------------------------------------------------
+// A launch over nq quads x nkb K-blocks has grid_of() work ITEMS (one K-segment of one quad, one whole quad, or one balanced range
+// of cells).  Which item a workgroup runs is decided in ONE place, item_cells(), shared by the kernels and the host (tests).
+//   block-index mapping (ticket == NULL, GV_DEAL=0): item = blockIdx.x, the grid has exactly `items` workgroups, and the remainder
+//       ranges of a hybrid decomposition come first;
+//   dealt (Deal below): a workgroup draws t with one relaxed agent-scope atomic add and runs item t.  Items are numbered BIG FIRST
+//       (uniform split: segment-major, segment lengths sorted longest first; balanced / hybrid: the whole quads, then the remainder
+//       ranges), and the grid has SPARE workgroups: blocks go round-robin over the eight XCDs, so with grid == items an XCD that frees
+//       its slots early could never run more than items / 8 of them.  With spare workgroups it starts them while tickets remain and takes
+//       more than an eighth; a workgroup whose ticket is past the last item returns at once.  No workgroup ever waits for another, and
+//       every item writes the partial-sum slots it always wrote: output is bit-identical by construction.
+#if defined(__HIPCC__)
+#define GV_HD __host__ __device__ __forceinline__
+#else
+#define GV_HD inline
+#endif
+// K-block boundaries of the segments of a uniform split (b[c][0] = 0 ... b[c][ks] = nkb; ks <= GV_MAX_KS).  [c]: the boundaries of a quad of
+// parity c = q & 1 -- they differ only under Decomp::xskew with the block-index mapping
+constexpr int GV_MAX_KS = 64;
+struct KBounds { uint32_t b[2][GV_MAX_KS + 1]; };
+
+struct Item {
+    uint32_t u, uend;    // cells [u, uend) of the quad-major linearisation u = quad * nkb + K-block
+    uint32_t r;          // uniform split: the segment number (= the piece the partial sums go to); balanced: index of the remainder range
+};
+// item t of `items` (t < items).  sk: balanced / hybrid (skL cells per range, the first piv quads whole); big_first: the dealt numbering
+GV_HD Item item_cells(bool sk, bool big_first, uint32_t t, uint32_t items, uint32_t nq, uint32_t nkb, uint32_t skL, uint32_t piv,
+                      const KBounds& kb) {
+    Item it;
+    if (sk) {
+        const uint32_t U = nq * nkb, nrem = items - piv;      // ranges of the balanced remainder (piv == 0: all of them)
+        const bool whole = big_first ? t < piv : t >= nrem;
+        if (whole) {                                          // one whole quad
+            it.r = 0;
+            it.u = (big_first ? t : t - nrem) * nkb;
+            it.uend = it.u + nkb;
+        } else {
+            it.r = big_first ? t - piv : t;
+            it.u = piv * nkb + it.r * skL;
+            it.uend = it.u + skL < U ? it.u + skL : U;
+        }
+    } else {
+        // segment ks0 of quad q0, segment-major.  With an even number of quads the quads are rotated by one per segment row, so that under the
+        // block-index mapping a quad's segments alternate between odd and even block indices either way (Decomp::xskew)
+        const uint32_t ks0 = t / nq;
+        uint32_t q0 = t % nq;
+        if (!(nq & 1)) q0 = (q0 + ks0) % nq;
+        it.r = ks0;
+        it.u = q0 * nkb + kb.b[q0 & 1][ks0];
+        it.uend = q0 * nkb + kb.b[q0 & 1][ks0 + 1];
+    }
+    return it;
+}
+// segment boundaries of a uniform split.  deal: the segments are sorted longest first and xskew is ignored
+inline KBounds make_bounds(const Decomp& d, int64_t nkb, bool deal) {
+    KBounds kb{};
+    if (d.skL <= 0) {
+        const int ks = d.ks < 1 ? 1 : (d.ks > GV_MAX_KS ? GV_MAX_KS : d.ks);
+        // cumulative segment lengths, every segment at least one K-block (ks <= nkb): geometric (big first), tapered, or equal;
+        // then, per quad parity c, the segments whose workgroup has an ODD block index ((c + j) odd) stretched by 1 + xskew, the others
+        // shrunk by 1 - xskew
+        const double xskew = deal ? 0.0 : (double)d.xskew;
+        double w[GV_MAX_KS];
+        for (int j = 0; j < ks; j++) {
+            if (d.geo > 0.f && ks > 1) w[j] = j ? w[j - 1] * (double)d.geo : 1.0;
+            else w[j] = ks > 1 ? 1.0 + (double)d.taper * (double)(ks - 1 - 2 * j) / (double)(ks - 1) : 1.0;
+        }
+        for (int c = 0; c < 2; c++) {
+            double tot = 0.0, acc = 0.0, v[GV_MAX_KS];
+            for (int j = 0; j < ks; j++) {
+                v[j] = w[j] * (((c + j) & 1) ? 1.0 + xskew : 1.0 - xskew);      // (c + j) odd <-> odd block index
+                tot += v[j];
+            }
+            kb.b[c][0] = 0;
+            for (int j = 0; j < ks; j++) {
+                acc += v[j];
+                int64_t e = (int64_t)((double)nkb * acc / tot + 0.5);
+                const int64_t lo = (int64_t)kb.b[c][j] + 1, hi = nkb - (ks - 1 - j);
+                e = e < lo ? lo : (e > hi ? hi : e);
+                kb.b[c][j + 1] = (uint32_t)e;
+            }
+            kb.b[c][ks] = (uint32_t)nkb;
+            if (deal) {      // rounding leaves lengths that wobble by one K-block: longest first (insertion sort, ks <= 64)
+                uint32_t len[GV_MAX_KS];
+                for (int j = 0; j < ks; j++) len[j] = kb.b[c][j + 1] - kb.b[c][j];
+                for (int j = 1; j < ks; j++) {
+                    const uint32_t x = len[j];
+                    int i = j - 1;
+                    for (; i >= 0 && len[i] < x; i--) len[i + 1] = len[i];
+                    len[i + 1] = x;
+                }
+                for (int j = 0; j < ks; j++) kb.b[c][j + 1] = kb.b[c][j] + len[j];
+            }
+        }
+    }
+    return kb;
+}
+// The ticket counter of a context: one uint32 in device memory that is NEVER reset.  Launch k is handed base = the sum of the grid
+// sizes of the launches before it and its workgroups compute t = old - base in unsigned arithmetic (both wrap together).  Every
+// workgroup of every dealt launch draws exactly once -- before the `go` test of a device-resident CG step -- so the host's sum stays
+// right when a pass is skipped on the device.  The launches that share a counter must run one after the other: they all go to `stream`
+// (the context's stream); a launch on any other stream falls back to the block-index mapping.
+struct Deal {
+    uint32_t* ctr = nullptr;
+    hipStream_t stream = nullptr;
+    uint32_t base = 0;
+    int spare_div = 8;       // spare workgroups = items / spare_div, at least 8 (GV_DEAL_SPARE, development)
+};
+// workgroups of a dealt launch: items + spare, rounded up so that every XCD gets the same number
+inline int64_t deal_grid(int64_t items, int spare_div) {
+    int64_t spare = spare_div > 0 ? items / spare_div : 0;
+    if (spare < 8) spare = 8;
+    return (items + spare + 7) / 8 * 8;
+}
 
 // ---- device-resident CG (gv_solvers.hip, cg_run_device) ------------------------------------------------------------
 // State block of one CG system in device memory (doubles).  The kernels of a CG step read alpha / beta / the activity
@@ -98,6 +216,7 @@ struct Plan {
     int32_t* partial = nullptr;     // per-(K-split, plane, row) digit sums
     size_t partial_bytes = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // when set: recorded around the matvec kernel launch (roofline timing)
+    Deal* deal = nullptr;           // != NULL: work items are dealt by ticket (owned by the context; copies of a Plan share it)
 };
 
 void stripes_m_chunk(hipStream_t s, const uint8_t* raw, int64_t pitch, int64_t mc, int64_t N, void* stripes,

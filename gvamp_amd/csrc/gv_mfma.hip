@@ -554,8 +554,9 @@ __device__ __forceinline__ void wg_barrier_lds() {
 //       workgroup over the whole K range (uniform, ks = 1: co-resident workgroups walk K in step, a digit block is fetched once
 //       per XCD), and only the remaining nq - piv quads are cut into balanced ranges of skL cells.  For shards whose quad count
 //       is just above a multiple of 768: neither the ragged last round of a uniform split nor the scattered K offsets of a
-//       fully balanced grid (1.13 x HBM over-fetch of digit blocks on the two-vector Ax at N = 400k x M = 125k).  The
-//       remainder's workgroups take the first block indices (they are dispatched first and are short).
+//       fully balanced grid (1.13 x HBM over-fetch of digit blocks on the two-vector Ax at N = 400k x M = 125k).
+// Which workgroup runs which item (by block index, or by a ticket with the big items first and spare workgroups): gv_mfma.h, item_cells.
+// Under the block-index mapping the remainder's ranges take the first block indices, under the dealt one the whole quads are drawn first.
 __device__ __forceinline__ int pieces_of(int64_t row, int ksplit, int64_t nkb, int64_t skL, int qshift = 8, int64_t piv = 0) {
     if (skL <= 0) return ksplit;
     int64_t q = row >> qshift;   // rows per quad of row groups: 256 (64-row groups) or 1024 (tile layout, Ax side)
@@ -567,11 +568,18 @@ __device__ __forceinline__ int pieces_of(int64_t row, int ksplit, int64_t nkb, i
 #ifdef GV_WGTIME
 __device__ unsigned long long g_wgt[4 * 16384];   // development build only: per-workgroup start / end clock, XCC id, CU id
 #endif
-// K-block boundaries of the segments of a uniform split (b[0] = 0 ... b[ks] = nkb; ks <= GV_MAX_KS)
-constexpr int GV_MAX_KS = 64;
-// [c]: the boundaries of a quad of parity c = q & 1 (Decomp::xskew: segment j of quad q is run by a workgroup whose block index has
-// the parity of q + j; odd block indices land on the four XCDs that stream 4-6 % faster -- their segments are made that much longer)
-struct KBounds { uint32_t b[2][GV_MAX_KS + 1]; };
+using gvm::KBounds;      // segment boundaries of a uniform split, and the item numbering: gv_mfma.h (item_cells, make_bounds)
+
+// The work item of this workgroup: its block index, or -- ticket != NULL -- a ticket drawn with ONE relaxed agent-scope atomic add by
+// one thread and broadcast through LDS.  Every workgroup draws, and draws before anything else (the host counts on it: gvm::Deal).
+// Nothing here or later waits for another workgroup: a wrong mapping could give a wrong number, never a hang.
+__device__ __forceinline__ uint32_t draw_item(uint32_t* __restrict__ ticket, uint32_t tbase) {
+    if (!ticket) return blockIdx.x;
+    __shared__ uint32_t s_ticket;
+    if (threadIdx.x == 0) s_ticket = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - tbase;
+    __syncthreads();
+    return __builtin_amdgcn_readfirstlane(s_ticket);
+}
 
 // GO: the instantiation the device-resident CG loop launches (cg_run_device) -- it alone carries the `go` test, and it shows up
 // under its own name in kernel traces, so that the ~3 us launches of a dropped CG step do not dilute the statistics of the
@@ -580,9 +588,12 @@ template <int MODE, bool SK, bool GO>
 __global__ __launch_bounds__(256, 3) void k_mfma_matvec(const u32x4* __restrict__ stripes, const u32x4* __restrict__ dig0,
                                                  const u32x4* __restrict__ dig1, int64_t nrg, int64_t nkb, int ksplit,
                                                  int64_t skL, int prio, KBounds kbnd, int32_t* __restrict__ partial,
-                                                 const int* __restrict__ go, uint32_t piv) {
+                                                 const int* __restrict__ go, uint32_t piv, uint32_t* __restrict__ ticket,
+                                                 uint32_t tbase, uint32_t items) {
+    const uint32_t item = draw_item(ticket, tbase);
     // device-resident CG: a step enqueued before the host knew that every system had converged is dropped here
     if (GO && __builtin_nontemporal_load(go) == 0) return;
+    if (item >= items) return;       // a spare workgroup: every item has been taken
     constexpr int KBS = (MODE == 0) ? 128 : 256;   // u32x4 per K-block of one digit buffer
     constexpr int SS = MD<MODE>::two_ax ? 512 : 256;    // u32x4 per LDS stage (MODE 0 uses the first 128; the rest is a dummy target)
     __shared__ u32x4 sB[2][SS];
@@ -593,34 +604,10 @@ __global__ __launch_bounds__(256, 3) void k_mfma_matvec(const u32x4* __restrict_
     const int dofs = (MODE == 0) ? (tid & 127) : tid;   // MODE 0: the block is 128 pieces; threads 128..255 copy pieces 0..127
     // again into the unused half of the stage, so that the copy has no divergent branch (the loop body stays one basic block)
     // cells of this workgroup: uniform over the workgroup, kept in SGPRs (32-bit: nq * nkb = M N / 65536 cells)
-    uint32_t u, uend;
     const uint32_t nkb32 = (uint32_t)nkb, skL32 = (uint32_t)skL;
-    if (SK) {
-        const uint32_t U = (uint32_t)nq * nkb32;
-        const uint32_t nrem = gridDim.x - piv;      // hybrid: workgroups of the balanced remainder (piv == 0: all of them)
-        if (blockIdx.x < nrem) {
-            u = piv * nkb32 + blockIdx.x * skL32;
-            uend = u + skL32 < U ? u + skL32 : U;
-        } else {                                    // one whole quad
-            u = (blockIdx.x - nrem) * nkb32;
-            uend = u + nkb32;
-        }
-    } else {
-        // workgroups are dealt to the eight XCDs round-robin by block index, so the parity of b decides whether a workgroup runs on one of
-        // the four faster or the four slower XCDs.  Segment ks0 of quad q0: with an odd number of quads b = q0 + nq ks0 has the parity
-        // of q0 + ks0; with an even one the quads are rotated by one per segment row so that it has, too -- a quad's segments
-        // alternate between the two kinds of XCD either way
-        const uint32_t ks0 = blockIdx.x / (uint32_t)nq;
-        uint32_t q0 = blockIdx.x % (uint32_t)nq;
-        if (!(nq & 1)) q0 = (q0 + ks0) % (uint32_t)nq;
-        u = q0 * nkb32 + kbnd.b[q0 & 1][ks0];
-        uend = q0 * nkb32 + kbnd.b[q0 & 1][ks0 + 1];
-    }
-    // Wave priority by remaining work (prio != 0).  The instruction arbiter favours the oldest wave of a SIMD, so the three
-    // workgroups of a CU finish one after the other (measured: 245 / 320 / 385 us for equal work) and a launch ends on a
-    // long, thinly occupied tail; a workgroup that is ahead of its neighbours now yields to them.  Four levels, lowered at
-    // each quarter of the workgroup's cells.  Whether it pays depends on the shape (many short rounds: yes; few long
-    // rounds: no), so it is one of the things autotune_ks measures.
+    const gvm::Item it = gvm::item_cells(SK, ticket != nullptr, item, items, (uint32_t)nq, nkb32, skL32, piv, kbnd);
+    uint32_t u = it.u;
+    const uint32_t uend = it.uend;
     const uint32_t p_quarter = (uend - u + 3) / 4;
     uint32_t p_thr = prio ? u + p_quarter : 0xffffffffu, p_lvl = 3;
     if (prio) __builtin_amdgcn_s_setprio(3);
@@ -635,7 +622,7 @@ __global__ __launch_bounds__(256, 3) void k_mfma_matvec(const u32x4* __restrict_
         unsigned xcc, hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        g_wgt[4 * blockIdx.x + 2] = (xcc & 0xf) | ((unsigned long long)(uend - u) << 8);     // XCC id | cells of this workgroup
+        g_wgt[4 * blockIdx.x + 2] = (xcc & 0xf) | ((unsigned long long)(uend - u) << 8) | ((unsigned long long)item << 40);   // XCC id | cells | item
         g_wgt[4 * blockIdx.x + 3] = hw;
     }
 #endif
@@ -645,8 +632,7 @@ __global__ __launch_bounds__(256, 3) void k_mfma_matvec(const u32x4* __restrict_
     const int64_t q = q32, kb0 = u - q32 * nkb32;
     const uint32_t seg = nkb32 - (uint32_t)kb0 < uend - u ? nkb32 - (uint32_t)kb0 : uend - u;   // to the end of the quad or of the range
     const int64_t nsteps = seg;
-    const int ks = SK ? (q32 < piv ? 0 : (int)__builtin_amdgcn_readfirstlane(blockIdx.x - ((q32 - piv) * nkb32) / skL32))
-                      : (int)(blockIdx.x / (uint32_t)nq);
+    const int ks = SK ? (q32 < piv ? 0 : (int)__builtin_amdgcn_readfirstlane(it.r - ((q32 - piv) * nkb32) / skL32)) : (int)it.r;
     const uint32_t useg0 = u;   // first cell of this segment
     u += seg;
     int64_t rg = q * 4 + (tid >> 6);
@@ -904,9 +890,12 @@ template <int DIR, int MODE, bool SK, bool GO>
 __global__ __launch_bounds__(256, 3) void k_mfma_tile(const u32x4* __restrict__ stripes, const u32x4* __restrict__ dig0,
                                                       const u32x4* __restrict__ dig1, int64_t nrg, int64_t nkb, int ksplit,
                                                       int64_t skL, int prio, KBounds kbnd, int32_t* __restrict__ partial, int nv,
-                                                      const int* __restrict__ go, int64_t rstride, uint32_t piv) {
+                                                      const int* __restrict__ go, int64_t rstride, uint32_t piv,
+                                                      uint32_t* __restrict__ ticket, uint32_t tbase, uint32_t items) {
     // rstride (DIR 1): row groups per K-step in memory -- nrg, or more when this launch covers a sub-range of the row groups
+    const uint32_t item = draw_item(ticket, tbase);
     if (GO && __builtin_nontemporal_load(go) == 0) return;
+    if (item >= items) return;       // a spare workgroup: every item has been taken
     constexpr int KBS = (DIR == 1) ? 64 : ((MODE == 0) ? 128 : 256);   // u32x4 per K-step of one digit buffer
     constexpr int SS = (DIR == 1) ? 128 : 256;                         // u32x4 per LDS stage
     constexpr int ROWS = (DIR == 1) ? 256 : 64;                        // rows per row group
@@ -919,29 +908,10 @@ __global__ __launch_bounds__(256, 3) void k_mfma_tile(const u32x4* __restrict__ 
     const int dofs = (DIR == 1) ? (tid & 63) : ((MODE == 0) ? (tid & 127) : tid);
     const u32x4* digsel = (DIR == 1 && (tid & 64)) ? dig1 : dig0;
     const int sofs = (DIR == 1) ? (tid & 127) : tid;
-    uint32_t u, uend;
     const uint32_t nkb32 = (uint32_t)nkb, skL32 = (uint32_t)skL;
-    if (SK) {
-        const uint32_t U = (uint32_t)nq * nkb32;
-        const uint32_t nrem = gridDim.x - piv;      // hybrid: workgroups of the balanced remainder (piv == 0: all of them)
-        if (blockIdx.x < nrem) {
-            u = piv * nkb32 + blockIdx.x * skL32;
-            uend = u + skL32 < U ? u + skL32 : U;
-        } else {                                    // one whole quad
-            u = (blockIdx.x - nrem) * nkb32;
-            uend = u + nkb32;
-        }
-    } else {
-        // workgroups are dealt to the eight XCDs round-robin by block index, so the parity of b decides whether a workgroup runs on one of
-        // the four faster or the four slower XCDs.  Segment ks0 of quad q0: with an odd number of quads b = q0 + nq ks0 has the parity
-        // of q0 + ks0; with an even one the quads are rotated by one per segment row so that it has, too -- a quad's segments
-        // alternate between the two kinds of XCD either way
-        const uint32_t ks0 = blockIdx.x / (uint32_t)nq;
-        uint32_t q0 = blockIdx.x % (uint32_t)nq;
-        if (!(nq & 1)) q0 = (q0 + ks0) % (uint32_t)nq;
-        u = q0 * nkb32 + kbnd.b[q0 & 1][ks0];
-        uend = q0 * nkb32 + kbnd.b[q0 & 1][ks0 + 1];
-    }
+    const gvm::Item it = gvm::item_cells(SK, ticket != nullptr, item, items, (uint32_t)nq, nkb32, skL32, piv, kbnd);
+    uint32_t u = it.u;
+    const uint32_t uend = it.uend;
     const uint32_t p_quarter = (uend - u + 3) / 4;
     uint32_t p_thr = prio ? u + p_quarter : 0xffffffffu, p_lvl = 3;
     if (prio) __builtin_amdgcn_s_setprio(3);
@@ -956,7 +926,7 @@ __global__ __launch_bounds__(256, 3) void k_mfma_tile(const u32x4* __restrict__ 
         unsigned xcc, hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        g_wgt[4 * blockIdx.x + 2] = (xcc & 0xf) | ((unsigned long long)(uend - u) << 8);     // XCC id | cells of this workgroup
+        g_wgt[4 * blockIdx.x + 2] = (xcc & 0xf) | ((unsigned long long)(uend - u) << 8) | ((unsigned long long)item << 40);   // XCC id | cells | item
         g_wgt[4 * blockIdx.x + 3] = hw;
     }
 #endif
@@ -968,8 +938,7 @@ __global__ __launch_bounds__(256, 3) void k_mfma_tile(const u32x4* __restrict__ 
     const int64_t q = q32, kb0 = u - q32 * nkb32;
     const uint32_t seg = nkb32 - (uint32_t)kb0 < uend - u ? nkb32 - (uint32_t)kb0 : uend - u;
     const int64_t nsteps = seg;
-    const int ks = SK ? (q32 < piv ? 0 : (int)__builtin_amdgcn_readfirstlane(blockIdx.x - ((q32 - piv) * nkb32) / skL32))
-                      : (int)(blockIdx.x / (uint32_t)nq);
+    const int ks = SK ? (q32 < piv ? 0 : (int)__builtin_amdgcn_readfirstlane(it.r - ((q32 - piv) * nkb32) / skL32)) : (int)it.r;
     const uint32_t useg0 = u;
     u += seg;
     int64_t rg = q * 4 + (tid >> 6);
@@ -1479,22 +1448,33 @@ __global__ __launch_bounds__(256) void k_fin_atx_wide(const int32_t* __restrict_
 inline int nblk(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
 
 // launch of the streaming kernel of one matvec (HIP events around it when the roofline timing is on)
-static KBounds make_bounds(const gvm::Decomp& d, int64_t nkb);
+// grid and ticket arguments of one streaming launch over `items` work items: dealt when the plan carries a ticket counter and the launch
+// goes to the counter's stream (the counter's base advances by the grid, whether or not the device then skips the pass)
+struct DealArgs { int64_t grid; uint32_t* ticket; uint32_t base; };
+static DealArgs deal_args(hipStream_t s, const gvm::Plan& pl, int64_t items) {
+    gvm::Deal* dl = pl.deal;
+    if (!dl || !dl->ctr || dl->stream != s) return {items, nullptr, 0u};
+    const DealArgs a{gvm::deal_grid(items, dl->spare_div), dl->ctr, dl->base};
+    dl->base += (uint32_t)a.grid;
+    return a;
+}
 // the streaming kernel on the tile layout (DIR 0: ATx side, MODE 0 / 2; DIR 1: Ax side, MODE 3 / 4, nv vectors)
 template <int DIR, int MODE>
 void launch_tile(hipStream_t s, const gvm::Plan& pl, const void* dig0, const void* dig1, int64_t nrg, int64_t nkb,
                  const gvm::Decomp& d, int nv, const int* go) {
     if (pl.ev0) (void)hipEventRecord(pl.ev0, s);
     const int64_t nq = (nrg + 3) / 4;
-    const int64_t grid = gvm::grid_of(d, nq, nkb);
-    if (grid <= 0) return;          // an empty shard: nothing to stream (a zero-size grid is an invalid launch)
-    const KBounds kb = make_bounds(d, nkb);
+    const int64_t items = gvm::grid_of(d, nq, nkb);
+    if (items <= 0) return;         // an empty shard: nothing to stream (a zero-size grid is an invalid launch)
+    const DealArgs da = deal_args(s, pl, items);
+    const int64_t grid = da.grid;
+    const KBounds kb = gvm::make_bounds(d, nkb, da.ticket != nullptr);
     const int64_t rstride = pl.rstride_n > 0 ? pl.rstride_n : nrg;
     const unsigned lds_pad = gvm::lds_pad_of(d);     // Decomp::occ: two workgroups per CU instead of three
 #define GV_LAUNCH_T(SKV, GOV)                                                                                              \
     hipLaunchKernelGGL((k_mfma_tile<DIR, MODE, SKV, GOV>), dim3((unsigned)grid), dim3(256), lds_pad, s, (const u32x4*)pl.tiles,     \
                        (const u32x4*)dig0, (const u32x4*)dig1, nrg, nkb, d.ks, d.skL, d.prio, kb, pl.partial, nv, go, rstride, \
-                       (uint32_t)gvm::piv_of(d, nq))
+                       (uint32_t)gvm::piv_of(d, nq), da.ticket, da.base, (uint32_t)items)
     if (MODE >= 4 || !go) {             // (the people-statistics plane and the two-level passes are never part of a device-resident CG step)
         if (d.skL > 0) GV_LAUNCH_T(true, false); else GV_LAUNCH_T(false, false);
     } else if constexpr (MODE < 4) {
@@ -1503,38 +1483,6 @@ void launch_tile(hipStream_t s, const gvm::Plan& pl, const void* dig0, const voi
 #undef GV_LAUNCH_T
     if (pl.ev1) (void)hipEventRecord(pl.ev1, s);
 }
-static KBounds make_bounds(const gvm::Decomp& d, int64_t nkb) {
-    KBounds kb{};
-    if (d.skL <= 0) {
-        const int ks = d.ks < 1 ? 1 : (d.ks > GV_MAX_KS ? GV_MAX_KS : d.ks);
-        // cumulative segment lengths, every segment at least one K-block (ks <= nkb): geometric (big first), tapered, or equal;
-        // then, per quad parity c, the segments whose workgroup has an ODD block index ((c + j) odd: the faster XCDs) stretched by
-        // 1 + xskew, the others shrunk by 1 - xskew
-        double w[GV_MAX_KS];
-        for (int j = 0; j < ks; j++) {
-            if (d.geo > 0.f && ks > 1) w[j] = j ? w[j - 1] * (double)d.geo : 1.0;
-            else w[j] = ks > 1 ? 1.0 + (double)d.taper * (double)(ks - 1 - 2 * j) / (double)(ks - 1) : 1.0;
-        }
-        for (int c = 0; c < 2; c++) {
-            double tot = 0.0, acc = 0.0, v[GV_MAX_KS];
-            for (int j = 0; j < ks; j++) {
-                v[j] = w[j] * (((c + j) & 1) ? 1.0 + (double)d.xskew : 1.0 - (double)d.xskew);      // (c + j) odd <-> odd block index
-                tot += v[j];
-            }
-            kb.b[c][0] = 0;
-            for (int j = 0; j < ks; j++) {
-                acc += v[j];
-                int64_t e = (int64_t)((double)nkb * acc / tot + 0.5);
-                const int64_t lo = (int64_t)kb.b[c][j] + 1, hi = nkb - (ks - 1 - j);
-                e = e < lo ? lo : (e > hi ? hi : e);
-                kb.b[c][j + 1] = (uint32_t)e;
-            }
-            kb.b[c][ks] = (uint32_t)nkb;
-        }
-    }
-    return kb;
-}
-
 template <int MODE>
 void launch_stream(hipStream_t s, const gvm::Plan& pl, const void* stripes, const void* dig0, const void* dig1, int64_t nrg,
                    int64_t nkb, const gvm::Decomp& d, const int* go = nullptr) {
@@ -1549,14 +1497,16 @@ void launch_stream(hipStream_t s, const gvm::Plan& pl, const void* stripes, cons
     }
     if (pl.ev0) (void)hipEventRecord(pl.ev0, s);
     const int64_t nq = (nrg + 3) / 4;
-    const int64_t grid = gvm::grid_of(d, nq, nkb);
-    if (grid <= 0) return;          // an empty shard: nothing to stream (a zero-size grid is an invalid launch)
-    const KBounds kb = make_bounds(d, nkb);
+    const int64_t items = gvm::grid_of(d, nq, nkb);
+    if (items <= 0) return;         // an empty shard: nothing to stream (a zero-size grid is an invalid launch)
+    const DealArgs da = deal_args(s, pl, items);
+    const int64_t grid = da.grid;
+    const KBounds kb = gvm::make_bounds(d, nkb, da.ticket != nullptr);
     const unsigned lds_pad = gvm::lds_pad_of(d);
 #define GV_LAUNCH_MV(SKV, GOV)                                                                                             \
     hipLaunchKernelGGL((k_mfma_matvec<MODE, SKV, GOV>), dim3((unsigned)grid), dim3(256), lds_pad, s, (const u32x4*)stripes,   \
                        (const u32x4*)dig0, (const u32x4*)dig1, nrg, nkb, d.ks, d.skL, d.prio, kb, pl.partial, go,        \
-                       (uint32_t)gvm::piv_of(d, nq))
+                       (uint32_t)gvm::piv_of(d, nq), da.ticket, da.base, (uint32_t)items)
     if (MODE >= 4 || !go) {            // (the people-statistics plane and the two-level passes are never part of a device-resident CG step)
         if (d.skL > 0) GV_LAUNCH_MV(true, false); else GV_LAUNCH_MV(false, false);
     } else if constexpr (MODE < 4) {

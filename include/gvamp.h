@@ -448,7 +448,8 @@ typedef struct {
                               * this) or 2 (the launch reserves LDS to that end: faster on some 12.5 GB shapes, slower at 100 GB) */
     float xcd_skew;          /* ABI 4, uniform split with ks >= 2: segments whose workgroup lands on one of the four faster XCDs of the
                               * part (odd block index) are 1 + xcd_skew, the others 1 - xcd_skew times their nominal length (equal
-                              * shares finish 4-6 % apart on an MI355X); 0 = equal, range -0.2 .. 0.2 */
+                              * shares finish 4-6 % apart on an MI355X); 0 = equal, range -0.2 .. 0.2.  Echoed by gv_get_decomp but
+                              * without effect while work items are dealt by ticket (the default; GV_DEAL=0 takes them by block index) */
 } gv_decomp_info;
 /* Wall time of the last ingest (gv_upload_bed / gv_upload_bed_file / gv_synth_bed), split into allocating the resident
  * layouts (hipMalloc of 100+ GB: the driver maps and wipes the pages; 0 when the buffers were reused) and filling them. */

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 name=$1; shift
 H=$(python3 -c "from gvamp_amd import build; print(build.kernel_src_hash()[:16])")
 O=/tmp/gv_var_$name; mkdir -p $O
-for s in gv_kernels gv_mfma gv_capi gv_solvers; do
+for s in gv_kernels gv_mfma gv_capi gv_solvers gv_dense gv_precond; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -Iinclude -Igvamp_amd/csrc -I/opt/rocm/include \
         "$@" -DGV_KERNEL_SRC_HASH="\"$H\"" -c gvamp_amd/csrc/$s.hip -o $O/$s.o &
 done

@@ -1,11 +1,15 @@
 """Measures the work decompositions of the shapes BASELINE.json names (and the per-GPU shards of the headline job) on this GPU
 and writes gvamp_amd/csrc/gv_tune_builtin.h for the current kernel sources.  Run on an MI355X after the LAST change to
-gv_mfma.hip / gv_mfma.h:   gpurun -- 'python scripts/tune_table.py && cp gvamp_amd/csrc/gv_tune_builtin.h gpurun_out/'
+gv_mfma.hip / gv_mfma.h:   python scripts/tune_table.py [--out FILE]
+The file is rewritten after every (shape, layout), so a run that is cut short leaves the rows it finished; `--shapes N:M,...` restricts
+a run to some shapes and `--append` keeps the rows the shipped table already holds FOR THE CURRENT kernel sources (a table measured in
+several runs).  A shape without a row is simply measured by the library on first contact.
 Each shape is measured `--votes` times in fresh contexts (cache and table off); the distinct picks of a class then meet in a play-off
 inside one context (kernel-alone HIP events, launches interleaved), and the lowest mean is shipped."""
 import argparse
 import collections
 import os
+import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -21,7 +25,33 @@ SHAPES = [(400000, 1000000), (400000, 500000), (400000, 250000), (400000, 125000
 ap = argparse.ArgumentParser()
 ap.add_argument("--votes", type=int, default=3)
 ap.add_argument("--out", default=os.path.join(build.CSRC, "gv_tune_builtin.h"))
+ap.add_argument("--shapes", default="", help="N:M,N:M,... (default: every shape)")
+ap.add_argument("--append", action="store_true", help="keep the rows of the shipped table when its hash is the current one")
 a = ap.parse_args()
+h = build.kernel_src_hash()[:16]
+src = open(os.path.join(build.CSRC, "gv_tune_builtin.h")).read()      # (the head of the shipped file; --out may not exist yet)
+head = src[:src.index("static const char* const GV_BUILTIN_FOR_HASH")]
+kept = []
+if a.append and 'GV_BUILTIN_FOR_HASH = "%s"' % h in src:
+    kept = [ln for ln in src.splitlines() if re.match(r"    \{\d+, \d+, [01], ", ln)]
+if a.shapes:
+    SHAPES = [tuple(int(v) for v in t.split(":")) for t in a.shapes.split(",")]
+
+
+def write_table(rows):
+    body = 'static const char* const GV_BUILTIN_FOR_HASH = "%s";\nstatic const BuiltinPick GV_BUILTIN_PICKS[] = {\n' % h
+    done = {(N, M, lay) for N, M, lay, _ in rows}
+    for ln in kept:
+        N, M, lay = (int(v) for v in re.match(r"    \{(\d+), (\d+), ([01]), ", ln).groups())
+        if (N, M, lay) not in done:
+            body += ln + "\n"
+    for N, M, lay, picks in rows:
+        ds = ", ".join("{%d, %d, %d, %d, %.2ff, %.2ff, %d, %.3ff}" % (ks, skl, piv, prio, taper, geo, occ, xs) for ks, skl, piv, prio, taper, geo, occ, xs in picks)
+        body += "    {%d, %d, %d, {%s}},\n" % (N, M, lay, ds)
+    body += "};\n}  // namespace gvi\n"
+    open(a.out, "w").write(head + body)
+
+
 rows = []
 for N, M in SHAPES:
     for layout in (1, 2):
@@ -89,13 +119,5 @@ for N, M in SHAPES:
             playoff = [playoff[[2, 0, 3, 1].index(k)] for k in range(4)]
         print(N, M, layout, picks, [dict(v) for v in votes], "play-off (ms):", playoff, flush=True)
         rows.append((N, M, layout - 1, picks))
-h = build.kernel_src_hash()[:16]
-src = open(os.path.join(build.CSRC, "gv_tune_builtin.h")).read()      # (the head of the shipped file; --out may not exist yet)
-head = src[:src.index("static const char* const GV_BUILTIN_FOR_HASH")]
-body = 'static const char* const GV_BUILTIN_FOR_HASH = "%s";\nstatic const BuiltinPick GV_BUILTIN_PICKS[] = {\n' % h
-for N, M, lay, picks in rows:
-    ds = ", ".join("{%d, %d, %d, %d, %.2ff, %.2ff, %d, %.3ff}" % (ks, skl, piv, prio, taper, geo, occ, xs) for ks, skl, piv, prio, taper, geo, occ, xs in picks)
-    body += "    {%d, %d, %d, {%s}},\n" % (N, M, lay, ds)
-body += "};\n}  // namespace gvi\n"
-open(a.out, "w").write(head + body)
+        write_table(rows)
 print("wrote", a.out, "for kernel sources", h)

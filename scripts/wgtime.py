@@ -69,7 +69,7 @@ with capi.Shard(N, M) as sh:
     t0 = a[:, 0].min()
     st, en = (a[:, 0] - t0) / 100.0, (a[:, 1] - t0) / 100.0          # wall_clock64: 100 MHz -> us
     dur = en - st
-    xcc, cells = a[:, 2] & 0xf, a[:, 2] >> 8
+    xcc, cells, item = a[:, 2] & 0xf, (a[:, 2] >> 8) & 0xffffffff, a[:, 2] >> 40      # (item: the work item the workgroup ran -- its ticket)
     blk = np.nonzero(np.frombuffer(buf, dtype=np.uint64).reshape(n, 4)[:, 1] > 0)[0]
     tab = {int(r): sorted(set(int(v) for v in xcc[blk % 8 == r])) for r in range(8)}
     print("block index mod 8 -> hardware XCC id (HW_REG_XCC_ID): %s" % ", ".join("%d -> %s" % (r, "/".join(map(str, tab[r]))) for r in range(8)))
@@ -121,6 +121,13 @@ with capi.Shard(N, M) as sh:
         rest = order[peak:]
         print("later workgroups: %d, dur p10 %.1f p50 %.1f p90 %.1f; bytes/us per workgroup p50: round 1 %.1f, later %.1f" % (
             len(rest), *np.percentile(dur[rest], [10, 50, 90]), np.median(rate[r1]), np.median(rate[rest])))
+    nblk = int(blk.max()) + 1
+    print("work items %d (last item drawn by block %d of >= %d launched; blocks whose ticket was past the last item leave no stamp); "
+          "last 5 %% of the items: dur p50 %.1f us, cells p50 %d" % (len(a), int(blk[np.argmax(item)]), nblk,
+          np.median(dur[item >= np.percentile(item, 95)]), int(np.median(cells[item >= np.percentile(item, 95)]))))
+    ends = [en[xcc == k].max() for k in range(8) if (xcc == k).any()]
+    print("per-XCD last ends: spread %.1f us (min %.1f, mean %.1f, max %.1f); launch end - mean of the per-XCD ends: %.1f us" % (
+        max(ends) - min(ends), min(ends), float(np.mean(ends)), max(ends), max(ends) - float(np.mean(ends))))
     for k in range(8):
         m = xcc == k
         if m.any():
