@@ -290,7 +290,8 @@ int factor(hipStream_t s, const double* gram, int W, int64_t S, int64_t M, doubl
 void apply(hipStream_t s, const double* inv, int W, int64_t S, int64_t M, const double* r, double* z);
 }  // namespace gvp
 
-// ---- internals shared by the translation units of the C ABI (gv_capi.hip, gv_solvers.hip) ------------------------------
+// ---- internals shared by the translation units of the C ABI: gv_capi.hip (context, vectors, scalar mailbox), gv_comm.hip,
+// gv_xfer.hip, gv_tune.hip, gv_matvec.hip, gv_ingest.hip, gv_stats.hip, gv_solvers.hip, gv_precond.hip ----------------------
 namespace gvi {
 int fail(gv_ctx* c, const char* fmt, ...);
 int vec_new(gv_ctx* c, int space, gv_vec** out);
@@ -308,18 +309,31 @@ int comm_allreduce(gv_ctx* c, double* dev, size_t n);
 int comm_allreduce_on(gv_ctx* c, double* dev, size_t n, hipStream_t stream);
 int to_host(gv_ctx* c, void* dst, const void* src_dev, size_t nbytes);
 int to_device(gv_ctx* c, void* dst_dev, const void* src, size_t nbytes, bool sync = true);
-// data::Ax / data::ATx (and their two-vector forms) on device pointers, in the kernel family of the context
-// (cg: the slots of the pass that belong to a CG system with device-resident scalars -- gvm::CgHook)
-int ax_device(gv_ctx* c, const double* x, double* out, const gvm::CgHook* cg = nullptr);
-int atx_device(gv_ctx* c, const double* p, double* out, const double* addx = nullptr, double tau = 1.0, double gam2 = 0.0,
-               const gvm::CgHook* cg = nullptr);
-int ax2_device(gv_ctx* c, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg = nullptr);
-int atx2_device(gv_ctx* c, const double* pa, const double* pb, double* outa, double* outb, const double* addxa = nullptr,
-                const double* addxb = nullptr, double tau = 1.0, double gam2 = 0.0, const gvm::CgHook* cg = nullptr);
+// data::Ax / data::ATx on device pointers, nv = 1 or 2 vectors, in the kernel family of the context (gv_matvec.hip)
+// (cg: the slots of the pass that belong to a CG system with device-resident scalars -- gvm::CgHook; kernel mode 1 only)
+int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg);
+int atx_pass(gv_ctx* c, int nv, const double* pa, const double* pb, double* outa, double* outb, const double* addxa,
+             const double* addxb, double tau, double gam2, const gvm::CgHook* cg);
+inline int ax_device(gv_ctx* c, const double* x, double* out, const gvm::CgHook* cg = nullptr) {
+    return ax_pass(c, 1, x, nullptr, out, nullptr, cg);
+}
+inline int atx_device(gv_ctx* c, const double* p, double* out, const double* addx = nullptr, double tau = 1.0, double gam2 = 0.0,
+                      const gvm::CgHook* cg = nullptr) {
+    return atx_pass(c, 1, p, nullptr, out, nullptr, addx, nullptr, tau, gam2, cg);
+}
+inline int ax2_device(gv_ctx* c, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg = nullptr) {
+    return ax_pass(c, 2, xa, xb, outa, outb, cg);
+}
+inline int atx2_device(gv_ctx* c, const double* pa, const double* pb, double* outa, double* outb, const double* addxa = nullptr,
+                       const double* addxb = nullptr, double tau = 1.0, double gam2 = 0.0, const gvm::CgHook* cg = nullptr) {
+    return atx_pass(c, 2, pa, pb, outa, outb, addxa, addxb, tau, gam2, cg);
+}
 int lmmse_device(gv_ctx* c, const double* v, double tau, double gam2, double* out);
 bool use_overlap(const gv_ctx* c);    // data::Ax cut into chunks whose exchange runs on the side stream (GV_OVERLAP)
 int ax_overlapped(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg);
 int autotune_ks(gv_ctx* c);     // picks the work decompositions of the streaming kernels (once per shard)
+int plan_decomps(gv_ctx* c);    // geometry and candidate decompositions for the layout that will be built (gv_set_dims, ingest)
+void ev_resolve(gv_ctx* c);     // timing == 2: the pending event pairs into the counters
 // kind 1 of gv_set_cg_precond: Grams built and (tau, gam2) factorised, ready for pc_apply (error when that cannot be)
 int pc_prepare(gv_ctx* c, double tau, double gam2);
 void pc_apply(gv_ctx* c, const double* r, double* z);

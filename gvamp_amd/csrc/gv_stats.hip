@@ -1,0 +1,232 @@
+// gv_stats.hip -- statistics over the resident dataset: the phenotype mask, marker and people statistics, and the per-marker
+// p-values of data::pvals_calc / pvals_calc_LOCO.
+#include <cmath>
+#include <cstring>
+
+#include "gv_internal.h"
+
+using namespace gvi;
+
+extern "C" {
+
+int gv_set_mask(gv_ctx* c, const uint8_t* mask4, int64_t nonas) {
+    NEED(c, c->N > 0, "gv_set_mask: gv_set_dims must be called first");
+    const int64_t P4 = c->pitch / 4;
+    std::vector<uint32_t> m2(P4, 0u);
+    for (int64_t n = 0; n < c->N; n++) {
+        bool present = mask4 ? ((mask4[n >> 2] >> (n & 3)) & 1u) : true;
+        if (present) m2[n >> 4] |= 3u << (2 * (n & 15));
+    }
+    if (!c->mask2) HIPCHK(c, hipMalloc(&c->mask2, sizeof(uint32_t) * P4));
+    HIPCHK(c, hipMemcpyAsync(c->mask2, m2.data(), sizeof(uint32_t) * P4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->nonas = nonas;
+    c->have_stats = false;
+    pc_invalidate(c, false);
+    return 0;
+}
+
+int gv_marker_stats(gv_ctx* c, double alpha_scale) {
+    pc_invalidate(c, false);
+    if (c->have_dense) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
+        NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
+        gvd::stats(c->stream, c->dense, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale, c->mave, c->msig);
+        c->alpha_scale = alpha_scale;
+        KCHK(c);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->have_stats = true;
+        return 0;
+    }
+    NEED(c, (c->have_raw || c->have_stripes) && c->mask2, "gv_marker_stats: bed and mask must be set first");
+    if (c->have_stripes && c->plan.layout == 1 && (c->kernel_mode != 0 || !c->have_raw))
+        gvm::stats_from_tiles(c->stream, c->plan.tiles, c->mask2, c->M, c->plan.nrg_m, c->plan.nkb_m, c->pitch / 4,
+                              (double)c->nonas, alpha_scale, c->mave, c->msig, c->counts);
+    else if (c->have_stripes && (c->kernel_mode != 0 || !c->have_raw))
+        gvm::stats_from_stripes(c->stream, c->plan.stripes_m, c->mask2, c->M, c->plan.nkb_m, c->pitch / 4,
+                                (double)c->nonas, alpha_scale, c->mave, c->msig, c->counts);
+    else
+        gvk::marker_stats(c->stream, c->bed, c->mask2, c->M, c->pitch, (double)c->nonas, alpha_scale, c->mave, c->msig,
+                          c->counts);
+    c->alpha_scale = alpha_scale;
+    KCHK(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_stats = true;
+    return 0;
+}
+
+int gv_get_marker_stats(gv_ctx* c, double* mave, double* msig) {
+    NEED(c, c->have_stats, "gv_get_marker_stats: gv_marker_stats has not run");
+    HIPCHK(c, hipMemcpyAsync(mave, c->mave, sizeof(double) * c->M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(msig, c->msig, sizeof(double) * c->M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- --use-XXT-denoiser 1: LMMSE through CG in N-space (denoiserXXT.cpp), matrix-free ------------------------------
+// data::compute_people_statistics (data.cpp:558-716): three table passes of the fp64 Ax kernel over the raw rows.
+int gv_people_stats(gv_ctx* c, double* mave_people, double* msig_people, double* numb_people) {
+    NEED(c, !c->have_dense, "gv_people_stats: not available for methylation data (the reference's meth branch of "
+                            "compute_people_statistics, data.cpp:633-672, never reduces or finalises its sums)");
+    NEED(c, c->have_stats && c->mask2, "gv_people_stats: marker statistics must be computed first");
+    const bool from_stripes = c->have_stripes && (c->kernel_mode != 0 || !c->have_raw);
+    NEED(c, c->have_raw || from_stripes, "gv_people_stats: no genotype layout resident");
+    if (ensure_work(c)) return 1;
+    for (gv_vec** v : {&c->mave_p, &c->msig_p, &c->numb_p})
+        if (!*v && vec_new(c, GV_SPACE_N, v)) return 1;
+    gv_vec* dst[3] = {c->mave_p, c->numb_p, c->msig_p};   // kinds 0 (sum value), 1 (count), 2 (sum value^2)
+    if (from_stripes) {
+        // four passes over stripes_n in exact fixed point: the sum is an Ax of the all-ones vector, the count and the
+        // two halves of the sum of squares have their own operand tables (k_prep_people); the quadratic half reads the
+        // a^2 plane of the codes (MODE 4 of the streaming kernel)
+        hipStream_t s = c->stream;
+        if (c->M == 0) {      // an empty shard adds zeros to the three sums, through the same collectives as its peers
+            for (int kind = 0; kind < 3; kind++) gvk::fill(s, dst[kind]->d, c->npad, 0.0);
+        } else {
+            double* ones = c->cg_d->d;
+            gvk::fill(s, ones, c->M, 1.0);
+            gvm::ax(s, c->plan, ones, c->mave, c->msig, c->mask2, c->npad, 1.0, c->red_partial, c->mave_p->d);
+            gvm::ax_people(s, c->plan, 0, c->mave, c->msig, c->mask2, c->npad, c->red_partial, c->numb_p->d);
+            gvm::ax_people(s, c->plan, 1, c->mave, c->msig, c->mask2, c->npad, c->red_partial, c->msig_p->d);
+            gvm::ax_people(s, c->plan, 2, c->mave, c->msig, c->mask2, c->npad, c->red_partial, c->w_n->d);
+            gvk::axpby(s, c->msig_p->d, 1.0, c->msig_p->d, 1.0, c->w_n->d, c->npad);
+        }
+        KCHK(c);
+        for (int kind = 0; kind < 3; kind++)
+            if (comm_allreduce(c, dst[kind]->d, c->npad)) return 1;     // data.cpp:604-606
+    }
+    for (int kind = 0; kind < 3 && !from_stripes; kind++) {
+        gvk::people_table(c->stream, c->mave, c->msig, c->M, kind, c->t3);
+        gvk::ax_f64(c->stream, c->bed, c->M, c->pitch, c->t3, c->ax_chunks, c->ax_partial, c->npad);
+        gvk::ax_reduce(c->stream, c->ax_partial, c->ax_chunks, c->npad, c->mask2, 1.0, dst[kind]->d);
+        KCHK(c);
+        if (comm_allreduce(c, dst[kind]->d, c->npad)) return 1;     // data.cpp:604-606
+    }
+    gvk::people_finish(c->stream, c->mave_p->d, c->msig_p->d, c->numb_p->d, c->mask2, c->N, c->npad);
+    KCHK(c);
+    const size_t n4 = sizeof(double) * 4 * c->mbytes;
+    if (mave_people) HIPCHK(c, hipMemcpyAsync(mave_people, c->mave_p->d, n4, hipMemcpyDeviceToHost, c->stream));
+    if (msig_people) HIPCHK(c, hipMemcpyAsync(msig_people, c->msig_p->d, n4, hipMemcpyDeviceToHost, c->stream));
+    if (numb_people) HIPCHK(c, hipMemcpyAsync(numb_people, c->numb_p->d, n4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- p-values: data::pvals_calc (data.cpp:1108-1226) and pvals_calc_LOCO (:1235-1353), one estimator ----------------
+// Kernel mode 1: per call ONE pass over the shard whose epilogue runs the per-marker regression test (gvm::marker_pvals: operands,
+// digits, stream, test -- four launches, no allocation: the operands live in the context's N-space scratch, the p-values in an
+// M-space work vector until they are copied out).  Kernel mode 0 (fp64 family, parity anchor): the sums of k_marker_sums2_f64, then
+// the stand-alone test kernel.
+// out4[4m..] = {sum a p, sum b p, sum a p^2, sum b p^2} for the N-space device vector p, fp64 family
+static int marker_sums_p_p2_f64(gv_ctx* c, const double* p, double* p2_scratch, double* out4_dev) {
+    NEED(c, c->have_raw, "p-values: kernel mode 0 needs the raw row layout");
+    gvk::mul(c->stream, p2_scratch, p, p, c->npad);
+    gvk::marker_sums2_f64(c->stream, c->bed, c->M, c->pitch, p, p2_scratch, out4_dev);
+    KCHK(c);
+    return 0;
+}
+
+// chrom == NULL: leave-one-out (the marker's own effect is added back analytically); else leave-one-chromosome-out.
+static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
+                      double* pvals, double* chrom_pred = nullptr) {
+    NEED(c, !c->have_dense, "gv_pvals: not available for methylation data (the reference's meth branch of pvals_calc, "
+                            "data.cpp:1187-1223, computes and stores nothing)");
+    NEED(c, z1->space == GV_SPACE_N && y->space == GV_SPACE_N && x1_hat->space == GV_SPACE_M, "gv_pvals: bad vector spaces");
+    NEED(c, c->have_stats, "gv_pvals: marker statistics must be computed first");
+    if (ensure_work(c) || ensure_w2(c)) return 1;
+    const int64_t M = c->M;
+    const double sqrtN = sqrt((double)c->N);
+    const bool fused = c->kernel_mode != 0;      // (kernel mode 2: the p-value pass is mode 1's -- its sums run over exact planes already)
+    if (fused && M > 0) {
+        NEED(c, c->have_stripes, "p-values: kernel modes 1 and 2 need a re-encoded layout");
+        if (!c->ks_tuned && autotune_ks(c)) return 1;      // (a p-value call may be the first streaming pass of a context)
+    }
+    gv_vec *ymod = nullptr, *ych = nullptr, *sq = nullptr, *xch = nullptr;
+    double* sums_dev = nullptr;
+    int* chrom_dev = nullptr;
+    int rc = 0;
+    const size_t Mn = (size_t)(M > 0 ? M : 1);
+    auto cleanup = [&]() {
+        for (gv_vec* v : {ymod, ych, sq, xch}) vec_del(c, v);
+        if (sums_dev) (void)hipFree(sums_dev);
+        if (chrom_dev) (void)hipFree(chrom_dev);
+    };
+#define PV_TRY(expr) do { if ((rc = (expr)) != 0) { cleanup(); return rc; } } while (0)
+#define PV_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(c, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
+    // an M-space work vector of the CG: INVARIANT -- ax_device / ax_overlapped (run per chromosome between the marker passes of the LOCO
+    // loop below) never touch the CG work vectors cg_r / cg_z / cg_p / cg_d; gv_ax / gv_atx (which stage through cg_d) are host entry
+    // points and cannot run inside this call
+    double* pv_dev = c->cg_d->d;
+    double *pa = c->w_n->d, *pb = c->w_n2->d;   // operands of the fused pass: p and p^2
+    gvm::PvArgs pva{c->counts, nullptr, 0.0, nullptr, 0};
+    if (!fused) {
+        PV_TRY(vec_new(c, GV_SPACE_N, &ymod));
+        PV_TRY(vec_new(c, GV_SPACE_N, &sq));
+        PV_HIP(hipMalloc(&sums_dev, sizeof(double) * 4 * Mn));
+        gvk::axpby(c->stream, ymod->d, 1.0, y->d, -1.0, z1->d, c->npad);            // y_mod = y - z1 (data.cpp:1117-1119)
+        // the reference masks every term of the regression sums with na_lut[mask4] (data.cpp:1155-1175); the sums here are
+        // matvec-shaped and need zeros at NA / pad slots instead, whatever the caller left there (an unfiltered y holds DBL_MAX)
+        gvk::mask_copy(c->stream, ymod->d, ymod->d, c->mask2, c->npad);
+    }
+    if (!chrom) {
+        // y_mark = y_mod + gen_part * x1_hat[k] (data.cpp:1145-1148): the marker's own column, c = x1_hat[k] / sqrt(N)
+        if (fused) {
+            pva.xself = x1_hat->d;
+            pva.self_scale = 1.0 / sqrtN;
+            if (M > 0)      // (an empty shard has no marker to test)
+                gvm::marker_pvals(c->stream, c->plan, y->d, z1->d, nullptr, c->mask2, c->npad, c->mave, c->msig, pa, pb, c->red_partial, pva, pv_dev);
+        } else if (M > 0) {
+            PV_TRY(marker_sums_p_p2_f64(c, ymod->d, sq->d, sums_dev));
+            gvk::pvals_test(c->stream, c->counts, c->mave, c->msig, sums_dev, x1_hat->d, 1.0 / sqrtN, nullptr, 0, M, pv_dev);
+        }
+    } else {
+        PV_HIP(hipMemsetAsync(pv_dev, 0, sizeof(double) * Mn, c->stream));      // markers of chromosomes outside 1..23 keep 0
+        PV_TRY(vec_new(c, GV_SPACE_N, &ych));
+        PV_TRY(vec_new(c, GV_SPACE_M, &xch));
+        PV_HIP(hipMalloc(&chrom_dev, sizeof(int) * Mn));
+        PV_HIP(hipMemcpyAsync(chrom_dev, chrom, sizeof(int) * M, hipMemcpyHostToDevice, c->stream));
+        double present[24];
+        for (int ch = 0; ch < 24; ch++) present[ch] = 0;
+        for (int64_t k = 0; k < M; k++) if (chrom[k] >= 1 && chrom[k] <= 23) present[chrom[k]] += 1;
+        PV_TRY(allreduce_scalars(c, present, 24));
+        if (chrom_pred) memset(chrom_pred, 0, sizeof(double) * 23 * 4 * (size_t)c->mbytes);   // chromosomes nobody holds: zeros
+        for (int ch = 1; ch <= 23; ch++) {
+            if (present[ch] == 0) continue;      // no rank holds a marker of this chromosome
+            gvk::select_eq(c->stream, xch->d, x1_hat->d, chrom_dev, ch, M);
+            PV_TRY(ax_device(c, xch->d, ych->d));                                // chromosome predictor, all ranks (:1268-1272)
+            if (chrom_pred)                                                      // the vector the reference dumps (:1276-1281)
+                PV_TRY(to_host(c, chrom_pred + (size_t)(ch - 1) * 4 * c->mbytes, ych->d, sizeof(double) * 4 * c->mbytes));
+            if (fused) {                                                         // p = chromosome predictor + y_mod (:1284)
+                pva.chrom = chrom_dev;
+                pva.ch = ch;
+                if (M > 0)
+                    gvm::marker_pvals(c->stream, c->plan, y->d, z1->d, ych->d, c->mask2, c->npad, c->mave, c->msig, pa, pb, c->red_partial, pva, pv_dev);
+            } else if (M > 0) {
+                gvk::axpby(c->stream, ych->d, 1.0, ych->d, 1.0, ymod->d, c->npad);
+                PV_TRY(marker_sums_p_p2_f64(c, ych->d, sq->d, sums_dev));
+                gvk::pvals_test(c->stream, c->counts, c->mave, c->msig, sums_dev, nullptr, 0.0, chrom_dev, ch, M, pv_dev);
+            }
+        }
+    }
+    KCHK(c);
+    if (M > 0) PV_TRY(to_host(c, pvals, pv_dev, sizeof(double) * M));
+#undef PV_TRY
+#undef PV_HIP
+    if (ymod || ych || sq || xch || sums_dev || chrom_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    cleanup();
+    return 0;
+}
+
+int gv_pvals_loo(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, double* pvals) {
+    return pvals_impl(c, z1, y, x1_hat, nullptr, pvals);
+}
+int gv_pvals_loco(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom, double* pvals) {
+    NEED(c, chrom != nullptr, "gv_pvals_loco: chrom is NULL");
+    return pvals_impl(c, z1, y, x1_hat, chrom, pvals);
+}
+int gv_pvals_loco_pred(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom, double* pvals,
+                       double* chrom_pred) {
+    NEED(c, chrom != nullptr, "gv_pvals_loco_pred: chrom is NULL");
+    return pvals_impl(c, z1, y, x1_hat, chrom, pvals, chrom_pred);
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 """Real .bed ingest at BASELINE config-2 size (N=100k x M=500k = 12.5 GB): file -> resident layout GB/s (data.cpp:201-234's
 read_genotype_data replaced by gv_upload_bed_file).  The file is written on the box first, from the seeded on-device
 generator (chunks through the raw-row layout), so it comes out of the page cache: what is measured is fread + the pinned
-staging copy + PCIe + the re-encoding kernels, double-buffered (gv_capi.hip: ingest), not the disk.
+staging copy + PCIe + the re-encoding kernels, double-buffered (gv_ingest.hip: ingest), not the disk.
 
   python scripts/ingest_rate.py [N] [M] [dir]      -> one JSON line
 """

@@ -357,7 +357,7 @@ def test_gathered_dots_equal_their_own_launches_bit_for_bit(N, M):
 
 
 def test_stripe_sets_survive_a_reingest():
-    """The two stripe sets are views into one allocation (gv_capi.hip: where the driver places a large allocation moves the kernel
+    """The two stripe sets are views into one allocation (gv_ingest.hip: where the driver places a large allocation moves the kernel
     that streams it).  A second ingest into the same context releases and re-allocates: same products for the same matrix."""
     N, M = 5003, 20011
     rng = np.random.default_rng(5)
