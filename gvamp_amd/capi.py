@@ -24,7 +24,7 @@ EXPORTS = [
     "gv_denoise", "gv_prior_estep", "gv_denoise_global", "gv_prior_estep_global",
     "gv_probit_denoise", "gv_probit_denoise_cov", "gv_people_stats", "gv_cg_solve_aat", "gv_cg_solve_aat2", "gv_cg_solve_aat2w", "gv_cg_solve2w", "gv_pvals_loo", "gv_pvals_loco", "gv_pvals_loco_pred", "gv_allreduce_host", "gv_comm_unique_id", "gv_comm_init", "gv_comm_init_local", "gv_comm_init_callback", "gv_comm_share", "gv_set_overlap", "gv_debug_force_multi", "gv_comm_rank", "gv_comm_size", "gv_bind_host_numa", "gv_set_timing",
     "gv_get_counters", "gv_reset_counters", "gv_get_decomp", "gv_set_decomp", "gv_tune_info", "gv_ingest_info", "gv_ingest_info2", "gv_set_expected_passes", "gv_copy_bandwidth", "gv_read_bandwidth",
-    "gv_upload_meth", "gv_upload_meth_file", "gv_synth_meth",
+    "gv_upload_meth", "gv_upload_meth_file", "gv_synth_meth", "gv_upload_dosage", "gv_upload_dosage_file", "gv_synth_dosage",
     "gv_huber_denoise", "gv_huber_delta",
     "gv_set_cg_precond", "gv_precond_info", "gv_precond_window_gram", "gv_precond_apply",
 ]
@@ -122,6 +122,9 @@ def load():
     L.gv_upload_meth.argtypes = [vp, dp, C.c_size_t]
     L.gv_upload_meth_file.argtypes = [vp, C.c_char_p, i64]
     L.gv_synth_meth.argtypes = [vp, C.c_uint64]
+    L.gv_upload_dosage.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_double]
+    L.gv_upload_dosage_file.argtypes = [vp, C.c_char_p, i64, C.c_int, C.c_double]
+    L.gv_synth_dosage.argtypes = [vp, C.c_uint64, C.c_int]
     L.gv_set_mask.argtypes = [vp, up, i64]
     L.gv_marker_stats.argtypes = [vp, C.c_double]
     L.gv_get_marker_stats.argtypes = [vp, dp, dp]
@@ -315,6 +318,24 @@ class Shard:
     def synth_meth(self, seed):
         """the device-generated methylation matrix that synth.synth_meth(N, M, seed, S) reproduces on the host"""
         self._ck(self.L.gv_synth_meth(self.h, seed))
+
+    def upload_dosage(self, codes, scale):
+        """compact dense data: M x N unsigned codes of this shard, marker-major, X = scale * codes; codes.dtype (uint8 / uint16)
+        selects the width"""
+        codes = np.ascontiguousarray(codes)
+        if codes.dtype not in (np.uint8, np.uint16):
+            raise GvError("upload_dosage: codes must be uint8 or uint16, not %s" % codes.dtype)
+        assert codes.size == self.M * self.N, (codes.size, self.M, self.N)
+        self._ck(self.L.gv_upload_dosage(self.h, codes.ctypes.data_as(C.c_void_p), codes.size, 8 * codes.dtype.itemsize, scale))
+
+    def upload_dosage_file(self, path, bits, scale, offset=None):
+        """M x N codes of `bits` bits at byte offset (default S * N * bits / 8) of a file of raw codes"""
+        off = self.S * self.N * (bits // 8) if offset is None else offset
+        self._ck(self.L.gv_upload_dosage_file(self.h, path.encode(), off, bits, scale))
+
+    def synth_dosage(self, seed, bits):
+        """the device-generated codes that synth.synth_dosage(N, M, seed, bits, S) reproduces on the host (scale 1/127, 1/16384)"""
+        self._ck(self.L.gv_synth_dosage(self.h, seed, bits))
 
     def download_bed(self):
         out = np.empty(self.M * self.mbytes, dtype=np.uint8)

@@ -156,7 +156,8 @@ static void free_dataset(gv_ctx* c) {
         p = nullptr;
     };
     F(c->bed); F(c->mask2); F(c->mave); F(c->msig); F(c->t3); F(c->ax_partial); F(c->counts);
-    F(c->dense); F(c->dense_part);
+    F(c->dense); F(c->dense_part); F(c->dcodes); F(c->dense_mu);
+    c->dense_bits = 0;
     c->dense_part_cap = 0;
     c->have_dense = false;
     if (c->stripes_slab) {
@@ -590,7 +591,10 @@ int gv_reset_counters(gv_ctx* c) {
     c->cnt = gv_counters{};
     return 0;
 }
-int gv_get_layout(const gv_ctx* c) { return c->have_dense ? 3 : (c->have_stripes ? (c->plan.layout == 1 ? 2 : 1) : 0); }
+int gv_get_layout(const gv_ctx* c) {
+    if (c->have_dense) return c->dense_bits == 8 ? 4 : (c->dense_bits == 16 ? 5 : 3);
+    return c->have_stripes ? (c->plan.layout == 1 ? 2 : 1) : 0;
+}
 int gv_copy_bandwidth(gv_ctx* c, size_t nbytes, int reps, double* gbps) {
     double *a = nullptr, *b = nullptr;
     int64_t n = (int64_t)(nbytes / 16) * 2;

@@ -13,12 +13,22 @@
 //                      a second kernel adds in segment order -- no atomics, results are bit-reproducible run to run.
 // The two-vector forms run the one-vector arithmetic per slot in the same order, so each slot is bit-identical to the
 // one-vector kernel on that vector.
+//
+// Compact dense data (gv_upload_dosage / gv_upload_dosage_file / gv_synth_dosage): the same kind with X = scale * B, B unsigned 8- or
+// 16-bit codes, marker-major, the row pitch padded to 64 codes.  Kernels of their own below (k_dosage_*): all arithmetic in code
+// units -- (b - mu') per entry with mu' the mean code, the factor `scale` folded into the per-marker weight -- so that a constant
+// row has q == 0 exactly whatever the scale.
+//   statistics : one wave per marker row; the sum of the codes is an exact integer sum.
+//   ATx        : one wave owns R consecutive rows (8 for one vector, 4 for two) and walks the individuals in steps of 1024: a lane
+//                loads four 4-code pieces per row (piece k at 256 k + 4 lane, so every wave load is contiguous) and keeps its 16
+//                entries of p in registers across the R rows.
+//   Ax         : as the fp64 kernel with a 16-byte load per lane: 16 (u8) or 8 (u16) individuals per lane, 4096 / 2048 per workgroup.
 #include "gv_internal.h"
 
 namespace {
 
 constexpr int WAVE = 64;
-constexpr int AX_COLS = 512;     // individuals per Ax workgroup: 256 lanes x one double2
+constexpr int AX_COLS = gvd::AX_COLS_F64;     // individuals per Ax workgroup: 256 lanes x one double2
 
 __device__ inline uint64_t splitmix64(uint64_t x) {
     x += 0x9E3779B97F4A7C15ull;
@@ -229,7 +239,275 @@ __global__ void k_dense_ax_reduce(const double* __restrict__ part, int64_t part_
     }
 }
 
+// ================================================ compact dense data: 8- / 16-bit codes ==========================================
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// Quad: four consecutive codes in one load; get(q, e) zero-extends code e (codes are unsigned: 128.. / 32768.. stay positive)
+template <typename T> struct Code;
+template <> struct Code<uint8_t> {
+    typedef uint32_t Quad;
+    static __device__ inline uint32_t get(Quad q, int e) { return (q >> (8 * e)) & 0xFFu; }
+    static __device__ inline uint32_t get16(const u32x4& x, int e) { return (x[e >> 2] >> (8 * (e & 3))) & 0xFFu; }
+};
+template <> struct Code<uint16_t> {
+    typedef u32x2 Quad;
+    static __device__ inline uint32_t get(Quad q, int e) { return ((e < 2 ? q.x : q.y) >> (16 * (e & 1))) & 0xFFFFu; }
+    static __device__ inline uint32_t get16(const u32x4& x, int e) { return (x[e >> 1] >> (16 * (e & 1))) & 0xFFFFu; }
+};
+template <typename T> __device__ inline typename Code<T>::Quad ntquad(const T* p) {
+    return __builtin_nontemporal_load(reinterpret_cast<const typename Code<T>::Quad*>(p));
+}
+
+// ---- synthetic codes: genotype g in {0, 1, 2} from two allele draws at the marker's frequency (655 + h mod 32113) / 65536 -- about
+// 0.01 to 0.5 -- plus an imputation-like jitter, the product of two 16-bit hash fields: code = g * 3 * 2^(bits-3) + (jitter >> (18 -
+// bits)), i.e. {0, 96, 192} + [0, 63] for 8 bits and {0, 24576, 49152} + [0, 16383] for 16.  Integer arithmetic only, so
+// gvamp_amd/synth.py:synth_dosage reproduces the matrix bit for bit.  Pad columns are written as zeros.
+template <typename T>
+__global__ void k_synth_dosage(T* __restrict__ A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed) {
+    constexpr int BITS = 8 * (int)sizeof(T);
+    for (int64_t m = blockIdx.x; m < M; m += gridDim.x) {
+        const uint64_t g = (uint64_t)(S + m);
+        const uint64_t hm = splitmix64(seed ^ (g * 0xD1342543DE82EF95ull));
+        const uint64_t base = splitmix64(hm + 0x632BE59BD9B4E019ull);
+        const uint64_t maf = 655ull + hm % 32113ull;
+        T* row = A + m * pitch;
+        for (int64_t j = threadIdx.x; j < pitch; j += blockDim.x) {
+            uint64_t v = 0;
+            if (j < N) {
+                const uint64_t r = splitmix64(base + (uint64_t)j);
+                const uint64_t geno = ((r & 0xFFFFull) < maf ? 1ull : 0ull) + (((r >> 16) & 0xFFFFull) < maf ? 1ull : 0ull);
+                const uint64_t jit = (((r >> 32) & 0xFFFFull) * (r >> 48)) >> 16;
+                v = geno * (3ull << (BITS - 3)) + (jit >> (18 - BITS));
+            }
+            row[j] = (T)v;
+        }
+    }
+}
+
+// ---- marker statistics in code units: mu' = (sum_present b) / nonas with the integer sum exact, q = sum_present (b - mu')^2 in a
+// second pass; mave = scale mu', msig = 1 if q == 0 else (scale sqrt(q / (nonas - 1)))^-alpha_scale.  mu' is kept for the products.
+template <typename T>
+__global__ __launch_bounds__(256) void k_dosage_stats(const T* __restrict__ A, int64_t M, int64_t N, int64_t pitch,
+                                                      const uint32_t* __restrict__ mask2, double nonas, double alpha_scale,
+                                                      double wscale, double* __restrict__ dmu, double* __restrict__ mave,
+                                                      double* __restrict__ msig) {
+    typedef typename Code<T>::Quad Quad;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= M) return;
+    const T* row = A + m * pitch;
+    unsigned long long s = 0;
+    for (int64_t j0 = 4 * lane; j0 < N; j0 += 4 * WAVE) {      // (j0 < N <= pitch, both multiples of 4 or beyond: the piece is in the row)
+        const Quad x = *reinterpret_cast<const Quad*>(row + j0);
+        const uint32_t mk = mask2[j0 >> 4] >> (2 * (j0 & 15));
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (j0 + e < N) s += (unsigned long long)(Code<T>::get(x, e) * ((mk >> (2 * e)) & 1u));
+    }
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, WAVE);
+    const double mu = (double)s / nonas;
+    double q = 0.0;
+    for (int64_t j0 = 4 * lane; j0 < N; j0 += 4 * WAVE) {
+        const Quad x = *reinterpret_cast<const Quad*>(row + j0);
+        const uint32_t mk = mask2[j0 >> 4] >> (2 * (j0 & 15));
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+            if (j0 + e < N) {
+                const double d = ((double)Code<T>::get(x, e) - mu) * (double)((mk >> (2 * e)) & 1u);
+                q = fma(d, d, q);
+            }
+    }
+    q = wave_sum(q);
+    if (lane == 0) {
+        dmu[m] = mu;
+        mave[m] = wscale * mu;
+        double sg = 1.0;      // a constant column: q == 0 exactly in code units, whatever the scale
+        if (q != 0.0) {
+            const double sd = wscale * sqrt(q / (nonas - 1.0));
+            sg = alpha_scale == 1.0 ? 1.0 / sd : 1.0 / pow(sd, alpha_scale);
+        }
+        msig[m] = sg;
+    }
+}
+
+// ---- ATx: out[m] = (msig[m] scale_x) sum_{j<N} (b[m][j] - mu'[m]) p[j] / sqrt(N), then the lmmse_mult epilogue.  A lane's sum runs
+// over its entries in ascending column step, piece and entry order whatever NV and R are, then the fixed butterfly: each slot of the
+// two-vector form is bit-identical to the one-vector call.
+constexpr int ATX_STEP = 1024;      // individuals per column step of a wave: 64 lanes x 4 pieces x 4 codes
+template <typename T, int NV, int R>
+__global__ __launch_bounds__(256) void k_dosage_atx(const T* __restrict__ A, int64_t M, int64_t N, int64_t pitch,
+                                                    const double* __restrict__ pa, const double* __restrict__ pb,
+                                                    const double* __restrict__ dmu, const double* __restrict__ msig, double wscale,
+                                                    double scale, double* __restrict__ outa, double* __restrict__ outb,
+                                                    const double* __restrict__ addxa, const double* __restrict__ addxb, double tau,
+                                                    double gam2) {
+    typedef typename Code<T>::Quad Quad;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * R;
+    if (m0 >= M) return;
+    const T* row[R];
+    double mu[R], acc[R][NV];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int64_t mr = m0 + r < M ? m0 + r : M - 1;      // (a row group's tail re-reads the last row; nothing is written for it)
+        row[r] = A + mr * pitch + 4 * lane;
+        mu[r] = dmu[mr];
+#pragma unroll
+        for (int v = 0; v < NV; v++) acc[r][v] = 0.0;
+    }
+    int64_t c0 = 0;
+    for (; c0 + ATX_STEP <= N; c0 += ATX_STEP) {
+        Quad x[R][4];
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) x[r][k] = ntquad<T>(row[r] + c0 + 256 * k);
+        double p[NV][4][4];
+#pragma unroll
+        for (int v = 0; v < NV; v++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const double2* q = reinterpret_cast<const double2*>((v == 0 ? pa : pb) + c0 + 256 * k + 4 * lane);
+                const double2 q0 = q[0], q1 = q[1];
+                p[v][k][0] = q0.x; p[v][k][1] = q0.y; p[v][k][2] = q1.x; p[v][k][3] = q1.y;
+            }
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const double d = (double)Code<T>::get(x[r][k], e) - mu[r];
+#pragma unroll
+                    for (int v = 0; v < NV; v++) acc[r][v] = fma(d, p[v][k][e], acc[r][v]);
+                }
+    }
+    if (c0 < N) {      // the last, partial step: a piece starts below N or is skipped; j0 < N implies j0 + 3 < pitch <= npad
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t j0 = c0 + 256 * k + 4 * lane;
+            if (j0 < N) {
+                double p[NV][4];
+#pragma unroll
+                for (int v = 0; v < NV; v++)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) p[v][e] = j0 + e < N ? (v == 0 ? pa : pb)[j0 + e] : 0.0;
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    const Quad x = ntquad<T>(row[r] + c0 + 256 * k);
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (j0 + e < N) {
+                            const double d = (double)Code<T>::get(x, e) - mu[r];
+#pragma unroll
+                            for (int v = 0; v < NV; v++) acc[r][v] = fma(d, p[v][e], acc[r][v]);
+                        }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int v = 0; v < NV; v++) acc[r][v] = wave_sum(acc[r][v]);
+    if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const int64_t m = m0 + r;
+            if (m < M) {
+                const double w = msig[m] * wscale;
+#pragma unroll
+                for (int v = 0; v < NV; v++) {
+                    const double res = w * acc[r][v] * scale;
+                    const double* addx = v == 0 ? addxa : addxb;
+                    (v == 0 ? outa : outb)[m] = addx ? fma(tau, res, gam2 * addx[m]) : res;
+                }
+            }
+        }
+    }
+}
+
+// ---- Ax, first stage: partial[seg][j] = sum over the segment's markers i of (b[i][j] - mu'[i]) * (msig[i] scale_x v[i]), markers in
+// ascending order; a lane owns the 16 / sizeof(T) individuals of one 16-byte load.  Second stage: k_dense_ax_reduce.
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void k_dosage_ax(const T* __restrict__ A, int64_t M, int64_t pitch, int64_t seg_len,
+                                                   const double* __restrict__ va, const double* __restrict__ vb,
+                                                   const double* __restrict__ dmu, const double* __restrict__ msig, double wscale,
+                                                   double* __restrict__ part, int64_t part_stride, int64_t npad) {
+    constexpr int EPL = 16 / (int)sizeof(T);
+    const int64_t col = ((int64_t)blockIdx.x * 256 + threadIdx.x) * EPL;
+    if (col >= pitch) return;      // (pitch is a multiple of 64: col < pitch implies col + EPL <= pitch <= npad)
+    const int64_t i0 = (int64_t)blockIdx.y * seg_len;
+    const int64_t i1 = i0 + seg_len < M ? i0 + seg_len : M;
+    const T* base = A + col;
+    double acc[NV][EPL];
+#pragma unroll
+    for (int v = 0; v < NV; v++)
+#pragma unroll
+        for (int e = 0; e < EPL; e++) acc[v][e] = 0.0;
+    int64_t i = i0;
+    for (; i + 3 < i1; i += 4) {
+        u32x4 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) x[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + (i + u) * pitch));
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const double mu = dmu[i + u], sw = msig[i + u] * wscale;
+            const double wa = sw * va[i + u], wb = sw * vb[i + u];
+#pragma unroll
+            for (int e = 0; e < EPL; e++) {
+                const double d = (double)Code<T>::get16(x[u], e) - mu;
+                acc[0][e] = fma(d, wa, acc[0][e]);
+                if (NV == 2) acc[NV - 1][e] = fma(d, wb, acc[NV - 1][e]);
+            }
+        }
+    }
+    for (; i < i1; i++) {
+        const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + i * pitch));
+        const double mu = dmu[i], sw = msig[i] * wscale;
+        const double wa = sw * va[i], wb = sw * vb[i];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) {
+            const double d = (double)Code<T>::get16(x, e) - mu;
+            acc[0][e] = fma(d, wa, acc[0][e]);
+            if (NV == 2) acc[NV - 1][e] = fma(d, wb, acc[NV - 1][e]);
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < NV; v++) {
+        double2* dst = reinterpret_cast<double2*>(part + v * part_stride + (int64_t)blockIdx.y * npad + col);
+#pragma unroll
+        for (int e = 0; e < EPL; e += 2) dst[e >> 1] = make_double2(acc[v][e], acc[v][e + 1]);
+    }
+}
+
 inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+template <typename T>
+void dosage_atx_t(hipStream_t s, int nv, const T* A, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
+                  const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb,
+                  const double* addxa, const double* addxb, double tau, double gam2) {
+    if (nv == 2)
+        hipLaunchKernelGGL((k_dosage_atx<T, 2, 4>), dim3(nblk(M, 16)), dim3(256), 0, s, A, M, N, pitch, pa, pb, dmu, msig, wscale, scale,
+                           outa, outb, addxa, addxb, tau, gam2);
+    else
+        hipLaunchKernelGGL((k_dosage_atx<T, 1, 8>), dim3(nblk(M, 32)), dim3(256), 0, s, A, M, N, pitch, pa, pa, dmu, msig, wscale, scale,
+                           outa, outa, addxa, addxa, tau, gam2);
+}
+
+template <typename T>
+void dosage_ax_t(hipStream_t s, int nv, const gvd::AxShape& sh, const T* A, int64_t M, int64_t pitch, const double* va,
+                 const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad) {
+    const int64_t stride = (int64_t)sh.segs * npad;
+    const dim3 grid((unsigned)sh.col_tiles, (unsigned)sh.segs);
+    if (nv == 2)
+        hipLaunchKernelGGL((k_dosage_ax<T, 2>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, vb, dmu, msig, wscale, part, stride, npad);
+    else
+        hipLaunchKernelGGL((k_dosage_ax<T, 1>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, va, dmu, msig, wscale, part, stride, npad);
+}
 
 }  // namespace
 
@@ -237,10 +515,12 @@ namespace gvd {
 
 int64_t row_pitch(int64_t N) { return (N + 63) / 64 * 64; }
 
-AxShape ax_shape(int64_t N, int64_t M, int cus) {
+int ax_cols(int bits) { return bits == 8 ? 4096 : (bits == 16 ? 2048 : AX_COLS); }
+
+AxShape ax_shape(int64_t N, int64_t M, int cus, int cols) {
     AxShape sh;
     const int64_t pitch = row_pitch(N);
-    sh.col_tiles = (pitch + AX_COLS - 1) / AX_COLS;
+    sh.col_tiles = (pitch + cols - 1) / cols;
     // about eight workgroups per CU in all, every segment at least 16 markers long
     int64_t k = ((int64_t)8 * (cus > 0 ? cus : 256) + sh.col_tiles - 1) / sh.col_tiles;
     const int64_t kmax = (M + 15) / 16;
@@ -295,6 +575,46 @@ void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int
     else
         hipLaunchKernelGGL(k_dense_ax_reduce<1>, dim3(nblk(npad, 256)), dim3(256), 0, s, part, stride, sh.segs, N, npad, scale,
                            outa, outa);
+}
+
+// ---- compact dense data: `bits` (8 or 16) selects the code type
+void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed) {
+    if (M <= 0) return;
+    const dim3 g((unsigned)(M < 16384 ? M : 16384));
+    if (bits == 8)
+        hipLaunchKernelGGL(k_synth_dosage<uint8_t>, g, dim3(256), 0, s, (uint8_t*)A, M, S, N, pitch, seed);
+    else
+        hipLaunchKernelGGL(k_synth_dosage<uint16_t>, g, dim3(256), 0, s, (uint16_t*)A, M, S, N, pitch, seed);
+}
+
+void dosage_stats(hipStream_t s, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
+                  double alpha_scale, double wscale, double* dmu, double* mave, double* msig) {
+    if (M <= 0) return;
+    if (bits == 8)
+        hipLaunchKernelGGL(k_dosage_stats<uint8_t>, dim3(nblk(M, 4)), dim3(256), 0, s, (const uint8_t*)A, M, N, pitch, mask2, nonas,
+                           alpha_scale, wscale, dmu, mave, msig);
+    else
+        hipLaunchKernelGGL(k_dosage_stats<uint16_t>, dim3(nblk(M, 4)), dim3(256), 0, s, (const uint16_t*)A, M, N, pitch, mask2, nonas,
+                           alpha_scale, wscale, dmu, mave, msig);
+}
+
+void dosage_atx(hipStream_t s, int nv, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
+                const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb, const double* addxa,
+                const double* addxb, double tau, double gam2) {
+    if (M <= 0) return;
+    if (bits == 8)
+        dosage_atx_t(s, nv, (const uint8_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
+    else
+        dosage_atx_t(s, nv, (const uint16_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
+}
+
+void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, int64_t M, int64_t pitch, const double* va,
+                       const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad) {
+    if (M <= 0) return;
+    if (bits == 8)
+        dosage_ax_t(s, nv, sh, (const uint8_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
+    else
+        dosage_ax_t(s, nv, sh, (const uint16_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
 }
 
 }  // namespace gvd

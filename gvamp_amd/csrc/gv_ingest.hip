@@ -1,8 +1,9 @@
 // gv_ingest.hip -- getting a dataset resident: PLINK .bed rows (host buffer, file, synthetic) re-encoded chunk by chunk into the
-// layouts of the streaming kernels, and the dense fp64 rows of methylation data.
+// layouts of the streaming kernels, the dense fp64 rows of methylation data, and the 8- / 16-bit code rows of compact dense data.
 #include <cctype>
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -60,6 +61,14 @@ static int read_slab(int fd, int64_t off, uint8_t* dst, size_t nbytes) {
     return 0;
 }
 
+// frees the dense matrix of either width (fp64 values, 8- / 16-bit codes) and what belongs to it
+static void drop_dense(gv_ctx* c) {
+    for (void** q : {(void**)&c->dense, &c->dcodes, (void**)&c->dense_mu})
+        if (*q) { (void)hipFree(*q); *q = nullptr; }
+    c->dense_bits = 0;
+    c->have_dense = false;
+}
+
 static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed, uint32_t miss_thr, FILE* file = nullptr,
                   uint32_t ld_block = 0, uint32_t ld_thr = 0, int64_t file_off = 0) {
     NEED(c, c->N > 0, "ingest: gv_set_dims must be called first");
@@ -68,11 +77,7 @@ static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed,
     const int64_t M = c->M, P = c->pitch;
     gvm::Plan& pl = c->plan;
     c->have_raw = c->have_stripes = c->have_stats = false;
-    if (c->dense) {      // uploading either kind replaces the dataset held before
-        (void)hipFree(c->dense);
-        c->dense = nullptr;
-        c->have_dense = false;
-    }
+    drop_dense(c);      // uploading any kind replaces the dataset held before
     if (c->want_raw && !c->bed) HIPCHK(c, hipMalloc(&c->bed, (size_t)(M > 0 ? M : 1) * P));
     if (!c->want_raw && c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
     const auto t_in0 = std::chrono::steady_clock::now();
@@ -318,8 +323,9 @@ int gv_synth_bed_ld(gv_ctx* c, uint64_t seed, uint32_t miss_ppm, uint32_t ld_blo
 
 // ---- methylation data (type_data == "meth"): the dense fp64 design matrix of gv_dense.hip ------------------------------------
 // Frees whatever genotype layout is resident (the next bed ingest rebuilds it) and allocates the dense rows, zeroed.
-static int meth_prepare(gv_ctx* c) {
-    NEED(c, c->N > 0, "methylation upload: gv_set_dims must be called first");
+// bits: 0 = fp64 values, 8 / 16 = unsigned codes (the mean codes of the statistics get their M doubles here too)
+static int dense_prepare(gv_ctx* c, int bits) {
+    NEED(c, c->N > 0, "dense upload: gv_set_dims must be called first");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     gvm::Plan& pl = c->plan;
@@ -336,24 +342,32 @@ static int meth_prepare(gv_ctx* c) {
         c->dense_cus = cus > 0 ? cus : 256;
     }
     c->dpitch = gvd::row_pitch(c->N);
-    const size_t bytes = sizeof(double) * (size_t)(c->M > 0 ? c->M : 1) * (size_t)c->dpitch;
-    if (!c->dense) {
-        const hipError_t e = hipMalloc(&c->dense, bytes);
-        if (e != hipSuccess) {
-            c->dense = nullptr;
-            return fail(c, "methylation upload: no room for %lld x %lld doubles in HBM: %s", (long long)c->M, (long long)c->dpitch,
-                        hipGetErrorString(e));
+    const size_t rows = (size_t)(c->M > 0 ? c->M : 1);
+    const size_t bytes = (bits ? (size_t)bits / 8 : sizeof(double)) * rows * (size_t)c->dpitch;
+    if (bits != c->dense_bits || (bits ? !c->dcodes : !c->dense)) {      // another width (or nothing) is held: allocate afresh
+        drop_dense(c);
+        void* p = nullptr;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess && bits) {
+            e = hipMalloc(&c->dense_mu, sizeof(double) * rows);
+            if (e != hipSuccess) { (void)hipFree(p); c->dense_mu = nullptr; }
         }
+        if (e != hipSuccess)
+            return fail(c, "dense upload: no room for %lld x %lld %s in HBM: %s", (long long)c->M, (long long)c->dpitch,
+                        bits == 8 ? "8-bit codes" : (bits == 16 ? "16-bit codes" : "doubles"), hipGetErrorString(e));
+        if (bits) c->dcodes = p; else c->dense = (double*)p;
+        c->dense_bits = bits;
     }
-    HIPCHK(c, hipMemsetAsync(c->dense, 0, bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(bits ? c->dcodes : (void*)c->dense, 0, bytes, c->stream));
     return 0;
 }
+static int meth_prepare(gv_ctx* c) { return dense_prepare(c, 0); }
 static int meth_done(gv_ctx* c, double t_alloc, std::chrono::steady_clock::time_point t0) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->ingest_alloc_s = t_alloc;
     c->ingest_overlap_s = 0.0;
     c->ingest_fill_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_alloc;
-    c->ingest_bytes = sizeof(double) * (size_t)c->M * (size_t)c->dpitch;
+    c->ingest_bytes = (c->dense_bits ? (size_t)c->dense_bits / 8 : sizeof(double)) * (size_t)c->M * (size_t)c->dpitch;
     c->have_dense = true;
     return 0;
 }
@@ -376,15 +390,16 @@ int gv_upload_meth(gv_ctx* c, const double* x, size_t n) {
 
 // read_methylation_data (data.cpp:241-278): M*N doubles at byte `offset` (= S*N*8, :259), streamed through two bounded pinned
 // buffers as gv_upload_bed_file streams a .bed: reading chunk k + 1 overlaps the copy of chunk k, host memory stays O(chunk).
-int gv_upload_meth_file(gv_ctx* c, const char* path, int64_t offset) {
-    NEED(c, c->N > 0, "gv_upload_meth_file: gv_set_dims must be called first");
-    NEED(c, offset >= 0, "gv_upload_meth_file: negative offset");
+// (shared with gv_upload_dosage_file: bits = 0 reads doubles, 8 / 16 reads codes of that width; `who` names the entry point)
+static int dense_upload_file(gv_ctx* c, const char* who, const char* path, int64_t offset, int bits) {
     const int fd = open(path, O_RDONLY);
-    if (fd < 0) return fail(c, "gv_upload_meth_file: could not open methylation file: %s", path);
+    if (fd < 0) return fail(c, "%s: could not open %s file: %s", who, bits ? "dosage" : "methylation", path);
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = meth_prepare(c);
+    int rc = dense_prepare(c, bits);
     const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const size_t rowb = sizeof(double) * (size_t)c->N;
+    const size_t esz = bits ? (size_t)bits / 8 : sizeof(double);
+    const size_t rowb = esz * (size_t)c->N, pitchb = esz * (size_t)c->dpitch;
+    char* const dst = bits ? (char*)c->dcodes : (char*)c->dense;
     int64_t CH = (int64_t)(((size_t)64 << 20) / rowb);
     if (CH < 1) CH = 1;
     if (CH > c->M) CH = c->M > 0 ? c->M : 1;
@@ -393,7 +408,7 @@ int gv_upload_meth_file(gv_ctx* c, const char* path, int64_t offset) {
     for (int b = 0; b < 2 && !rc; b++) {
         hipError_t e = hipHostMalloc(&stage[b], (size_t)CH * rowb);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&stage_free[b], hipEventDisableTiming);
-        if (e != hipSuccess) rc = fail(c, "gv_upload_meth_file: no pinned staging buffer: %s", hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(c, "%s: no pinned staging buffer: %s", who, hipGetErrorString(e));
     }
     int64_t chunk = 0;
     for (int64_t m0 = 0; m0 < c->M && !rc; m0 += CH, chunk++) {
@@ -401,17 +416,16 @@ int gv_upload_meth_file(gv_ctx* c, const char* path, int64_t offset) {
         const int sb = (int)(chunk & 1);
         hipError_t e = hipSuccess;
         if (chunk >= 2) e = hipEventSynchronize(stage_free[sb]);      // the copy of chunk - 2 has left this buffer
-        if (e != hipSuccess) { rc = fail(c, "gv_upload_meth_file: %s", hipGetErrorString(e)); break; }
+        if (e != hipSuccess) { rc = fail(c, "%s: %s", who, hipGetErrorString(e)); break; }
         const int io = read_slab(fd, offset + m0 * (int64_t)rowb, (uint8_t*)stage[sb], (size_t)mc * rowb);
         if (io) {
-            rc = io < 0 ? fail(c, "gv_upload_meth_file: %s ends before marker %lld is complete (short file)", path, (long long)(c->S + m0 + mc - 1))
-                        : fail(c, "gv_upload_meth_file: reading %s at marker %lld failed: %s", path, (long long)(c->S + m0), strerror(io));
+            rc = io < 0 ? fail(c, "%s: %s ends before marker %lld is complete (short file)", who, path, (long long)(c->S + m0 + mc - 1))
+                        : fail(c, "%s: reading %s at marker %lld failed: %s", who, path, (long long)(c->S + m0), strerror(io));
             break;
         }
-        e = hipMemcpy2DAsync(c->dense + m0 * c->dpitch, sizeof(double) * c->dpitch, stage[sb], rowb, rowb, mc,
-                             hipMemcpyHostToDevice, c->stream);
+        e = hipMemcpy2DAsync(dst + (size_t)m0 * pitchb, pitchb, stage[sb], rowb, rowb, mc, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipEventRecord(stage_free[sb], c->stream);
-        if (e != hipSuccess) rc = fail(c, "gv_upload_meth_file: copy at marker %lld failed: %s", (long long)(c->S + m0), hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(c, "%s: copy at marker %lld failed: %s", who, (long long)(c->S + m0), hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
     for (int b = 0; b < 2; b++) {
@@ -421,6 +435,12 @@ int gv_upload_meth_file(gv_ctx* c, const char* path, int64_t offset) {
     close(fd);
     if (rc) return rc;
     return meth_done(c, ta, t0);
+}
+
+int gv_upload_meth_file(gv_ctx* c, const char* path, int64_t offset) {
+    NEED(c, c->N > 0, "gv_upload_meth_file: gv_set_dims must be called first");
+    NEED(c, offset >= 0, "gv_upload_meth_file: negative offset");
+    return dense_upload_file(c, "gv_upload_meth_file", path, offset, 0);
 }
 
 int gv_synth_meth(gv_ctx* c, uint64_t seed) {
@@ -433,7 +453,53 @@ int gv_synth_meth(gv_ctx* c, uint64_t seed) {
     return meth_done(c, ta, t0);
 }
 
+// ---- compact dense data: X = scale * B, B unsigned codes of 8 or 16 bits (gv_dense.hip: k_dosage_*) ------------------------------
+static int dosage_args(gv_ctx* c, const char* who, int bits, double scale) {
+    if (c->N <= 0) return fail(c, "%s: gv_set_dims must be called first", who);
+    if (bits != 8 && bits != 16) return fail(c, "%s: bits must be 8 or 16, not %d", who, bits);
+    if (!(scale > 0.0) || !std::isfinite(scale)) return fail(c, "%s: scale must be positive and finite, not %g", who, scale);
+    return 0;
+}
+
+int gv_upload_dosage(gv_ctx* c, const void* codes, size_t n, int bits, double scale) {
+    if (dosage_args(c, "gv_upload_dosage", bits, scale)) return 1;
+    NEED(c, n == (size_t)c->M * (size_t)c->N, "gv_upload_dosage: n != M * N");
+    const auto t0 = std::chrono::steady_clock::now();
+    if (dense_prepare(c, bits)) return 1;
+    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const size_t esz = (size_t)bits / 8, rowb = esz * (size_t)c->N, pitchb = esz * (size_t)c->dpitch;
+    const int64_t rows = c->M < 16384 ? c->M : 16384;      // rows per copy: a caller-owned pageable buffer, nothing to overlap
+    for (int64_t m0 = 0; m0 < c->M; m0 += rows) {
+        const int64_t mc = c->M - m0 < rows ? c->M - m0 : rows;
+        HIPCHK(c, hipMemcpy2DAsync((char*)c->dcodes + (size_t)m0 * pitchb, pitchb, (const char*)codes + (size_t)m0 * rowb, rowb, rowb, mc,
+                                   hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    c->dense_scale = scale;
+    return meth_done(c, ta, t0);
+}
+
+// M*N codes at byte `offset` (= S*N*bits/8), streamed through the two bounded pinned buffers of gv_upload_meth_file
+int gv_upload_dosage_file(gv_ctx* c, const char* path, int64_t offset, int bits, double scale) {
+    if (dosage_args(c, "gv_upload_dosage_file", bits, scale)) return 1;
+    NEED(c, offset >= 0, "gv_upload_dosage_file: negative offset");
+    c->dense_scale = scale;
+    return dense_upload_file(c, "gv_upload_dosage_file", path, offset, bits);
+}
+
+int gv_synth_dosage(gv_ctx* c, uint64_t seed, int bits) {
+    if (dosage_args(c, "gv_synth_dosage", bits, 1.0)) return 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (dense_prepare(c, bits)) return 1;
+    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    gvd::dosage_synth(c->stream, c->dcodes, bits, c->M, c->S, c->N, c->dpitch, seed);
+    KCHK(c);
+    c->dense_scale = bits == 8 ? 1.0 / 127.0 : 1.0 / 16384.0;
+    return meth_done(c, ta, t0);
+}
+
 int gv_download_bed(gv_ctx* c, uint8_t* bed, size_t nbytes) {
+    REFUSE_DOSAGE(c, "gv_download_bed", "the resident dataset is a matrix of dosage codes, not PLINK rows");
     NEED(c, !c->have_dense, "gv_download_bed: the resident dataset is methylation data (a dense fp64 matrix), not PLINK rows");
     NEED(c, c->have_raw, "gv_download_bed: the raw row layout is not resident (not the default: call gv_set_layout(ctx, 1, stripes) before the ingest)");
     NEED(c, nbytes == (size_t)c->M * (size_t)c->mbytes, "gv_download_bed: nbytes != M * ceil(N/4)");

@@ -68,6 +68,12 @@ struct gv_ctx {
     double* dense_part = nullptr;   // Ax partial vectors: 2 * segs * npad doubles
     size_t dense_part_cap = 0;
     int dense_cus = 0;              // CU count of the device (the decomposition's only input beyond N and M)
+    // compact dense data (gv_upload_dosage / gv_upload_dosage_file / gv_synth_dosage): X = dense_scale * B, B unsigned codes of
+    // dense_bits (8 or 16) bits.  have_dense is set and `dense` is NULL; dense_bits == 0 means the fp64 matrix above.
+    void* dcodes = nullptr;         // M * dpitch codes, marker-major rows, zeros in the padding
+    int dense_bits = 0;
+    double dense_scale = 1.0;
+    double* dense_mu = nullptr;     // M mean codes mu' (mave = dense_scale * mu'): the products work in code units
     double tune_seconds = 0.0;      // wall time the pick cost (0 when it came from the cache)
     int tune_source = 0;            // 0 model's first candidate, 1 measured, 2 cache, 3 fixed by an override / nothing to tune
 
@@ -265,7 +271,9 @@ struct AxShape {
     int64_t seg_len = 1;            // markers per segment
     int segs = 1;                   // marker segments = partial vectors
 };
-AxShape ax_shape(int64_t N, int64_t M, int cus);
+constexpr int AX_COLS_F64 = 512;
+int ax_cols(int bits);              // individuals per Ax workgroup: 512 (fp64, bits == 0), 4096 (8-bit codes), 2048 (16-bit codes)
+AxShape ax_shape(int64_t N, int64_t M, int cus, int cols = AX_COLS_F64);
 void synth(hipStream_t s, double* A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed);
 void stats(hipStream_t s, const double* A, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
            double alpha_scale, double* mave, double* msig);
@@ -278,6 +286,16 @@ void ax_partial(hipStream_t s, int nv, const AxShape& sh, const double* A, int64
                 const double* vb, const double* mave, const double* msig, double* part, int64_t npad);
 void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int64_t N, int64_t npad, double scale, double* outa,
                double* outb);
+// compact dense data: A holds M * pitch unsigned codes of `bits` (8 or 16) bits, pitch in codes; dmu the mean codes; wscale the
+// factor between codes and values.  Same contracts as the fp64 forms above; the second Ax stage is ax_reduce.
+void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed);
+void dosage_stats(hipStream_t s, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
+                  double alpha_scale, double wscale, double* dmu, double* mave, double* msig);
+void dosage_atx(hipStream_t s, int nv, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
+                const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb, const double* addxa,
+                const double* addxb, double tau, double gam2);
+void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, int64_t M, int64_t pitch, const double* va,
+                       const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad);
 }  // namespace gvd
 
 // ---- LD-block preconditioner (gv_precond.hip) --------------------------------------------------------------------------------
@@ -372,5 +390,11 @@ struct Timer {
 #define NEED(c, cond, msg)                 \
     do {                                   \
         if (!(cond)) return fail(c, msg);  \
+    } while (0)
+// an entry point the dense kinds refuse, when the resident dataset is compact dense data (the fp64 kind keeps its own message)
+#define REFUSE_DOSAGE(c, who, why)                                                                                      \
+    do {                                                                                                                \
+        if ((c)->have_dense && (c)->dense_bits)                                                                         \
+            return fail(c, "%s: not available for compact dosage data (%d-bit codes): %s", who, (c)->dense_bits, why); \
     } while (0)
 

@@ -1,5 +1,5 @@
 // gv_matvec.hip -- data::Ax / data::ATx of the C ABI: one dispatcher per product direction (ax_pass / atx_pass) over the dense
-// fp64 kernels of methylation data and the three genotype kernel families, the N-space exchange of a sharded job (in one
+// kernels of the dense kinds (fp64 methylation data, 8- / 16-bit dosage codes) and the three genotype kernel families, the N-space exchange of a sharded job (in one
 // piece, or overlapped with the decode), and the event pairs of set_timing 2.
 #include <cmath>
 
@@ -146,7 +146,7 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
         const bool mfma = !dense && c->kernel_mode != 0;
         gvd::AxShape sh;
         if (dense) {
-            sh = gvd::ax_shape(c->N, c->M, c->dense_cus);
+            sh = gvd::ax_shape(c->N, c->M, c->dense_cus, gvd::ax_cols(c->dense_bits));
             const size_t need = (size_t)2 * sh.segs * c->npad;
             if (need > c->dense_part_cap) {
                 if (c->dense_part) (void)hipFree(c->dense_part);
@@ -165,7 +165,11 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
         gv_ctx::EvRec* er = ev_next(c, 0);     // timing == 2: around the streaming kernel (the MFMA family records the pair itself)
         if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
-            gvd::ax_partial(c->stream, nv, sh, c->dense, c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->mave, c->msig, c->dense_part, c->npad);
+            if (c->dense_bits)
+                gvd::dosage_ax_partial(c->stream, nv, sh, c->dcodes, c->dense_bits, c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->dense_mu,
+                                       c->msig, c->dense_scale, c->dense_part, c->npad);
+            else
+                gvd::ax_partial(c->stream, nv, sh, c->dense, c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->mave, c->msig, c->dense_part, c->npad);
             if (er) (void)hipEventRecord(er->b, c->stream);
             gvd::ax_reduce(c->stream, nv, sh, c->dense_part, c->N, c->npad, multi ? 1.0 : scale, outa, nv == 2 ? outb : outa);
         } else if (mfma) {
@@ -226,8 +230,12 @@ int atx_pass(gv_ctx* c, int nv, const double* pa, const double* pb, double* outa
         gv_ctx::EvRec* er = ev_next(c, 1);
         if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
-            gvd::atx(c->stream, nv, c->dense, c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->mave, c->msig, scale, outa,
-                     nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2);
+            if (c->dense_bits)
+                gvd::dosage_atx(c->stream, nv, c->dcodes, c->dense_bits, c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->dense_mu, c->msig,
+                                c->dense_scale, scale, outa, nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2);
+            else
+                gvd::atx(c->stream, nv, c->dense, c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->mave, c->msig, scale, outa,
+                         nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2);
             if (er) (void)hipEventRecord(er->b, c->stream);
         } else if (mfma) {
             c->plan.ev0 = er ? er->a : nullptr;

@@ -875,6 +875,7 @@ int gv_cg_solve_aat(gv_ctx* c, const gv_vec* v, const gv_vec* mu_start, double t
                     gv_vec* mu_out, gv_cg_stats* st, double* relres) {
     NEED(c, v->space == GV_SPACE_N && mu_out->space == GV_SPACE_N, "gv_cg_solve_aat: N-space vectors required");
     NEED(c, mu_out != v && mu_out != mu_start, "gv_cg_solve_aat: mu_out must not alias v or mu_start");
+    REFUSE_DOSAGE(c, "gv_cg_solve_aat", "the N-space solver needs people statistics");
     NEED(c, !c->have_dense, "gv_cg_solve_aat: the N-space solver needs people statistics, not available for methylation data");
     NEED(c, c->pc_kind == 0, "gv_cg_solve_aat: the N-space solver is refused while the LD preconditioner is set (gv_set_cg_precond kind 1)");
     NEED(c, c->mave_p, "gv_cg_solve_aat: gv_people_stats must run first");
@@ -1002,6 +1003,7 @@ int gv_cg_solve_aat2(gv_ctx* c, const gv_vec* v_a, const gv_vec* mu_start_a, con
 int gv_cg_solve_aat2w(gv_ctx* c, gv_vec* v_a, const gv_vec* mu_start_a, const gv_vec* v_b, double tau, double gam2,
                       int max_iter, gv_vec* mu_a, gv_vec* at_mu_a, gv_vec* mu_b, gv_cg_stats* st_a, gv_cg_stats* st_b,
                       double* relres_a, double* relres_b, gv_vec* aat_mu_a, gv_vec* ata_mu_b, const gv_aat_warm* wm) {
+    REFUSE_DOSAGE(c, "gv_cg_solve_aat2w", "the N-space solver needs people statistics");
     NEED(c, !c->have_dense, "gv_cg_solve_aat2w: the N-space solver needs people statistics, not available for methylation data");
     NEED(c, c->pc_kind == 0, "gv_cg_solve_aat2w: the N-space solver is refused while the LD preconditioner is set (gv_set_cg_precond kind 1)");
     gv_aat_warm nowarm{};

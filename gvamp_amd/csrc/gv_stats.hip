@@ -30,7 +30,11 @@ int gv_marker_stats(gv_ctx* c, double alpha_scale) {
     pc_invalidate(c, false);
     if (c->have_dense) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
         NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
-        gvd::stats(c->stream, c->dense, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale, c->mave, c->msig);
+        if (c->dense_bits)      // compact dense data: the same statistics in code units
+            gvd::dosage_stats(c->stream, c->dcodes, c->dense_bits, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale,
+                              c->dense_scale, c->dense_mu, c->mave, c->msig);
+        else
+            gvd::stats(c->stream, c->dense, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale, c->mave, c->msig);
         c->alpha_scale = alpha_scale;
         KCHK(c);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -65,6 +69,7 @@ int gv_get_marker_stats(gv_ctx* c, double* mave, double* msig) {
 // ---- --use-XXT-denoiser 1: LMMSE through CG in N-space (denoiserXXT.cpp), matrix-free ------------------------------
 // data::compute_people_statistics (data.cpp:558-716): three table passes of the fp64 Ax kernel over the raw rows.
 int gv_people_stats(gv_ctx* c, double* mave_people, double* msig_people, double* numb_people) {
+    REFUSE_DOSAGE(c, "gv_people_stats", "the dense kinds have no people statistics");
     NEED(c, !c->have_dense, "gv_people_stats: not available for methylation data (the reference's meth branch of "
                             "compute_people_statistics, data.cpp:633-672, never reduces or finalises its sums)");
     NEED(c, c->have_stats && c->mask2, "gv_people_stats: marker statistics must be computed first");
@@ -128,6 +133,7 @@ static int marker_sums_p_p2_f64(gv_ctx* c, const double* p, double* p2_scratch, 
 // chrom == NULL: leave-one-out (the marker's own effect is added back analytically); else leave-one-chromosome-out.
 static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
                       double* pvals, double* chrom_pred = nullptr) {
+    REFUSE_DOSAGE(c, "gv_pvals", "the dense kinds compute no p-values");
     NEED(c, !c->have_dense, "gv_pvals: not available for methylation data (the reference's meth branch of pvals_calc, "
                             "data.cpp:1187-1223, computes and stores nothing)");
     NEED(c, z1->space == GV_SPACE_N && y->space == GV_SPACE_N && x1_hat->space == GV_SPACE_M, "gv_pvals: bad vector spaces");

@@ -47,6 +47,14 @@ std::vector<std::string> split_ws(const std::string& line) {
 }
 }  // namespace
 
+namespace {
+int dosage_bits(const std::string& type_data) { return type_data == "dosage8" ? 8 : (type_data == "dosage16" ? 16 : 0); }
+void check_type_data(const std::string& type_data) {
+    if (type_data != "bed" && type_data != "meth" && !dosage_bits(type_data))
+        die("FATAL: type_data must be \"bed\", \"meth\", \"dosage8\" or \"dosage16\", not \"" + type_data + "\"");
+}
+}  // namespace
+
 void data::open_device(int device, int kernel_mode) {
     if (device < 0) device = gv_env_local_rank();
     if (gv_env_nranks() > 1) (void)gv_bind_host_numa(device, nullptr);   // one process per GPU: stay on the CPUs next to it
@@ -117,9 +125,11 @@ void gv_host_finalize() {
 void data::push_mask() { ck(ctx, gv_set_mask(ctx, mask4.data(), nonas), "gv_set_mask"); }
 
 data::data(std::vector<double> y, std::string genofp, const int N, const int M, const int Mt, const int S,
-           const int rank, std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode)
-    : bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), phen_data(y), alpha_scale(alpha_scale) {
-    if (type_data != "bed" && type_data != "meth") die("FATAL: type_data must be \"bed\" or \"meth\", not \"" + type_data + "\"");
+           const int rank, std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode,
+           double dosage_scale)
+    : bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), phen_data(y), alpha_scale(alpha_scale),
+      dosage_scale(dosage_scale) {
+    check_type_data(type_data);
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
     mask4.assign(mbytes, 0x0F);                       // data.cpp:86-89
@@ -133,6 +143,9 @@ data::data(std::vector<double> y, std::string genofp, const int N, const int M, 
     if (type_data == "meth") {                        // data.cpp:107-110
         methfp = genofp;
         read_methylation_data();
+    } else if (dosage_bits(type_data)) {
+        methfp = genofp;
+        read_dosage_data();
     } else {
         bedfp = genofp;
         read_genotype_data();
@@ -141,9 +154,10 @@ data::data(std::vector<double> y, std::string genofp, const int N, const int M, 
 }
 
 data::data(std::string fp, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
-           std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode)
-    : phenfp(fp), bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), alpha_scale(alpha_scale) {
-    if (type_data != "bed" && type_data != "meth") die("FATAL: type_data must be \"bed\" or \"meth\", not \"" + type_data + "\"");
+           std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode, double dosage_scale)
+    : phenfp(fp), bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), alpha_scale(alpha_scale),
+      dosage_scale(dosage_scale) {
+    check_type_data(type_data);
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
     read_phen();
@@ -152,6 +166,9 @@ data::data(std::string fp, std::string genofp, const int N, const int M, const i
     if (type_data == "meth") {                        // data.cpp:54-57
         methfp = genofp;
         read_methylation_data();
+    } else if (dosage_bits(type_data)) {
+        methfp = genofp;
+        read_dosage_data();
     } else {
         bedfp = genofp;
         read_genotype_data();
@@ -163,6 +180,8 @@ data::data(gv_ctx* resident, std::vector<double> y, const int N, const int M, co
            const std::vector<unsigned char>* m4, int nonas_, double alpha_scale)
     : N(N), M(M), Mt(Mt), S(S), rank(rank), phen_data(y), alpha_scale(alpha_scale), ctx(resident), owns_ctx(false) {
     if (gv_get_layout(ctx) == 3) type_data = "meth";      // a dense matrix is resident
+    if (gv_get_layout(ctx) == 4) type_data = "dosage8";   // ... of 8- / 16-bit dosage codes
+    if (gv_get_layout(ctx) == 5) type_data = "dosage16";
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
     if (m4) {
@@ -254,6 +273,22 @@ void data::read_methylation_data() {
     ck(ctx, gv_upload_meth_file(ctx, methfp.c_str(), (int64_t)(size_t(S) * size_t(N) * sizeof(double))), "gv_upload_meth_file");
     if (rank == 0)
         std::cout << "reading methylation data took "
+                  << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " seconds." << std::endl;
+}
+
+// [ext] compact dense data: this rank's M x N dosage codes (8 or 16 bits each, marker-major) at byte offset S*N*bits/8, streamed to
+// the device as the methylation matrix is.  No missing entries: hard-call missings are mean-imputed before the codes are written.
+void data::read_dosage_data() {
+    const int bits = dosage_bits(type_data);
+    const size_t size_bytes = size_t(M) * size_t(N) * size_t(bits / 8);
+    if (dosage_scale <= 0) dosage_scale = bits == 8 ? 1.0 / 127.0 : 1.0 / 16384.0;
+    if (rank == 0) std::cout << "dosage file name = " << methfp << " (" << bits << "-bit codes, scale " << dosage_scale << ")" << std::endl;
+    printf("INFO   : rank %d streams %zu bytes (%.3f GB) of dosage codes to the device.\n", rank, size_bytes, double(size_bytes) / 1.0E9);
+    const auto t0 = std::chrono::steady_clock::now();
+    ck(ctx, gv_upload_dosage_file(ctx, methfp.c_str(), (int64_t)(size_t(S) * size_t(N) * size_t(bits / 8)), bits, dosage_scale),
+       "gv_upload_dosage_file");
+    if (rank == 0)
+        std::cout << "reading dosage data took "
                   << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " seconds." << std::endl;
 }
 

@@ -23,6 +23,7 @@ private:
     std::vector<double> mave, msig;    // host copies of the device statistics (get_mave / get_msig)
     std::vector<std::vector<double>> covs;
     double intercept = 0, scale = 1, alpha_scale = 1;
+    double dosage_scale = 0;           // [ext] type_data "dosage8" / "dosage16": value = scale * code; <= 0 = 1/127, 1/16384
     gv_ctx* ctx = nullptr;
     bool owns_ctx = true;
 
@@ -33,11 +34,11 @@ public:
     // data.cpp:69-113 -- phenotype given as a vector, every individual present
     data(std::vector<double> y, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
          std::string type_data = "bed", double alpha_scale = 1, std::string bimfp = "", int device = -1,
-         int kernel_mode = 1);
+         int kernel_mode = 1, double dosage_scale = 0);
     // data.cpp:30-61 -- phenotype file (.phen) with NA handling
     data(std::string fp, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
          std::string type_data = "bed", double alpha_scale = 1, std::string bimfp = "", int device = -1,
-         int kernel_mode = 1);
+         int kernel_mode = 1, double dosage_scale = 0);
     // [ext] adopt a context whose genotype shard is already resident (synthetic shards, bench, tests).
     // The context's mask is replaced by the full mask unless mask4 is given.
     data(gv_ctx* resident, std::vector<double> y, const int N, const int M, const int Mt, const int S, const int rank,
@@ -68,6 +69,7 @@ public:
     void read_phen();                       // data.cpp:128-192
     void read_genotype_data();              // data.cpp:201-234
     void read_methylation_data();           // data.cpp:241-278 (type_data == "meth")
+    void read_dosage_data();                // [ext] type_data == "dosage8" / "dosage16": 8- / 16-bit dosage codes
     std::vector<int> read_chromosome_info(std::string bim_file);   // data.cpp:346-380
     void compute_markers_statistics();      // data.cpp:392-546
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled

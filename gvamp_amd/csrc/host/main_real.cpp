@@ -45,7 +45,8 @@ int main(int argc, char** argv) {
     const Options opt(argc, argv);
     const int rank = gv_env_rank();
     const std::string mode = opt.get_run_mode();
-    const std::string type_data = "bed";
+    const std::string type_data = opt.get_geno_format();      // [ext] --geno-format: "bed", or "dosage8" / "dosage16" code matrices
+    const double dscale = opt.get_dosage_scale();
     const double alpha_scale = opt.get_alpha_scale();
     const std::string bimfp = opt.get_bim_file();
     const int dev = opt.get_device(), km = opt.get_kernel_mode();
@@ -61,7 +62,7 @@ int main(int argc, char** argv) {
         std::vector<double> MS = divide_work(Mt);
         const int M = (int)MS[0], S = (int)MS[1];
         need_phen(opt.get_phen_files(), "--phen-files");
-        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km);
+        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale);
         // infere: gam1 = 1e-6, gamw from --h2 (:64-69); restart: both from --gam1-init / --gamw-init (:381-382), r1 is
         // reloaded from --estimate-file inside infere_linear (vamp.cpp:226-233)
         const double gam1 = (mode == "restart") ? opt.get_gam1_init() : 1e-6;
@@ -74,7 +75,7 @@ int main(int argc, char** argv) {
         const int M_test = (int)MS[0], S_test = (int)MS[1];
         need_phen(opt.get_phen_files_test(), "--phen-files-test");
         data dataset_test(opt.get_phen_files_test()[0], opt.get_bed_file_test(), N_test, M_test, Mt_test, S_test, rank,
-                          type_data, alpha_scale, bimfp, dev, km);
+                          type_data, alpha_scale, bimfp, dev, km, dscale);
         std::vector<double> y_test = dataset_test.get_phen();
         const std::string est = opt.get_estimate_file();
         const size_t dot = est.find("."), pos_it = est.rfind("it");
@@ -115,7 +116,7 @@ int main(int argc, char** argv) {
         std::vector<double> x_est;
         double intercept, scale;
         {
-            data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km);
+            data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale);
             vamp emvamp(M, 1e-6, initial_gamw(opt), std::vector<double>(M, 0.0), rank, opt);
             x_est = infere_or_exit(emvamp, &dataset);
             intercept = dataset.get_intercept();
@@ -124,7 +125,7 @@ int main(int argc, char** argv) {
         if (rank == 0) std::cout << "intercept = " << intercept << std::endl << "scale = " << scale << std::endl;
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         data dataset_test(opt.get_phen_files_test()[0], opt.get_bed_file_test(), N_test, M, Mt_test, S, rank, type_data,
-                          alpha_scale, bimfp, dev, km);
+                          alpha_scale, bimfp, dev, km, dscale);
         std::vector<double> y_test = dataset_test.get_phen();
         double err2 = 0;
         const double R2 = test_r2(dataset_test, x_est, N_test, y_test, &err2, intercept, scale);   // :262-272
@@ -139,7 +140,7 @@ int main(int argc, char** argv) {
         std::vector<double> MS = divide_work(Mt);
         const int M = (int)MS[0], S = (int)MS[1];
         need_phen(opt.get_phen_files(), "--phen-files");
-        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km);
+        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale);
         const std::string est = opt.get_estimate_file();
         const size_t dot = est.rfind("."), pos_it = est.rfind("it");
         const std::string ext = est.substr(dot + 1);
@@ -170,7 +171,7 @@ int main(int argc, char** argv) {
         std::vector<double> MS = divide_work(Mt_test);
         const int M_test = (int)MS[0], S_test = (int)MS[1];
         data dataset_test(std::vector<double>(N_test, 0.0), opt.get_bed_file_test(), N_test, M_test, Mt_test, S_test, rank,
-                          type_data, alpha_scale, bimfp, dev, km);
+                          type_data, alpha_scale, bimfp, dev, km, dscale);
         const std::string est = opt.get_estimate_file();
         const std::string ext = est.substr(est.find(".") + 1);
         const std::string pre = opt.get_out_dir() + opt.get_out_name();

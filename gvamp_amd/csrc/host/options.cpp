@@ -133,6 +133,16 @@ void Options::read_command_line_options(int argc, char** argv) {
             fatal(std::string("FATAL  : option --cg-precond-window has to be 32, 64 or 128! (") + a + " was passed)");
         cg_precond_window = atoi(a);
     };
+    H["--geno-format"] = [&](const char* a) {
+        if (strcmp(a, "bed") && strcmp(a, "dosage8") && strcmp(a, "dosage16"))
+            fatal(std::string("FATAL  : option --geno-format has to be bed, dosage8 or dosage16! (") + a + " was passed)");
+        geno_format = a;
+    };
+    H["--dosage-scale"] = [&](const char* a) {
+        if (!(atof(a) > 0) || atof(a) > 1e300)
+            fatal(std::string("FATAL  : option --dosage-scale has to be a positive number! (") + a + " was passed)");
+        dosage_scale = atof(a);
+    };
     H["--resident-layout"] = [&](const char* a) {      // read by data::open_device (every data object of the run)
         resident_layout = atoi(a);
         setenv("GVAMP_RESIDENT_LAYOUT", a, 1);

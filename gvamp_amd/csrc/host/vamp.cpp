@@ -17,6 +17,8 @@
 #include "utilities.hpp"
 
 namespace {
+// what a dense dataset is called in the messages that refuse it (gv_get_layout: 3 fp64, 4 / 5 dosage codes)
+const char* dense_kind_name(int layout) { return layout == 3 ? "methylation data" : "compact dosage data"; }
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 }
 
@@ -126,14 +128,15 @@ std::vector<double> vamp::infere(data* dataset) {
     ctx = dataset->get_ctx();
     if (cg_precond == 1 && reverse == 1)
         throw std::invalid_argument("--cg-precond ld is not available with --use-XXT-denoiser 1 (the N-space solve has no LD preconditioner)");
-    if (cg_precond == 1 && gv_get_layout(ctx) == 3)
-        throw std::invalid_argument("--cg-precond ld is not available for methylation data (genotype windows only)");
+    if (cg_precond == 1 && gv_get_layout(ctx) >= 3)
+        throw std::invalid_argument(std::string("--cg-precond ld is not available for ") + dense_kind_name(gv_get_layout(ctx)) +
+                                    " (genotype windows only)");
     if (gv_set_cg_precond(ctx, cg_precond, cg_precond_window)) throw std::runtime_error(gv_last_error(ctx));
     if (reverse == 1) {                                       // vamp.cpp:169-170
         ctx = dataset->get_ctx();
-        if (gv_get_layout(ctx) == 3) {
-            std::cout << "FATAL: --use-XXT-denoiser 1 is not available for methylation data (the reference's meth branch of "
-                         "compute_people_statistics never reduces or finalises its sums)" << std::endl;
+        if (gv_get_layout(ctx) >= 3) {
+            std::cout << "FATAL: --use-XXT-denoiser 1 is not available for " << dense_kind_name(gv_get_layout(ctx))
+                      << " (the reference's meth branch of compute_people_statistics never reduces or finalises its sums)" << std::endl;
             exit(EXIT_FAILURE);
         }
         ck(gv_people_stats(ctx, nullptr, nullptr, nullptr), "gv_people_stats (--use-XXT-denoiser needs --kernel-mode 0 or both layouts)");
@@ -758,8 +761,8 @@ std::vector<double> vamp::infere_linear(data* dataset) {
         ck(gv_vec_download(ctx, x1_hat, x1_hat_stored.data()), "gv_vec_download");
         for (double& v : x1_hat_stored) v /= sqrtN;
     }
-    if (store_pvals == 1 && gv_get_layout(ctx) == 3) {
-        if (rank == 0) std::cout << "p-values: skipped for methylation data (the reference's meth branch of pvals_calc stores nothing)" << std::endl;
+    if (store_pvals == 1 && gv_get_layout(ctx) >= 3) {
+        if (rank == 0) std::cout << "p-values: skipped for " << dense_kind_name(gv_get_layout(ctx)) << " (the reference's meth branch of pvals_calc stores nothing)" << std::endl;
     } else if (store_pvals == 1) {                                          // vamp.cpp:761-776
         // z1 / x1_hat of the last completed iteration, y = filtered phenotype (all still resident on the device)
         const double t0 = now_s();

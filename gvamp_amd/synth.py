@@ -79,3 +79,29 @@ def synth_meth(N, M, seed, S=0):
             s = (r & f) + ((r >> np.uint64(16)) & f) + ((r >> np.uint64(32)) & f) + (r >> np.uint64(48))
             out[m0:m1] = centre[m0:m1, None] + s.astype(np.float64) * 2.0 ** -19
     return out
+
+
+def synth_dosage(N, M, seed, bits, S=0):
+    """Host twin of gv_synth_dosage (csrc/gv_dense.hip:k_synth_dosage): the M x N dosage codes (marker-major uint8 / uint16) of global
+    markers S..S+M.  Genotype g in {0, 1, 2} from two allele draws at the marker's frequency (655 + h mod 32113) / 65536, about
+    0.01-0.5, plus a jitter, the product of two 16-bit hash fields: code = g * 3 * 2^(bits-3) + (jitter >> (18 - bits)).  Integer
+    arithmetic only: the two agree bit for bit."""
+    if bits not in (8, 16):
+        raise ValueError("synth_dosage: bits must be 8 or 16")
+    out = np.empty((M, N), dtype=np.uint8 if bits == 8 else np.uint16)
+    with np.errstate(over="ignore"):
+        g = np.arange(S, S + M, dtype=np.uint64)
+        hm = _splitmix64(np.uint64(seed) ^ (g * np.uint64(0xD1342543DE82EF95)))
+        base = _splitmix64(hm + np.uint64(0x632BE59BD9B4E019))
+        maf = np.uint64(655) + hm % np.uint64(32113)
+        n = np.arange(N, dtype=np.uint64)
+        f = np.uint64(0xFFFF)
+        step = max(1, (1 << 22) // max(N, 1))
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            r = _splitmix64(base[m0:m1, None] + n[None, :])
+            q = maf[m0:m1, None]
+            geno = ((r & f) < q).astype(np.uint64) + (((r >> np.uint64(16)) & f) < q).astype(np.uint64)
+            jit = (((r >> np.uint64(32)) & f) * (r >> np.uint64(48))) >> np.uint64(16)
+            out[m0:m1] = (geno * np.uint64(3 << (bits - 3)) + (jit >> np.uint64(18 - bits))).astype(out.dtype)
+    return out

@@ -89,6 +89,32 @@ int gv_upload_meth_file(gv_ctx* ctx, const char* path, int64_t offset);
  * an 11-bit per-marker centre c_g and four 16-bit hash fields u_k (an Irwin-Hall sum): every value is exact in fp64, so
  * gvamp_amd.synth.synth_meth(N, M, seed, S) reproduces the matrix bit for bit on the host. */
 int gv_synth_meth(gv_ctx* ctx, uint64_t seed);
+/* ---- compact dense data: dosages as 8- or 16-bit codes (`data` with type_data == "dosage8" / "dosage16") -----------------------
+ * The dense kind above at 1 or 2 bytes per entry: X[m][n] = scale * B[m][n] with B unsigned integer codes, M*N of them, marker-major,
+ * resident with the row pitch padded to a multiple of 64 codes (zeros in the padding).  PLINK 2 stores a dosage as a 16-bit code
+ * (scale 1/16384); 8-bit codes are the usual compressed form (scale 1/127).  There are NO missing entries, as in the reference's
+ * meth branch: hard-call missings must be mean-imputed upstream, before the codes are written.  Uploading any kind -- bed, meth,
+ * dosage -- replaces the dataset held before; gv_get_layout returns 4 (8-bit) or 5 (16-bit) while codes are resident.
+ * Semantics are exactly those of the dense fp64 kind: statistics over the individuals with a phenotype, gv_ax applies no mask
+ * and writes exact zeros at the pad slots, gv_atx uses p as given, the two-vector forms read the matrix once and each slot is
+ * bit-identical to the one-vector call, results are bit-reproducible (no atomics), offsets are 64-bit, kernel mode and layout
+ * are ignored.  The statistics are DEFINED in code units (this is the contract, not an implementation detail):
+ *   mu'  = (sum_present b) / nonas, the integer sum exact;       mave = scale * mu'
+ *   q    = sum_present (b - mu')^2 (second pass);                msig = 1 if q == 0 else (scale * sqrt(q / (nonas - 1)))^-alpha_scale
+ * so a constant column has q == 0 and msig = 1 exactly whatever the scale (in value units a non-dyadic scale such as 1/127 hides
+ * it behind rounding).  The products form (b - mu') per entry and carry msig * scale in the per-marker weight.
+ * Not available (non-zero return, the message names compact dosage data): everything the dense fp64 kind refuses --
+ * gv_download_bed, gv_people_stats, gv_cg_solve_aat*, gv_pvals_*, gv_set_decomp -- and gv_set_cg_precond kind 1.
+ * bits other than 8 or 16 and a scale that is not positive and finite are refused. */
+/* codes: M*N codes of this shard, marker-major: uint8_t when bits == 8, uint16_t (host byte order) when bits == 16. */
+int gv_upload_dosage(gv_ctx* ctx, const void* codes, size_t n, int bits, double scale);
+/* The same from a file: M*N codes starting at byte `offset` of `path` -- offset = S*N*bits/8 -- streamed through the bounded
+ * pinned buffers of gv_upload_meth_file; a file that ends early is reported with the marker it ends in. */
+int gv_upload_dosage_file(gv_ctx* ctx, const char* path, int64_t offset, int bits, double scale);
+/* Synthetic codes generated on the device (scale 1/127 for 8 bits, 1/16384 for 16): per-marker allele frequencies spread over about
+ * 0.01-0.5, genotype g in {0, 1, 2} from two allele draws, code = g * 3 * 2^(bits-3) + jitter with jitter < 2^(bits-2): the full
+ * code range is used (codes >= 128 / >= 32768 occur).  gvamp_amd.synth.synth_dosage(N, M, seed, bits, S) reproduces it bit for bit. */
+int gv_synth_dosage(gv_ctx* ctx, uint64_t seed, int bits);
 
 /* The PLINK rows back from HBM: only when the raw row layout is resident, i.e. gv_set_layout(ctx, 1, ..) was called before
  * the ingest (not the default). */
@@ -116,7 +142,8 @@ int gv_atx(gv_ctx* ctx, const double* p, double* out);
  * section B): the rows stream through a chunk buffer at ingest and only the re-encoded layout stays resident, so a 100 GB
  * shard occupies 100 GB (or 200 GB) of HBM, not 300.  raw_rows = 1 is needed by kernel mode 0 and gv_download_bed only. */
 int gv_set_layout(gv_ctx* ctx, int raw_rows, int stripes);
-int gv_get_layout(const gv_ctx* ctx);   /* resident now: 0 none, 1 two stripe sets, 2 tile layout, 3 dense fp64 matrix (meth) */
+int gv_get_layout(const gv_ctx* ctx);   /* resident now: 0 none, 1 two stripe sets, 2 tile layout, 3 dense fp64 matrix (meth),
+                                         * 4 / 5 dense 8- / 16-bit dosage codes */
 /* kernel family for Ax/ATx: 1 (default) = i8 MFMA fixed-point kernels on the re-encoded layout (0.8 of the HBM roofline,
  * results within 2e-14 of fp64 sums, bit-reproducible); 0 = fp64 VALU kernels on the raw rows (parity anchor, 4-9 % of the
  * roofline; needs gv_set_layout(ctx, 1, ..) before ingest); 2 = two-level fixed point on the re-encoded layout (below). */
