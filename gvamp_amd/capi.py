@@ -27,6 +27,7 @@ EXPORTS = [
     "gv_upload_meth", "gv_upload_meth_file", "gv_synth_meth", "gv_upload_dosage", "gv_upload_dosage_file", "gv_synth_dosage",
     "gv_huber_denoise", "gv_huber_delta",
     "gv_set_cg_precond", "gv_precond_info", "gv_precond_window_gram", "gv_precond_apply",
+    "gv_assoc_loo", "gv_assoc_loco",
 ]
 
 
@@ -36,6 +37,11 @@ class GvError(RuntimeError):
 
 class DotSpec(C.Structure):            # gv_dot_spec (include/gvamp.h)
     _fields_ = [("xa", C.c_void_p), ("xb", C.c_void_p), ("ya", C.c_void_p), ("yb", C.c_void_p), ("sync", C.c_int)]
+
+
+class AssocOut(C.Structure):           # gv_assoc_out
+    _fields_ = [("beta", C.POINTER(C.c_double)), ("se", C.POINTER(C.c_double)), ("t", C.POINTER(C.c_double)),
+                ("p", C.POINTER(C.c_double))]
 
 
 class CgStats(C.Structure):
@@ -181,6 +187,8 @@ def load():
     L.gv_pvals_loo.argtypes = [vp, vp, vp, vp, dp]
     L.gv_pvals_loco.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int), dp]
     L.gv_pvals_loco_pred.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int), dp, dp]
+    L.gv_assoc_loo.argtypes = [vp, vp, vp, vp, C.POINTER(AssocOut)]
+    L.gv_assoc_loco.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(AssocOut), dp]
     L.gv_comm_unique_id.argtypes = [C.c_void_p]
     L.gv_comm_init.argtypes = [vp, C.c_int, C.c_int, C.c_void_p]
     L.gv_comm_init_local.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -588,6 +596,23 @@ class Shard:
             assert ch.size == self.M
             self._ck(self.L.gv_pvals_loco(self.h, z1.h, y.h, x1_hat.h, ch.ctypes.data_as(C.POINTER(C.c_int)), _dp(out)))
         return out[:self.M].copy()
+
+    def assoc_calc(self, z1, y, x1_hat, chrom=None, want_pred=False):
+        """gv_assoc_loo (chrom None) / gv_assoc_loco on device handles: the whole per-marker test, a dict of beta, se, t, p (M
+        each); beta is the effect per unit of the standardised column.  want_pred (LOCO): also the predictors[23, 4*mbytes]."""
+        res = {k: np.zeros(max(self.M, 1)) for k in ("beta", "se", "t", "p")}
+        out = AssocOut(*[_dp(res[k]) for k in ("beta", "se", "t", "p")])
+        if chrom is None:
+            assert not want_pred, "the chromosome predictors belong to the LOCO test"
+            self._ck(self.L.gv_assoc_loo(self.h, z1.h, y.h, x1_hat.h, C.byref(out)))
+            return {k: v[:self.M].copy() for k, v in res.items()}
+        ch = np.ascontiguousarray(chrom, dtype=np.int32)
+        assert ch.size == self.M
+        pred = np.zeros((23, 4 * self.mbytes)) if want_pred else None
+        self._ck(self.L.gv_assoc_loco(self.h, z1.h, y.h, x1_hat.h, ch.ctypes.data_as(C.POINTER(C.c_int)), C.byref(out),
+                                      _dp(pred) if want_pred else None))
+        res = {k: v[:self.M].copy() for k, v in res.items()}
+        return (res, pred) if want_pred else res
 
     def allreduce_host(self, a):
         a = np.ascontiguousarray(a, dtype=np.float64)

@@ -23,7 +23,10 @@
 //                loads four 4-code pieces per row (piece k at 256 k + 4 lane, so every wave load is contiguous) and keeps its 16
 //                entries of p in registers across the R rows.
 //   Ax         : as the fp64 kernel with a 16-byte load per lane: 16 (u8) or 8 (u16) individuals per lane, 4096 / 2048 per workgroup.
+//   assoc      : the per-marker association test (gv_assoc_*): the streaming structure of ATx with R = 4 rows per wave taken from an
+//                index list, three sums per row and the regression test in the epilogue.
 #include "gv_internal.h"
+#include "gv_pval_dev.h"
 
 namespace {
 
@@ -430,6 +433,130 @@ __global__ __launch_bounds__(256) void k_dosage_atx(const T* __restrict__ A, int
     }
 }
 
+// ---- association test (gv_assoc_*; data::pvals_calc / pvals_calc_LOCO restated for codes with b == 1).  First the residual:
+// p = y - z1 (+ add) at the individuals with a phenotype, 0 at NA and pad slots whatever the caller left in y, and the block partials
+// {sum p, sum p^2} (K = 2) that gvk::finalize adds up in its fixed order.  The grid depends on npad alone.
+__global__ __launch_bounds__(256) void k_assoc_prep(const double* __restrict__ y, const double* __restrict__ z1,
+                                                    const double* __restrict__ add, const uint32_t* __restrict__ mask2, int64_t npad,
+                                                    double* __restrict__ p, double* __restrict__ partial) {
+    __shared__ double sh[2][4];
+    double s1 = 0.0, s2 = 0.0;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < npad; j += (int64_t)gridDim.x * 256) {
+        double v = 0.0;
+        if ((mask2[j >> 4] >> (2 * (j & 15))) & 1u) {
+            v = y[j] - z1[j];
+            if (add) v += add[j];
+        }
+        p[j] = v;
+        s1 += v;
+        s2 = fma(v, v, s2);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    if ((threadIdx.x & (WAVE - 1)) == 0) { sh[0][threadIdx.x >> 6] = s1; sh[1][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        partial[(int64_t)blockIdx.x * 2 + threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
+}
+
+// The marker pass: one wave owns R rows of the index list `rows` (NULL: the identity) and walks the individuals as k_dosage_atx does.
+// Per row three sums with d = code - mu' formed per entry: sum d p, sum d na, sum (d na) d, each over the lane's entries in ascending
+// column step, piece and entry order, then the fixed butterfly -- a row's bits depend neither on R nor on the group or the list it
+// arrives in.  (d na) is a select: d * 1 and d * 0 of a finite d, without the multiply.  Lane 0 runs the test (gvp::dosage_stats).
+template <typename T, int R>
+__global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, int64_t N, int64_t pitch, const int64_t* __restrict__ rows,
+                                                      int64_t nrows, const double* __restrict__ p, const uint32_t* __restrict__ mask2,
+                                                      const double* __restrict__ dmu, const double* __restrict__ msig, double wscale,
+                                                      const double* __restrict__ psums, double nonas,
+                                                      const double* __restrict__ xself, double self_scale, double* __restrict__ beta,
+                                                      double* __restrict__ se, double* __restrict__ tstat, double* __restrict__ pval) {
+    typedef typename Code<T>::Quad Quad;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * R;
+    if (i0 >= nrows) return;
+    const T* row[R];
+    double mu[R], acc[R][3];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int64_t ir = i0 + r < nrows ? i0 + r : nrows - 1;      // (a group's tail re-reads the last row; nothing is written for it)
+        const int64_t mr = rows ? rows[ir] : ir;
+        row[r] = A + mr * pitch + 4 * lane;
+        mu[r] = dmu[mr];
+        acc[r][0] = acc[r][1] = acc[r][2] = 0.0;
+    }
+    int64_t c0 = 0;
+    for (; c0 + ATX_STEP <= N; c0 += ATX_STEP) {
+        Quad x[R][4];
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int k = 0; k < 4; k++) x[r][k] = ntquad<T>(row[r] + c0 + 256 * k);
+        double q[4][4];
+        uint32_t mk[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t j0 = c0 + 256 * k + 4 * lane;
+            const double2* q2 = reinterpret_cast<const double2*>(p + j0);
+            const double2 q0 = q2[0], q1 = q2[1];
+            q[k][0] = q0.x; q[k][1] = q0.y; q[k][2] = q1.x; q[k][3] = q1.y;
+            mk[k] = mask2[j0 >> 4] >> (2 * (j0 & 15));
+        }
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const double d = (double)Code<T>::get(x[r][k], e) - mu[r];
+                    const double dn = (mk[k] >> (2 * e)) & 1u ? d : 0.0;
+                    acc[r][0] = fma(d, q[k][e], acc[r][0]);
+                    acc[r][1] += dn;
+                    acc[r][2] = fma(dn, d, acc[r][2]);
+                }
+    }
+    if (c0 < N) {      // the last, partial step: a piece starts below N or is skipped; j0 < N implies j0 + 3 < pitch <= npad
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t j0 = c0 + 256 * k + 4 * lane;
+            if (j0 < N) {
+                double q[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++) q[e] = j0 + e < N ? p[j0 + e] : 0.0;
+                const uint32_t mk = mask2[j0 >> 4] >> (2 * (j0 & 15));
+#pragma unroll
+                for (int r = 0; r < R; r++) {
+                    const Quad x = ntquad<T>(row[r] + c0 + 256 * k);
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (j0 + e < N) {
+                            const double d = (double)Code<T>::get(x, e) - mu[r];
+                            const double dn = (mk >> (2 * e)) & 1u ? d : 0.0;
+                            acc[r][0] = fma(d, q[e], acc[r][0]);
+                            acc[r][1] += dn;
+                            acc[r][2] = fma(dn, d, acc[r][2]);
+                        }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++)
+#pragma unroll
+        for (int v = 0; v < 3; v++) acc[r][v] = wave_sum(acc[r][v]);
+    if (lane == 0) {
+        const double sp = psums[0], sp2 = psums[1];
+#pragma unroll
+        for (int r = 0; r < R; r++)
+            if (i0 + r < nrows) {
+                const int64_t m = rows ? rows[i0 + r] : i0 + r;
+                const double cself = xself ? xself[m] * self_scale : 0.0;
+                const gvp::Reg1d res = gvp::dosage_stats(acc[r][0], acc[r][1], acc[r][2], msig[m] * wscale, sp, sp2, nonas, cself);
+                beta[m] = res.beta; se[m] = res.se; tstat[m] = res.t; pval[m] = res.p;
+            }
+    }
+}
+
 // ---- Ax, first stage: partial[seg][j] = sum over the segment's markers i of (b[i][j] - mu'[i]) * (msig[i] scale_x v[i]), markers in
 // ascending order; a lane owns the 16 / sizeof(T) individuals of one 16-byte load.  Second stage: k_dense_ax_reduce.
 template <typename T, int NV>
@@ -615,6 +742,28 @@ void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, 
         dosage_ax_t(s, nv, sh, (const uint8_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
     else
         dosage_ax_t(s, nv, sh, (const uint16_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
+}
+
+constexpr int ASSOC_R = 4;
+void assoc_prep(hipStream_t s, const double* y, const double* z1, const double* add, const uint32_t* mask2, int64_t npad, double* p,
+                double* partial, double* sums) {
+    const int64_t b = (npad + 255) / 256;
+    const int nb = (int)(b < 1 ? 1 : (b > RED_BLOCKS ? RED_BLOCKS : b));
+    hipLaunchKernelGGL(k_assoc_prep, dim3(nb), dim3(256), 0, s, y, z1, add, mask2, npad, p, partial);
+    gvk::finalize(s, partial, nb, 2, sums);
+}
+
+void dosage_assoc(hipStream_t s, const void* A, int bits, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows, const double* p,
+                  const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums, double nonas,
+                  const double* xself, double self_scale, double* beta, double* se, double* tstat, double* pval) {
+    if (nrows <= 0) return;
+    const dim3 g(nblk(nrows, 4 * ASSOC_R));
+    if (bits == 8)
+        hipLaunchKernelGGL((k_dosage_assoc<uint8_t, ASSOC_R>), g, dim3(256), 0, s, (const uint8_t*)A, N, pitch, rows, nrows, p, mask2, dmu,
+                           msig, wscale, psums, nonas, xself, self_scale, beta, se, tstat, pval);
+    else
+        hipLaunchKernelGGL((k_dosage_assoc<uint16_t, ASSOC_R>), g, dim3(256), 0, s, (const uint16_t*)A, N, pitch, rows, nrows, p, mask2, dmu,
+                           msig, wscale, psums, nonas, xself, self_scale, beta, se, tstat, pval);
 }
 
 }  // namespace gvd

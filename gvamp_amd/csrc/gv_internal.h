@@ -258,7 +258,8 @@ void denoise(hipStream_t s, const double* r1, int64_t n, double gam1, const gv_p
 void prior_estep(hipStream_t s, const double* r1, int64_t n, double gam1, double lambda, const gv_prior& om_vars,
                  double* partial, double* out);               // out[0..1+2(L-1))
 void pvals_test(hipStream_t s, const uint32_t* cnt, const double* mave, const double* msig, const double* sums4,
-                const double* xself, double self_scale, const int* chrom, int ch, int64_t M, double* pvals);
+                const double* xself, double self_scale, const int* chrom, int ch, int64_t M, double* pvals, double* beta = nullptr,
+                double* se = nullptr, double* tstat = nullptr);      // beta / se / tstat: all three (gv_assoc_*) or none
 void copy_bw(hipStream_t s, const double* src, double* dst, int64_t n);
 void read_bw(hipStream_t s, const void* src, int64_t blocks_per_wave, int64_t nwaves, unsigned int* sink, int perm = 0);
 }  // namespace gvk
@@ -296,6 +297,15 @@ void dosage_atx(hipStream_t s, int nv, const void* A, int bits, int64_t M, int64
                 const double* addxb, double tau, double gam2);
 void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, int64_t M, int64_t pitch, const double* va,
                        const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad);
+// gv_assoc_* on compact dense data.  assoc_prep: p[npad] = y - z1 (+ add when not NULL) at the individuals with a phenotype, 0 at NA and
+// pad slots; sums[0..2) = {sum p, sum p^2} through the block partials (>= 2 * RED_BLOCKS doubles) in a fixed order.  dosage_assoc: the
+// test of the rows rows[0..nrows) (NULL: rows 0..nrows) against p; beta / se / tstat / pval are M-space device vectors written at the
+// tested rows only.  xself != NULL (leave-one-out): the row's own effect xself[m] * self_scale is added back analytically.
+void assoc_prep(hipStream_t s, const double* y, const double* z1, const double* add, const uint32_t* mask2, int64_t npad, double* p,
+                double* partial, double* sums);
+void dosage_assoc(hipStream_t s, const void* A, int bits, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows, const double* p,
+                  const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums, double nonas,
+                  const double* xself, double self_scale, double* beta, double* se, double* tstat, double* pval);
 }  // namespace gvd
 
 // ---- LD-block preconditioner (gv_precond.hip) --------------------------------------------------------------------------------

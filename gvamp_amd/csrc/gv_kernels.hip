@@ -1179,17 +1179,25 @@ __global__ __launch_bounds__(256, LC <= 16 ? 4 : (LC <= 24 ? 3 : 2)) void k_prio
 // One marker per thread.  sums4[4k..] = {sum a p, sum b p, sum a p^2, sum b p^2} of the phenotype residual p over the
 // marker's column (one two-vector pass); the column's own sums are exact, from the genotype counts.  xself != NULL
 // (leave-one-out): the marker's own effect c = xself[k] * self_scale is added back analytically (data.cpp:1145-1148).
-// chrom != NULL (LOCO): only the markers of chromosome ch are tested and written.
+// chrom != NULL (LOCO): only the markers of chromosome ch are tested and written.  WIDE (gv_assoc_*): effect, standard error and t
+// statistic are stored beside the p-value.
+template <bool WIDE>
 __global__ __launch_bounds__(128) void k_pvals_test(const uint32_t* __restrict__ cnt, const double* __restrict__ mave,
                                                     const double* __restrict__ msig, const double* __restrict__ sums4,
                                                     const double* __restrict__ xself, double self_scale,
                                                     const int* __restrict__ chrom, int ch, int64_t M,
-                                                    double* __restrict__ pvals) {
+                                                    double* __restrict__ pvals, double* __restrict__ beta,
+                                                    double* __restrict__ se, double* __restrict__ tstat) {
     const int64_t k = (int64_t)blockIdx.x * 128 + threadIdx.x;
     if (k >= M) return;
     if (chrom && chrom[k] != ch) return;
     const double cself = xself ? xself[k] * self_scale : 0.0;
     const double s4[4] = {sums4[4 * k], sums4[4 * k + 1], sums4[4 * k + 2], sums4[4 * k + 3]};
+    if (WIDE) {
+        const gvp::Reg1d r = gvp::marker_stats(cnt[3 * k], cnt[3 * k + 1], cnt[3 * k + 2], mave[k], msig[k], s4, cself);
+        pvals[k] = r.p; beta[k] = r.beta; se[k] = r.se; tstat[k] = r.t;
+        return;
+    }
     pvals[k] = gvp::marker_pval(cnt[3 * k], cnt[3 * k + 1], cnt[3 * k + 2], mave[k], msig[k], s4, cself);
 }
 
@@ -1532,10 +1540,15 @@ void prior_estep(hipStream_t s, const double* r1, int64_t n, double gam1, double
 }
 
 void pvals_test(hipStream_t s, const uint32_t* cnt, const double* mave, const double* msig, const double* sums4,
-                const double* xself, double self_scale, const int* chrom, int ch, int64_t M, double* pvals) {
+                const double* xself, double self_scale, const int* chrom, int ch, int64_t M, double* pvals, double* beta, double* se,
+                double* tstat) {
     if (M == 0) return;
-    hipLaunchKernelGGL(k_pvals_test, dim3(nblk(M, 128)), dim3(128), 0, s, cnt, mave, msig, sums4, xself, self_scale, chrom,
-                       ch, M, pvals);
+    if (beta)
+        hipLaunchKernelGGL(k_pvals_test<true>, dim3(nblk(M, 128)), dim3(128), 0, s, cnt, mave, msig, sums4, xself, self_scale, chrom,
+                           ch, M, pvals, beta, se, tstat);
+    else
+        hipLaunchKernelGGL(k_pvals_test<false>, dim3(nblk(M, 128)), dim3(128), 0, s, cnt, mave, msig, sums4, xself, self_scale, chrom,
+                           ch, M, pvals, beta, se, tstat);
 }
 
 void copy_bw(hipStream_t s, const double* src, double* dst, int64_t n) {

@@ -238,6 +238,7 @@ struct PvArgs {
     double self_scale;
     const int* chrom;         // LOCO: chromosome of every marker, or NULL
     int ch;
+    double *beta = nullptr, *se = nullptr, *t = nullptr;   // gv_assoc_*: M device doubles each, all three or none (gv_pvals_*)
 };
 void marker_pvals(hipStream_t s, const Plan& pl, const double* y, const double* z1, const double* add, const uint32_t* mask2,
                   int64_t npad, const double* mave, const double* msig, double* pa, double* pb, double* red_partial, const PvArgs& a,

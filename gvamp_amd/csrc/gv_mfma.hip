@@ -1249,7 +1249,9 @@ __device__ __forceinline__ void gather_pieces(const int32_t* __restrict__ partia
 // recombined from the digit planes and handed straight to the regression test (gvp::marker_pval) -- the sums never go through
 // memory (32 MB written and read back at M = 1M when the test was a launch of its own).
 struct FinPvals { const uint32_t* cnt; const double* mave; const double* msig; const double* xself; double self_scale;
-                  const int* chrom; int ch; double* pvals; };
+                  const int* chrom; int ch; double* pvals; double *beta, *se, *t; };
+// WIDE (gv_assoc_*): effect, standard error and t statistic are stored beside the p-value; gv_pvals_* runs the narrow form
+template <bool WIDE>
 __global__ __launch_bounds__(128) void k_fin_pvals(const int32_t* __restrict__ partial, int ksplit, int64_t rows_p, int64_t M,
                                                    const double* __restrict__ scal1, const double* __restrict__ scal2, FinPvals a,
                                                    int64_t nkb, int64_t skL, int64_t piv) {
@@ -1271,6 +1273,11 @@ __global__ __launch_bounds__(128) void k_fin_pvals(const int32_t* __restrict__ p
         s4[2 * v + 1] = sc[1] - sm;
     }
     const double cself = a.xself ? a.xself[m] * a.self_scale : 0.0;
+    if (WIDE) {
+        const gvp::Reg1d r = gvp::marker_stats(a.cnt[3 * m], a.cnt[3 * m + 1], a.cnt[3 * m + 2], a.mave[m], a.msig[m], s4, cself);
+        a.pvals[m] = r.p; a.beta[m] = r.beta; a.se[m] = r.se; a.t[m] = r.t;
+        return;
+    }
     a.pvals[m] = gvp::marker_pval(a.cnt[3 * m], a.cnt[3 * m + 1], a.cnt[3 * m + 2], a.mave[m], a.msig[m], s4, cself);
 }
 
@@ -1637,9 +1644,13 @@ void marker_pvals(hipStream_t s, const Plan& pl, const double* y, const double* 
         q2.ev0 = q2.ev1 = nullptr;
         launch_stream<2>(s, q2, pl.stripes_m, pl.dig0, nullptr, pl.nrg_m, pl.nkb_m, pl.dm[1]);
     }
-    FinPvals f{a.cnt, mave, msig, a.xself, a.self_scale, a.chrom, a.ch, pvals};
-    hipLaunchKernelGGL(k_fin_pvals, dim3(nblk(pl.M, 128)), dim3(128), 0, s, pl.partial, pl.dm[1].ks, pl.nrg_m * 64, pl.M, pl.scal,
-                       pl.scal + 4, f, pl.nkb_m, pl.dm[1].skL, piv_of(pl.dm[1], (pl.nrg_m + 3) / 4));
+    FinPvals f{a.cnt, mave, msig, a.xself, a.self_scale, a.chrom, a.ch, pvals, a.beta, a.se, a.t};
+    if (a.beta)
+        hipLaunchKernelGGL(k_fin_pvals<true>, dim3(nblk(pl.M, 128)), dim3(128), 0, s, pl.partial, pl.dm[1].ks, pl.nrg_m * 64, pl.M, pl.scal,
+                           pl.scal + 4, f, pl.nkb_m, pl.dm[1].skL, piv_of(pl.dm[1], (pl.nrg_m + 3) / 4));
+    else
+        hipLaunchKernelGGL(k_fin_pvals<false>, dim3(nblk(pl.M, 128)), dim3(128), 0, s, pl.partial, pl.dm[1].ks, pl.nrg_m * 64, pl.M, pl.scal,
+                           pl.scal + 4, f, pl.nkb_m, pl.dm[1].skL, piv_of(pl.dm[1], (pl.nrg_m + 3) / 4));
 }
 
 // operands cv / ev (and cv2 / ev2) -> digit buffers of the Ax side.  Two stripe sets: one vector dig0 = [c | e], two vectors

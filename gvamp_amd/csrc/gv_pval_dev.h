@@ -89,6 +89,22 @@ __device__ inline double reg1d_pval(double sumx, double sumsqx, double sumxy, do
     const double t = rxy * sqrt((n - 2) / (1 - rxy * rxy));
     return t_two_sided(fabs(t), n - 2);
 }
+// The whole test result (gv_assoc_*): effect per unit of the standardised column, its standard error, the signed t statistic and the
+// p-value.  s2y .. t and p are reg1d_pval's expressions, token for token and in its order (the p of gv_assoc_* is bit-identical to
+// gv_pvals_*); se = beta / t, evaluated without the quotient so that t == 0 gives no 0/0.
+struct Reg1d { double beta, se, t, p; };
+__device__ inline Reg1d reg1d_stats(double sumx, double sumsqx, double sumxy, double sumy, double sumsqy, double n) {
+    const double s2y = (sumsqy - sumy * sumy / n) / (n - 1), s2x = (sumsqx - sumx * sumx / n) / (n - 1);
+    const double sxy = (sumxy - sumx * sumy / n) / (n - 1);
+    const double rxy = sxy / sqrt(s2x * s2y);
+    const double t = rxy * sqrt((n - 2) / (1 - rxy * rxy));
+    Reg1d r;
+    r.p = t_two_sided(fabs(t), n - 2);
+    r.t = t;
+    r.beta = sxy / s2x;
+    r.se = sqrt((n - 1) / (n - 2) * s2y * (1 - rxy * rxy) / ((n - 1) * s2x));
+    return r;
+}
 // The test of one marker from the sums of a p-value pass: s4 = {sum a p, sum b p, sum a p^2, sum b p^2} of the phenotype residual p
 // over the marker's column; the column's own sums are exact, from the genotype counts (n2, n1, n0 present individuals with a = 2,
 // 1, 0).  cself != 0 (leave-one-out): the marker's own effect is added back analytically (data.cpp:1145-1148).
@@ -101,6 +117,29 @@ __device__ inline double marker_pval(double n2, double n1, double n0, double mu,
     const double sumy = s4[1] + cself * sumx;
     const double sumsqy = s4[3] + 2.0 * cself * svy + cself * cself * sumsqx;
     return reg1d_pval(sumx, sumsqx, sumxy, sumy, sumsqy, count);
+}
+// marker_pval with the whole result: the same sums, in the same expressions
+__device__ inline Reg1d marker_stats(double n2, double n1, double n0, double mu, double sg, const double (&s4)[4], double cself) {
+    const double count = n0 + n1 + n2;
+    const double sumx = sg * (2.0 * n2 + n1 - mu * count);
+    const double sumsqx = sg * sg * (n2 * (2.0 - mu) * (2.0 - mu) + n1 * (1.0 - mu) * (1.0 - mu) + n0 * mu * mu);
+    const double svy = sg * (s4[0] - mu * s4[1]);
+    const double sumxy = svy + cself * sumsqx;
+    const double sumy = s4[1] + cself * sumx;
+    const double sumsqy = s4[3] + 2.0 * cself * svy + cself * cself * sumsqx;
+    return reg1d_stats(sumx, sumsqx, sumxy, sumy, sumsqy, count);
+}
+// The test of one row of compact dense data (k_dosage_assoc): b == 1, n = nonas for every marker.  s1 = sum d p, s2 = sum d na,
+// s3 = sum (d na) d with d = code - mu' and p the masked residual; w = msig * scale turns code units into the standardised column;
+// sp, sp2 = sum p, sum p^2 over the individuals with a phenotype.  cself as above.
+__device__ inline Reg1d dosage_stats(double s1, double s2, double s3, double w, double sp, double sp2, double n, double cself) {
+    const double sumx = w * s2;
+    const double sumsqx = w * w * s3;
+    const double svy = w * s1;
+    const double sumxy = svy + cself * sumsqx;
+    const double sumy = sp + cself * sumx;
+    const double sumsqy = sp2 + 2.0 * cself * svy + cself * cself * sumsqx;
+    return reg1d_stats(sumx, sumsqx, sumxy, sumy, sumsqy, n);
 }
 
 }  // namespace gvp

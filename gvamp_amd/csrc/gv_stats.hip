@@ -1,5 +1,5 @@
 // gv_stats.hip -- statistics over the resident dataset: the phenotype mask, marker and people statistics, and the per-marker
-// p-values of data::pvals_calc / pvals_calc_LOCO.
+// p-values of data::pvals_calc / pvals_calc_LOCO (gv_pvals_*) with the whole test result beside them (gv_assoc_*).
 #include <cmath>
 #include <cstring>
 
@@ -131,30 +131,42 @@ static int marker_sums_p_p2_f64(gv_ctx* c, const double* p, double* p2_scratch, 
 }
 
 // chrom == NULL: leave-one-out (the marker's own effect is added back analytically); else leave-one-chromosome-out.
-static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
-                      double* pvals, double* chrom_pred = nullptr) {
-    REFUSE_DOSAGE(c, "gv_pvals", "the dense kinds compute no p-values");
-    NEED(c, !c->have_dense, "gv_pvals: not available for methylation data (the reference's meth branch of pvals_calc, "
-                            "data.cpp:1187-1223, computes and stores nothing)");
-    NEED(c, z1->space == GV_SPACE_N && y->space == GV_SPACE_N && x1_hat->space == GV_SPACE_M, "gv_pvals: bad vector spaces");
-    NEED(c, c->have_stats, "gv_pvals: marker statistics must be computed first");
+// One loop for both entry-point families.  out[0] = p-values; assoc (gv_assoc_*): out[1..3] = beta, se, t as well (host pointers, each
+// may be NULL), compact dense data take the marker pass of their own (gvd::dosage_assoc) and the bed families the passes of gv_pvals_*
+// with the wide epilogue.  assoc == false is gv_pvals_* to the bit: the narrow epilogue kernels, the same launches in the same order.
+static int pvals_impl(gv_ctx* c, bool assoc, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
+                      double* const (&out)[4], double* chrom_pred = nullptr) {
+    const char* who = assoc ? "gv_assoc" : "gv_pvals";
+    if (assoc)
+        NEED(c, !(c->have_dense && !c->dense_bits), "gv_assoc: not available for methylation data (dense fp64 matrix): the reference's "
+                                                    "meth branch of pvals_calc, data.cpp:1187-1223, defines no test and none is defined here");
+    else {
+        REFUSE_DOSAGE(c, "gv_pvals", "the dense kinds compute no p-values");
+        NEED(c, !c->have_dense, "gv_pvals: not available for methylation data (the reference's meth branch of pvals_calc, "
+                                "data.cpp:1187-1223, computes and stores nothing)");
+    }
+    if (!(z1->space == GV_SPACE_N && y->space == GV_SPACE_N && x1_hat->space == GV_SPACE_M)) return fail(c, "%s: bad vector spaces", who);
+    if (!c->have_stats) return fail(c, "%s: marker statistics must be computed first", who);
     if (ensure_work(c) || ensure_w2(c)) return 1;
     const int64_t M = c->M;
     const double sqrtN = sqrt((double)c->N);
-    const bool fused = c->kernel_mode != 0;      // (kernel mode 2: the p-value pass is mode 1's -- its sums run over exact planes already)
+    const bool dosage = c->have_dense;            // (assoc only: gv_pvals_* has refused the dense kinds above)
+    const bool fused = !dosage && c->kernel_mode != 0;      // (kernel mode 2: the p-value pass is mode 1's -- its sums run over exact planes already)
     if (fused && M > 0) {
         NEED(c, c->have_stripes, "p-values: kernel modes 1 and 2 need a re-encoded layout");
         if (!c->ks_tuned && autotune_ks(c)) return 1;      // (a p-value call may be the first streaming pass of a context)
     }
-    gv_vec *ymod = nullptr, *ych = nullptr, *sq = nullptr, *xch = nullptr;
+    gv_vec *ymod = nullptr, *ych = nullptr, *sq = nullptr, *xch = nullptr, *wide[3] = {nullptr, nullptr, nullptr};
     double* sums_dev = nullptr;
     int* chrom_dev = nullptr;
+    int64_t* rows_dev = nullptr;
     int rc = 0;
     const size_t Mn = (size_t)(M > 0 ? M : 1);
     auto cleanup = [&]() {
-        for (gv_vec* v : {ymod, ych, sq, xch}) vec_del(c, v);
+        for (gv_vec* v : {ymod, ych, sq, xch, wide[0], wide[1], wide[2]}) vec_del(c, v);
         if (sums_dev) (void)hipFree(sums_dev);
         if (chrom_dev) (void)hipFree(chrom_dev);
+        if (rows_dev) (void)hipFree(rows_dev);
     };
 #define PV_TRY(expr) do { if ((rc = (expr)) != 0) { cleanup(); return rc; } } while (0)
 #define PV_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(c, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
@@ -162,9 +174,13 @@ static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec
     // loop below) never touch the CG work vectors cg_r / cg_z / cg_p / cg_d; gv_ax / gv_atx (which stage through cg_d) are host entry
     // points and cannot run inside this call
     double* pv_dev = c->cg_d->d;
-    double *pa = c->w_n->d, *pb = c->w_n2->d;   // operands of the fused pass: p and p^2
+    double *pa = c->w_n->d, *pb = c->w_n2->d;   // operands of the fused pass: p and p^2 (compact dense data: pa holds the residual)
     gvm::PvArgs pva{c->counts, nullptr, 0.0, nullptr, 0};
-    if (!fused) {
+    if (assoc) {
+        for (int k = 0; k < 3; k++) PV_TRY(vec_new(c, GV_SPACE_M, &wide[k]));
+        pva.beta = wide[0]->d; pva.se = wide[1]->d; pva.t = wide[2]->d;
+    }
+    if (!fused && !dosage) {
         PV_TRY(vec_new(c, GV_SPACE_N, &ymod));
         PV_TRY(vec_new(c, GV_SPACE_N, &sq));
         PV_HIP(hipMalloc(&sums_dev, sizeof(double) * 4 * Mn));
@@ -173,19 +189,36 @@ static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec
         // matvec-shaped and need zeros at NA / pad slots instead, whatever the caller left there (an unfiltered y holds DBL_MAX)
         gvk::mask_copy(c->stream, ymod->d, ymod->d, c->mask2, c->npad);
     }
-    if (!chrom) {
-        // y_mark = y_mod + gen_part * x1_hat[k] (data.cpp:1145-1148): the marker's own column, c = x1_hat[k] / sqrt(N)
-        if (fused) {
-            pva.xself = x1_hat->d;
-            pva.self_scale = 1.0 / sqrtN;
-            if (M > 0)      // (an empty shard has no marker to test)
-                gvm::marker_pvals(c->stream, c->plan, y->d, z1->d, nullptr, c->mask2, c->npad, c->mave, c->msig, pa, pb, c->red_partial, pva, pv_dev);
-        } else if (M > 0) {
-            PV_TRY(marker_sums_p_p2_f64(c, ymod->d, sq->d, sums_dev));
-            gvk::pvals_test(c->stream, c->counts, c->mave, c->msig, sums_dev, x1_hat->d, 1.0 / sqrtN, nullptr, 0, M, pv_dev);
+    // the marker pass of one residual: add == NULL, every marker with its own effect added back (leave-one-out); else the markers of
+    // chromosome ch -- compact dense data: the rows rows_dev[r0 .. r0 + nr) -- against y - z1 + add
+    auto marker_pass = [&](double* add, int ch, int64_t r0, int64_t nr) -> int {
+        if (M == 0) return 0;      // (an empty shard has no marker to test)
+        const bool loo = add == nullptr;
+        if (dosage) {
+            gvd::assoc_prep(c->stream, y->d, z1->d, add, c->mask2, c->npad, pa, c->red_partial, c->red_out);
+            gvd::dosage_assoc(c->stream, c->dcodes, c->dense_bits, c->N, c->dpitch, loo ? nullptr : rows_dev + r0, loo ? M : nr, pa,
+                              c->mask2, c->dense_mu, c->msig, c->dense_scale, c->red_out, (double)c->nonas, loo ? x1_hat->d : nullptr,
+                              1.0 / sqrtN, pva.beta, pva.se, pva.t, pv_dev);
+        } else if (fused) {
+            pva.xself = loo ? x1_hat->d : nullptr;      // y_mark = y_mod + gen_part * x1_hat[k] (data.cpp:1145-1148): c = x1_hat[k] / sqrt(N)
+            pva.self_scale = loo ? 1.0 / sqrtN : 0.0;
+            pva.chrom = loo ? nullptr : chrom_dev;
+            pva.ch = ch;
+            gvm::marker_pvals(c->stream, c->plan, y->d, z1->d, add, c->mask2, c->npad, c->mave, c->msig, pa, pb, c->red_partial, pva, pv_dev);
+        } else {
+            if (!loo) gvk::axpby(c->stream, add, 1.0, add, 1.0, ymod->d, c->npad);   // p = chromosome predictor + y_mod (:1284)
+            if (marker_sums_p_p2_f64(c, loo ? ymod->d : add, sq->d, sums_dev)) return 1;
+            gvk::pvals_test(c->stream, c->counts, c->mave, c->msig, sums_dev, loo ? x1_hat->d : nullptr, loo ? 1.0 / sqrtN : 0.0,
+                            loo ? nullptr : chrom_dev, ch, M, pv_dev, pva.beta, pva.se, pva.t);
         }
+        return 0;
+    };
+    if (!chrom) {
+        PV_TRY(marker_pass(nullptr, 0, 0, M));
     } else {
         PV_HIP(hipMemsetAsync(pv_dev, 0, sizeof(double) * Mn, c->stream));      // markers of chromosomes outside 1..23 keep 0
+        for (gv_vec* v : wide)
+            if (v) PV_HIP(hipMemsetAsync(v->d, 0, sizeof(double) * Mn, c->stream));
         PV_TRY(vec_new(c, GV_SPACE_N, &ych));
         PV_TRY(vec_new(c, GV_SPACE_M, &xch));
         PV_HIP(hipMalloc(&chrom_dev, sizeof(int) * Mn));
@@ -193,6 +226,20 @@ static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec
         double present[24];
         for (int ch = 0; ch < 24; ch++) present[ch] = 0;
         for (int64_t k = 0; k < M; k++) if (chrom[k] >= 1 && chrom[k] <= 23) present[chrom[k]] += 1;
+        // compact dense data: the rows of every chromosome side by side, in marker order, so that the pass for chromosome ch streams
+        // that chromosome's rows alone -- the 23 passes together read the matrix once
+        int64_t row0[25] = {0};
+        std::vector<int64_t> rows_host;
+        if (dosage) {
+            for (int ch = 1; ch <= 23; ch++) row0[ch + 1] = row0[ch] + (int64_t)present[ch];
+            rows_host.resize(Mn);
+            int64_t fill[24];
+            for (int ch = 1; ch <= 23; ch++) fill[ch] = row0[ch];
+            for (int64_t k = 0; k < M; k++) if (chrom[k] >= 1 && chrom[k] <= 23) rows_host[fill[chrom[k]]++] = k;
+            PV_HIP(hipMalloc(&rows_dev, sizeof(int64_t) * Mn));
+            PV_HIP(hipMemcpyAsync(rows_dev, rows_host.data(), sizeof(int64_t) * Mn, hipMemcpyHostToDevice, c->stream));
+            PV_HIP(hipStreamSynchronize(c->stream));      // (rows_host is pageable memory of this frame)
+        }
         PV_TRY(allreduce_scalars(c, present, 24));
         if (chrom_pred) memset(chrom_pred, 0, sizeof(double) * 23 * 4 * (size_t)c->mbytes);   // chromosomes nobody holds: zeros
         for (int ch = 1; ch <= 23; ch++) {
@@ -201,38 +248,45 @@ static int pvals_impl(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec
             PV_TRY(ax_device(c, xch->d, ych->d));                                // chromosome predictor, all ranks (:1268-1272)
             if (chrom_pred)                                                      // the vector the reference dumps (:1276-1281)
                 PV_TRY(to_host(c, chrom_pred + (size_t)(ch - 1) * 4 * c->mbytes, ych->d, sizeof(double) * 4 * c->mbytes));
-            if (fused) {                                                         // p = chromosome predictor + y_mod (:1284)
-                pva.chrom = chrom_dev;
-                pva.ch = ch;
-                if (M > 0)
-                    gvm::marker_pvals(c->stream, c->plan, y->d, z1->d, ych->d, c->mask2, c->npad, c->mave, c->msig, pa, pb, c->red_partial, pva, pv_dev);
-            } else if (M > 0) {
-                gvk::axpby(c->stream, ych->d, 1.0, ych->d, 1.0, ymod->d, c->npad);
-                PV_TRY(marker_sums_p_p2_f64(c, ych->d, sq->d, sums_dev));
-                gvk::pvals_test(c->stream, c->counts, c->mave, c->msig, sums_dev, nullptr, 0.0, chrom_dev, ch, M, pv_dev);
-            }
+            PV_TRY(marker_pass(ych->d, ch, row0[ch], row0[ch + 1] - row0[ch]));
         }
     }
     KCHK(c);
-    if (M > 0) PV_TRY(to_host(c, pvals, pv_dev, sizeof(double) * M));
+    if (M > 0) {
+        double* const dev[4] = {pv_dev, pva.beta, pva.se, pva.t};
+        for (int k = 0; k < 4; k++)
+            if (out[k] && dev[k]) PV_TRY(to_host(c, out[k], dev[k], sizeof(double) * M));
+    }
 #undef PV_TRY
 #undef PV_HIP
-    if (ymod || ych || sq || xch || sums_dev || chrom_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ymod || ych || sq || xch || wide[0] || sums_dev || chrom_dev || rows_dev) HIPCHK(c, hipStreamSynchronize(c->stream));
     cleanup();
     return 0;
 }
 
 int gv_pvals_loo(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, double* pvals) {
-    return pvals_impl(c, z1, y, x1_hat, nullptr, pvals);
+    return pvals_impl(c, false, z1, y, x1_hat, nullptr, {pvals, nullptr, nullptr, nullptr});
 }
 int gv_pvals_loco(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom, double* pvals) {
     NEED(c, chrom != nullptr, "gv_pvals_loco: chrom is NULL");
-    return pvals_impl(c, z1, y, x1_hat, chrom, pvals);
+    return pvals_impl(c, false, z1, y, x1_hat, chrom, {pvals, nullptr, nullptr, nullptr});
 }
 int gv_pvals_loco_pred(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom, double* pvals,
                        double* chrom_pred) {
     NEED(c, chrom != nullptr, "gv_pvals_loco_pred: chrom is NULL");
-    return pvals_impl(c, z1, y, x1_hat, chrom, pvals, chrom_pred);
+    return pvals_impl(c, false, z1, y, x1_hat, chrom, {pvals, nullptr, nullptr, nullptr}, chrom_pred);
+}
+
+// the whole test result: p through the passes of gv_pvals_* (bed data) or the pass of compact dense data, beta / se / t beside it
+int gv_assoc_loo(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const gv_assoc_out* out) {
+    NEED(c, out != nullptr, "gv_assoc_loo: out is NULL");
+    return pvals_impl(c, true, z1, y, x1_hat, nullptr, {out->p, out->beta, out->se, out->t});
+}
+int gv_assoc_loco(gv_ctx* c, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom, const gv_assoc_out* out,
+                  double* chrom_pred) {
+    NEED(c, out != nullptr, "gv_assoc_loco: out is NULL");
+    NEED(c, chrom != nullptr, "gv_assoc_loco: chrom is NULL");
+    return pvals_impl(c, true, z1, y, x1_hat, chrom, {out->p, out->beta, out->se, out->t}, chrom_pred);
 }
 
 }  // extern "C"

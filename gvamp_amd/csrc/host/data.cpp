@@ -330,6 +330,15 @@ std::vector<double> data::ATx(double* __restrict__ phen) {
     return out;
 }
 
+// the per-chromosome predictors of data.cpp:1276-1281: <prefix>_LOCO_chr_<ch>.csv, 4*mbytes values, rank 0
+static void store_chrom_pred(const std::vector<double>& pred, size_t mbytes, int rank, const std::string& pred_prefix) {
+    for (int ch = 1; ch <= 23 && rank == 0; ch++) {
+        const std::string fp = pred_prefix + "_LOCO_chr_" + std::to_string(ch) + ".csv";
+        store_vec_to_file(fp, std::vector<double>(pred.begin() + (size_t)(ch - 1) * 4 * mbytes, pred.begin() + (size_t)ch * 4 * mbytes));
+        if (!gv_host_quiet()) std::cout << "filepath predictors = " << fp << std::endl;
+    }
+}
+
 std::vector<double> data::pvals_calc_dev(gv_vec* z1, gv_vec* y, gv_vec* x1_hat, bool loco, const std::string& pred_prefix) {
     std::vector<double> pv(M > 0 ? M : 1, 0.0);
     if (loco) {
@@ -338,19 +347,29 @@ std::vector<double> data::pvals_calc_dev(gv_vec* z1, gv_vec* y, gv_vec* x1_hat, 
         if (pred_prefix.empty())
             ck(ctx, gv_pvals_loco(ctx, z1, y, x1_hat, ch_info.data(), pv.data()), "gv_pvals_loco");
         else {
-            // the per-chromosome predictors of data.cpp:1276-1281: <prefix>_LOCO_chr_<ch>.csv, 4*mbytes values, rank 0
             std::vector<double> pred((size_t)23 * 4 * mbytes, 0.0);
             ck(ctx, gv_pvals_loco_pred(ctx, z1, y, x1_hat, ch_info.data(), pv.data(), pred.data()), "gv_pvals_loco_pred");
-            for (int ch = 1; ch <= 23 && rank == 0; ch++) {
-                const std::string fp = pred_prefix + "_LOCO_chr_" + std::to_string(ch) + ".csv";
-                store_vec_to_file(fp, std::vector<double>(pred.begin() + (size_t)(ch - 1) * 4 * mbytes, pred.begin() + (size_t)ch * 4 * mbytes));
-                if (!gv_host_quiet()) std::cout << "filepath predictors = " << fp << std::endl;
-            }
+            store_chrom_pred(pred, mbytes, rank, pred_prefix);
         }
     } else
         ck(ctx, gv_pvals_loo(ctx, z1, y, x1_hat, pv.data()), "gv_pvals_loo");
     pv.resize(M > 0 ? M : 0);
     return pv;
+}
+
+std::vector<std::vector<double>> data::assoc_calc_dev(gv_vec* z1, gv_vec* y, gv_vec* x1_hat, bool loco, const std::string& pred_prefix) {
+    std::vector<std::vector<double>> res(4, std::vector<double>(M > 0 ? M : 1, 0.0));
+    const gv_assoc_out out{res[0].data(), res[1].data(), res[2].data(), res[3].data()};
+    if (loco) {
+        std::vector<int> ch_info = read_chromosome_info(bimfp);
+        ch_info.resize(M > 0 ? M : 1, 0);
+        std::vector<double> pred(pred_prefix.empty() ? 0 : (size_t)23 * 4 * mbytes, 0.0);
+        ck(ctx, gv_assoc_loco(ctx, z1, y, x1_hat, ch_info.data(), &out, pred.empty() ? nullptr : pred.data()), "gv_assoc_loco");
+        if (!pred.empty()) store_chrom_pred(pred, mbytes, rank, pred_prefix);
+    } else
+        ck(ctx, gv_assoc_loo(ctx, z1, y, x1_hat, &out), "gv_assoc_loo");
+    for (auto& v : res) v.resize(M > 0 ? M : 0);
+    return res;
 }
 
 static std::vector<std::vector<double>> pvals_host(data* d, gv_ctx* ctx, int M, size_t mbytes,

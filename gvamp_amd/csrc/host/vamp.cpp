@@ -44,6 +44,7 @@ void vamp::common_init(const Options& opt) {
     gam1_init = opt.get_gam1_init();
     gamw_init = opt.get_gamw_init();
     r1_init_file = opt.get_estimate_file();
+    store_assoc = (int)opt.get_store_assoc();
     store_pvals = opt.get_store_pvals();   // the reference's ctor 1 leaves 1 here (vamp.hpp:53); --store-pvals is honoured
     diagnostics = opt.get_diagnostics();
     store_iterates = opt.get_store_iterates();
@@ -775,6 +776,22 @@ std::vector<double> vamp::infere_linear(data* dataset) {
             if (verbose && rank == 0) std::cout << "filepath_out_pvals_LOCO = " << pre << std::endl;
         }
         if (verbose && rank == 0) std::cout << "p-values took " << now_s() - t0 << " seconds." << std::endl;
+    }
+    // [ext] --store-assoc 1: the whole test (effect, standard error, t, p) of the same iterate, independent of --store-pvals
+    if (store_assoc == 1 && gv_get_layout(ctx) == 3) {
+        if (rank == 0) std::cout << "association statistics: skipped for " << dense_kind_name(gv_get_layout(ctx)) << " (no test is defined for it)" << std::endl;
+    } else if (store_assoc == 1) {
+        const double t0 = now_s();
+        static const char* const part[4] = {"beta", "se", "t", "p"};
+        const std::vector<std::vector<double>> loo = dataset->assoc_calc_dev(z1, y, x1_hat, false);
+        for (int k = 0; k < 4; k++) mpi_store_vec_to_file(pre + "_assoc_" + part[k] + ".bin", loo[k], S, M);
+        if (verbose && rank == 0) std::cout << "filepath_out_assoc = " << pre + "_assoc_{beta,se,t,p}.bin" << std::endl;
+        if (dataset->get_bimfp() != "") {
+            const std::vector<std::vector<double>> loco = dataset->assoc_calc_dev(z1, y, x1_hat, true);
+            for (int k = 0; k < 4; k++) mpi_store_vec_to_file(pre + "_assoc_LOCO_" + part[k] + ".bin", loco[k], S, M);
+            if (verbose && rank == 0) std::cout << "filepath_out_assoc_LOCO = " << pre + "_assoc_LOCO_{beta,se,t,p}.bin" << std::endl;
+        }
+        if (verbose && rank == 0) std::cout << "association statistics took " << now_s() - t0 << " seconds." << std::endl;
     }
     if (store_iterates && rank == 0) {                                      // :779-794 (rank 0 only, App. B)
         store_vec_to_file(pre + "_gam1s.csv", gam1s);

@@ -36,7 +36,7 @@ private:
     int learn_vars, init_est = 0;
     long unsigned int seed;
     std::string model, out_dir, out_name;
-    int store_pvals = 0, use_lmmse_damp = 0, reverse = 0;
+    int store_pvals = 0, store_assoc = 0, use_lmmse_damp = 0, reverse = 0;
     double gam1_init = -1, gamw_init = 0;
     std::string r1_init_file, estimate_file;
     int diagnostics = 0, store_iterates = 1, verbose = 1;

@@ -393,6 +393,36 @@ int gv_pvals_loco(gv_ctx* ctx, const gv_vec* z1, const gv_vec* y, const gv_vec* 
 int gv_pvals_loco_pred(gv_ctx* ctx, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
                        double* pvals, double* chrom_pred);
 
+/* ---- the whole association test: effect, standard error, t and p (additions only: GV_ABI_VERSION stays 4) ----------------------
+ * gv_pvals_* above return a p-value alone (the reference leaves beta commented out in linear_reg1d_pvals) and refuse the dense
+ * kinds.  gv_assoc_* return the full result of the same test, for bed data in both kernel families and for compact dosage data
+ * of both widths.  Per local marker k and individual n
+ *     value_n = (x_kn - mave_k) * msig_k * b_kn * na_n
+ *   bed data    : x = a (0, 1, 2), b = 1 where the genotype is present (data.cpp:1155-1175);
+ *   dosage data : x = scale * code, b == 1 (no missing entry), formed in code units as (code - mu'_k) * (msig_k * scale).
+ * p is the phenotype residual of pvals_calc / pvals_calc_LOCO, zero at NA and pad slots whatever the caller left in y there:
+ *   leave-one-out            : y - z1 + value * x1_hat[k] / sqrt(N)
+ *   leave-one-chromosome-out : y - z1 + (A x1_hat restricted to the marker's chromosome).
+ * With sumx = sum value, sumsqx = sum value^2, sumxy = sum value p, sumy = sum b na p, sumsqy = sum b na p^2, n = sum b na
+ * (data.cpp:1164-1176) and s2x, s2y, sxy, rxy as in utilities.cpp:323-326:
+ *   beta = sxy / s2x                       effect per unit of the STANDARDISED column; beta * msig_k is the effect per unit of
+ *                                          genotype (bed) or dosage value (dosage data)
+ *   t    = rxy * sqrt((n - 2) / (1 - rxy^2)), signed
+ *   se   = beta / t, evaluated as sqrt((n - 1) / (n - 2) * s2y * (1 - rxy^2) / ((n - 1) * s2x)): t == 0 gives no 0/0
+ *   p    = two-sided Student-t tail of |t| with n - 2 degrees of freedom -- for bed data bit-identical to gv_pvals_*.
+ * Dosage data: n = nonas for every marker; a constant column (q == 0, msig = 1, value == 0) yields NaN in all four outputs, as a
+ * monomorphic bed marker does.  The sums of a row are formed in a fixed order that depends neither on the call (LOO / LOCO) nor
+ * on the other rows of the pass: results are bit-reproducible, and LOCO with x1_hat == 0 on one chromosome equals LOO bit for bit.
+ * LOCO: markers whose chromosome is outside 1..23 get 0 in all four outputs; a pass streams the rows of its chromosome only, so the
+ * 23 passes read a dosage matrix once.  Vector spaces and marker statistics are checked as gv_pvals_* check them.
+ * Not available for methylation data (dense fp64 matrix; non-zero return, the message names methylation data): no test is
+ * defined for it. */
+typedef struct { double *beta, *se, *t, *p; } gv_assoc_out;   /* each M host doubles, or NULL: that output is not copied out */
+int gv_assoc_loo(gv_ctx* ctx, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const gv_assoc_out* out);
+/* chrom as gv_pvals_loco; chrom_pred as gv_pvals_loco_pred: 23 * 4*mbytes host doubles, or NULL. */
+int gv_assoc_loco(gv_ctx* ctx, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
+                  const gv_assoc_out* out, double* chrom_pred);
+
 /* SUM all-reduce of n host doubles over the attached communicator (identity when none): MPI_Allreduce of
  * scalars in vamp.cpp:313,990,1012-1013 */
 int gv_allreduce_host(gv_ctx* ctx, double* buf, int n);
