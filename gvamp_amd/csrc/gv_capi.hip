@@ -354,8 +354,14 @@ int gv_set_dims(gv_ctx* c, int64_t N, int64_t M, int64_t Mt, int64_t S) {
     if (chunks < 1) chunks = 1;
     c->ax_chunks = (int)chunks;
     HIPCHK(c, hipMalloc(&c->ax_partial, sizeof(double) * c->ax_chunks * c->npad));
-    // i8 MFMA family: int32 digit sums must not overflow (|r'| <= 3, |digit| <= 128; Ax adds the miss plane)
+    // i8 MFMA family: no int32 digit sum may wrap (|r'| <= 3, |digit| <= 128).  ATx side: K is the individuals, a K-entry adds at most
+    // 3 * 128 and no K-segment is longer than N, so N itself is bounded here.  Ax side: K is the markers and a K-entry adds up to 512
+    // (the r' plane and the miss plane share one accumulator plane); M is not bounded, the LONGEST K-segment of the decomposition is
+    // (gvm::ax_bound_ok in gv_mfma.h, asked wherever a decomposition is admitted) -- only a shard that no split into 64 segments
+    // can serve is refused here, on either layout
     NEED(c, N * 384 < 2147483647LL, "gv_set_dims: N too large for the int32 accumulators of kernel mode 1");
+    NEED(c, gvm::ax_min_ks((M + 255) / 256, 256, M) > 0 && gvm::ax_min_ks((M + 63) / 64, 64, M) > 0,
+         "gv_set_dims: M too large for the int32 accumulators of kernel mode 1 (no split into 64 K-segments keeps the Ax-side sums below 2^31)");
     // the streaming kernel counts (quad, K-block) cells in 32 bits: M N / 65536 of them (35 TB of genotypes at the limit)
     NEED(c, ((M + 255) / 256 + 1) * ((N + 255) / 256 + 1) < 2147483647LL, "gv_set_dims: shard too large for the 32-bit cell index");
     if (plan_decomps(c)) return 1;

@@ -139,6 +139,55 @@ inline KBounds make_bounds(const Decomp& d, int64_t nkb, bool deal) {
     }
     return kb;
 }
+// ---- the int32 bound of the Ax side -------------------------------------------------------------------------------------
+// A work item adds up one int32 digit sum per row and column over ITS K-blocks, and the products are exact only while no such sum
+// wraps.  On the ATx side K is the individuals: gv_set_dims refuses N * 384 >= 2^31 and no segment is longer than N.  On the Ax side
+// K is the markers of the shard, which nothing limits, and one K-entry adds up to 512 in magnitude: MODE 1 / 4 store accX + accY as
+// ONE plane, and a missing genotype contributes 3 * digit(c) + 1 * digit(e) with digits down to -128.  So the LONGEST item of an
+// Ax-side decomposition, counted in real markers (kb_markers per K-block: 256 on the stripe layout, 64 on the tile layout; the last
+// K-block is clipped at M), times 512 must not exceed 2^31 - 1.  Every path that admits an Ax-side decomposition asks ax_bound_ok():
+// decomp_ok (gv_set_decomp, the cache file, the built-in table), the tuner's candidate list and its variants of a winner, the
+// GV_KS_N override and the fallback (gv_tune.hip).  The segments of a uniform split are NOT equal -- geo, taper, xskew and the
+// rounding to whole K-blocks -- so the number of segments alone decides nothing: the boundaries are those of make_bounds, for both
+// quad parities and both mappings (a dealt context still launches by block index on a foreign stream).
+constexpr int64_t GV_AX_ENTRY_MAX = 512;            // largest |contribution| of one K-entry to an int32 sum of the Ax side
+constexpr int64_t GV_I32_MAX = 2147483647LL;
+// markers of the longest item of decomposition d on the Ax side of a shard of M markers; -1: d is no decomposition of nkb K-blocks
+inline int64_t ax_longest_item(const Decomp& d, int64_t nkb, int64_t kb_markers, int64_t M) {
+    if (d.skL > 0) {     // balanced: at most skL cells, all of one quad's K range at most; hybrid: the whole quads span K
+        const int64_t L = d.piv > 0 || d.skL > nkb ? nkb : d.skL;
+        return L * kb_markers < M ? L * kb_markers : M;
+    }
+    if (d.ks < 1 || d.ks > GV_MAX_KS || d.ks > nkb) return -1;
+    int64_t longest = 0;
+    for (int deal = 0; deal < 2; deal++) {
+        const KBounds kb = make_bounds(d, nkb, deal != 0);
+        for (int c = 0; c < 2; c++)
+            for (int j = 0; j < d.ks; j++) {
+                const int64_t lo = (int64_t)kb.b[c][j] * kb_markers;
+                int64_t hi = (int64_t)kb.b[c][j + 1] * kb_markers;
+                if (hi > M) hi = M;
+                if (hi - lo > longest) longest = hi - lo;
+            }
+    }
+    return longest;
+}
+inline bool ax_bound_ok(const Decomp& d, int64_t nkb, int64_t kb_markers, int64_t M) {
+    const int64_t longest = ax_longest_item(d, nkb, kb_markers, M);
+    return longest >= 0 && longest * GV_AX_ENTRY_MAX <= GV_I32_MAX;
+}
+// the fewest equal K-segments that keep the bound: ceil(M * 512 / (2^31 - 1)), or one more where the rounding to whole K-blocks
+// makes a segment longer than M / ks (M = 8 388 606 on the stripe layout: two halves of 16 384 K-blocks = 4 194 304 markers).
+// 0: no split of at most GV_MAX_KS segments does (a shard of more than 64 * 4 194 303 markers)
+inline int ax_min_ks(int64_t nkb, int64_t kb_markers, int64_t M) {
+    if (M * GV_AX_ENTRY_MAX <= GV_I32_MAX) return 1;
+    Decomp d;
+    for (int64_t ks = (M * GV_AX_ENTRY_MAX + GV_I32_MAX - 1) / GV_I32_MAX; ks <= GV_MAX_KS && ks <= nkb; ks++) {
+        d.ks = (int)ks;
+        if (ax_bound_ok(d, nkb, kb_markers, M)) return d.ks;
+    }
+    return 0;
+}
 // The ticket counter of a context: one uint32 in device memory that is NEVER reset.  Launch k is handed base = the sum of the grid
 // sizes of the launches before it and its workgroups compute t = old - base in unsigned arithmetic (both wrap together).  Every
 // workgroup of every dealt launch draws exactly once -- before the `go` test of a device-resident CG step -- so the host's sum stays

@@ -47,22 +47,34 @@ static std::string tune_key(gv_ctx* c) {
              pr.multiProcessorCount, (long long)c->N, (long long)c->M, c->plan.layout, c->deal.ctr ? 1 : 0);
     return buf;
 }
-// is decomposition d admissible for side (0: ATx / stripes_m, 1: Ax / stripes_n) of this context?
-static bool decomp_ok(const gv_ctx* c, const gvm::Decomp& d, int side) {
+// markers per K-block of the Ax side: 256 on the stripe layout, 64 on the tile layout (which the Ax side walks transposed)
+static inline int64_t ax_kb_markers(const gvm::Plan& pl) { return pl.layout == 1 ? 64 : 256; }
+// does no int32 digit sum of an Ax-side pass under d wrap, whatever the vector?  (gvm::ax_bound_ok, gv_mfma.h)
+static bool ax_bound_ok(const gv_ctx* c, const gvm::Decomp& d) {
+    return gvm::ax_bound_ok(d, c->plan.nkb_n, ax_kb_markers(c->plan), c->M);
+}
+// is decomposition d admissible for side (0: ATx / stripes_m, 1: Ax / stripes_n) of this context?  why (may be NULL): set to 1 when
+// the int32 bound of the Ax side is what refuses it
+static bool decomp_ok(const gv_ctx* c, const gvm::Decomp& d, int side, int* why = nullptr) {
     const gvm::Plan& pl = c->plan;
     const int64_t nkb = side ? pl.nkb_n : pl.nkb_m, nrg = side ? pl.nrg_n : pl.nrg_m;
-    const int64_t min_ks = side ? (c->M * 512 + 2147483646LL) / 2147483647LL : 1;
+    // (a fast necessary condition: fewer than min_ks segments cannot keep the bound; whether d's own segments do is asked below)
+    const int64_t min_ks = side ? (c->M * gvm::GV_AX_ENTRY_MAX + gvm::GV_I32_MAX - 1) / gvm::GV_I32_MAX : 1;
+    if (why) *why = 0;
     int64_t pieces;
     if (d.skL > 0) {
-        if (d.skL < 8 || (side && min_ks > 1) || nkb < 2 || d.piv < 0 || d.piv > (nrg + 3) / 4) return false;
+        if (side && min_ks > 1 && d.skL >= 8) { if (why) *why = 1; return false; }     // balanced ranges and whole quads: never past one segment's worth
+        if (d.skL < 8 || nkb < 2 || d.piv < 0 || d.piv > (nrg + 3) / 4) return false;
         pieces = (nkb + d.skL - 1) / d.skL + 1;
     } else {
-        if (d.ks < 1 || d.ks > 64 || d.ks > nkb || d.ks < min_ks || d.piv != 0) return false;
+        if (d.ks < 1 || d.ks > 64 || d.ks > nkb || d.piv != 0) return false;
+        if (d.ks < min_ks) { if (why) *why = 1; return false; }
         pieces = d.ks;
     }
     if (!(d.taper >= 0.f && d.taper < 1.f) || !(d.geo >= 0.f && d.geo < 1.f) || (d.geo > 0.f && d.skL > 0) || (d.prio != 0 && d.prio != 1)) return false;
     if (d.occ != 0 && d.occ != 2 && d.occ != 3) return false;
     if (!(d.xskew >= -0.2f && d.xskew <= 0.2f) || (d.xskew != 0.f && d.skL > 0)) return false;
+    if (side && !ax_bound_ok(c, d)) { if (why) *why = 1; return false; }
     return (size_t)pieces * 4 * nrg * (side ? pl.rows_n : 64) * 8 * 4 <= pl.partial_bytes;
 }
 static bool tune_cache_load(gv_ctx* c) {
@@ -263,6 +275,7 @@ int autotune_ks(gv_ctx* c) {
         gvm::Decomp best = cand[0];
         double best_t = -1;
         auto consider = [&](const gvm::Decomp& cd) -> int {
+            if (is_ax && !ax_bound_ok(c, cd)) return 0;      // a taper or skew of the winner may stretch a segment past the int32 bound
             const double t = measure(cd);
             if (t < 0) return 1;
             if (best_t < 0 || t < best_t * 0.997) { best_t = t; best = cd; }   // the list order breaks near-ties
@@ -379,7 +392,12 @@ int plan_decomps(gv_ctx* c) {
         }
         for (int j = n; j < 3; j++) out3[j] = out3[n > 0 ? n - 1 : 0];
     };
-    const int64_t min_ks_n = (M * 512 + 2147483646LL) / 2147483647LL;
+    // Ax side: the int32 bound (gv_mfma.h, ax_bound_ok).  min_ks_n: the fewest EQUAL segments that keep it; every candidate below is
+    // asked with its own segment lengths (ax_ok).  gv_set_dims has refused a shard that no split of 64 segments can serve.
+    const int64_t kbm_n = ax_kb_markers(pl);
+    int64_t min_ks_n = gvm::ax_min_ks(pl.nkb_n, kbm_n, M);
+    if (min_ks_n < 1) min_ks_n = 1;
+    auto ax_ok = [&](const gvm::Decomp& d) { return gvm::ax_bound_ok(d, pl.nkb_n, kbm_n, M); };
     int ks3_m[3], ks3_n[3];
     rank_ks(pl.nrg_m, pl.nkb_m, 1, 0.4, ks3_m);
     rank_ks(pl.nrg_n, pl.nkb_n, min_ks_n, 0.8, ks3_n);
@@ -415,6 +433,7 @@ int plan_decomps(gv_ctx* c) {
         return h;
     };
     const bool dealt = c->deal.ctr != nullptr;      // work items dealt by ticket (gv_create)
+    // (geo_side: the Ax side -- the many-segment geometric splits are listed there, and every uniform split is asked for the int32 bound)
     auto build = [&](const int* ks3, int64_t nrg, int64_t nkb, int64_t rows, bool balanced_ok, int64_t min_ks_u, bool geo_side, std::vector<gvm::Decomp>& out) {
         out.clear();
         for (int prio = 0; prio < 2; prio++) {
@@ -422,6 +441,7 @@ int plan_decomps(gv_ctx* c) {
             for (int j = 0; j < 3; j++) {
                 if (j > 0 && (ks3[j] == ks3[0] || (j == 2 && ks3[2] == ks3[1]))) continue;
                 gvm::Decomp d; d.ks = ks3[j]; d.skL = 0; d.prio = prio;
+                if (geo_side && !ax_ok(d)) continue;
                 out.push_back(d);
             }
         }
@@ -447,6 +467,7 @@ int plan_decomps(gv_ctx* c) {
                 for (const gvm::Decomp& o : out) dup |= o.skL <= 0 && o.ks == gk.first && o.geo == gk.second;
                 if (dup) continue;
                 gvm::Decomp d; d.ks = gk.first; d.skL = 0; d.prio = 1; d.geo = gk.second;
+                if (geo_side && !ax_ok(d)) continue;
                 out.push_back(d);
             }
         }
@@ -481,7 +502,8 @@ int plan_decomps(gv_ctx* c) {
         if (dealt && geo_side && prio_only != 0 && 12 >= min_ks_u) {
             double tot = 0.0, wlast = 1.0;
             for (int j = 0; j < 12; j++) { tot += wlast; if (j + 1 < 12) wlast *= 0.7; }
-            if ((double)nkb * wlast / tot >= 8.0) { gvm::Decomp d; d.ks = 12; d.skL = 0; d.prio = 1; d.geo = 0.7f; out.push_back(d); }
+            gvm::Decomp d; d.ks = 12; d.skL = 0; d.prio = 1; d.geo = 0.7f;
+            if ((double)nkb * wlast / tot >= 8.0 && ax_ok(d)) out.push_back(d);
         }
     };
     build(ks3_m, pl.nrg_m, pl.nkb_m, 64, true, 1, false, c->dec_cand_m);
@@ -499,7 +521,8 @@ int plan_decomps(gv_ctx* c) {
     }
     if (const char* e = getenv("GV_KS_N")) {
         int v = atoi(e);
-        if (v >= min_ks_n && v >= 1 && v <= pl.nkb_n && v <= 64) { gvm::Decomp d; d.ks = v; d.prio = prio_only == 1; d.taper = taper_env; d.geo = geo_env; fix(c->dec_cand_n, c->ks_fixed_n, d); }
+        gvm::Decomp d; d.ks = v; d.prio = prio_only == 1; d.taper = taper_env; d.geo = geo_env;
+        if (v >= min_ks_n && v >= 1 && v <= pl.nkb_n && v <= 64 && ax_ok(d)) fix(c->dec_cand_n, c->ks_fixed_n, d);
     }
     if (const char* e = getenv("GV_SK_M")) {
         gvm::Decomp d; d.skL = skL_of(pl.nrg_m, pl.nkb_m, atoi(e)); d.prio = prio_only != 0;
@@ -573,7 +596,11 @@ int gv_set_decomp(gv_ctx* c, int cls, const gv_decomp_info* in) {
     d.occ = in->wgs_per_cu == 2 ? 2 : 0;
     d.xskew = in->balanced_cells > 0 ? 0.f : in->xcd_skew;
     if (d.skL > 0) d.ks = 1;
-    NEED(c, decomp_ok(c, d, cls >> 1), "gv_set_decomp: the decomposition is not admissible for this shard (range, or too many pieces for the partial-sum buffer)");
+    int why = 0;
+    const bool ok = decomp_ok(c, d, cls >> 1, &why);
+    NEED(c, ok || why != 1, "gv_set_decomp: the decomposition is not admissible for this shard (int32 bound of the Ax side: the longest K-segment times 512 "
+                           "must stay below 2^31)");
+    NEED(c, ok, "gv_set_decomp: the decomposition is not admissible for this shard (range, or too many pieces for the partial-sum buffer)");
     (cls >> 1 ? c->plan.dn : c->plan.dm)[cls & 1] = d;
     return 0;
 }

@@ -532,7 +532,9 @@ int gv_get_decomp(gv_ctx* ctx, gv_decomp_info* out4);
 /* Pins the decomposition of class cls (0 ATx, 1 two-vector ATx, 2 Ax, 3 two-vector Ax), e.g. one a deployment measured itself:
  * `tuned` is ignored, balanced_cells > 0 selects a balanced / hybrid grid (ks unused), else a uniform split of ks segments with
  * taper or geo.  Call it after the ingest; a first matvec that tunes (gv_tune_info source 1 / 2 / 4) overwrites it, one that has
- * already happened does not.  Refused when the decomposition needs more partial-sum pieces than the context holds room for.
+ * already happened does not.  Refused when the decomposition needs more partial-sum pieces than the context holds room for, and
+ * on the Ax side (cls 2, 3) when its longest K-segment is more than 4 194 303 markers (512 per marker would wrap an int32 digit
+ * sum: only a shard of more markers than that can be cut so); the message names the reason.
  * Never changes a bit of output (exact integer accumulation). */
 int gv_set_decomp(gv_ctx* ctx, int cls, const gv_decomp_info* in);
 /* How the picks were made: *source = -1 not yet (the first matvec in kernel mode 1 makes them), 0 the cost model's first
