@@ -28,6 +28,7 @@ EXPORTS = [
     "gv_huber_denoise", "gv_huber_delta",
     "gv_set_cg_precond", "gv_precond_info", "gv_precond_window_gram", "gv_precond_apply",
     "gv_assoc_loo", "gv_assoc_loco",
+    "gv_set_dosage_missing", "gv_synth_dosage_na", "gv_dosage_info", "gv_marker_counts",
 ]
 
 
@@ -42,6 +43,11 @@ class DotSpec(C.Structure):            # gv_dot_spec (include/gvamp.h)
 class AssocOut(C.Structure):           # gv_assoc_out
     _fields_ = [("beta", C.POINTER(C.c_double)), ("se", C.POINTER(C.c_double)), ("t", C.POINTER(C.c_double)),
                 ("p", C.POINTER(C.c_double))]
+
+
+class DosageStats(C.Structure):        # gv_dosage_stats
+    _fields_ = [("scale", C.c_double), ("reserved", C.c_uint64), ("bits", C.c_int), ("missing", C.c_int), ("na_kernels", C.c_int),
+                ("pad_", C.c_int)]
 
 
 class CgStats(C.Structure):
@@ -131,6 +137,10 @@ def load():
     L.gv_upload_dosage.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int, C.c_double]
     L.gv_upload_dosage_file.argtypes = [vp, C.c_char_p, i64, C.c_int, C.c_double]
     L.gv_synth_dosage.argtypes = [vp, C.c_uint64, C.c_int]
+    L.gv_set_dosage_missing.argtypes = [vp, C.c_int]
+    L.gv_synth_dosage_na.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint32]
+    L.gv_dosage_info.argtypes = [vp, C.POINTER(DosageStats)]
+    L.gv_marker_counts.argtypes = [vp, dp]
     L.gv_set_mask.argtypes = [vp, up, i64]
     L.gv_marker_stats.argtypes = [vp, C.c_double]
     L.gv_get_marker_stats.argtypes = [vp, dp, dp]
@@ -327,23 +337,46 @@ class Shard:
         """the device-generated methylation matrix that synth.synth_meth(N, M, seed, S) reproduces on the host"""
         self._ck(self.L.gv_synth_meth(self.h, seed))
 
-    def upload_dosage(self, codes, scale):
+    def upload_dosage(self, codes, scale, missing=False):
         """compact dense data: M x N unsigned codes of this shard, marker-major, X = scale * codes; codes.dtype (uint8 / uint16)
-        selects the width"""
+        selects the width.  missing: the all-ones code (255 / 65535) is a missing entry (gv_set_dosage_missing)"""
         codes = np.ascontiguousarray(codes)
         if codes.dtype not in (np.uint8, np.uint16):
             raise GvError("upload_dosage: codes must be uint8 or uint16, not %s" % codes.dtype)
         assert codes.size == self.M * self.N, (codes.size, self.M, self.N)
+        self.set_dosage_missing(missing)
         self._ck(self.L.gv_upload_dosage(self.h, codes.ctypes.data_as(C.c_void_p), codes.size, 8 * codes.dtype.itemsize, scale))
 
-    def upload_dosage_file(self, path, bits, scale, offset=None):
-        """M x N codes of `bits` bits at byte offset (default S * N * bits / 8) of a file of raw codes"""
+    def upload_dosage_file(self, path, bits, scale, offset=None, missing=False):
+        """M x N codes of `bits` bits at byte offset (default S * N * bits / 8) of a file of raw codes; missing as upload_dosage"""
         off = self.S * self.N * (bits // 8) if offset is None else offset
+        self.set_dosage_missing(missing)
         self._ck(self.L.gv_upload_dosage_file(self.h, path.encode(), off, bits, scale))
 
     def synth_dosage(self, seed, bits):
         """the device-generated codes that synth.synth_dosage(N, M, seed, bits, S) reproduces on the host (scale 1/127, 1/16384)"""
         self._ck(self.L.gv_synth_dosage(self.h, seed, bits))
+
+    def set_dosage_missing(self, on):
+        """gv_set_dosage_missing: read by the next upload of codes; refused while codes uploaded with the other setting are resident"""
+        self._ck(self.L.gv_set_dosage_missing(self.h, int(bool(on))))
+
+    def synth_dosage_na(self, seed, bits, miss_ppm):
+        """the device-generated codes with missing entries that synth.synth_dosage_na(N, M, seed, bits, miss_ppm, S) reproduces on the
+        host; turns the missing option on"""
+        self._ck(self.L.gv_synth_dosage_na(self.h, seed, bits, miss_ppm))
+
+    def dosage_info(self):
+        """gv_dosage_info as a dict: bits, scale, missing (option on), reserved (codes counted at ingest), na_kernels (in use)"""
+        st = DosageStats()
+        self._ck(self.L.gv_dosage_info(self.h, C.byref(st)))
+        return dict(bits=st.bits, scale=st.scale, missing=bool(st.missing), reserved=int(st.reserved), na_kernels=bool(st.na_kernels))
+
+    def marker_counts(self):
+        """gv_marker_counts: the M per-marker counts sum b na after compute_markers_statistics (dosage data)"""
+        cnt = np.empty(self.M)
+        self._ck(self.L.gv_marker_counts(self.h, _dp(cnt)))
+        return cnt
 
     def download_bed(self):
         out = np.empty(self.M * self.mbytes, dtype=np.uint8)

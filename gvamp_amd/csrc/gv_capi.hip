@@ -156,8 +156,10 @@ static void free_dataset(gv_ctx* c) {
         p = nullptr;
     };
     F(c->bed); F(c->mask2); F(c->mave); F(c->msig); F(c->t3); F(c->ax_partial); F(c->counts);
-    F(c->dense); F(c->dense_part); F(c->dcodes); F(c->dense_mu);
+    F(c->dense); F(c->dense_part); F(c->dcodes); F(c->dense_mu); F(c->dense_cnt); F(c->dense_rcount); F(c->dense_rpart);
     c->dense_bits = 0;
+    c->dense_na = false;
+    c->dense_reserved = 0;
     c->dense_part_cap = 0;
     c->have_dense = false;
     if (c->stripes_slab) {
@@ -261,6 +263,9 @@ int gv_create(int device, gv_ctx** out) {
             c->plan.deal = &c->deal;
         }
     }
+    // GV_DOSAGE_NA_KERNELS=1 (development, read per context as GV_DEAL is): the missing-aware dosage kernels whenever gv_set_dosage_missing
+    // is on, also for a shard without a reserved code
+    if (const char* nk = getenv("GV_DOSAGE_NA_KERNELS")) c->force_na_kernels = atoi(nk) != 0;
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)

@@ -250,24 +250,35 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 template <typename T> struct Code;
 template <> struct Code<uint8_t> {
     typedef uint32_t Quad;
+    static constexpr uint32_t RESERVED = 0xFFu;      // the missing entry of gv_set_dosage_missing: the all-ones code
     static __device__ inline uint32_t get(Quad q, int e) { return (q >> (8 * e)) & 0xFFu; }
     static __device__ inline uint32_t get16(const u32x4& x, int e) { return (x[e >> 2] >> (8 * (e & 3))) & 0xFFu; }
 };
 template <> struct Code<uint16_t> {
     typedef u32x2 Quad;
+    static constexpr uint32_t RESERVED = 0xFFFFu;
     static __device__ inline uint32_t get(Quad q, int e) { return ((e < 2 ? q.x : q.y) >> (16 * (e & 1))) & 0xFFFFu; }
     static __device__ inline uint32_t get16(const u32x4& x, int e) { return (x[e >> 1] >> (16 * (e & 1))) & 0xFFFFu; }
 };
 template <typename T> __device__ inline typename Code<T>::Quad ntquad(const T* p) {
     return __builtin_nontemporal_load(reinterpret_cast<const typename Code<T>::Quad*>(p));
 }
+// d = code - mu'; NA (gv_set_dosage_missing): the reserved code gives +0.0 instead, compared where the code is extracted.  A select,
+// not a multiply: every sum below then adds an exact zero for a missing entry, and a row without one gets the bits of NA = false.
+template <typename T, bool NA> __device__ inline double code_diff(uint32_t code, double mu) {
+    const double d = (double)code - mu;
+    if (NA) return code == Code<T>::RESERVED ? 0.0 : d;
+    return d;
+}
 
 // ---- synthetic codes: genotype g in {0, 1, 2} from two allele draws at the marker's frequency (655 + h mod 32113) / 65536 -- about
 // 0.01 to 0.5 -- plus an imputation-like jitter, the product of two 16-bit hash fields: code = g * 3 * 2^(bits-3) + (jitter >> (18 -
 // bits)), i.e. {0, 96, 192} + [0, 63] for 8 bits and {0, 24576, 49152} + [0, 16383] for 16.  Integer arithmetic only, so
 // gvamp_amd/synth.py:synth_dosage reproduces the matrix bit for bit.  Pad columns are written as zeros.
-template <typename T>
-__global__ void k_synth_dosage(T* __restrict__ A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed) {
+// NA (gv_synth_dosage_na): the generated code is clamped one below the reserved code, then an independent draw -- the high half of a
+// second hash of the entry -- below miss_thr = miss_ppm 2^32 / 10^6 replaces it by the reserved code.
+template <typename T, bool NA>
+__global__ void k_synth_dosage(T* __restrict__ A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed, uint64_t miss_thr) {
     constexpr int BITS = 8 * (int)sizeof(T);
     for (int64_t m = blockIdx.x; m < M; m += gridDim.x) {
         const uint64_t g = (uint64_t)(S + m);
@@ -282,6 +293,10 @@ __global__ void k_synth_dosage(T* __restrict__ A, int64_t M, int64_t S, int64_t 
                 const uint64_t geno = ((r & 0xFFFFull) < maf ? 1ull : 0ull) + (((r >> 16) & 0xFFFFull) < maf ? 1ull : 0ull);
                 const uint64_t jit = (((r >> 32) & 0xFFFFull) * (r >> 48)) >> 16;
                 v = geno * (3ull << (BITS - 3)) + (jit >> (18 - BITS));
+                if (NA) {
+                    if (v >= Code<T>::RESERVED) v = Code<T>::RESERVED - 1;
+                    if ((splitmix64(r ^ 0x9FB21C651E98DF25ull) >> 32) < miss_thr) v = Code<T>::RESERVED;
+                }
             }
             row[j] = (T)v;
         }
@@ -290,27 +305,41 @@ __global__ void k_synth_dosage(T* __restrict__ A, int64_t M, int64_t S, int64_t 
 
 // ---- marker statistics in code units: mu' = (sum_present b) / nonas with the integer sum exact, q = sum_present (b - mu')^2 in a
 // second pass; mave = scale mu', msig = 1 if q == 0 else (scale sqrt(q / (nonas - 1)))^-alpha_scale.  mu' is kept for the products.
-template <typename T>
+// NA: b = 0 at the reserved code.  A second integer sum cnt = sum b na rides the butterfly of the first; mu' = (sum code b na) / cnt, 0
+// when cnt == 0; q runs over the present entries; the divisor under the root stays nonas - 1, as the bed statistics divide.  cnt is
+// kept in dcnt (exact in a double).  A row without the reserved code has cnt == nonas and gets the bits of NA = false.
+template <typename T, bool NA>
 __global__ __launch_bounds__(256) void k_dosage_stats(const T* __restrict__ A, int64_t M, int64_t N, int64_t pitch,
                                                       const uint32_t* __restrict__ mask2, double nonas, double alpha_scale,
                                                       double wscale, double* __restrict__ dmu, double* __restrict__ mave,
-                                                      double* __restrict__ msig) {
+                                                      double* __restrict__ msig, double* __restrict__ dcnt) {
     typedef typename Code<T>::Quad Quad;
     const int lane = threadIdx.x & (WAVE - 1);
     const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= M) return;
     const T* row = A + m * pitch;
-    unsigned long long s = 0;
+    unsigned long long s = 0, cnt = 0;
     for (int64_t j0 = 4 * lane; j0 < N; j0 += 4 * WAVE) {      // (j0 < N <= pitch, both multiples of 4 or beyond: the piece is in the row)
         const Quad x = *reinterpret_cast<const Quad*>(row + j0);
         const uint32_t mk = mask2[j0 >> 4] >> (2 * (j0 & 15));
 #pragma unroll
         for (int e = 0; e < 4; e++)
-            if (j0 + e < N) s += (unsigned long long)(Code<T>::get(x, e) * ((mk >> (2 * e)) & 1u));
+            if (j0 + e < N) {
+                const uint32_t code = Code<T>::get(x, e);
+                if (NA) {
+                    const uint32_t bn = code != Code<T>::RESERVED ? (mk >> (2 * e)) & 1u : 0u;
+                    s += (unsigned long long)(code * bn);
+                    cnt += bn;
+                } else
+                    s += (unsigned long long)(code * ((mk >> (2 * e)) & 1u));
+            }
     }
 #pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, WAVE);
-    const double mu = (double)s / nonas;
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        s += __shfl_xor(s, off, WAVE);
+        if (NA) cnt += __shfl_xor(cnt, off, WAVE);
+    }
+    const double mu = NA ? (cnt ? (double)s / (double)cnt : 0.0) : (double)s / nonas;
     double q = 0.0;
     for (int64_t j0 = 4 * lane; j0 < N; j0 += 4 * WAVE) {
         const Quad x = *reinterpret_cast<const Quad*>(row + j0);
@@ -318,13 +347,14 @@ __global__ __launch_bounds__(256) void k_dosage_stats(const T* __restrict__ A, i
 #pragma unroll
         for (int e = 0; e < 4; e++)
             if (j0 + e < N) {
-                const double d = ((double)Code<T>::get(x, e) - mu) * (double)((mk >> (2 * e)) & 1u);
+                const double d = code_diff<T, NA>(Code<T>::get(x, e), mu) * (double)((mk >> (2 * e)) & 1u);
                 q = fma(d, d, q);
             }
     }
     q = wave_sum(q);
     if (lane == 0) {
         dmu[m] = mu;
+        if (NA) dcnt[m] = (double)cnt;
         mave[m] = wscale * mu;
         double sg = 1.0;      // a constant column: q == 0 exactly in code units, whatever the scale
         if (q != 0.0) {
@@ -338,8 +368,9 @@ __global__ __launch_bounds__(256) void k_dosage_stats(const T* __restrict__ A, i
 // ---- ATx: out[m] = (msig[m] scale_x) sum_{j<N} (b[m][j] - mu'[m]) p[j] / sqrt(N), then the lmmse_mult epilogue.  A lane's sum runs
 // over its entries in ascending column step, piece and entry order whatever NV and R are, then the fixed butterfly: each slot of the
 // two-vector form is bit-identical to the one-vector call.
+// NA: d is +0.0 at the reserved code (code_diff), in the same place of the same order.
 constexpr int ATX_STEP = 1024;      // individuals per column step of a wave: 64 lanes x 4 pieces x 4 codes
-template <typename T, int NV, int R>
+template <typename T, int NV, int R, bool NA>
 __global__ __launch_bounds__(256) void k_dosage_atx(const T* __restrict__ A, int64_t M, int64_t N, int64_t pitch,
                                                     const double* __restrict__ pa, const double* __restrict__ pb,
                                                     const double* __restrict__ dmu, const double* __restrict__ msig, double wscale,
@@ -383,7 +414,7 @@ __global__ __launch_bounds__(256) void k_dosage_atx(const T* __restrict__ A, int
             for (int k = 0; k < 4; k++)
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    const double d = (double)Code<T>::get(x[r][k], e) - mu[r];
+                    const double d = code_diff<T, NA>(Code<T>::get(x[r][k], e), mu[r]);
 #pragma unroll
                     for (int v = 0; v < NV; v++) acc[r][v] = fma(d, p[v][k][e], acc[r][v]);
                 }
@@ -404,7 +435,7 @@ __global__ __launch_bounds__(256) void k_dosage_atx(const T* __restrict__ A, int
 #pragma unroll
                     for (int e = 0; e < 4; e++)
                         if (j0 + e < N) {
-                            const double d = (double)Code<T>::get(x, e) - mu[r];
+                            const double d = code_diff<T, NA>(Code<T>::get(x, e), mu[r]);
 #pragma unroll
                             for (int v = 0; v < NV; v++) acc[r][v] = fma(d, p[v][e], acc[r][v]);
                         }
@@ -463,11 +494,14 @@ __global__ __launch_bounds__(256) void k_assoc_prep(const double* __restrict__ y
 // Per row three sums with d = code - mu' formed per entry: sum d p, sum d na, sum (d na) d, each over the lane's entries in ascending
 // column step, piece and entry order, then the fixed butterfly -- a row's bits depend neither on R nor on the group or the list it
 // arrives in.  (d na) is a select: d * 1 and d * 0 of a finite d, without the multiply.  Lane 0 runs the test (gvp::dosage_stats).
-template <typename T, int R>
+// NA: d is +0.0 at the reserved code, and two more sums per row, sum b p and sum b p^2 of the masked residual, stand where the
+// pass's totals sp, sp2 stand otherwise; the sample size is the count the statistics left in dcnt.  A row whose count is nonas misses
+// nobody with a phenotype: its sums ARE sp and sp2, which it takes -- the bits of NA = false.
+template <typename T, int R, bool NA>
 __global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, int64_t N, int64_t pitch, const int64_t* __restrict__ rows,
                                                       int64_t nrows, const double* __restrict__ p, const uint32_t* __restrict__ mask2,
                                                       const double* __restrict__ dmu, const double* __restrict__ msig, double wscale,
-                                                      const double* __restrict__ psums, double nonas,
+                                                      const double* __restrict__ psums, double nonas, const double* __restrict__ dcnt,
                                                       const double* __restrict__ xself, double self_scale, double* __restrict__ beta,
                                                       double* __restrict__ se, double* __restrict__ tstat, double* __restrict__ pval) {
     typedef typename Code<T>::Quad Quad;
@@ -476,14 +510,16 @@ __global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, i
     const int64_t i0 = ((int64_t)blockIdx.x * 4 + wave) * R;
     if (i0 >= nrows) return;
     const T* row[R];
-    double mu[R], acc[R][3];
+    constexpr int NS = NA ? 5 : 3;
+    double mu[R], acc[R][NS];
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const int64_t ir = i0 + r < nrows ? i0 + r : nrows - 1;      // (a group's tail re-reads the last row; nothing is written for it)
         const int64_t mr = rows ? rows[ir] : ir;
         row[r] = A + mr * pitch + 4 * lane;
         mu[r] = dmu[mr];
-        acc[r][0] = acc[r][1] = acc[r][2] = 0.0;
+#pragma unroll
+        for (int v = 0; v < NS; v++) acc[r][v] = 0.0;
     }
     int64_t c0 = 0;
     for (; c0 + ATX_STEP <= N; c0 += ATX_STEP) {
@@ -508,11 +544,17 @@ __global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, i
             for (int k = 0; k < 4; k++)
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    const double d = (double)Code<T>::get(x[r][k], e) - mu[r];
+                    const uint32_t code = Code<T>::get(x[r][k], e);
+                    const double d = code_diff<T, NA>(code, mu[r]);
                     const double dn = (mk[k] >> (2 * e)) & 1u ? d : 0.0;
                     acc[r][0] = fma(d, q[k][e], acc[r][0]);
                     acc[r][1] += dn;
                     acc[r][2] = fma(dn, d, acc[r][2]);
+                    if (NA) {
+                        const double pb = code == Code<T>::RESERVED ? 0.0 : q[k][e];
+                        acc[r][NS - 2] += pb;
+                        acc[r][NS - 1] = fma(pb, pb, acc[r][NS - 1]);
+                    }
                 }
     }
     if (c0 < N) {      // the last, partial step: a piece starts below N or is skipped; j0 < N implies j0 + 3 < pitch <= npad
@@ -530,11 +572,17 @@ __global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, i
 #pragma unroll
                     for (int e = 0; e < 4; e++)
                         if (j0 + e < N) {
-                            const double d = (double)Code<T>::get(x, e) - mu[r];
+                            const uint32_t code = Code<T>::get(x, e);
+                            const double d = code_diff<T, NA>(code, mu[r]);
                             const double dn = (mk >> (2 * e)) & 1u ? d : 0.0;
                             acc[r][0] = fma(d, q[e], acc[r][0]);
                             acc[r][1] += dn;
                             acc[r][2] = fma(dn, d, acc[r][2]);
+                            if (NA) {
+                                const double pb = code == Code<T>::RESERVED ? 0.0 : q[e];
+                                acc[r][NS - 2] += pb;
+                                acc[r][NS - 1] = fma(pb, pb, acc[r][NS - 1]);
+                            }
                         }
                 }
             }
@@ -543,7 +591,7 @@ __global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, i
 #pragma unroll
     for (int r = 0; r < R; r++)
 #pragma unroll
-        for (int v = 0; v < 3; v++) acc[r][v] = wave_sum(acc[r][v]);
+        for (int v = 0; v < NS; v++) acc[r][v] = wave_sum(acc[r][v]);
     if (lane == 0) {
         const double sp = psums[0], sp2 = psums[1];
 #pragma unroll
@@ -551,7 +599,15 @@ __global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, i
             if (i0 + r < nrows) {
                 const int64_t m = rows ? rows[i0 + r] : i0 + r;
                 const double cself = xself ? xself[m] * self_scale : 0.0;
-                const gvp::Reg1d res = gvp::dosage_stats(acc[r][0], acc[r][1], acc[r][2], msig[m] * wscale, sp, sp2, nonas, cself);
+                gvp::Reg1d res;
+                if (NA) {      // sample size cnt_k; fewer than three present individuals leave no test
+                    const double n = dcnt[m];
+                    const bool whole = n == nonas;
+                    res = gvp::dosage_stats(acc[r][0], acc[r][1], acc[r][2], msig[m] * wscale, whole ? sp : acc[r][NS - 2],
+                                            whole ? sp2 : acc[r][NS - 1], n, cself);
+                    if (n < 3.0) res.beta = res.se = res.t = res.p = __builtin_nan("");
+                } else
+                    res = gvp::dosage_stats(acc[r][0], acc[r][1], acc[r][2], msig[m] * wscale, sp, sp2, nonas, cself);
                 beta[m] = res.beta; se[m] = res.se; tstat[m] = res.t; pval[m] = res.p;
             }
     }
@@ -559,7 +615,8 @@ __global__ __launch_bounds__(256) void k_dosage_assoc(const T* __restrict__ A, i
 
 // ---- Ax, first stage: partial[seg][j] = sum over the segment's markers i of (b[i][j] - mu'[i]) * (msig[i] scale_x v[i]), markers in
 // ascending order; a lane owns the 16 / sizeof(T) individuals of one 16-byte load.  Second stage: k_dense_ax_reduce.
-template <typename T, int NV>
+// NA: (b - mu') is +0.0 at the reserved code (code_diff): the entry adds an exact zero.
+template <typename T, int NV, bool NA>
 __global__ __launch_bounds__(256) void k_dosage_ax(const T* __restrict__ A, int64_t M, int64_t pitch, int64_t seg_len,
                                                    const double* __restrict__ va, const double* __restrict__ vb,
                                                    const double* __restrict__ dmu, const double* __restrict__ msig, double wscale,
@@ -586,7 +643,7 @@ __global__ __launch_bounds__(256) void k_dosage_ax(const T* __restrict__ A, int6
             const double wa = sw * va[i + u], wb = sw * vb[i + u];
 #pragma unroll
             for (int e = 0; e < EPL; e++) {
-                const double d = (double)Code<T>::get16(x[u], e) - mu;
+                const double d = code_diff<T, NA>(Code<T>::get16(x[u], e), mu);
                 acc[0][e] = fma(d, wa, acc[0][e]);
                 if (NV == 2) acc[NV - 1][e] = fma(d, wb, acc[NV - 1][e]);
             }
@@ -598,7 +655,7 @@ __global__ __launch_bounds__(256) void k_dosage_ax(const T* __restrict__ A, int6
         const double wa = sw * va[i], wb = sw * vb[i];
 #pragma unroll
         for (int e = 0; e < EPL; e++) {
-            const double d = (double)Code<T>::get16(x, e) - mu;
+            const double d = code_diff<T, NA>(Code<T>::get16(x, e), mu);
             acc[0][e] = fma(d, wa, acc[0][e]);
             if (NV == 2) acc[NV - 1][e] = fma(d, wb, acc[NV - 1][e]);
         }
@@ -613,27 +670,30 @@ __global__ __launch_bounds__(256) void k_dosage_ax(const T* __restrict__ A, int6
 
 inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
-template <typename T>
+template <typename T, bool NA>
 void dosage_atx_t(hipStream_t s, int nv, const T* A, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
                   const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb,
                   const double* addxa, const double* addxb, double tau, double gam2) {
     if (nv == 2)
-        hipLaunchKernelGGL((k_dosage_atx<T, 2, 4>), dim3(nblk(M, 16)), dim3(256), 0, s, A, M, N, pitch, pa, pb, dmu, msig, wscale, scale,
+        hipLaunchKernelGGL((k_dosage_atx<T, 2, 4, NA>), dim3(nblk(M, 16)), dim3(256), 0, s, A, M, N, pitch, pa, pb, dmu, msig, wscale, scale,
                            outa, outb, addxa, addxb, tau, gam2);
-    else
-        hipLaunchKernelGGL((k_dosage_atx<T, 1, 8>), dim3(nblk(M, 32)), dim3(256), 0, s, A, M, N, pitch, pa, pa, dmu, msig, wscale, scale,
-                           outa, outa, addxa, addxa, tau, gam2);
+    else {
+        // (NA on 16-bit codes: R = 8 costs 151 VGPRs and 30 spilled SGPRs, so four rows per wave there; a row's bits do not depend on R)
+        constexpr int R1 = NA && sizeof(T) == 2 ? 4 : 8;
+        hipLaunchKernelGGL((k_dosage_atx<T, 1, R1, NA>), dim3(nblk(M, 4 * R1)), dim3(256), 0, s, A, M, N, pitch, pa, pa, dmu, msig, wscale,
+                           scale, outa, outa, addxa, addxa, tau, gam2);
+    }
 }
 
-template <typename T>
+template <typename T, bool NA>
 void dosage_ax_t(hipStream_t s, int nv, const gvd::AxShape& sh, const T* A, int64_t M, int64_t pitch, const double* va,
                  const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad) {
     const int64_t stride = (int64_t)sh.segs * npad;
     const dim3 grid((unsigned)sh.col_tiles, (unsigned)sh.segs);
     if (nv == 2)
-        hipLaunchKernelGGL((k_dosage_ax<T, 2>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, vb, dmu, msig, wscale, part, stride, npad);
+        hipLaunchKernelGGL((k_dosage_ax<T, 2, NA>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, vb, dmu, msig, wscale, part, stride, npad);
     else
-        hipLaunchKernelGGL((k_dosage_ax<T, 1>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, va, dmu, msig, wscale, part, stride, npad);
+        hipLaunchKernelGGL((k_dosage_ax<T, 1, NA>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, va, dmu, msig, wscale, part, stride, npad);
 }
 
 }  // namespace
@@ -704,44 +764,58 @@ void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int
                            outa, outa);
 }
 
-// ---- compact dense data: `bits` (8 or 16) selects the code type
-void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed) {
+// ---- compact dense data: `bits` (8 or 16) selects the code type, `na` the missing-aware instantiation (gv_set_dosage_missing)
+void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed, bool na,
+                  uint64_t miss_thr) {
     if (M <= 0) return;
     const dim3 g((unsigned)(M < 16384 ? M : 16384));
-    if (bits == 8)
-        hipLaunchKernelGGL(k_synth_dosage<uint8_t>, g, dim3(256), 0, s, (uint8_t*)A, M, S, N, pitch, seed);
-    else
-        hipLaunchKernelGGL(k_synth_dosage<uint16_t>, g, dim3(256), 0, s, (uint16_t*)A, M, S, N, pitch, seed);
+    if (bits == 8) {
+        if (na) hipLaunchKernelGGL((k_synth_dosage<uint8_t, true>), g, dim3(256), 0, s, (uint8_t*)A, M, S, N, pitch, seed, miss_thr);
+        else hipLaunchKernelGGL((k_synth_dosage<uint8_t, false>), g, dim3(256), 0, s, (uint8_t*)A, M, S, N, pitch, seed, miss_thr);
+    } else {
+        if (na) hipLaunchKernelGGL((k_synth_dosage<uint16_t, true>), g, dim3(256), 0, s, (uint16_t*)A, M, S, N, pitch, seed, miss_thr);
+        else hipLaunchKernelGGL((k_synth_dosage<uint16_t, false>), g, dim3(256), 0, s, (uint16_t*)A, M, S, N, pitch, seed, miss_thr);
+    }
 }
 
-void dosage_stats(hipStream_t s, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
-                  double alpha_scale, double wscale, double* dmu, double* mave, double* msig) {
+template <typename T, bool NA>
+static void dosage_stats_t(hipStream_t s, const void* A, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
+                           double alpha_scale, double wscale, double* dmu, double* mave, double* msig, double* dcnt) {
+    hipLaunchKernelGGL((k_dosage_stats<T, NA>), dim3(nblk(M, 4)), dim3(256), 0, s, (const T*)A, M, N, pitch, mask2, nonas, alpha_scale,
+                       wscale, dmu, mave, msig, dcnt);
+}
+void dosage_stats(hipStream_t s, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2,
+                  double nonas, double alpha_scale, double wscale, double* dmu, double* mave, double* msig, double* dcnt) {
     if (M <= 0) return;
-    if (bits == 8)
-        hipLaunchKernelGGL(k_dosage_stats<uint8_t>, dim3(nblk(M, 4)), dim3(256), 0, s, (const uint8_t*)A, M, N, pitch, mask2, nonas,
-                           alpha_scale, wscale, dmu, mave, msig);
-    else
-        hipLaunchKernelGGL(k_dosage_stats<uint16_t>, dim3(nblk(M, 4)), dim3(256), 0, s, (const uint16_t*)A, M, N, pitch, mask2, nonas,
-                           alpha_scale, wscale, dmu, mave, msig);
+    auto f = bits == 8 ? (na ? dosage_stats_t<uint8_t, true> : dosage_stats_t<uint8_t, false>)
+                       : (na ? dosage_stats_t<uint16_t, true> : dosage_stats_t<uint16_t, false>);
+    f(s, A, M, N, pitch, mask2, nonas, alpha_scale, wscale, dmu, mave, msig, dcnt);
 }
 
-void dosage_atx(hipStream_t s, int nv, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
-                const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb, const double* addxa,
-                const double* addxb, double tau, double gam2) {
+void dosage_atx(hipStream_t s, int nv, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const double* pa,
+                const double* pb, const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb,
+                const double* addxa, const double* addxb, double tau, double gam2) {
     if (M <= 0) return;
-    if (bits == 8)
-        dosage_atx_t(s, nv, (const uint8_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
-    else
-        dosage_atx_t(s, nv, (const uint16_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
+    if (bits == 8) {
+        auto f = na ? dosage_atx_t<uint8_t, true> : dosage_atx_t<uint8_t, false>;
+        f(s, nv, (const uint8_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
+    } else {
+        auto f = na ? dosage_atx_t<uint16_t, true> : dosage_atx_t<uint16_t, false>;
+        f(s, nv, (const uint16_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
+    }
 }
 
-void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, int64_t M, int64_t pitch, const double* va,
-                       const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad) {
+void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, bool na, int64_t M, int64_t pitch,
+                       const double* va, const double* vb, const double* dmu, const double* msig, double wscale, double* part,
+                       int64_t npad) {
     if (M <= 0) return;
-    if (bits == 8)
-        dosage_ax_t(s, nv, sh, (const uint8_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
-    else
-        dosage_ax_t(s, nv, sh, (const uint16_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
+    if (bits == 8) {
+        auto f = na ? dosage_ax_t<uint8_t, true> : dosage_ax_t<uint8_t, false>;
+        f(s, nv, sh, (const uint8_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
+    } else {
+        auto f = na ? dosage_ax_t<uint16_t, true> : dosage_ax_t<uint16_t, false>;
+        f(s, nv, sh, (const uint16_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
+    }
 }
 
 constexpr int ASSOC_R = 4;
@@ -753,17 +827,66 @@ void assoc_prep(hipStream_t s, const double* y, const double* z1, const double* 
     gvk::finalize(s, partial, nb, 2, sums);
 }
 
-void dosage_assoc(hipStream_t s, const void* A, int bits, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows, const double* p,
-                  const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums, double nonas,
-                  const double* xself, double self_scale, double* beta, double* se, double* tstat, double* pval) {
+template <typename T, bool NA>
+static void dosage_assoc_t(hipStream_t s, const void* A, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows, const double* p,
+                           const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums,
+                           double nonas, const double* dcnt, const double* xself, double self_scale, double* beta, double* se,
+                           double* tstat, double* pval) {
+    hipLaunchKernelGGL((k_dosage_assoc<T, ASSOC_R, NA>), dim3(nblk(nrows, 4 * ASSOC_R)), dim3(256), 0, s, (const T*)A, N, pitch, rows,
+                       nrows, p, mask2, dmu, msig, wscale, psums, nonas, dcnt, xself, self_scale, beta, se, tstat, pval);
+}
+void dosage_assoc(hipStream_t s, const void* A, int bits, bool na, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows,
+                  const double* p, const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums,
+                  double nonas, const double* dcnt, const double* xself, double self_scale, double* beta, double* se, double* tstat,
+                  double* pval) {
     if (nrows <= 0) return;
-    const dim3 g(nblk(nrows, 4 * ASSOC_R));
+    auto f = bits == 8 ? (na ? dosage_assoc_t<uint8_t, true> : dosage_assoc_t<uint8_t, false>)
+                       : (na ? dosage_assoc_t<uint16_t, true> : dosage_assoc_t<uint16_t, false>);
+    f(s, A, N, pitch, rows, nrows, p, mask2, dmu, msig, wscale, psums, nonas, dcnt, xself, self_scale, beta, se, tstat, pval);
+}
+
+// The reserved codes of n consecutive codes (whole pitched rows of an upload: the zero padding is not the reserved code): a count per
+// lane, the fixed butterfly, the four wave counts of a block in order, then one block adds the block partials strided and by a fixed
+// tree and adds the result to *total -- in stream order after the copy it counts, exact integers, no atomics.
+template <typename T>
+__global__ __launch_bounds__(256) void k_count_reserved(const T* __restrict__ A, int64_t n, unsigned long long* __restrict__ partial) {
+    __shared__ unsigned long long sh[4];
+    unsigned long long cnt = 0;
+    constexpr int EPL = 16 / (int)sizeof(T);      // (n is a multiple of the row pitch, 64 codes: whole 16-byte pieces)
+    const u32x4* A4 = reinterpret_cast<const u32x4*>(A);
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n / EPL; j += (int64_t)gridDim.x * 256) {
+        const u32x4 x = A4[j];
+#pragma unroll
+        for (int e = 0; e < EPL; e++) cnt += Code<T>::get16(x, e) == Code<T>::RESERVED ? 1u : 0u;
+    }
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) sh[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__global__ __launch_bounds__(256) void k_count_finish(const unsigned long long* __restrict__ partial, int nb,
+                                                      unsigned long long* __restrict__ total) {
+    __shared__ unsigned long long sh[256];
+    unsigned long long cnt = 0;
+    for (int b = threadIdx.x; b < nb; b += 256) cnt += partial[b];
+    sh[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total += sh[0];
+}
+void dosage_count_reserved(hipStream_t s, const void* A, int bits, int64_t n, unsigned long long* partial, unsigned long long* total) {
+    if (n <= 0) return;
+    const int64_t b = (n / 8 + 255) / 256;
+    const int nb = (int)(b > COUNT_BLOCKS ? COUNT_BLOCKS : b);
     if (bits == 8)
-        hipLaunchKernelGGL((k_dosage_assoc<uint8_t, ASSOC_R>), g, dim3(256), 0, s, (const uint8_t*)A, N, pitch, rows, nrows, p, mask2, dmu,
-                           msig, wscale, psums, nonas, xself, self_scale, beta, se, tstat, pval);
+        hipLaunchKernelGGL(k_count_reserved<uint8_t>, dim3(nb), dim3(256), 0, s, (const uint8_t*)A, n, partial);
     else
-        hipLaunchKernelGGL((k_dosage_assoc<uint16_t, ASSOC_R>), g, dim3(256), 0, s, (const uint16_t*)A, N, pitch, rows, nrows, p, mask2, dmu,
-                           msig, wscale, psums, nonas, xself, self_scale, beta, se, tstat, pval);
+        hipLaunchKernelGGL(k_count_reserved<uint16_t>, dim3(nb), dim3(256), 0, s, (const uint16_t*)A, n, partial);
+    hipLaunchKernelGGL(k_count_finish, dim3(1), dim3(256), 0, s, partial, nb, total);
 }
 
 }  // namespace gvd

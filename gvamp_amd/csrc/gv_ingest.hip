@@ -63,10 +63,12 @@ static int read_slab(int fd, int64_t off, uint8_t* dst, size_t nbytes) {
 
 // frees the dense matrix of either width (fp64 values, 8- / 16-bit codes) and what belongs to it
 static void drop_dense(gv_ctx* c) {
-    for (void** q : {(void**)&c->dense, &c->dcodes, (void**)&c->dense_mu})
+    for (void** q : {(void**)&c->dense, &c->dcodes, (void**)&c->dense_mu, (void**)&c->dense_cnt})
         if (*q) { (void)hipFree(*q); *q = nullptr; }
     c->dense_bits = 0;
     c->have_dense = false;
+    c->dense_na = false;      // whatever kind comes next starts without a missing code and with no reserved code counted
+    c->dense_reserved = 0;
 }
 
 static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed, uint32_t miss_thr, FILE* file = nullptr,
@@ -336,6 +338,8 @@ static int dense_prepare(gv_ctx* c, int bits) {
     if (c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
     c->have_raw = c->have_stripes = c->have_stats = c->have_dense = false;
     c->ingest_bytes = 0;
+    c->dense_na = false;
+    c->dense_reserved = 0;
     if (!c->dense_cus) {
         int cus = 0;
         HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
@@ -350,7 +354,12 @@ static int dense_prepare(gv_ctx* c, int bits) {
         hipError_t e = hipMalloc(&p, bytes);
         if (e == hipSuccess && bits) {
             e = hipMalloc(&c->dense_mu, sizeof(double) * rows);
-            if (e != hipSuccess) { (void)hipFree(p); c->dense_mu = nullptr; }
+            if (e == hipSuccess) e = hipMalloc(&c->dense_cnt, sizeof(double) * rows);
+            if (e != hipSuccess) {
+                (void)hipFree(p);
+                if (c->dense_mu) (void)hipFree(c->dense_mu);
+                c->dense_mu = c->dense_cnt = nullptr;
+            }
         }
         if (e != hipSuccess)
             return fail(c, "dense upload: no room for %lld x %lld %s in HBM: %s", (long long)c->M, (long long)c->dpitch,
@@ -359,11 +368,27 @@ static int dense_prepare(gv_ctx* c, int bits) {
         c->dense_bits = bits;
     }
     HIPCHK(c, hipMemsetAsync(bits ? c->dcodes : (void*)c->dense, 0, bytes, c->stream));
+    if (bits && c->dosage_missing) {      // the count of reserved codes of this upload starts at zero (count_reserved)
+        if (!c->dense_rcount) HIPCHK(c, hipMalloc(&c->dense_rcount, sizeof(unsigned long long)));
+        if (!c->dense_rpart) HIPCHK(c, hipMalloc(&c->dense_rpart, sizeof(unsigned long long) * gvd::COUNT_BLOCKS));
+        HIPCHK(c, hipMemsetAsync(c->dense_rcount, 0, sizeof(unsigned long long), c->stream));
+    }
     return 0;
+}
+// gv_set_dosage_missing: the reserved codes of the pitched rows [m0, m0 + mc), counted on the device behind their copy
+static void count_reserved(gv_ctx* c, int64_t m0, int64_t mc) {
+    if (!c->dosage_missing || !c->dense_bits || mc <= 0) return;
+    const size_t esz = (size_t)c->dense_bits / 8;
+    gvd::dosage_count_reserved(c->stream, (const char*)c->dcodes + (size_t)m0 * esz * (size_t)c->dpitch, c->dense_bits, mc * c->dpitch,
+                               c->dense_rpart, c->dense_rcount);
 }
 static int meth_prepare(gv_ctx* c) { return dense_prepare(c, 0); }
 static int meth_done(gv_ctx* c, double t_alloc, std::chrono::steady_clock::time_point t0) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->dense_bits && c->dosage_missing) {
+        HIPCHK(c, hipMemcpy(&c->dense_reserved, c->dense_rcount, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        c->dense_na = true;
+    }
     c->ingest_alloc_s = t_alloc;
     c->ingest_overlap_s = 0.0;
     c->ingest_fill_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_alloc;
@@ -425,6 +450,7 @@ static int dense_upload_file(gv_ctx* c, const char* who, const char* path, int64
         }
         e = hipMemcpy2DAsync(dst + (size_t)m0 * pitchb, pitchb, stage[sb], rowb, rowb, mc, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipEventRecord(stage_free[sb], c->stream);
+        if (e == hipSuccess && bits) count_reserved(c, m0, mc);
         if (e != hipSuccess) rc = fail(c, "%s: copy at marker %lld failed: %s", who, (long long)(c->S + m0), hipGetErrorString(e));
     }
     (void)hipStreamSynchronize(c->stream);
@@ -473,8 +499,10 @@ int gv_upload_dosage(gv_ctx* c, const void* codes, size_t n, int bits, double sc
         const int64_t mc = c->M - m0 < rows ? c->M - m0 : rows;
         HIPCHK(c, hipMemcpy2DAsync((char*)c->dcodes + (size_t)m0 * pitchb, pitchb, (const char*)codes + (size_t)m0 * rowb, rowb, rowb, mc,
                                    hipMemcpyHostToDevice, c->stream));
+        count_reserved(c, m0, mc);
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    KCHK(c);
     c->dense_scale = scale;
     return meth_done(c, ta, t0);
 }
@@ -487,15 +515,48 @@ int gv_upload_dosage_file(gv_ctx* c, const char* path, int64_t offset, int bits,
     return dense_upload_file(c, "gv_upload_dosage_file", path, offset, bits);
 }
 
-int gv_synth_dosage(gv_ctx* c, uint64_t seed, int bits) {
-    if (dosage_args(c, "gv_synth_dosage", bits, 1.0)) return 1;
+static int synth_dosage(gv_ctx* c, uint64_t seed, int bits, bool na, uint64_t miss_thr) {
     const auto t0 = std::chrono::steady_clock::now();
     if (dense_prepare(c, bits)) return 1;
     const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    gvd::dosage_synth(c->stream, c->dcodes, bits, c->M, c->S, c->N, c->dpitch, seed);
+    gvd::dosage_synth(c->stream, c->dcodes, bits, c->M, c->S, c->N, c->dpitch, seed, na, miss_thr);
+    count_reserved(c, 0, c->M);
     KCHK(c);
     c->dense_scale = bits == 8 ? 1.0 / 127.0 : 1.0 / 16384.0;
     return meth_done(c, ta, t0);
+}
+
+int gv_synth_dosage(gv_ctx* c, uint64_t seed, int bits) {
+    if (dosage_args(c, "gv_synth_dosage", bits, 1.0)) return 1;
+    return synth_dosage(c, seed, bits, false, 0);
+}
+
+int gv_synth_dosage_na(gv_ctx* c, uint64_t seed, int bits, uint32_t miss_ppm) {
+    if (dosage_args(c, "gv_synth_dosage_na", bits, 1.0)) return 1;
+    NEED(c, miss_ppm <= 1000000u, "gv_synth_dosage_na: miss_ppm above 1000000");
+    c->dosage_missing = true;      // (the data set held before is replaced: nothing resident goes stale)
+    return synth_dosage(c, seed, bits, true, ((uint64_t)miss_ppm << 32) / 1000000ull);
+}
+
+int gv_set_dosage_missing(gv_ctx* c, int on) {
+    const bool want = on != 0;
+    if (c->have_dense && c->dense_bits && want != c->dense_na)
+        return fail(c, "gv_set_dosage_missing: %d-bit codes are resident and were uploaded with the option %s; their statistics would be "
+                       "stale -- set it before the upload", c->dense_bits, c->dense_na ? "on" : "off");
+    c->dosage_missing = want;
+    return 0;
+}
+
+int gv_dosage_info(gv_ctx* c, gv_dosage_stats* out) {
+    NEED(c, out != nullptr, "gv_dosage_info: out is NULL");
+    const bool res = c->have_dense && c->dense_bits;
+    out->bits = res ? c->dense_bits : 0;
+    out->scale = res ? c->dense_scale : 0.0;
+    out->missing = (res ? c->dense_na : c->dosage_missing) ? 1 : 0;
+    out->reserved = res ? (uint64_t)c->dense_reserved : 0;
+    out->na_kernels = res && dosage_na_kernels(c) ? 1 : 0;
+    out->pad_ = 0;
+    return 0;
 }
 
 int gv_download_bed(gv_ctx* c, uint8_t* bed, size_t nbytes) {

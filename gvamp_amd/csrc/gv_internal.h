@@ -74,6 +74,14 @@ struct gv_ctx {
     int dense_bits = 0;
     double dense_scale = 1.0;
     double* dense_mu = nullptr;     // M mean codes mu' (mave = dense_scale * mu'): the products work in code units
+    // missing entries (gv_set_dosage_missing): the all-ones code is a missing entry.  dosage_missing is the setting, read by the next
+    // upload; dense_na what the resident codes were uploaded with; dense_reserved the reserved codes counted at that ingest (device
+    // word dense_rcount, block partials dense_rpart); the missing-aware kernels run when dosage_na_kernels(c) says so.
+    bool dosage_missing = false, dense_na = false;
+    bool force_na_kernels = false;  // GV_DOSAGE_NA_KERNELS=1 (development, read by gv_create per context)
+    unsigned long long dense_reserved = 0;
+    unsigned long long *dense_rcount = nullptr, *dense_rpart = nullptr;
+    double* dense_cnt = nullptr;    // M per-marker counts sum b na of the last gv_marker_stats (missing-aware kernels only)
     double tune_seconds = 0.0;      // wall time the pick cost (0 when it came from the cache)
     int tune_source = 0;            // 0 model's first candidate, 1 measured, 2 cache, 3 fixed by an override / nothing to tune
 
@@ -288,24 +296,32 @@ void ax_partial(hipStream_t s, int nv, const AxShape& sh, const double* A, int64
 void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int64_t N, int64_t npad, double scale, double* outa,
                double* outb);
 // compact dense data: A holds M * pitch unsigned codes of `bits` (8 or 16) bits, pitch in codes; dmu the mean codes; wscale the
-// factor between codes and values.  Same contracts as the fp64 forms above; the second Ax stage is ax_reduce.
-void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed);
-void dosage_stats(hipStream_t s, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
-                  double alpha_scale, double wscale, double* dmu, double* mave, double* msig);
-void dosage_atx(hipStream_t s, int nv, const void* A, int bits, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
-                const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb, const double* addxa,
-                const double* addxb, double tau, double gam2);
-void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, int64_t M, int64_t pitch, const double* va,
-                       const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad);
+// factor between codes and values.  Same contracts as the fp64 forms above; the second Ax stage is ax_reduce.  na: the missing-aware
+// instantiation (gv_set_dosage_missing: the all-ones code is a missing entry); dcnt: M per-marker counts sum b na, written by
+// dosage_stats and read by dosage_assoc when na is set, untouched otherwise (may be NULL then).
+void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed, bool na,
+                  uint64_t miss_thr);
+void dosage_stats(hipStream_t s, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2,
+                  double nonas, double alpha_scale, double wscale, double* dmu, double* mave, double* msig, double* dcnt);
+void dosage_atx(hipStream_t s, int nv, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const double* pa,
+                const double* pb, const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb,
+                const double* addxa, const double* addxb, double tau, double gam2);
+void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, bool na, int64_t M, int64_t pitch,
+                       const double* va, const double* vb, const double* dmu, const double* msig, double wscale, double* part,
+                       int64_t npad);
+// *total += the reserved codes among the n codes at A (whole pitched rows); partial: COUNT_BLOCKS device words of scratch
+constexpr int COUNT_BLOCKS = 1024;
+void dosage_count_reserved(hipStream_t s, const void* A, int bits, int64_t n, unsigned long long* partial, unsigned long long* total);
 // gv_assoc_* on compact dense data.  assoc_prep: p[npad] = y - z1 (+ add when not NULL) at the individuals with a phenotype, 0 at NA and
 // pad slots; sums[0..2) = {sum p, sum p^2} through the block partials (>= 2 * RED_BLOCKS doubles) in a fixed order.  dosage_assoc: the
 // test of the rows rows[0..nrows) (NULL: rows 0..nrows) against p; beta / se / tstat / pval are M-space device vectors written at the
 // tested rows only.  xself != NULL (leave-one-out): the row's own effect xself[m] * self_scale is added back analytically.
 void assoc_prep(hipStream_t s, const double* y, const double* z1, const double* add, const uint32_t* mask2, int64_t npad, double* p,
                 double* partial, double* sums);
-void dosage_assoc(hipStream_t s, const void* A, int bits, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows, const double* p,
-                  const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums, double nonas,
-                  const double* xself, double self_scale, double* beta, double* se, double* tstat, double* pval);
+void dosage_assoc(hipStream_t s, const void* A, int bits, bool na, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows,
+                  const double* p, const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums,
+                  double nonas, const double* dcnt, const double* xself, double self_scale, double* beta, double* se, double* tstat,
+                  double* pval);
 }  // namespace gvd
 
 // ---- LD-block preconditioner (gv_precond.hip) --------------------------------------------------------------------------------
@@ -366,6 +382,9 @@ void ev_resolve(gv_ctx* c);     // timing == 2: the pending event pairs into the
 int pc_prepare(gv_ctx* c, double tau, double gam2);
 void pc_apply(gv_ctx* c, const double* r, double* z);
 void pc_invalidate(gv_ctx* c, bool free_mem);
+// compact dense data: the missing-aware kernels run when the codes were uploaded with gv_set_dosage_missing on AND the ingest counted a
+// reserved code in this shard (a shard without one gets the same bits from the plain kernels) or GV_DOSAGE_NA_KERNELS=1 forces them
+inline bool dosage_na_kernels(const gv_ctx* c) { return c->dense_na && (c->dense_reserved != 0 || c->force_na_kernels); }
 
 struct Timer {
     gv_ctx* c;

@@ -166,7 +166,7 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
         if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
             if (c->dense_bits)
-                gvd::dosage_ax_partial(c->stream, nv, sh, c->dcodes, c->dense_bits, c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->dense_mu,
+                gvd::dosage_ax_partial(c->stream, nv, sh, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->dense_mu,
                                        c->msig, c->dense_scale, c->dense_part, c->npad);
             else
                 gvd::ax_partial(c->stream, nv, sh, c->dense, c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->mave, c->msig, c->dense_part, c->npad);
@@ -231,7 +231,7 @@ int atx_pass(gv_ctx* c, int nv, const double* pa, const double* pb, double* outa
         if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
             if (c->dense_bits)
-                gvd::dosage_atx(c->stream, nv, c->dcodes, c->dense_bits, c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->dense_mu, c->msig,
+                gvd::dosage_atx(c->stream, nv, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->dense_mu, c->msig,
                                 c->dense_scale, scale, outa, nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2);
             else
                 gvd::atx(c->stream, nv, c->dense, c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->mave, c->msig, scale, outa,

@@ -31,8 +31,8 @@ int gv_marker_stats(gv_ctx* c, double alpha_scale) {
     if (c->have_dense) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
         NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
         if (c->dense_bits)      // compact dense data: the same statistics in code units
-            gvd::dosage_stats(c->stream, c->dcodes, c->dense_bits, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale,
-                              c->dense_scale, c->dense_mu, c->mave, c->msig);
+            gvd::dosage_stats(c->stream, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->M, c->N, c->dpitch, c->mask2, (double)c->nonas,
+                              alpha_scale, c->dense_scale, c->dense_mu, c->mave, c->msig, c->dense_cnt);
         else
             gvd::stats(c->stream, c->dense, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale, c->mave, c->msig);
         c->alpha_scale = alpha_scale;
@@ -55,6 +55,19 @@ int gv_marker_stats(gv_ctx* c, double alpha_scale) {
     KCHK(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_stats = true;
+    return 0;
+}
+
+// the per-marker counts sum b na: what the missing-aware statistics left, nonas for every marker where no entry can be missing
+int gv_marker_counts(gv_ctx* c, double* cnt) {
+    NEED(c, cnt != nullptr, "gv_marker_counts: cnt is NULL");
+    NEED(c, c->have_dense && c->dense_bits, "gv_marker_counts: the resident dataset is not compact dosage data");
+    NEED(c, c->have_stats, "gv_marker_counts: gv_marker_stats has not run");
+    if (dosage_na_kernels(c)) {
+        HIPCHK(c, hipMemcpyAsync(cnt, c->dense_cnt, sizeof(double) * c->M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else
+        for (int64_t m = 0; m < c->M; m++) cnt[m] = (double)c->nonas;
     return 0;
 }
 
@@ -196,9 +209,9 @@ static int pvals_impl(gv_ctx* c, bool assoc, const gv_vec* z1, const gv_vec* y, 
         const bool loo = add == nullptr;
         if (dosage) {
             gvd::assoc_prep(c->stream, y->d, z1->d, add, c->mask2, c->npad, pa, c->red_partial, c->red_out);
-            gvd::dosage_assoc(c->stream, c->dcodes, c->dense_bits, c->N, c->dpitch, loo ? nullptr : rows_dev + r0, loo ? M : nr, pa,
-                              c->mask2, c->dense_mu, c->msig, c->dense_scale, c->red_out, (double)c->nonas, loo ? x1_hat->d : nullptr,
-                              1.0 / sqrtN, pva.beta, pva.se, pva.t, pv_dev);
+            gvd::dosage_assoc(c->stream, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->N, c->dpitch, loo ? nullptr : rows_dev + r0,
+                              loo ? M : nr, pa, c->mask2, c->dense_mu, c->msig, c->dense_scale, c->red_out, (double)c->nonas, c->dense_cnt,
+                              loo ? x1_hat->d : nullptr, 1.0 / sqrtN, pva.beta, pva.se, pva.t, pv_dev);
         } else if (fused) {
             pva.xself = loo ? x1_hat->d : nullptr;      // y_mark = y_mod + gen_part * x1_hat[k] (data.cpp:1145-1148): c = x1_hat[k] / sqrt(N)
             pva.self_scale = loo ? 1.0 / sqrtN : 0.0;

@@ -126,9 +126,9 @@ void data::push_mask() { ck(ctx, gv_set_mask(ctx, mask4.data(), nonas), "gv_set_
 
 data::data(std::vector<double> y, std::string genofp, const int N, const int M, const int Mt, const int S,
            const int rank, std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode,
-           double dosage_scale)
+           double dosage_scale, int dosage_missing)
     : bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), phen_data(y), alpha_scale(alpha_scale),
-      dosage_scale(dosage_scale) {
+      dosage_scale(dosage_scale), dosage_missing(dosage_missing) {
     check_type_data(type_data);
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
@@ -154,9 +154,10 @@ data::data(std::vector<double> y, std::string genofp, const int N, const int M, 
 }
 
 data::data(std::string fp, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
-           std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode, double dosage_scale)
+           std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode, double dosage_scale,
+           int dosage_missing)
     : phenfp(fp), bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), alpha_scale(alpha_scale),
-      dosage_scale(dosage_scale) {
+      dosage_scale(dosage_scale), dosage_missing(dosage_missing) {
     check_type_data(type_data);
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
@@ -277,12 +278,16 @@ void data::read_methylation_data() {
 }
 
 // [ext] compact dense data: this rank's M x N dosage codes (8 or 16 bits each, marker-major) at byte offset S*N*bits/8, streamed to
-// the device as the methylation matrix is.  No missing entries: hard-call missings are mean-imputed before the codes are written.
+// the device as the methylation matrix is.  dosage_missing: the all-ones code is a missing entry, kept out of every sum as the bed
+// path keeps a missing genotype out (gv_set_dosage_missing); otherwise every code is a value.
 void data::read_dosage_data() {
     const int bits = dosage_bits(type_data);
     const size_t size_bytes = size_t(M) * size_t(N) * size_t(bits / 8);
     if (dosage_scale <= 0) dosage_scale = bits == 8 ? 1.0 / 127.0 : 1.0 / 16384.0;
-    if (rank == 0) std::cout << "dosage file name = " << methfp << " (" << bits << "-bit codes, scale " << dosage_scale << ")" << std::endl;
+    if (rank == 0)
+        std::cout << "dosage file name = " << methfp << " (" << bits << "-bit codes, scale " << dosage_scale
+                  << (dosage_missing ? ", the all-ones code is a missing entry)" : ")") << std::endl;
+    ck(ctx, gv_set_dosage_missing(ctx, dosage_missing), "gv_set_dosage_missing");
     printf("INFO   : rank %d streams %zu bytes (%.3f GB) of dosage codes to the device.\n", rank, size_bytes, double(size_bytes) / 1.0E9);
     const auto t0 = std::chrono::steady_clock::now();
     ck(ctx, gv_upload_dosage_file(ctx, methfp.c_str(), (int64_t)(size_t(S) * size_t(N) * size_t(bits / 8)), bits, dosage_scale),

@@ -143,6 +143,11 @@ void Options::read_command_line_options(int argc, char** argv) {
             fatal(std::string("FATAL  : option --dosage-scale has to be a positive number! (") + a + " was passed)");
         dosage_scale = atof(a);
     };
+    H["--dosage-missing"] = [&](const char* a) {
+        if (strcmp(a, "0") && strcmp(a, "1"))
+            fatal(std::string("FATAL  : option --dosage-missing has to be 0 or 1! (") + a + " was passed)");
+        dosage_missing = atoi(a);
+    };
     H["--store-assoc"] = [&](const char* a) {
         if (strcmp(a, "0") && strcmp(a, "1"))
             fatal(std::string("FATAL  : option --store-assoc has to be 0 or 1! (") + a + " was passed)");

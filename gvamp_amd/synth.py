@@ -105,3 +105,27 @@ def synth_dosage(N, M, seed, bits, S=0):
             jit = (((r >> np.uint64(32)) & f) * (r >> np.uint64(48))) >> np.uint64(16)
             out[m0:m1] = (geno * np.uint64(3 << (bits - 3)) + (jit >> np.uint64(18 - bits))).astype(out.dtype)
     return out
+
+
+def synth_dosage_na(N, M, seed, bits, miss_ppm, S=0):
+    """Host twin of gv_synth_dosage_na: the codes of synth_dosage clamped one below the reserved code (255 / 65535), then, per entry,
+    an independent draw -- the high 32 bits of a second hash of the entry below miss_ppm * 2^32 / 10^6 -- replaces the code by the
+    reserved one.  Integer arithmetic only: the two agree bit for bit."""
+    if not 0 <= miss_ppm <= 1000000:
+        raise ValueError("synth_dosage_na: miss_ppm must be within 0..1000000")
+    out = synth_dosage(N, M, seed, bits, S)
+    reserved = (1 << bits) - 1
+    out[out == reserved] = reserved - 1
+    miss_thr = np.uint64((miss_ppm << 32) // 1000000)
+    with np.errstate(over="ignore"):
+        g = np.arange(S, S + M, dtype=np.uint64)
+        hm = _splitmix64(np.uint64(seed) ^ (g * np.uint64(0xD1342543DE82EF95)))
+        base = _splitmix64(hm + np.uint64(0x632BE59BD9B4E019))
+        n = np.arange(N, dtype=np.uint64)
+        step = max(1, (1 << 22) // max(N, 1))
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            r = _splitmix64(base[m0:m1, None] + n[None, :])
+            rs = _splitmix64(r ^ np.uint64(0x9FB21C651E98DF25))
+            out[m0:m1][(rs >> np.uint64(32)) < miss_thr] = reserved
+    return out

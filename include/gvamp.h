@@ -92,8 +92,8 @@ int gv_synth_meth(gv_ctx* ctx, uint64_t seed);
 /* ---- compact dense data: dosages as 8- or 16-bit codes (`data` with type_data == "dosage8" / "dosage16") -----------------------
  * The dense kind above at 1 or 2 bytes per entry: X[m][n] = scale * B[m][n] with B unsigned integer codes, M*N of them, marker-major,
  * resident with the row pitch padded to a multiple of 64 codes (zeros in the padding).  PLINK 2 stores a dosage as a 16-bit code
- * (scale 1/16384); 8-bit codes are the usual compressed form (scale 1/127).  There are NO missing entries, as in the reference's
- * meth branch: hard-call missings must be mean-imputed upstream, before the codes are written.  Uploading any kind -- bed, meth,
+ * (scale 1/16384); 8-bit codes are the usual compressed form (scale 1/127).  By default every code is a value; missing entries are
+ * opt-in per context (gv_set_dosage_missing below: the all-ones code, as PLINK 2 writes it).  Uploading any kind -- bed, meth,
  * dosage -- replaces the dataset held before; gv_get_layout returns 4 (8-bit) or 5 (16-bit) while codes are resident.
  * Semantics are exactly those of the dense fp64 kind: statistics over the individuals with a phenotype, gv_ax applies no mask
  * and writes exact zeros at the pad slots, gv_atx uses p as given, the two-vector forms read the matrix once and each slot is
@@ -115,6 +115,47 @@ int gv_upload_dosage_file(gv_ctx* ctx, const char* path, int64_t offset, int bit
  * 0.01-0.5, genotype g in {0, 1, 2} from two allele draws, code = g * 3 * 2^(bits-3) + jitter with jitter < 2^(bits-2): the full
  * code range is used (codes >= 128 / >= 32768 occur).  gvamp_amd.synth.synth_dosage(N, M, seed, bits, S) reproduces it bit for bit. */
 int gv_synth_dosage(gv_ctx* ctx, uint64_t seed, int bits);
+/* ---- missing entries in compact dosage data (additions only: GV_ABI_VERSION stays 4) -------------------------------------------
+ * gv_set_dosage_missing(ctx, 1): the all-ones code -- 255 at 8 bits, 65535 at 16 bits, the code PLINK 2 reserves -- is a MISSING entry.
+ * A reserved code, not a mask plane: no extra byte is stored or read.  The setting is read by the next gv_upload_dosage,
+ * gv_upload_dosage_file or gv_synth_dosage*; changing it while codes are resident is refused (their statistics would be stale).
+ * Default 0: 255 / 65535 are the values they are, and nothing changes by a bit.  Methylation data have no missing code.
+ * With the option on let b_kn = 0 where the code of marker k, individual n is the reserved one, 1 otherwise, na_n the phenotype mask.
+ * Everything is the definition above with b put where the bed kind has it (data.cpp:951-988, :1155-1176):
+ *   cnt_k = sum_n b_kn na_n                          an exact integer (gv_marker_counts)
+ *   mu'_k = (sum_n code b na) / cnt_k                the integer sum exact; mu'_k = 0 when cnt_k == 0
+ *   q_k   = sum_n ((code - mu'_k) b na)^2            second pass
+ *   msig_k = 1 if q_k == 0 else (scale * sqrt(q_k / (nonas - 1)))^-alpha_scale;     mave_k = scale * mu'_k
+ *            -- the divisor is the global nonas - 1, not cnt_k - 1, exactly as the bed statistics divide
+ *   operator entry = (code - mu'_k) * (msig_k * scale) * b_kn / sqrt(N): formed per entry, never split into two sums; a missing
+ *            entry contributes an exact zero to gv_ax, gv_atx and their two-vector forms.
+ * The dense rules are unchanged: gv_ax applies no phenotype mask, gv_atx uses p as given, pad slots are exact zeros, each slot of a
+ * two-vector call is bit-identical to the one-vector call, no atomics anywhere.
+ * gv_assoc_loo / gv_assoc_loco: value_n = (code - mu'_k) * (msig_k * scale) * b_kn * na_n, the LOO self term uses the same value, and
+ * the sample size of marker k is cnt_k where it is nonas otherwise; sumy = sum b na p and sumsqy = sum b na p^2 run over the marker's
+ * present entries (a marker with cnt_k == nonas takes the pass's totals, which they are).  A marker with cnt_k < 3 or q_k == 0 gives
+ * NaN in all four outputs.
+ * The summation order of every kernel is that of the plain kernels, so a data set without a reserved code gives the same bits with
+ * the option on or off; a shard in which the ingest counted no reserved code therefore runs the plain kernels (gv_dosage_info). */
+int gv_set_dosage_missing(gv_ctx* ctx, int on);
+/* gv_synth_dosage's generator with missing entries; implies gv_set_dosage_missing(ctx, 1).  The generated code is CLAMPED one below
+ * the reserved code (254 / 65534 where gv_synth_dosage emits 255 / 65535); then, per entry, an independent draw -- the high 32 bits of
+ * a second hash of the entry below miss_ppm * 2^32 / 10^6 -- replaces it by the reserved code.  miss_ppm <= 1000000.
+ * gvamp_amd.synth.synth_dosage_na(N, M, seed, bits, miss_ppm, S) reproduces it bit for bit. */
+int gv_synth_dosage_na(gv_ctx* ctx, uint64_t seed, int bits, uint32_t miss_ppm);
+typedef struct {
+    double scale;          /* of the resident codes; 0 when none are resident */
+    uint64_t reserved;     /* reserved codes found at the last ingest of this shard: counted on the device behind the copy into the
+                            * pitched rows, exact; 0 when the option was off at that ingest (nothing is counted then) */
+    int bits;              /* 8 or 16; 0 when no codes are resident */
+    int missing;           /* the option the resident codes were uploaded with; without resident codes, the current setting */
+    int na_kernels;        /* 1: the missing-aware kernels are in use (option on and reserved != 0, or GV_DOSAGE_NA_KERNELS=1) */
+    int pad_;
+} gv_dosage_stats;
+int gv_dosage_info(gv_ctx* ctx, gv_dosage_stats* out);
+/* cnt: M host doubles, the per-marker counts cnt_k after gv_marker_stats -- nonas for every marker when nothing is missing.
+ * Compact dosage data only. */
+int gv_marker_counts(gv_ctx* ctx, double* cnt);
 
 /* The PLINK rows back from HBM: only when the raw row layout is resident, i.e. gv_set_layout(ctx, 1, ..) was called before
  * the ingest (not the default). */
@@ -399,7 +440,8 @@ int gv_pvals_loco_pred(gv_ctx* ctx, const gv_vec* z1, const gv_vec* y, const gv_
  * of both widths.  Per local marker k and individual n
  *     value_n = (x_kn - mave_k) * msig_k * b_kn * na_n
  *   bed data    : x = a (0, 1, 2), b = 1 where the genotype is present (data.cpp:1155-1175);
- *   dosage data : x = scale * code, b == 1 (no missing entry), formed in code units as (code - mu'_k) * (msig_k * scale).
+ *   dosage data : x = scale * code, formed in code units as (code - mu'_k) * (msig_k * scale); b == 1, or with
+ *                 gv_set_dosage_missing b = 0 at the reserved code.
  * p is the phenotype residual of pvals_calc / pvals_calc_LOCO, zero at NA and pad slots whatever the caller left in y there:
  *   leave-one-out            : y - z1 + value * x1_hat[k] / sqrt(N)
  *   leave-one-chromosome-out : y - z1 + (A x1_hat restricted to the marker's chromosome).
@@ -410,7 +452,7 @@ int gv_pvals_loco_pred(gv_ctx* ctx, const gv_vec* z1, const gv_vec* y, const gv_
  *   t    = rxy * sqrt((n - 2) / (1 - rxy^2)), signed
  *   se   = beta / t, evaluated as sqrt((n - 1) / (n - 2) * s2y * (1 - rxy^2) / ((n - 1) * s2x)): t == 0 gives no 0/0
  *   p    = two-sided Student-t tail of |t| with n - 2 degrees of freedom -- for bed data bit-identical to gv_pvals_*.
- * Dosage data: n = nonas for every marker; a constant column (q == 0, msig = 1, value == 0) yields NaN in all four outputs, as a
+ * Dosage data: n = nonas for every marker (cnt_k with gv_set_dosage_missing); a constant column (q == 0, msig = 1, value == 0) yields NaN in all four outputs, as a
  * monomorphic bed marker does.  The sums of a row are formed in a fixed order that depends neither on the call (LOO / LOCO) nor
  * on the other rows of the pass: results are bit-reproducible, and LOCO with x1_hat == 0 on one chromosome equals LOO bit for bit.
  * LOCO: markers whose chromosome is outside 1..23 get 0 in all four outputs; a pass streams the rows of its chromosome only, so the

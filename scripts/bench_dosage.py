@@ -2,6 +2,7 @@
 JSON line and, with --out, writes it to a file (profiles/dosage_bench_<shape>.json).
 
   python scripts/bench_dosage.py [--N 20000] [--M 800000] [--kinds u8,u16,f64] [--reps 10] [--rounds 3] [--seed 2026] [--out FILE]
+                                 [--miss-ppm P]
 
 Every kind asked for is resident at once (one context each; u8 + u16 + f64 at 20 000 x 800 000 are 16 + 32 + 128 GB) and the timed
 rounds alternate between them in one process: round r times Ax, ATx and both two-vector forms of every kind before round r + 1
@@ -11,7 +12,12 @@ device-generated gv_synth_meth matrix of the same shape: these kernels stream ev
 depend on the values.  Times are HIP events around each whole product (gv_set_timing 1: the streaming kernel plus, for Ax, its
 segment reduction), the median over the rounds of the mean over --reps calls.  TB/s are algorithmic: N * M * bits / 8 bytes of matrix
 per pass (the padding and the vectors not counted); `share` is against 8 TB/s; `x_f64` is the fp64 pass time over this kind's.
---kinds u8 alone serves the GWAS-shaped run (N 200 000 x M 500 000, 100 GB)."""
+--kinds u8 alone serves the GWAS-shaped run (N 200 000 x M 500 000, 100 GB).
+
+--miss-ppm P (missing entries, gv_set_dosage_missing): every code kind k runs twice in the same alternation -- `k`, the plain kernels,
+on gv_synth_dosage_na(seed, bits, 0) in a context that takes the shortcut (no reserved code counted), and `k_na`, the missing-aware
+kernels forced by GV_DOSAGE_NA_KERNELS=1, on gv_synth_dosage_na(seed, bits, P).  With P = 0 the two hold the same codes, read the same
+bytes and give the same bits, so `<product>_x_plain` = time(k_na) / time(k) is the cost of the compare and select alone."""
 import argparse
 import json
 import os
@@ -37,18 +43,29 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2026)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--miss-ppm", type=int, default=None)
     a = ap.parse_args()
     N, M = a.N, a.M
     kinds = [k for k in a.kinds.split(",") if k]
     assert kinds and all(k in BYTES for k in kinds), a.kinds
+    if a.miss_ppm is not None:
+        kinds = [kk for k in kinds for kk in ((k, k + "_na") if k != "f64" else (k,))]
+        for k in list(BYTES):
+            BYTES[k + "_na"] = BYTES[k]
     rng = np.random.default_rng(a.seed)
     xs = [rng.standard_normal(M), rng.standard_normal(M)]
     res = {"metric": "dosage_products", "N": N, "M": M, "reps": a.reps, "rounds": a.rounds, "peak_TBs": PEAK_TBS, "kinds": {}}
     same_values = N * M <= 2e8
     res["f64_values"] = "scale * codes (u8)" if same_values else "gv_synth_meth (same shape)"
+    if a.miss_ppm is not None:
+        res["miss_ppm"] = a.miss_ppm
     shards, run = {}, {}
     try:
         for k in kinds:
+            if k.endswith("_na"):                  # read by gv_create, per context
+                os.environ["GV_DOSAGE_NA_KERNELS"] = "1"
+            else:
+                os.environ.pop("GV_DOSAGE_NA_KERNELS", None)
             sh = capi.Shard(N, M)
             shards[k] = sh
             t0 = time.perf_counter()
@@ -56,6 +73,8 @@ def main():
                 sh.upload_meth(synth.synth_dosage(N, M, a.seed, 8).astype(np.float64) / 127.0)
             elif k == "f64":
                 sh.synth_meth(a.seed)
+            elif a.miss_ppm is not None:
+                sh.synth_dosage_na(a.seed, 8 * BYTES[k], a.miss_ppm if k.endswith("_na") else 0)
             else:
                 sh.synth_dosage(a.seed, 8 * BYTES[k])
             ingest = time.perf_counter() - t0
@@ -63,6 +82,8 @@ def main():
             sh.compute_markers_statistics()
             info = {"matrix_GB": N * M * BYTES[k] / 1e9, "ingest_s": ingest, "stats_ms": (time.perf_counter() - t0) * 1e3,
                     "layout": sh.get_layout()}
+            if k != "f64":
+                info["dosage_info"] = sh.dosage_info()
             res["kinds"][k] = info
             x, x2 = sh.vecM(xs[0]), sh.vecM(xs[1])
             pn = np.zeros(4 * sh.mbytes)
@@ -100,6 +121,10 @@ def main():
             for k in kinds:
                 for pr in PRODUCTS:
                     res["kinds"][k][pr + "_x_f64"] = res["kinds"]["f64"][pr + "_ms"] / res["kinds"][k][pr + "_ms"]
+        for k in kinds:
+            if k.endswith("_na"):
+                for pr in PRODUCTS:
+                    res["kinds"][k][pr + "_x_plain"] = res["kinds"][k][pr + "_ms"] / res["kinds"][k[:-3]][pr + "_ms"]
     finally:
         for sh in shards.values():
             sh.close()
