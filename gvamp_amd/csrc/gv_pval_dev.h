@@ -15,8 +15,13 @@ namespace gvp {
 //     J_0 = Q(b, u) / h ,   J_{n+1} = [(b + 2n)(b + 2n + 1) J_n + (u + b + 2n + 1) (ln x / 2)^{2n}] / (4 T^2) ,
 // with b = 1/2: Q(1/2, u) = erfc(sqrt u), and p_n constants (below).  The terms fall like 1 / (4 T^2): three or four of them reach
 // 1e-16 at the sample sizes of a genotype panel, where the Lentz continued fraction needs O(sqrt(nu)) ~ 450 steps of four fp64
-// divisions -- 7.4 ms for the 1M markers of the headline shard against 15 ms for the pass over the shard itself.  Checked against
-// scipy.stats.t.sf for nu = 28 ... 1e6, t = 1e-6 ... 37: relative error <= 4e-15 * (a few) (tests/test_gpu_pvals.py runs the kernel).
+// divisions -- 7.4 ms for the 1M markers of the headline shard against 15 ms for the pass over the shard itself.
+// Accuracy: tests/test_gpu_assoc_plane.py runs the three kernels that inline this function over nu = 1 ... 126 and 12000 ... 19998,
+// t^2 / nu = 1e-10 ... 1e5 (both sides of a = 15, a = 30 and w = 0.42, the far corner, p down to 1e-287, the underflow and the h == 0
+// cut) against a decimal evaluation of the finite closed forms (tests/student_t_reference.py) at the kernel's own t.  Its bar is the
+// error budget |p / p_ref - 1| <= 2^-52 (1024 + 16 |ln p|); measured on an MI355X the worst is 8.2 % of it (1.9e-13 at p = 6e-263,
+// nu = 19997), 1.0e-14 near p ~ 1 (nu = 29) and 5.0e-14 in the fraction's far tail (p = 3e-159, nu = 63): the error grows with
+// |ln p|, as the products a log1p(w) and T ln x under the exp make it.
 // p_n for b = 1/2: p_0 = 1, p_n = (b - 1)/(2n + 1)! + (1/n) sum_{m=1}^{n-1} (m b - n) p_{n-m} / (2m + 1)!
 __device__ __forceinline__ double bgrat_half_pn(int n) {
     const double P[10] = {1.0, -8.333333333333333e-02, 6.25e-03, -5.042989417989418e-04, 4.343722442680776e-05, -3.896385732323232e-06,
@@ -118,11 +123,17 @@ __device__ inline double marker_pval(double n2, double n1, double n0, double mu,
     const double sumsqy = s4[3] + 2.0 * cself * svy + cself * cself * sumsqx;
     return reg1d_pval(sumx, sumsqx, sumxy, sumy, sumsqy, count);
 }
-// marker_pval with the whole result: the same sums, in the same expressions
+// marker_pval with the whole result: the same sums, in the same expressions.  Fewer than three present genotypes leave the test no
+// degree of freedom: p is NaN by the formulas (nu <= 0), and beta, se, t are NaN by rule, as in k_dosage_assoc -- with two points
+// beta is finite, and se, t are NaN, inf or 0 by the last bit of 1 - rxy^2, i.e. by the summation order.  A marker monomorphic among
+// its present genotypes (mu is that genotype exactly, sumx = sumsqx = 0 exactly) has no regressor: NaN by rule as well -- sxy is an
+// exact 0 from the fp64 family's sums and a rounding error from the fixed-point ones, whose beta = sxy / 0 came out as -inf.  p is NaN
+// by the formulas in both cases (rxy is 0/0 or +-inf, t = inf * sqrt(-0) = NaN), so the narrow form needs no rule.
 __device__ inline Reg1d marker_stats(double n2, double n1, double n0, double mu, double sg, const double (&s4)[4], double cself) {
     const double count = n0 + n1 + n2;
     const double sumx = sg * (2.0 * n2 + n1 - mu * count);
     const double sumsqx = sg * sg * (n2 * (2.0 - mu) * (2.0 - mu) + n1 * (1.0 - mu) * (1.0 - mu) + n0 * mu * mu);
+    if (count < 3.0 || sumsqx == 0.0) return Reg1d{NAN, NAN, NAN, NAN};
     const double svy = sg * (s4[0] - mu * s4[1]);
     const double sumxy = svy + cself * sumsqx;
     const double sumy = s4[1] + cself * sumx;

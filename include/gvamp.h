@@ -453,7 +453,9 @@ int gv_pvals_loco_pred(gv_ctx* ctx, const gv_vec* z1, const gv_vec* y, const gv_
  *   se   = beta / t, evaluated as sqrt((n - 1) / (n - 2) * s2y * (1 - rxy^2) / ((n - 1) * s2x)): t == 0 gives no 0/0
  *   p    = two-sided Student-t tail of |t| with n - 2 degrees of freedom -- for bed data bit-identical to gv_pvals_*.
  * Dosage data: n = nonas for every marker (cnt_k with gv_set_dosage_missing); a constant column (q == 0, msig = 1, value == 0) yields NaN in all four outputs, as a
- * monomorphic bed marker does.  The sums of a row are formed in a fixed order that depends neither on the call (LOO / LOCO) nor
+ * monomorphic bed marker does.  Bed and dosage data alike: a marker with n < 3 -- fewer than three present genotypes or entries among
+ * the individuals with a phenotype -- has no degree of freedom left and yields NaN in all four outputs (gv_pvals_* give NaN there
+ * too), in every kernel family; so does a bed marker that is monomorphic among its present genotypes.  The sums of a row are formed in a fixed order that depends neither on the call (LOO / LOCO) nor
  * on the other rows of the pass: results are bit-reproducible, and LOCO with x1_hat == 0 on one chromosome equals LOO bit for bit.
  * LOCO: markers whose chromosome is outside 1..23 get 0 in all four outputs; a pass streams the rows of its chromosome only, so the
  * 23 passes read a dosage matrix once.  Vector spaces and marker statistics are checked as gv_pvals_* check them.

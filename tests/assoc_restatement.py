@@ -71,7 +71,8 @@ def t_two_sided(t, nu):
 
 
 def reg1d(sumx, sumsqx, sumxy, sumy, sumsqy, n, with_p=True):
-    """utilities.cpp:321-334 with the effect restored; se = beta / t written without the quotient (t == 0 gives no 0/0)"""
+    """utilities.cpp:321-334 with the effect restored; se = beta / t written without the quotient (t == 0 gives no 0/0).  n < 3 -- no
+    degree of freedom left for the test -- gives NaN in every output (include/gvamp.h)"""
     with np.errstate(invalid="ignore", divide="ignore"):
         s2y = (sumsqy - sumy * sumy / n) / (n - 1)
         s2x = (sumsqx - sumx * sumx / n) / (n - 1)
@@ -81,6 +82,8 @@ def reg1d(sumx, sumsqx, sumxy, sumy, sumsqy, n, with_p=True):
         beta = sxy / s2x
         se = np.sqrt((n - 1) / (n - 2) * s2y * (1 - rxy * rxy) / ((n - 1) * s2x))
     out = dict(beta=beta, se=se, t=t)
+    for k in out:
+        out[k] = np.where(np.asarray(n) < 3, np.asarray(beta).dtype.type("nan"), out[k])
     if with_p:
         out["p"] = t_two_sided(t, n - 2)
     return out

@@ -77,6 +77,20 @@ def test_student_t_tail_of_the_restatement_at_known_values():
     assert np.isnan(ar.t_two_sided(np.array([np.nan]), 5.0))[0]
 
 
+def test_fewer_than_three_observations_give_nan_in_every_output():
+    """two points always lie on a line: beta would be finite, 1 - rxy^2 is 0 or a rounding error of either sign, and se, t come out as
+    NaN, inf or 0 by the last bit of it.  include/gvamp.h: n < 3 gives NaN in all four outputs"""
+    x, y = np.array([0.5, -1.5], dtype=LD), np.array([0.3, 0.9], dtype=LD)
+    for n in (0, 1, 2):
+        r = ar.reg1d(x[:n].sum(keepdims=True), (x[:n] ** 2).sum(keepdims=True), (x[:n] * y[:n]).sum(keepdims=True),
+                     y[:n].sum(keepdims=True), (y[:n] ** 2).sum(keepdims=True), np.array([n], dtype=LD))
+        assert all(np.isnan(r[k][0]) for k in ("beta", "se", "t", "p")), (n, r)
+    x, y = np.array([0.5, -1.5, 1.0], dtype=LD), np.array([0.3, 0.9, -0.2], dtype=LD)
+    r = ar.reg1d(x.sum(keepdims=True), (x ** 2).sum(keepdims=True), (x * y).sum(keepdims=True), y.sum(keepdims=True),
+                 (y ** 2).sum(keepdims=True), np.array([3], dtype=LD))
+    assert all(np.isfinite(r[k][0]) for k in ("beta", "se", "t", "p")) and 0 < r["p"][0] < 1
+
+
 def test_header_declares_the_assoc_family_and_the_abi_version_stays():
     txt = open(os.path.join(ROOT, "include", "gvamp.h")).read()
     assert re.search(r"^#define GV_ABI_VERSION 4$", txt, flags=re.M)
