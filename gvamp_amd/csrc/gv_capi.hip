@@ -150,26 +150,37 @@ int read_scalars(gv_ctx* c, int K, double* out) {
     return 0;
 }
 
+void dense_release(gv_ctx* c, bool keep_alloc) {
+    DenseData& d = c->dense;
+    d.resident = d.na = false;
+    d.reserved = 0;
+    if (keep_alloc) return;
+    for (void** q : {&d.rows, (void**)&d.mu, (void**)&d.cnt, (void**)&d.rcount, (void**)&d.rpart, (void**)&d.part})
+        if (*q) { (void)hipFree(*q); *q = nullptr; }
+    d.bits = 0;
+    d.part_cap = 0;
+}
+
+void free_layouts(gv_ctx* c) {
+    gvm::Plan& pl = c->plan;
+    if (c->stripes_slab) {       // the two stripe sets are views into one allocation
+        (void)hipFree(c->stripes_slab);
+        c->stripes_slab = nullptr;
+        pl.stripes_m = pl.stripes_n = nullptr;
+    }
+    for (void** q : {&pl.stripes_m, &pl.stripes_n, &pl.tiles, &pl.dig0, &pl.dig1, (void**)&pl.cv, (void**)&pl.ev, (void**)&pl.cv2,
+                     (void**)&pl.ev2, (void**)&pl.scal, (void**)&pl.partial})
+        if (*q) { (void)hipFree(*q); *q = nullptr; }
+}
+
 static void free_dataset(gv_ctx* c) {
     auto F = [](auto*& p) {
         if (p) (void)hipFree(p);
         p = nullptr;
     };
     F(c->bed); F(c->mask2); F(c->mave); F(c->msig); F(c->t3); F(c->ax_partial); F(c->counts);
-    F(c->dense); F(c->dense_part); F(c->dcodes); F(c->dense_mu); F(c->dense_cnt); F(c->dense_rcount); F(c->dense_rpart);
-    c->dense_bits = 0;
-    c->dense_na = false;
-    c->dense_reserved = 0;
-    c->dense_part_cap = 0;
-    c->have_dense = false;
-    if (c->stripes_slab) {
-        (void)hipFree(c->stripes_slab);
-        c->stripes_slab = nullptr;
-        c->plan.stripes_m = c->plan.stripes_n = nullptr;
-    }
-    F(c->plan.stripes_m); F(c->plan.stripes_n); F(c->plan.tiles); F(c->plan.dig0); F(c->plan.dig1); F(c->plan.cv); F(c->plan.ev);
-    F(c->plan.cv2); F(c->plan.ev2);
-    F(c->plan.scal); F(c->plan.partial);
+    dense_release(c);
+    free_layouts(c);
     F(c->cgx_state); F(c->cgx_go);
     if (c->cgx_rel_h) (void)hipHostFree(c->cgx_rel_h);
     c->cgx_rel = c->cgx_rel_h = nullptr;
@@ -603,7 +614,7 @@ int gv_reset_counters(gv_ctx* c) {
     return 0;
 }
 int gv_get_layout(const gv_ctx* c) {
-    if (c->have_dense) return c->dense_bits == 8 ? 4 : (c->dense_bits == 16 ? 5 : 3);
+    if (c->dense.resident) return c->dense.bits == 8 ? 4 : (c->dense.bits == 16 ? 5 : 3);
     return c->have_stripes ? (c->plan.layout == 1 ? 2 : 1) : 0;
 }
 int gv_copy_bandwidth(gv_ctx* c, size_t nbytes, int reps, double* gbps) {

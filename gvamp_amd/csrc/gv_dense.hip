@@ -25,6 +25,10 @@
 //   Ax         : as the fp64 kernel with a 16-byte load per lane: 16 (u8) or 8 (u16) individuals per lane, 4096 / 2048 per workgroup.
 //   assoc      : the per-marker association test (gv_assoc_*): the streaming structure of ATx with R = 4 rows per wave taken from an
 //                index list, three sums per row and the regression test in the epilogue.
+//
+// Host side (namespace gvd, at the end): one set of launchers for the three widths.  Each takes the resident matrix as a gvd::View
+// (gv_internal.h) and forks inside: bits == 0 launches the fp64 kernels, 8 / 16 go through with_codes, the one place where (bits, na)
+// picks a k_dosage_* instantiation.
 #include "gv_internal.h"
 #include "gv_pval_dev.h"
 
@@ -670,30 +674,36 @@ __global__ __launch_bounds__(256) void k_dosage_ax(const T* __restrict__ A, int6
 
 inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
-template <typename T, bool NA>
-void dosage_atx_t(hipStream_t s, int nv, const T* A, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
-                  const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb,
-                  const double* addxa, const double* addxb, double tau, double gam2) {
+// the fp64 launches of gvd::atx / gvd::ax_partial (M > 0)
+void atx_f64(hipStream_t s, int nv, const gvd::View& v, const double* pa, const double* pb, double scale, double* outa, double* outb,
+             const double* addxa, const double* addxb, double tau, double gam2) {
+    const double* A = (const double*)v.rows;
     if (nv == 2)
-        hipLaunchKernelGGL((k_dosage_atx<T, 2, 4, NA>), dim3(nblk(M, 16)), dim3(256), 0, s, A, M, N, pitch, pa, pb, dmu, msig, wscale, scale,
-                           outa, outb, addxa, addxb, tau, gam2);
-    else {
-        // (NA on 16-bit codes: R = 8 costs 151 VGPRs and 30 spilled SGPRs, so four rows per wave there; a row's bits do not depend on R)
-        constexpr int R1 = NA && sizeof(T) == 2 ? 4 : 8;
-        hipLaunchKernelGGL((k_dosage_atx<T, 1, R1, NA>), dim3(nblk(M, 4 * R1)), dim3(256), 0, s, A, M, N, pitch, pa, pa, dmu, msig, wscale,
-                           scale, outa, outa, addxa, addxa, tau, gam2);
-    }
+        hipLaunchKernelGGL(k_dense_atx<2>, dim3(nblk(v.M, 4)), dim3(256), 0, s, A, v.M, v.N, v.pitch, pa, pb, v.centre, v.msig, scale, outa,
+                           outb, addxa, addxb, tau, gam2);
+    else
+        hipLaunchKernelGGL(k_dense_atx<1>, dim3(nblk(v.M, 4)), dim3(256), 0, s, A, v.M, v.N, v.pitch, pa, pa, v.centre, v.msig, scale, outa,
+                           outa, addxa, addxa, tau, gam2);
 }
-
-template <typename T, bool NA>
-void dosage_ax_t(hipStream_t s, int nv, const gvd::AxShape& sh, const T* A, int64_t M, int64_t pitch, const double* va,
-                 const double* vb, const double* dmu, const double* msig, double wscale, double* part, int64_t npad) {
-    const int64_t stride = (int64_t)sh.segs * npad;
+void ax_partial_f64(hipStream_t s, int nv, const gvd::AxShape& sh, const gvd::View& v, const double* va, const double* vb, double* part,
+                    int64_t stride, int64_t npad) {
+    const double* A = (const double*)v.rows;
     const dim3 grid((unsigned)sh.col_tiles, (unsigned)sh.segs);
     if (nv == 2)
-        hipLaunchKernelGGL((k_dosage_ax<T, 2, NA>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, vb, dmu, msig, wscale, part, stride, npad);
+        hipLaunchKernelGGL(k_dense_ax<2>, grid, dim3(256), 0, s, A, v.M, v.pitch, sh.seg_len, va, vb, v.centre, v.msig, part, stride, npad);
     else
-        hipLaunchKernelGGL((k_dosage_ax<T, 1, NA>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, va, dmu, msig, wscale, part, stride, npad);
+        hipLaunchKernelGGL(k_dense_ax<1>, grid, dim3(256), 0, s, A, v.M, v.pitch, sh.seg_len, va, va, v.centre, v.msig, part, stride, npad);
+}
+
+// The one place where (bits, na) picks the instantiation of a k_dosage_* kernel: f is called with a CodeKind carrying the code type
+// and whether the all-ones code is a missing entry.
+template <typename T, bool NA> struct CodeKind { typedef T type; static constexpr bool na = NA; };
+template <typename F> void with_codes(int bits, bool na, F&& f) {
+    if (bits == 8) {
+        if (na) f(CodeKind<uint8_t, true>()); else f(CodeKind<uint8_t, false>());
+    } else {
+        if (na) f(CodeKind<uint16_t, true>()); else f(CodeKind<uint16_t, false>());
+    }
 }
 
 }  // namespace
@@ -718,41 +728,7 @@ AxShape ax_shape(int64_t N, int64_t M, int cus, int cols) {
     return sh;
 }
 
-void synth(hipStream_t s, double* A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed) {
-    if (M <= 0) return;
-    const int64_t g = M < 16384 ? M : 16384;
-    hipLaunchKernelGGL(k_synth_meth, dim3((unsigned)g), dim3(256), 0, s, A, M, S, N, pitch, seed);
-}
-
-void stats(hipStream_t s, const double* A, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
-           double alpha_scale, double* mave, double* msig) {
-    if (M <= 0) return;
-    hipLaunchKernelGGL(k_dense_stats, dim3(nblk(M, 4)), dim3(256), 0, s, A, M, N, pitch, mask2, nonas, alpha_scale, mave, msig);
-}
-
-void atx(hipStream_t s, int nv, const double* A, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
-         const double* mave, const double* msig, double scale, double* outa, double* outb, const double* addxa,
-         const double* addxb, double tau, double gam2) {
-    if (M <= 0) return;
-    if (nv == 2)
-        hipLaunchKernelGGL(k_dense_atx<2>, dim3(nblk(M, 4)), dim3(256), 0, s, A, M, N, pitch, pa, pb, mave, msig, scale, outa,
-                           outb, addxa, addxb, tau, gam2);
-    else
-        hipLaunchKernelGGL(k_dense_atx<1>, dim3(nblk(M, 4)), dim3(256), 0, s, A, M, N, pitch, pa, pa, mave, msig, scale, outa,
-                           outa, addxa, addxa, tau, gam2);
-}
-
-void ax_partial(hipStream_t s, int nv, const AxShape& sh, const double* A, int64_t M, int64_t pitch, const double* va,
-                const double* vb, const double* mave, const double* msig, double* part, int64_t npad) {
-    if (M <= 0) return;
-    const int64_t stride = (int64_t)sh.segs * npad;
-    const dim3 grid((unsigned)sh.col_tiles, (unsigned)sh.segs);
-    if (nv == 2)
-        hipLaunchKernelGGL(k_dense_ax<2>, grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, vb, mave, msig, part, stride, npad);
-    else
-        hipLaunchKernelGGL(k_dense_ax<1>, grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, va, mave, msig, part, stride, npad);
-}
-
+// (the fp64 launches stand ahead of the first code dispatch: kernels are emitted in the order of their first use)
 void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int64_t N, int64_t npad, double scale, double* outa,
                double* outb) {
     const int64_t stride = (int64_t)sh.segs * npad;
@@ -764,58 +740,73 @@ void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int
                            outa, outa);
 }
 
-// ---- compact dense data: `bits` (8 or 16) selects the code type, `na` the missing-aware instantiation (gv_set_dosage_missing)
-void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed, bool na,
-                  uint64_t miss_thr) {
+void synth(hipStream_t s, const View& v, int64_t S, uint64_t seed, uint64_t miss_thr) {
+    const int64_t M = v.M, N = v.N, pitch = v.pitch;
     if (M <= 0) return;
     const dim3 g((unsigned)(M < 16384 ? M : 16384));
-    if (bits == 8) {
-        if (na) hipLaunchKernelGGL((k_synth_dosage<uint8_t, true>), g, dim3(256), 0, s, (uint8_t*)A, M, S, N, pitch, seed, miss_thr);
-        else hipLaunchKernelGGL((k_synth_dosage<uint8_t, false>), g, dim3(256), 0, s, (uint8_t*)A, M, S, N, pitch, seed, miss_thr);
-    } else {
-        if (na) hipLaunchKernelGGL((k_synth_dosage<uint16_t, true>), g, dim3(256), 0, s, (uint16_t*)A, M, S, N, pitch, seed, miss_thr);
-        else hipLaunchKernelGGL((k_synth_dosage<uint16_t, false>), g, dim3(256), 0, s, (uint16_t*)A, M, S, N, pitch, seed, miss_thr);
+    if (!v.bits) {
+        hipLaunchKernelGGL(k_synth_meth, g, dim3(256), 0, s, (double*)v.rows, M, S, N, pitch, seed);
+        return;
     }
+    with_codes(v.bits, v.na, [&](auto kind) {
+        typedef typename decltype(kind)::type T;
+        hipLaunchKernelGGL((k_synth_dosage<T, decltype(kind)::na>), g, dim3(256), 0, s, (T*)v.rows, M, S, N, pitch, seed, miss_thr);
+    });
 }
 
-template <typename T, bool NA>
-static void dosage_stats_t(hipStream_t s, const void* A, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
-                           double alpha_scale, double wscale, double* dmu, double* mave, double* msig, double* dcnt) {
-    hipLaunchKernelGGL((k_dosage_stats<T, NA>), dim3(nblk(M, 4)), dim3(256), 0, s, (const T*)A, M, N, pitch, mask2, nonas, alpha_scale,
-                       wscale, dmu, mave, msig, dcnt);
-}
-void dosage_stats(hipStream_t s, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2,
-                  double nonas, double alpha_scale, double wscale, double* dmu, double* mave, double* msig, double* dcnt) {
+void stats(hipStream_t s, const View& v, const uint32_t* mask2, double nonas, double alpha_scale, double* mave) {
+    const int64_t M = v.M, N = v.N, pitch = v.pitch;
     if (M <= 0) return;
-    auto f = bits == 8 ? (na ? dosage_stats_t<uint8_t, true> : dosage_stats_t<uint8_t, false>)
-                       : (na ? dosage_stats_t<uint16_t, true> : dosage_stats_t<uint16_t, false>);
-    f(s, A, M, N, pitch, mask2, nonas, alpha_scale, wscale, dmu, mave, msig, dcnt);
+    if (!v.bits) {
+        hipLaunchKernelGGL(k_dense_stats, dim3(nblk(M, 4)), dim3(256), 0, s, (const double*)v.rows, M, N, pitch, mask2, nonas, alpha_scale,
+                           mave, v.msig);
+        return;
+    }
+    with_codes(v.bits, v.na, [&](auto kind) {
+        typedef typename decltype(kind)::type T;
+        hipLaunchKernelGGL((k_dosage_stats<T, decltype(kind)::na>), dim3(nblk(M, 4)), dim3(256), 0, s, (const T*)v.rows, M, N, pitch, mask2,
+                           nonas, alpha_scale, v.wscale, v.centre, mave, v.msig, v.cnt);
+    });
 }
 
-void dosage_atx(hipStream_t s, int nv, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const double* pa,
-                const double* pb, const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb,
-                const double* addxa, const double* addxb, double tau, double gam2) {
+void atx(hipStream_t s, int nv, const View& v, const double* pa, const double* pb, double scale, double* outa, double* outb,
+         const double* addxa, const double* addxb, double tau, double gam2) {
+    const int64_t M = v.M, N = v.N, pitch = v.pitch;
     if (M <= 0) return;
-    if (bits == 8) {
-        auto f = na ? dosage_atx_t<uint8_t, true> : dosage_atx_t<uint8_t, false>;
-        f(s, nv, (const uint8_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
-    } else {
-        auto f = na ? dosage_atx_t<uint16_t, true> : dosage_atx_t<uint16_t, false>;
-        f(s, nv, (const uint16_t*)A, M, N, pitch, pa, pb, dmu, msig, wscale, scale, outa, outb, addxa, addxb, tau, gam2);
-    }
+    if (!v.bits) return atx_f64(s, nv, v, pa, pb, scale, outa, outb, addxa, addxb, tau, gam2);
+    with_codes(v.bits, v.na, [&](auto kind) {
+        typedef typename decltype(kind)::type T;
+        constexpr bool NA = decltype(kind)::na;
+        const T* A = (const T*)v.rows;
+        if (nv == 2)
+            hipLaunchKernelGGL((k_dosage_atx<T, 2, 4, NA>), dim3(nblk(M, 16)), dim3(256), 0, s, A, M, N, pitch, pa, pb, v.centre, v.msig,
+                               v.wscale, scale, outa, outb, addxa, addxb, tau, gam2);
+        else {
+            // (NA on 16-bit codes: R = 8 costs 151 VGPRs and 30 spilled SGPRs, so four rows per wave there; a row's bits do not depend on R)
+            constexpr int R1 = NA && sizeof(T) == 2 ? 4 : 8;
+            hipLaunchKernelGGL((k_dosage_atx<T, 1, R1, NA>), dim3(nblk(M, 4 * R1)), dim3(256), 0, s, A, M, N, pitch, pa, pa, v.centre, v.msig,
+                               v.wscale, scale, outa, outa, addxa, addxa, tau, gam2);
+        }
+    });
 }
 
-void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, bool na, int64_t M, int64_t pitch,
-                       const double* va, const double* vb, const double* dmu, const double* msig, double wscale, double* part,
-                       int64_t npad) {
+void ax_partial(hipStream_t s, int nv, const AxShape& sh, const View& v, const double* va, const double* vb, double* part, int64_t npad) {
+    const int64_t M = v.M, pitch = v.pitch;
     if (M <= 0) return;
-    if (bits == 8) {
-        auto f = na ? dosage_ax_t<uint8_t, true> : dosage_ax_t<uint8_t, false>;
-        f(s, nv, sh, (const uint8_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
-    } else {
-        auto f = na ? dosage_ax_t<uint16_t, true> : dosage_ax_t<uint16_t, false>;
-        f(s, nv, sh, (const uint16_t*)A, M, pitch, va, vb, dmu, msig, wscale, part, npad);
-    }
+    const int64_t stride = (int64_t)sh.segs * npad;
+    const dim3 grid((unsigned)sh.col_tiles, (unsigned)sh.segs);
+    if (!v.bits) return ax_partial_f64(s, nv, sh, v, va, vb, part, stride, npad);
+    with_codes(v.bits, v.na, [&](auto kind) {
+        typedef typename decltype(kind)::type T;
+        constexpr bool NA = decltype(kind)::na;
+        const T* A = (const T*)v.rows;
+        if (nv == 2)
+            hipLaunchKernelGGL((k_dosage_ax<T, 2, NA>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, vb, v.centre, v.msig, v.wscale,
+                               part, stride, npad);
+        else
+            hipLaunchKernelGGL((k_dosage_ax<T, 1, NA>), grid, dim3(256), 0, s, A, M, pitch, sh.seg_len, va, va, v.centre, v.msig, v.wscale,
+                               part, stride, npad);
+    });
 }
 
 constexpr int ASSOC_R = 4;
@@ -827,22 +818,15 @@ void assoc_prep(hipStream_t s, const double* y, const double* z1, const double* 
     gvk::finalize(s, partial, nb, 2, sums);
 }
 
-template <typename T, bool NA>
-static void dosage_assoc_t(hipStream_t s, const void* A, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows, const double* p,
-                           const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums,
-                           double nonas, const double* dcnt, const double* xself, double self_scale, double* beta, double* se,
-                           double* tstat, double* pval) {
-    hipLaunchKernelGGL((k_dosage_assoc<T, ASSOC_R, NA>), dim3(nblk(nrows, 4 * ASSOC_R)), dim3(256), 0, s, (const T*)A, N, pitch, rows,
-                       nrows, p, mask2, dmu, msig, wscale, psums, nonas, dcnt, xself, self_scale, beta, se, tstat, pval);
-}
-void dosage_assoc(hipStream_t s, const void* A, int bits, bool na, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows,
-                  const double* p, const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums,
-                  double nonas, const double* dcnt, const double* xself, double self_scale, double* beta, double* se, double* tstat,
-                  double* pval) {
+void assoc(hipStream_t s, const View& v, const int64_t* rows, int64_t nrows, const double* p, const uint32_t* mask2, const double* psums,
+           double nonas, const double* xself, double self_scale, double* beta, double* se, double* tstat, double* pval) {
     if (nrows <= 0) return;
-    auto f = bits == 8 ? (na ? dosage_assoc_t<uint8_t, true> : dosage_assoc_t<uint8_t, false>)
-                       : (na ? dosage_assoc_t<uint16_t, true> : dosage_assoc_t<uint16_t, false>);
-    f(s, A, N, pitch, rows, nrows, p, mask2, dmu, msig, wscale, psums, nonas, dcnt, xself, self_scale, beta, se, tstat, pval);
+    with_codes(v.bits, v.na, [&](auto kind) {
+        typedef typename decltype(kind)::type T;
+        hipLaunchKernelGGL((k_dosage_assoc<T, ASSOC_R, decltype(kind)::na>), dim3(nblk(nrows, 4 * ASSOC_R)), dim3(256), 0, s,
+                           (const T*)v.rows, v.N, v.pitch, rows, nrows, p, mask2, v.centre, v.msig, v.wscale, psums, nonas, v.cnt, xself,
+                           self_scale, beta, se, tstat, pval);
+    });
 }
 
 // The reserved codes of n consecutive codes (whole pitched rows of an upload: the zero padding is not the reserved code): a count per
@@ -878,14 +862,15 @@ __global__ __launch_bounds__(256) void k_count_finish(const unsigned long long* 
     }
     if (threadIdx.x == 0) *total += sh[0];
 }
-void dosage_count_reserved(hipStream_t s, const void* A, int bits, int64_t n, unsigned long long* partial, unsigned long long* total) {
+void count_reserved(hipStream_t s, const View& v, int64_t m0, int64_t mc, unsigned long long* partial, unsigned long long* total) {
+    const int64_t n = mc * v.pitch;
     if (n <= 0) return;
     const int64_t b = (n / 8 + 255) / 256;
     const int nb = (int)(b > COUNT_BLOCKS ? COUNT_BLOCKS : b);
-    if (bits == 8)
-        hipLaunchKernelGGL(k_count_reserved<uint8_t>, dim3(nb), dim3(256), 0, s, (const uint8_t*)A, n, partial);
-    else
-        hipLaunchKernelGGL(k_count_reserved<uint16_t>, dim3(nb), dim3(256), 0, s, (const uint16_t*)A, n, partial);
+    with_codes(v.bits, false, [&](auto kind) {      // (the count does not depend on na)
+        typedef typename decltype(kind)::type T;
+        hipLaunchKernelGGL(k_count_reserved<T>, dim3(nb), dim3(256), 0, s, (const T*)v.rows + m0 * v.pitch, n, partial);
+    });
     hipLaunchKernelGGL(k_count_finish, dim3(1), dim3(256), 0, s, partial, nb, total);
 }
 

@@ -1,5 +1,6 @@
 // gv_ingest.hip -- getting a dataset resident: PLINK .bed rows (host buffer, file, synthetic) re-encoded chunk by chunk into the
-// layouts of the streaming kernels, the dense fp64 rows of methylation data, and the 8- / 16-bit code rows of compact dense data.
+// layouts of the streaming kernels, and the rows of the dense kinds -- fp64 values of methylation data, 8- / 16-bit codes of compact
+// dense data -- through one begin / copy / finish path (dense_begin, dense_finish).
 #include <cctype>
 #include <cerrno>
 #include <chrono>
@@ -61,16 +62,6 @@ static int read_slab(int fd, int64_t off, uint8_t* dst, size_t nbytes) {
     return 0;
 }
 
-// frees the dense matrix of either width (fp64 values, 8- / 16-bit codes) and what belongs to it
-static void drop_dense(gv_ctx* c) {
-    for (void** q : {(void**)&c->dense, &c->dcodes, (void**)&c->dense_mu, (void**)&c->dense_cnt})
-        if (*q) { (void)hipFree(*q); *q = nullptr; }
-    c->dense_bits = 0;
-    c->have_dense = false;
-    c->dense_na = false;      // whatever kind comes next starts without a missing code and with no reserved code counted
-    c->dense_reserved = 0;
-}
-
 static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed, uint32_t miss_thr, FILE* file = nullptr,
                   uint32_t ld_block = 0, uint32_t ld_thr = 0, int64_t file_off = 0) {
     NEED(c, c->N > 0, "ingest: gv_set_dims must be called first");
@@ -79,7 +70,7 @@ static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed,
     const int64_t M = c->M, P = c->pitch;
     gvm::Plan& pl = c->plan;
     c->have_raw = c->have_stripes = c->have_stats = false;
-    drop_dense(c);      // uploading any kind replaces the dataset held before
+    dense_release(c);      // uploading any kind replaces the dataset held before
     if (c->want_raw && !c->bed) HIPCHK(c, hipMalloc(&c->bed, (size_t)(M > 0 ? M : 1) * P));
     if (!c->want_raw && c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
     const auto t_in0 = std::chrono::steady_clock::now();
@@ -106,14 +97,7 @@ static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed,
     const bool rebuild = c->want_stripes && (pl.layout != want_layout || !(want_layout ? pl.tiles : pl.stripes_m));
     if (rebuild) {
         // (re)build the geometry and the buffers of the MFMA family for the layout asked for
-        if (c->stripes_slab) {       // the two stripe sets are views into one allocation
-            (void)hipFree(c->stripes_slab);
-            c->stripes_slab = nullptr;
-            pl.stripes_m = pl.stripes_n = nullptr;
-        }
-        for (void** q : {&pl.stripes_m, &pl.stripes_n, &pl.tiles, &pl.dig0, &pl.dig1, (void**)&pl.cv, (void**)&pl.ev,
-                         (void**)&pl.cv2, (void**)&pl.ev2, (void**)&pl.scal, (void**)&pl.partial})
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
+        free_layouts(c);
         if (plan_decomps(c)) return 1;
     }
     // The allocation of the resident layout -- seconds when the driver is still wiping what an earlier process freed -- runs on a
@@ -214,10 +198,7 @@ static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed,
     if (!alloc_err.empty()) {
         // nothing half-built stays behind: a retry on this context must allocate everything again (rebuild is decided from these
         // pointers), and the streaming kernels must never meet a layout whose digit / partial-sum buffers are missing
-        if (c->stripes_slab) { (void)hipFree(c->stripes_slab); c->stripes_slab = nullptr; pl.stripes_m = pl.stripes_n = nullptr; }
-        for (void** q : {&pl.stripes_m, &pl.stripes_n, &pl.tiles, &pl.dig0, &pl.dig1, (void**)&pl.cv, (void**)&pl.ev,
-                         (void**)&pl.cv2, (void**)&pl.ev2, (void**)&pl.scal, (void**)&pl.partial})
-            if (*q) { (void)hipFree(*q); *q = nullptr; }
+        free_layouts(c);
         (void)hipGetLastError();
         if (!rc) rc = fail(c, "ingest: allocating the resident layout failed: %s", alloc_err.c_str());
     }
@@ -323,108 +304,105 @@ int gv_synth_bed_ld(gv_ctx* c, uint64_t seed, uint32_t miss_ppm, uint32_t ld_blo
     return ingest(c, nullptr, true, seed, thr, nullptr, ld_block, (uint32_t)(lt > 0xFFFFFFFFull ? 0xFFFFFFFFull : lt));
 }
 
-// ---- methylation data (type_data == "meth"): the dense fp64 design matrix of gv_dense.hip ------------------------------------
+// ---- the dense kinds: the fp64 design matrix of methylation data (type_data == "meth") and the code rows of compact dense data ----
+// An upload runs between dense_begin and dense_finish; the clock carries its start and the seconds the allocation took.
+struct DenseClock {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double alloc_s = 0.0;
+};
 // Frees whatever genotype layout is resident (the next bed ingest rebuilds it) and allocates the dense rows, zeroed.
-// bits: 0 = fp64 values, 8 / 16 = unsigned codes (the mean codes of the statistics get their M doubles here too)
-static int dense_prepare(gv_ctx* c, int bits) {
+// bits: 0 = fp64 values, 8 / 16 = unsigned codes, X = scale * B (the mean codes of the statistics get their M doubles here too)
+static int dense_begin(gv_ctx* c, int bits, double scale, DenseClock* clk) {
     NEED(c, c->N > 0, "dense upload: gv_set_dims must be called first");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    gvm::Plan& pl = c->plan;
-    if (c->stripes_slab) { (void)hipFree(c->stripes_slab); c->stripes_slab = nullptr; pl.stripes_m = pl.stripes_n = nullptr; }
-    for (void** q : {&pl.stripes_m, &pl.stripes_n, &pl.tiles, &pl.dig0, &pl.dig1, (void**)&pl.cv, (void**)&pl.ev, (void**)&pl.cv2,
-                     (void**)&pl.ev2, (void**)&pl.scal, (void**)&pl.partial})
-        if (*q) { (void)hipFree(*q); *q = nullptr; }
+    free_layouts(c);
     if (c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
-    c->have_raw = c->have_stripes = c->have_stats = c->have_dense = false;
+    c->have_raw = c->have_stripes = c->have_stats = false;
     c->ingest_bytes = 0;
-    c->dense_na = false;
-    c->dense_reserved = 0;
-    if (!c->dense_cus) {
+    DenseData& d = c->dense;
+    dense_release(c, bits == d.bits && d.rows);      // rows of this width are held: their allocation is used again
+    if (!d.cus) {
         int cus = 0;
         HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        c->dense_cus = cus > 0 ? cus : 256;
+        d.cus = cus > 0 ? cus : 256;
     }
-    c->dpitch = gvd::row_pitch(c->N);
     const size_t rows = (size_t)(c->M > 0 ? c->M : 1);
-    const size_t bytes = (bits ? (size_t)bits / 8 : sizeof(double)) * rows * (size_t)c->dpitch;
-    if (bits != c->dense_bits || (bits ? !c->dcodes : !c->dense)) {      // another width (or nothing) is held: allocate afresh
-        drop_dense(c);
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess && bits) {
-            e = hipMalloc(&c->dense_mu, sizeof(double) * rows);
-            if (e == hipSuccess) e = hipMalloc(&c->dense_cnt, sizeof(double) * rows);
-            if (e != hipSuccess) {
-                (void)hipFree(p);
-                if (c->dense_mu) (void)hipFree(c->dense_mu);
-                c->dense_mu = c->dense_cnt = nullptr;
-            }
-        }
-        if (e != hipSuccess)
-            return fail(c, "dense upload: no room for %lld x %lld %s in HBM: %s", (long long)c->M, (long long)c->dpitch,
+    d.pitch = gvd::row_pitch(c->N);
+    if (!d.rows) {      // another width (or nothing) was held: allocate afresh
+        d.bits = bits;
+        hipError_t e = hipMalloc(&d.rows, d.bytes((int64_t)rows));
+        if (e == hipSuccess && bits) e = hipMalloc(&d.mu, sizeof(double) * rows);
+        if (e == hipSuccess && bits) e = hipMalloc(&d.cnt, sizeof(double) * rows);
+        if (e != hipSuccess) {
+            dense_release(c);
+            return fail(c, "dense upload: no room for %lld x %lld %s in HBM: %s", (long long)c->M, (long long)d.pitch,
                         bits == 8 ? "8-bit codes" : (bits == 16 ? "16-bit codes" : "doubles"), hipGetErrorString(e));
-        if (bits) c->dcodes = p; else c->dense = (double*)p;
-        c->dense_bits = bits;
+        }
     }
-    HIPCHK(c, hipMemsetAsync(bits ? c->dcodes : (void*)c->dense, 0, bytes, c->stream));
+    d.scale = scale;
+    HIPCHK(c, hipMemsetAsync(d.rows, 0, d.bytes((int64_t)rows), c->stream));
     if (bits && c->dosage_missing) {      // the count of reserved codes of this upload starts at zero (count_reserved)
-        if (!c->dense_rcount) HIPCHK(c, hipMalloc(&c->dense_rcount, sizeof(unsigned long long)));
-        if (!c->dense_rpart) HIPCHK(c, hipMalloc(&c->dense_rpart, sizeof(unsigned long long) * gvd::COUNT_BLOCKS));
-        HIPCHK(c, hipMemsetAsync(c->dense_rcount, 0, sizeof(unsigned long long), c->stream));
+        if (!d.rcount) HIPCHK(c, hipMalloc(&d.rcount, sizeof(unsigned long long)));
+        if (!d.rpart) HIPCHK(c, hipMalloc(&d.rpart, sizeof(unsigned long long) * gvd::COUNT_BLOCKS));
+        HIPCHK(c, hipMemsetAsync(d.rcount, 0, sizeof(unsigned long long), c->stream));
     }
+    clk->alloc_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - clk->t0).count();
     return 0;
 }
 // gv_set_dosage_missing: the reserved codes of the pitched rows [m0, m0 + mc), counted on the device behind their copy
 static void count_reserved(gv_ctx* c, int64_t m0, int64_t mc) {
-    if (!c->dosage_missing || !c->dense_bits || mc <= 0) return;
-    const size_t esz = (size_t)c->dense_bits / 8;
-    gvd::dosage_count_reserved(c->stream, (const char*)c->dcodes + (size_t)m0 * esz * (size_t)c->dpitch, c->dense_bits, mc * c->dpitch,
-                               c->dense_rpart, c->dense_rcount);
+    if (!c->dosage_missing || !c->dense.bits || mc <= 0) return;
+    gvd::count_reserved(c->stream, dense_view(c), m0, mc, c->dense.rpart, c->dense.rcount);
 }
-static int meth_prepare(gv_ctx* c) { return dense_prepare(c, 0); }
-static int meth_done(gv_ctx* c, double t_alloc, std::chrono::steady_clock::time_point t0) {
+static int dense_finish(gv_ctx* c, const DenseClock& clk) {
+    DenseData& d = c->dense;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->dense_bits && c->dosage_missing) {
-        HIPCHK(c, hipMemcpy(&c->dense_reserved, c->dense_rcount, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        c->dense_na = true;
+    if (d.bits && c->dosage_missing) {
+        HIPCHK(c, hipMemcpy(&d.reserved, d.rcount, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        d.na = true;
     }
-    c->ingest_alloc_s = t_alloc;
+    c->ingest_alloc_s = clk.alloc_s;
     c->ingest_overlap_s = 0.0;
-    c->ingest_fill_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - t_alloc;
-    c->ingest_bytes = (c->dense_bits ? (size_t)c->dense_bits / 8 : sizeof(double)) * (size_t)c->M * (size_t)c->dpitch;
-    c->have_dense = true;
+    c->ingest_fill_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - clk.t0).count() - clk.alloc_s;
+    c->ingest_bytes = d.bytes(c->M);
+    d.resident = true;
+    return 0;
+}
+// M * N elements of a caller-owned pageable host buffer into the pitched rows, `step` rows per copy (nothing to overlap)
+static int dense_copy_host(gv_ctx* c, const void* src, int64_t step) {
+    const DenseData& d = c->dense;
+    const size_t rowb = d.elem_bytes() * (size_t)c->N, pitchb = d.elem_bytes() * (size_t)d.pitch;
+    const int64_t rows = c->M < step ? c->M : step;
+    for (int64_t m0 = 0; m0 < c->M; m0 += rows) {
+        const int64_t mc = c->M - m0 < rows ? c->M - m0 : rows;
+        HIPCHK(c, hipMemcpy2DAsync((char*)d.rows + (size_t)m0 * pitchb, pitchb, (const char*)src + (size_t)m0 * rowb, rowb, rowb, mc,
+                                   hipMemcpyHostToDevice, c->stream));
+        count_reserved(c, m0, mc);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return 0;
 }
 
 int gv_upload_meth(gv_ctx* c, const double* x, size_t n) {
     NEED(c, c->N > 0, "gv_upload_meth: gv_set_dims must be called first");
     NEED(c, n == (size_t)c->M * (size_t)c->N, "gv_upload_meth: n != M * N");
-    const auto t0 = std::chrono::steady_clock::now();
-    if (meth_prepare(c)) return 1;
-    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const int64_t rows = c->M < 4096 ? c->M : 4096;      // rows per copy: a caller-owned pageable buffer, nothing to overlap
-    for (int64_t m0 = 0; m0 < c->M; m0 += rows) {
-        const int64_t mc = c->M - m0 < rows ? c->M - m0 : rows;
-        HIPCHK(c, hipMemcpy2DAsync(c->dense + m0 * c->dpitch, sizeof(double) * c->dpitch, x + m0 * c->N, sizeof(double) * c->N,
-                                   sizeof(double) * c->N, mc, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return meth_done(c, ta, t0);
+    DenseClock clk;
+    if (dense_begin(c, 0, 1.0, &clk) || dense_copy_host(c, x, 4096)) return 1;
+    return dense_finish(c, clk);
 }
 
 // read_methylation_data (data.cpp:241-278): M*N doubles at byte `offset` (= S*N*8, :259), streamed through two bounded pinned
 // buffers as gv_upload_bed_file streams a .bed: reading chunk k + 1 overlaps the copy of chunk k, host memory stays O(chunk).
 // (shared with gv_upload_dosage_file: bits = 0 reads doubles, 8 / 16 reads codes of that width; `who` names the entry point)
-static int dense_upload_file(gv_ctx* c, const char* who, const char* path, int64_t offset, int bits) {
+static int dense_upload_file(gv_ctx* c, const char* who, const char* path, int64_t offset, int bits, double scale) {
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(c, "%s: could not open %s file: %s", who, bits ? "dosage" : "methylation", path);
-    const auto t0 = std::chrono::steady_clock::now();
-    int rc = dense_prepare(c, bits);
-    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    DenseClock clk;
+    int rc = dense_begin(c, bits, scale, &clk);
     const size_t esz = bits ? (size_t)bits / 8 : sizeof(double);
-    const size_t rowb = esz * (size_t)c->N, pitchb = esz * (size_t)c->dpitch;
-    char* const dst = bits ? (char*)c->dcodes : (char*)c->dense;
+    const size_t rowb = esz * (size_t)c->N, pitchb = esz * (size_t)c->dense.pitch;
+    char* const dst = (char*)c->dense.rows;
     int64_t CH = (int64_t)(((size_t)64 << 20) / rowb);
     if (CH < 1) CH = 1;
     if (CH > c->M) CH = c->M > 0 ? c->M : 1;
@@ -460,23 +438,22 @@ static int dense_upload_file(gv_ctx* c, const char* who, const char* path, int64
     }
     close(fd);
     if (rc) return rc;
-    return meth_done(c, ta, t0);
+    return dense_finish(c, clk);
 }
 
 int gv_upload_meth_file(gv_ctx* c, const char* path, int64_t offset) {
     NEED(c, c->N > 0, "gv_upload_meth_file: gv_set_dims must be called first");
     NEED(c, offset >= 0, "gv_upload_meth_file: negative offset");
-    return dense_upload_file(c, "gv_upload_meth_file", path, offset, 0);
+    return dense_upload_file(c, "gv_upload_meth_file", path, offset, 0, 1.0);
 }
 
 int gv_synth_meth(gv_ctx* c, uint64_t seed) {
     NEED(c, c->N > 0, "gv_synth_meth: gv_set_dims must be called first");
-    const auto t0 = std::chrono::steady_clock::now();
-    if (meth_prepare(c)) return 1;
-    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    gvd::synth(c->stream, c->dense, c->M, c->S, c->N, c->dpitch, seed);
+    DenseClock clk;
+    if (dense_begin(c, 0, 1.0, &clk)) return 1;
+    gvd::synth(c->stream, dense_view(c), c->S, seed);
     KCHK(c);
-    return meth_done(c, ta, t0);
+    return dense_finish(c, clk);
 }
 
 // ---- compact dense data: X = scale * B, B unsigned codes of 8 or 16 bits (gv_dense.hip: k_dosage_*) ------------------------------
@@ -490,40 +467,28 @@ static int dosage_args(gv_ctx* c, const char* who, int bits, double scale) {
 int gv_upload_dosage(gv_ctx* c, const void* codes, size_t n, int bits, double scale) {
     if (dosage_args(c, "gv_upload_dosage", bits, scale)) return 1;
     NEED(c, n == (size_t)c->M * (size_t)c->N, "gv_upload_dosage: n != M * N");
-    const auto t0 = std::chrono::steady_clock::now();
-    if (dense_prepare(c, bits)) return 1;
-    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    const size_t esz = (size_t)bits / 8, rowb = esz * (size_t)c->N, pitchb = esz * (size_t)c->dpitch;
-    const int64_t rows = c->M < 16384 ? c->M : 16384;      // rows per copy: a caller-owned pageable buffer, nothing to overlap
-    for (int64_t m0 = 0; m0 < c->M; m0 += rows) {
-        const int64_t mc = c->M - m0 < rows ? c->M - m0 : rows;
-        HIPCHK(c, hipMemcpy2DAsync((char*)c->dcodes + (size_t)m0 * pitchb, pitchb, (const char*)codes + (size_t)m0 * rowb, rowb, rowb, mc,
-                                   hipMemcpyHostToDevice, c->stream));
-        count_reserved(c, m0, mc);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    DenseClock clk;
+    if (dense_begin(c, bits, scale, &clk) || dense_copy_host(c, codes, 16384)) return 1;
     KCHK(c);
-    c->dense_scale = scale;
-    return meth_done(c, ta, t0);
+    return dense_finish(c, clk);
 }
 
 // M*N codes at byte `offset` (= S*N*bits/8), streamed through the two bounded pinned buffers of gv_upload_meth_file
 int gv_upload_dosage_file(gv_ctx* c, const char* path, int64_t offset, int bits, double scale) {
     if (dosage_args(c, "gv_upload_dosage_file", bits, scale)) return 1;
     NEED(c, offset >= 0, "gv_upload_dosage_file: negative offset");
-    c->dense_scale = scale;
-    return dense_upload_file(c, "gv_upload_dosage_file", path, offset, bits);
+    return dense_upload_file(c, "gv_upload_dosage_file", path, offset, bits, scale);
 }
 
 static int synth_dosage(gv_ctx* c, uint64_t seed, int bits, bool na, uint64_t miss_thr) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (dense_prepare(c, bits)) return 1;
-    const double ta = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    gvd::dosage_synth(c->stream, c->dcodes, bits, c->M, c->S, c->N, c->dpitch, seed, na, miss_thr);
+    DenseClock clk;
+    if (dense_begin(c, bits, bits == 8 ? 1.0 / 127.0 : 1.0 / 16384.0, &clk)) return 1;
+    gvd::View v = dense_view(c);
+    v.na = na;      // (of the generator: nothing is resident yet)
+    gvd::synth(c->stream, v, c->S, seed, miss_thr);
     count_reserved(c, 0, c->M);
     KCHK(c);
-    c->dense_scale = bits == 8 ? 1.0 / 127.0 : 1.0 / 16384.0;
-    return meth_done(c, ta, t0);
+    return dense_finish(c, clk);
 }
 
 int gv_synth_dosage(gv_ctx* c, uint64_t seed, int bits) {
@@ -540,20 +505,21 @@ int gv_synth_dosage_na(gv_ctx* c, uint64_t seed, int bits, uint32_t miss_ppm) {
 
 int gv_set_dosage_missing(gv_ctx* c, int on) {
     const bool want = on != 0;
-    if (c->have_dense && c->dense_bits && want != c->dense_na)
+    if (c->dense.resident && c->dense.bits && want != c->dense.na)
         return fail(c, "gv_set_dosage_missing: %d-bit codes are resident and were uploaded with the option %s; their statistics would be "
-                       "stale -- set it before the upload", c->dense_bits, c->dense_na ? "on" : "off");
+                       "stale -- set it before the upload", c->dense.bits, c->dense.na ? "on" : "off");
     c->dosage_missing = want;
     return 0;
 }
 
 int gv_dosage_info(gv_ctx* c, gv_dosage_stats* out) {
     NEED(c, out != nullptr, "gv_dosage_info: out is NULL");
-    const bool res = c->have_dense && c->dense_bits;
-    out->bits = res ? c->dense_bits : 0;
-    out->scale = res ? c->dense_scale : 0.0;
-    out->missing = (res ? c->dense_na : c->dosage_missing) ? 1 : 0;
-    out->reserved = res ? (uint64_t)c->dense_reserved : 0;
+    const DenseData& d = c->dense;
+    const bool res = d.resident && d.bits;
+    out->bits = res ? d.bits : 0;
+    out->scale = res ? d.scale : 0.0;
+    out->missing = (res ? d.na : c->dosage_missing) ? 1 : 0;
+    out->reserved = res ? (uint64_t)d.reserved : 0;
     out->na_kernels = res && dosage_na_kernels(c) ? 1 : 0;
     out->pad_ = 0;
     return 0;
@@ -561,7 +527,7 @@ int gv_dosage_info(gv_ctx* c, gv_dosage_stats* out) {
 
 int gv_download_bed(gv_ctx* c, uint8_t* bed, size_t nbytes) {
     REFUSE_DOSAGE(c, "gv_download_bed", "the resident dataset is a matrix of dosage codes, not PLINK rows");
-    NEED(c, !c->have_dense, "gv_download_bed: the resident dataset is methylation data (a dense fp64 matrix), not PLINK rows");
+    NEED(c, !c->dense.resident, "gv_download_bed: the resident dataset is methylation data (a dense fp64 matrix), not PLINK rows");
     NEED(c, c->have_raw, "gv_download_bed: the raw row layout is not resident (not the default: call gv_set_layout(ctx, 1, stripes) before the ingest)");
     NEED(c, nbytes == (size_t)c->M * (size_t)c->mbytes, "gv_download_bed: nbytes != M * ceil(N/4)");
     if (c->M > 0)

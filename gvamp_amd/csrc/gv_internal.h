@@ -21,6 +21,29 @@ struct gv_vec {
     bool owns = true;   // false: d points into another vector's allocation (w_n2 behind w_n)
 };
 
+// The resident dense matrix of the dense kinds (gv_dense.hip): fp64 values of methylation data (gv_upload_meth / gv_upload_meth_file /
+// gv_synth_meth; bits == 0) or unsigned 8- / 16-bit codes of compact dense data, X = scale * B (gv_upload_dosage /
+// gv_upload_dosage_file / gv_synth_dosage).  One owner of the rows whatever the width; freed and reset by gvi::dense_release alone.
+struct DenseData {
+    void* rows = nullptr;           // M * pitch elements, marker-major, zeros in the padding
+    int bits = 0;                   // 0 = doubles, 8 / 16 = codes of that width
+    int64_t pitch = 0;              // elements per row: N rounded up to a multiple of 64
+    bool resident = false;
+    double scale = 1.0;             // codes only: the factor between codes and values
+    double* mu = nullptr;           // codes only: M mean codes mu' (mave = scale * mu'): the products work in code units
+    double* cnt = nullptr;          // codes only: M per-marker counts sum b na of the last gv_marker_stats (missing-aware kernels only)
+    // missing entries: na = the codes were uploaded with gv_set_dosage_missing on; reserved = the reserved codes counted at that ingest
+    // (device word rcount, block partials rpart)
+    bool na = false;
+    unsigned long long reserved = 0;
+    unsigned long long *rcount = nullptr, *rpart = nullptr;
+    double* part = nullptr;         // Ax partial vectors: 2 * segs * npad doubles
+    size_t part_cap = 0;
+    int cus = 0;                    // CU count of the device (the Ax decomposition's only input beyond N and M)
+    size_t elem_bytes() const { return bits ? (size_t)bits / 8 : sizeof(double); }
+    size_t bytes(int64_t M) const { return elem_bytes() * (size_t)M * (size_t)pitch; }
+};
+
 struct gv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -60,28 +83,14 @@ struct gv_ctx {
     double ingest_overlap_s = 0.0;  // ... of which the allocation ran beside the preparation of the source (helper thread)
     size_t ingest_bytes = 0;        // bytes of genotype layouts resident after the last ingest
     int64_t expected_passes = 0;    // gv_set_expected_passes: 0 = unknown
-    // dense fp64 design matrix of methylation data (gv_upload_meth / gv_upload_meth_file / gv_synth_meth; gv_dense.hip).  When it is
-    // resident no genotype layout is, and every product dispatches on it ahead of the kernel mode and the layout.
-    double* dense = nullptr;        // M * dpitch doubles, marker-major rows, zeros in the padding
-    int64_t dpitch = 0;             // doubles per row: N rounded up to a multiple of 64
-    bool have_dense = false;
-    double* dense_part = nullptr;   // Ax partial vectors: 2 * segs * npad doubles
-    size_t dense_part_cap = 0;
-    int dense_cus = 0;              // CU count of the device (the decomposition's only input beyond N and M)
-    // compact dense data (gv_upload_dosage / gv_upload_dosage_file / gv_synth_dosage): X = dense_scale * B, B unsigned codes of
-    // dense_bits (8 or 16) bits.  have_dense is set and `dense` is NULL; dense_bits == 0 means the fp64 matrix above.
-    void* dcodes = nullptr;         // M * dpitch codes, marker-major rows, zeros in the padding
-    int dense_bits = 0;
-    double dense_scale = 1.0;
-    double* dense_mu = nullptr;     // M mean codes mu' (mave = dense_scale * mu'): the products work in code units
-    // missing entries (gv_set_dosage_missing): the all-ones code is a missing entry.  dosage_missing is the setting, read by the next
-    // upload; dense_na what the resident codes were uploaded with; dense_reserved the reserved codes counted at that ingest (device
-    // word dense_rcount, block partials dense_rpart); the missing-aware kernels run when dosage_na_kernels(c) says so.
-    bool dosage_missing = false, dense_na = false;
+    // the resident dense matrix (DenseData above).  While it is resident no genotype layout is, and every product dispatches on it
+    // ahead of the kernel mode and the layout.
+    DenseData dense;
+    // missing entries of compact dense data (gv_set_dosage_missing): the all-ones code is a missing entry.  dosage_missing is the
+    // setting, read by the next upload of codes; it outlives the dataset.  What the resident codes were uploaded with is dense.na;
+    // the missing-aware kernels run when dosage_na_kernels(c) says so.
+    bool dosage_missing = false;
     bool force_na_kernels = false;  // GV_DOSAGE_NA_KERNELS=1 (development, read by gv_create per context)
-    unsigned long long dense_reserved = 0;
-    unsigned long long *dense_rcount = nullptr, *dense_rpart = nullptr;
-    double* dense_cnt = nullptr;    // M per-marker counts sum b na of the last gv_marker_stats (missing-aware kernels only)
     double tune_seconds = 0.0;      // wall time the pick cost (0 when it came from the cache)
     int tune_source = 0;            // 0 model's first candidate, 1 measured, 2 cache, 3 fixed by an override / nothing to tune
 
@@ -272,56 +281,52 @@ void copy_bw(hipStream_t s, const double* src, double* dst, int64_t n);
 void read_bw(hipStream_t s, const void* src, int64_t blocks_per_wave, int64_t nwaves, unsigned int* sink, int perm = 0);
 }  // namespace gvk
 
-// ---- dense fp64 design matrix (gv_dense.hip) ----------------------------------------------------------------------------------
+// ---- the dense kinds: fp64 design matrix and 8- / 16-bit codes (gv_dense.hip) ----------------------------------------------------
 namespace gvd {
-int64_t row_pitch(int64_t N);       // doubles per resident row: N rounded up to 64
+int64_t row_pitch(int64_t N);       // elements per resident row: N rounded up to 64
 struct AxShape {
-    int64_t col_tiles = 1;          // workgroups across the individuals (512 each)
+    int64_t col_tiles = 1;          // workgroups across the individuals
     int64_t seg_len = 1;            // markers per segment
     int segs = 1;                   // marker segments = partial vectors
 };
 constexpr int AX_COLS_F64 = 512;
 int ax_cols(int bits);              // individuals per Ax workgroup: 512 (fp64, bits == 0), 4096 (8-bit codes), 2048 (16-bit codes)
 AxShape ax_shape(int64_t N, int64_t M, int cus, int cols = AX_COLS_F64);
-void synth(hipStream_t s, double* A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed);
-void stats(hipStream_t s, const double* A, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2, double nonas,
-           double alpha_scale, double* mave, double* msig);
+// What every kernel call on the resident matrix repeats (gvi::dense_view builds it from the context).  bits selects the kernels: 0 the
+// fp64 kernels, 8 / 16 the kernels of that code type, na their missing-aware instantiation (gv_set_dosage_missing: the all-ones code
+// is a missing entry).
+struct View {
+    void* rows;                     // M * pitch doubles or codes
+    int bits;
+    bool na;
+    int64_t M, N, pitch;
+    double* centre;                 // what a kernel subtracts per row: mave (fp64), the mean codes mu' (codes)
+    double* msig;
+    double wscale;                  // the factor between codes and values; 1 for fp64
+    double* cnt;                    // codes: M per-marker counts sum b na, written by stats and read by assoc when na is set
+};
+// the device-generated matrix of the rows [S, S + M); miss_thr: codes with na set only (gv_synth_dosage_na)
+void synth(hipStream_t s, const View& v, int64_t S, uint64_t seed, uint64_t miss_thr = 0);
+// marker statistics: mave, v.msig (codes: v.centre and, with na, v.cnt beside them; fp64: mave is v.centre)
+void stats(hipStream_t s, const View& v, const uint32_t* mask2, double nonas, double alpha_scale, double* mave);
 // out[m] = msig[m] sum_j (x[m][j] - mave[m]) p[j] * scale, then tau * out + gam2 * addx when addx != NULL (nv = 1 or 2 vectors)
-void atx(hipStream_t s, int nv, const double* A, int64_t M, int64_t N, int64_t pitch, const double* pa, const double* pb,
-         const double* mave, const double* msig, double scale, double* outa, double* outb, const double* addxa,
-         const double* addxb, double tau, double gam2);
+void atx(hipStream_t s, int nv, const View& v, const double* pa, const double* pb, double scale, double* outa, double* outb,
+         const double* addxa, const double* addxb, double tau, double gam2);
 // partial[v][seg][j] over the segments of sh, then out[j] = scale * sum_seg partial (j < N), 0 at j >= N
-void ax_partial(hipStream_t s, int nv, const AxShape& sh, const double* A, int64_t M, int64_t pitch, const double* va,
-                const double* vb, const double* mave, const double* msig, double* part, int64_t npad);
+void ax_partial(hipStream_t s, int nv, const AxShape& sh, const View& v, const double* va, const double* vb, double* part, int64_t npad);
 void ax_reduce(hipStream_t s, int nv, const AxShape& sh, const double* part, int64_t N, int64_t npad, double scale, double* outa,
                double* outb);
-// compact dense data: A holds M * pitch unsigned codes of `bits` (8 or 16) bits, pitch in codes; dmu the mean codes; wscale the
-// factor between codes and values.  Same contracts as the fp64 forms above; the second Ax stage is ax_reduce.  na: the missing-aware
-// instantiation (gv_set_dosage_missing: the all-ones code is a missing entry); dcnt: M per-marker counts sum b na, written by
-// dosage_stats and read by dosage_assoc when na is set, untouched otherwise (may be NULL then).
-void dosage_synth(hipStream_t s, void* A, int bits, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed, bool na,
-                  uint64_t miss_thr);
-void dosage_stats(hipStream_t s, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const uint32_t* mask2,
-                  double nonas, double alpha_scale, double wscale, double* dmu, double* mave, double* msig, double* dcnt);
-void dosage_atx(hipStream_t s, int nv, const void* A, int bits, bool na, int64_t M, int64_t N, int64_t pitch, const double* pa,
-                const double* pb, const double* dmu, const double* msig, double wscale, double scale, double* outa, double* outb,
-                const double* addxa, const double* addxb, double tau, double gam2);
-void dosage_ax_partial(hipStream_t s, int nv, const AxShape& sh, const void* A, int bits, bool na, int64_t M, int64_t pitch,
-                       const double* va, const double* vb, const double* dmu, const double* msig, double wscale, double* part,
-                       int64_t npad);
-// *total += the reserved codes among the n codes at A (whole pitched rows); partial: COUNT_BLOCKS device words of scratch
+// *total += the reserved codes among the pitched rows [m0, m0 + mc) of codes; partial: COUNT_BLOCKS device words of scratch
 constexpr int COUNT_BLOCKS = 1024;
-void dosage_count_reserved(hipStream_t s, const void* A, int bits, int64_t n, unsigned long long* partial, unsigned long long* total);
+void count_reserved(hipStream_t s, const View& v, int64_t m0, int64_t mc, unsigned long long* partial, unsigned long long* total);
 // gv_assoc_* on compact dense data.  assoc_prep: p[npad] = y - z1 (+ add when not NULL) at the individuals with a phenotype, 0 at NA and
-// pad slots; sums[0..2) = {sum p, sum p^2} through the block partials (>= 2 * RED_BLOCKS doubles) in a fixed order.  dosage_assoc: the
-// test of the rows rows[0..nrows) (NULL: rows 0..nrows) against p; beta / se / tstat / pval are M-space device vectors written at the
-// tested rows only.  xself != NULL (leave-one-out): the row's own effect xself[m] * self_scale is added back analytically.
+// pad slots; sums[0..2) = {sum p, sum p^2} through the block partials (>= 2 * RED_BLOCKS doubles) in a fixed order.  assoc: the test of
+// the rows rows[0..nrows) (NULL: rows 0..nrows) against p; beta / se / tstat / pval are M-space device vectors written at the tested
+// rows only.  xself != NULL (leave-one-out): the row's own effect xself[m] * self_scale is added back analytically.
 void assoc_prep(hipStream_t s, const double* y, const double* z1, const double* add, const uint32_t* mask2, int64_t npad, double* p,
                 double* partial, double* sums);
-void dosage_assoc(hipStream_t s, const void* A, int bits, bool na, int64_t N, int64_t pitch, const int64_t* rows, int64_t nrows,
-                  const double* p, const uint32_t* mask2, const double* dmu, const double* msig, double wscale, const double* psums,
-                  double nonas, const double* dcnt, const double* xself, double self_scale, double* beta, double* se, double* tstat,
-                  double* pval);
+void assoc(hipStream_t s, const View& v, const int64_t* rows, int64_t nrows, const double* p, const uint32_t* mask2, const double* psums,
+           double nonas, const double* xself, double self_scale, double* beta, double* se, double* tstat, double* pval);
 }  // namespace gvd
 
 // ---- LD-block preconditioner (gv_precond.hip) --------------------------------------------------------------------------------
@@ -384,7 +389,17 @@ void pc_apply(gv_ctx* c, const double* r, double* z);
 void pc_invalidate(gv_ctx* c, bool free_mem);
 // compact dense data: the missing-aware kernels run when the codes were uploaded with gv_set_dosage_missing on AND the ingest counted a
 // reserved code in this shard (a shard without one gets the same bits from the plain kernels) or GV_DOSAGE_NA_KERNELS=1 forces them
-inline bool dosage_na_kernels(const gv_ctx* c) { return c->dense_na && (c->dense_reserved != 0 || c->force_na_kernels); }
+inline bool dosage_na_kernels(const gv_ctx* c) { return c->dense.na && (c->dense.reserved != 0 || c->force_na_kernels); }
+// the resident dense matrix as the gvd:: launchers take it
+inline gvd::View dense_view(const gv_ctx* c) {
+    const DenseData& d = c->dense;
+    return {d.rows, d.bits, dosage_na_kernels(c), c->M, c->N, d.pitch, d.bits ? d.mu : c->mave, c->msig, d.bits ? d.scale : 1.0, d.cnt};
+}
+// Frees the dense matrix with everything that belongs to it and resets its state: whatever kind comes next starts without a missing
+// code and with no reserved code counted.  keep_alloc: the allocations stay for an upload of the same width (shape is the context's).
+void dense_release(gv_ctx* c, bool keep_alloc = false);
+// frees the genotype layouts of the MFMA family: the stripe slab, the two stripe sets, the tiles and the plan's digit / weight / sum buffers
+void free_layouts(gv_ctx* c);
 
 struct Timer {
     gv_ctx* c;
@@ -423,7 +438,7 @@ struct Timer {
 // an entry point the dense kinds refuse, when the resident dataset is compact dense data (the fp64 kind keeps its own message)
 #define REFUSE_DOSAGE(c, who, why)                                                                                      \
     do {                                                                                                                \
-        if ((c)->have_dense && (c)->dense_bits)                                                                         \
-            return fail(c, "%s: not available for compact dosage data (%d-bit codes): %s", who, (c)->dense_bits, why); \
+        if ((c)->dense.resident && (c)->dense.bits)                                                                     \
+            return fail(c, "%s: not available for compact dosage data (%d-bit codes): %s", who, (c)->dense.bits, why); \
     } while (0)
 

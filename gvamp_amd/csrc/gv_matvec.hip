@@ -1,6 +1,7 @@
-// gv_matvec.hip -- data::Ax / data::ATx of the C ABI: one dispatcher per product direction (ax_pass / atx_pass) over the dense
-// kernels of the dense kinds (fp64 methylation data, 8- / 16-bit dosage codes) and the three genotype kernel families, the N-space exchange of a sharded job (in one
-// piece, or overlapped with the decode), and the event pairs of set_timing 2.
+// gv_matvec.hip -- data::Ax / data::ATx of the C ABI: one dispatcher per product direction (ax_pass / atx_pass) over the launchers
+// of the dense kinds (gvd::ax_partial / ax_reduce / atx on the context's DenseData, whatever its width: fp64 methylation data, 8- /
+// 16-bit dosage codes) and the three genotype kernel families, the N-space exchange of a sharded job (in one piece, or overlapped
+// with the decode), and the event pairs of set_timing 2.
 #include <cmath>
 
 #include "gv_internal.h"
@@ -121,7 +122,7 @@ static int exchange_n(gv_ctx* c, int nv, double* outa, double* outb) {
 // The collective sequence must not depend on rank-local state (an empty shard, M == 0, enters the same calls with zeros): it
 // is chosen by the kind of data, the kernel mode, use_overlap -- the same on every rank of a job -- and the output pointers only.
 int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa, double* outb, const gvm::CgHook* cg) {
-    const bool dense = c->have_dense;
+    const bool dense = c->dense.resident;
     // (the hooks of the device-resident loops exist in gvm::ax / ax2 / ax_rows only: cgx_usable keeps every caller to kernel mode 1)
     NEED(c, !cg || (!dense && c->kernel_mode == 1), dense ? "Ax: the device-resident CG does not run on methylation data"
                                                           : "Ax: the device-resident CG runs in kernel mode 1 only");
@@ -146,14 +147,15 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
         const bool mfma = !dense && c->kernel_mode != 0;
         gvd::AxShape sh;
         if (dense) {
-            sh = gvd::ax_shape(c->N, c->M, c->dense_cus, gvd::ax_cols(c->dense_bits));
+            DenseData& d = c->dense;
+            sh = gvd::ax_shape(c->N, c->M, d.cus, gvd::ax_cols(d.bits));
             const size_t need = (size_t)2 * sh.segs * c->npad;
-            if (need > c->dense_part_cap) {
-                if (c->dense_part) (void)hipFree(c->dense_part);
-                c->dense_part = nullptr;
-                c->dense_part_cap = 0;
-                HIPCHK(c, hipMalloc(&c->dense_part, sizeof(double) * need));
-                c->dense_part_cap = need;
+            if (need > d.part_cap) {
+                if (d.part) (void)hipFree(d.part);
+                d.part = nullptr;
+                d.part_cap = 0;
+                HIPCHK(c, hipMalloc(&d.part, sizeof(double) * need));
+                d.part_cap = need;
             }
         } else if (mfma) {
             NEED(c, c->have_stripes, nv == 2 ? "Ax: kernel mode 1 needs the stripe layouts (gv_set_layout before ingest)"
@@ -165,13 +167,9 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
         gv_ctx::EvRec* er = ev_next(c, 0);     // timing == 2: around the streaming kernel (the MFMA family records the pair itself)
         if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
-            if (c->dense_bits)
-                gvd::dosage_ax_partial(c->stream, nv, sh, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->dense_mu,
-                                       c->msig, c->dense_scale, c->dense_part, c->npad);
-            else
-                gvd::ax_partial(c->stream, nv, sh, c->dense, c->M, c->dpitch, xa, nv == 2 ? xb : xa, c->mave, c->msig, c->dense_part, c->npad);
+            gvd::ax_partial(c->stream, nv, sh, dense_view(c), xa, nv == 2 ? xb : xa, c->dense.part, c->npad);
             if (er) (void)hipEventRecord(er->b, c->stream);
-            gvd::ax_reduce(c->stream, nv, sh, c->dense_part, c->N, c->npad, multi ? 1.0 : scale, outa, nv == 2 ? outb : outa);
+            gvd::ax_reduce(c->stream, nv, sh, c->dense.part, c->N, c->npad, multi ? 1.0 : scale, outa, nv == 2 ? outb : outa);
         } else if (mfma) {
             c->plan.ev0 = er ? er->a : nullptr;
             c->plan.ev1 = er ? er->b : nullptr;
@@ -202,7 +200,7 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
 // complete single passes otherwise.  No collective in ATx.
 int atx_pass(gv_ctx* c, int nv, const double* pa, const double* pb, double* outa, double* outb, const double* addxa,
              const double* addxb, double tau, double gam2, const gvm::CgHook* cg) {
-    const bool dense = c->have_dense;
+    const bool dense = c->dense.resident;
     NEED(c, !cg || (!dense && c->kernel_mode == 1), dense ? "ATx: the device-resident CG does not run on methylation data"
                                                           : "ATx: the device-resident CG runs in kernel mode 1 only");
     // (the two-vector form of an empty genotype shard has never asked for the statistics it does not read)
@@ -230,12 +228,8 @@ int atx_pass(gv_ctx* c, int nv, const double* pa, const double* pb, double* outa
         gv_ctx::EvRec* er = ev_next(c, 1);
         if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
-            if (c->dense_bits)
-                gvd::dosage_atx(c->stream, nv, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->dense_mu, c->msig,
-                                c->dense_scale, scale, outa, nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2);
-            else
-                gvd::atx(c->stream, nv, c->dense, c->M, c->N, c->dpitch, pa, nv == 2 ? pb : pa, c->mave, c->msig, scale, outa,
-                         nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2);
+            gvd::atx(c->stream, nv, dense_view(c), pa, nv == 2 ? pb : pa, scale, outa, nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa,
+                     tau, gam2);
             if (er) (void)hipEventRecord(er->b, c->stream);
         } else if (mfma) {
             c->plan.ev0 = er ? er->a : nullptr;
@@ -310,7 +304,7 @@ int gv_atx(gv_ctx* c, const double* p, double* out) {
     // a no-op for filtered input, a defined result (the NA individuals dropped) otherwise.  Methylation data: p is used as given at
     // every individual below N, as the reference's meth dot_product (data.cpp:783-797) uses it -- its Ax leaves NA individuals
     // unmasked too, and its ATx must see them.
-    if (!c->have_dense) gvk::mask_copy(c->stream, c->w_n->d, c->w_n->d, c->mask2, c->npad);
+    if (!c->dense.resident) gvk::mask_copy(c->stream, c->w_n->d, c->w_n->d, c->mask2, c->npad);
     KCHK(c);
     if (atx_device(c, c->w_n->d, c->cg_d->d)) return 1;
     return to_host(c, out, c->cg_d->d, sizeof(double) * (c->M > 0 ? c->M : 0));

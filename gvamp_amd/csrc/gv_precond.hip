@@ -259,7 +259,7 @@ void pc_invalidate(gv_ctx* c, bool free_mem) {
 static int pc_build_gram(gv_ctx* c) {
     NEED(c, c->pc_kind == 1, "LD preconditioner: not enabled (gv_set_cg_precond(ctx, 1, window))");
     REFUSE_DOSAGE(c, "LD preconditioner", "genotype windows only");
-    NEED(c, !c->have_dense, "LD preconditioner: refused for dense (meth) data -- genotype windows only");
+    NEED(c, !c->dense.resident, "LD preconditioner: refused for dense (meth) data -- genotype windows only");
     NEED(c, c->have_stripes, "LD preconditioner: needs a re-encoded genotype layout resident (tile layout or two stripe sets); "
                              "raw rows alone are not supported");
     NEED(c, c->have_stats && c->mask2, "LD preconditioner: marker statistics must be computed first");
@@ -319,7 +319,7 @@ int gv_set_cg_precond(gv_ctx* c, int kind, int window) {
     NEED(c, kind == 0 || kind == 1, "gv_set_cg_precond: kind must be 0 (scalar, the default) or 1 (ld)");
     NEED(c, kind == 0 || window == 32 || window == 64 || window == 128, "gv_set_cg_precond: window must be 32, 64 or 128");
     if (kind != 0) REFUSE_DOSAGE(c, "gv_set_cg_precond", "the LD preconditioner works on genotype windows only");
-    NEED(c, kind == 0 || !c->have_dense, "gv_set_cg_precond: the LD preconditioner is refused for dense (meth) data");
+    NEED(c, kind == 0 || !c->dense.resident, "gv_set_cg_precond: the LD preconditioner is refused for dense (meth) data");
     if (kind == 0 || window != c->pc_W) pc_invalidate(c, true);     // (kind 0 releases the Grams and inverses)
     c->pc_kind = kind;
     if (kind == 1) c->pc_W = window;

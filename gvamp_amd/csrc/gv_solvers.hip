@@ -476,7 +476,7 @@ static int cg_run_device(gv_ctx* c, CgSys* sys, int nsys, double tau, double gam
 static bool cgx_usable(const gv_ctx* c) {
     const char* cgdev = getenv("GV_CG_DEVICE");
     // (nothing rank-local in here: an empty shard, M == 0, must take the same sequence of collectives as its peers)
-    return c->kernel_mode == 1 && c->have_stripes && !c->have_dense && c->use_mbox && !(cgdev && atoi(cgdev) == 0);
+    return c->kernel_mode == 1 && c->have_stripes && !c->dense.resident && c->use_mbox && !(cgdev && atoi(cgdev) == 0);
 }
 // initial state of one system -> device block blk (0 / 1); normv: ||v|| (M-space systems) or ||v||^2 (CG_solverAAT)
 static int cgx_upload_state(gv_ctx* c, int blk, double rz, double normv, int denoiser, bool active) {
@@ -876,7 +876,7 @@ int gv_cg_solve_aat(gv_ctx* c, const gv_vec* v, const gv_vec* mu_start, double t
     NEED(c, v->space == GV_SPACE_N && mu_out->space == GV_SPACE_N, "gv_cg_solve_aat: N-space vectors required");
     NEED(c, mu_out != v && mu_out != mu_start, "gv_cg_solve_aat: mu_out must not alias v or mu_start");
     REFUSE_DOSAGE(c, "gv_cg_solve_aat", "the N-space solver needs people statistics");
-    NEED(c, !c->have_dense, "gv_cg_solve_aat: the N-space solver needs people statistics, not available for methylation data");
+    NEED(c, !c->dense.resident, "gv_cg_solve_aat: the N-space solver needs people statistics, not available for methylation data");
     NEED(c, c->pc_kind == 0, "gv_cg_solve_aat: the N-space solver is refused while the LD preconditioner is set (gv_set_cg_precond kind 1)");
     NEED(c, c->mave_p, "gv_cg_solve_aat: gv_people_stats must run first");
     if (ensure_work(c)) return 1;
@@ -1004,7 +1004,7 @@ int gv_cg_solve_aat2w(gv_ctx* c, gv_vec* v_a, const gv_vec* mu_start_a, const gv
                       int max_iter, gv_vec* mu_a, gv_vec* at_mu_a, gv_vec* mu_b, gv_cg_stats* st_a, gv_cg_stats* st_b,
                       double* relres_a, double* relres_b, gv_vec* aat_mu_a, gv_vec* ata_mu_b, const gv_aat_warm* wm) {
     REFUSE_DOSAGE(c, "gv_cg_solve_aat2w", "the N-space solver needs people statistics");
-    NEED(c, !c->have_dense, "gv_cg_solve_aat2w: the N-space solver needs people statistics, not available for methylation data");
+    NEED(c, !c->dense.resident, "gv_cg_solve_aat2w: the N-space solver needs people statistics, not available for methylation data");
     NEED(c, c->pc_kind == 0, "gv_cg_solve_aat2w: the N-space solver is refused while the LD preconditioner is set (gv_set_cg_precond kind 1)");
     gv_aat_warm nowarm{};
     if (!wm) wm = &nowarm;

@@ -28,13 +28,9 @@ int gv_set_mask(gv_ctx* c, const uint8_t* mask4, int64_t nonas) {
 
 int gv_marker_stats(gv_ctx* c, double alpha_scale) {
     pc_invalidate(c, false);
-    if (c->have_dense) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
+    if (c->dense.resident) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
         NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
-        if (c->dense_bits)      // compact dense data: the same statistics in code units
-            gvd::dosage_stats(c->stream, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->M, c->N, c->dpitch, c->mask2, (double)c->nonas,
-                              alpha_scale, c->dense_scale, c->dense_mu, c->mave, c->msig, c->dense_cnt);
-        else
-            gvd::stats(c->stream, c->dense, c->M, c->N, c->dpitch, c->mask2, (double)c->nonas, alpha_scale, c->mave, c->msig);
+        gvd::stats(c->stream, dense_view(c), c->mask2, (double)c->nonas, alpha_scale, c->mave);      // (codes: the same, in code units)
         c->alpha_scale = alpha_scale;
         KCHK(c);
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -61,10 +57,10 @@ int gv_marker_stats(gv_ctx* c, double alpha_scale) {
 // the per-marker counts sum b na: what the missing-aware statistics left, nonas for every marker where no entry can be missing
 int gv_marker_counts(gv_ctx* c, double* cnt) {
     NEED(c, cnt != nullptr, "gv_marker_counts: cnt is NULL");
-    NEED(c, c->have_dense && c->dense_bits, "gv_marker_counts: the resident dataset is not compact dosage data");
+    NEED(c, c->dense.resident && c->dense.bits, "gv_marker_counts: the resident dataset is not compact dosage data");
     NEED(c, c->have_stats, "gv_marker_counts: gv_marker_stats has not run");
     if (dosage_na_kernels(c)) {
-        HIPCHK(c, hipMemcpyAsync(cnt, c->dense_cnt, sizeof(double) * c->M, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cnt, c->dense.cnt, sizeof(double) * c->M, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     } else
         for (int64_t m = 0; m < c->M; m++) cnt[m] = (double)c->nonas;
@@ -83,7 +79,7 @@ int gv_get_marker_stats(gv_ctx* c, double* mave, double* msig) {
 // data::compute_people_statistics (data.cpp:558-716): three table passes of the fp64 Ax kernel over the raw rows.
 int gv_people_stats(gv_ctx* c, double* mave_people, double* msig_people, double* numb_people) {
     REFUSE_DOSAGE(c, "gv_people_stats", "the dense kinds have no people statistics");
-    NEED(c, !c->have_dense, "gv_people_stats: not available for methylation data (the reference's meth branch of "
+    NEED(c, !c->dense.resident, "gv_people_stats: not available for methylation data (the reference's meth branch of "
                             "compute_people_statistics, data.cpp:633-672, never reduces or finalises its sums)");
     NEED(c, c->have_stats && c->mask2, "gv_people_stats: marker statistics must be computed first");
     const bool from_stripes = c->have_stripes && (c->kernel_mode != 0 || !c->have_raw);
@@ -145,17 +141,17 @@ static int marker_sums_p_p2_f64(gv_ctx* c, const double* p, double* p2_scratch, 
 
 // chrom == NULL: leave-one-out (the marker's own effect is added back analytically); else leave-one-chromosome-out.
 // One loop for both entry-point families.  out[0] = p-values; assoc (gv_assoc_*): out[1..3] = beta, se, t as well (host pointers, each
-// may be NULL), compact dense data take the marker pass of their own (gvd::dosage_assoc) and the bed families the passes of gv_pvals_*
+// may be NULL), compact dense data take the marker pass of their own (gvd::assoc) and the bed families the passes of gv_pvals_*
 // with the wide epilogue.  assoc == false is gv_pvals_* to the bit: the narrow epilogue kernels, the same launches in the same order.
 static int pvals_impl(gv_ctx* c, bool assoc, const gv_vec* z1, const gv_vec* y, const gv_vec* x1_hat, const int* chrom,
                       double* const (&out)[4], double* chrom_pred = nullptr) {
     const char* who = assoc ? "gv_assoc" : "gv_pvals";
     if (assoc)
-        NEED(c, !(c->have_dense && !c->dense_bits), "gv_assoc: not available for methylation data (dense fp64 matrix): the reference's "
+        NEED(c, !(c->dense.resident && !c->dense.bits), "gv_assoc: not available for methylation data (dense fp64 matrix): the reference's "
                                                     "meth branch of pvals_calc, data.cpp:1187-1223, defines no test and none is defined here");
     else {
         REFUSE_DOSAGE(c, "gv_pvals", "the dense kinds compute no p-values");
-        NEED(c, !c->have_dense, "gv_pvals: not available for methylation data (the reference's meth branch of pvals_calc, "
+        NEED(c, !c->dense.resident, "gv_pvals: not available for methylation data (the reference's meth branch of pvals_calc, "
                                 "data.cpp:1187-1223, computes and stores nothing)");
     }
     if (!(z1->space == GV_SPACE_N && y->space == GV_SPACE_N && x1_hat->space == GV_SPACE_M)) return fail(c, "%s: bad vector spaces", who);
@@ -163,7 +159,7 @@ static int pvals_impl(gv_ctx* c, bool assoc, const gv_vec* z1, const gv_vec* y, 
     if (ensure_work(c) || ensure_w2(c)) return 1;
     const int64_t M = c->M;
     const double sqrtN = sqrt((double)c->N);
-    const bool dosage = c->have_dense;            // (assoc only: gv_pvals_* has refused the dense kinds above)
+    const bool dosage = c->dense.resident;            // (assoc only: gv_pvals_* has refused the dense kinds above)
     const bool fused = !dosage && c->kernel_mode != 0;      // (kernel mode 2: the p-value pass is mode 1's -- its sums run over exact planes already)
     if (fused && M > 0) {
         NEED(c, c->have_stripes, "p-values: kernel modes 1 and 2 need a re-encoded layout");
@@ -209,9 +205,8 @@ static int pvals_impl(gv_ctx* c, bool assoc, const gv_vec* z1, const gv_vec* y, 
         const bool loo = add == nullptr;
         if (dosage) {
             gvd::assoc_prep(c->stream, y->d, z1->d, add, c->mask2, c->npad, pa, c->red_partial, c->red_out);
-            gvd::dosage_assoc(c->stream, c->dcodes, c->dense_bits, dosage_na_kernels(c), c->N, c->dpitch, loo ? nullptr : rows_dev + r0,
-                              loo ? M : nr, pa, c->mask2, c->dense_mu, c->msig, c->dense_scale, c->red_out, (double)c->nonas, c->dense_cnt,
-                              loo ? x1_hat->d : nullptr, 1.0 / sqrtN, pva.beta, pva.se, pva.t, pv_dev);
+            gvd::assoc(c->stream, dense_view(c), loo ? nullptr : rows_dev + r0, loo ? M : nr, pa, c->mask2, c->red_out, (double)c->nonas,
+                       loo ? x1_hat->d : nullptr, 1.0 / sqrtN, pva.beta, pva.se, pva.t, pv_dev);
         } else if (fused) {
             pva.xself = loo ? x1_hat->d : nullptr;      // y_mark = y_mod + gen_part * x1_hat[k] (data.cpp:1145-1148): c = x1_hat[k] / sqrt(N)
             pva.self_scale = loo ? 1.0 / sqrtN : 0.0;

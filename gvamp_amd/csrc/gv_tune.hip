@@ -586,7 +586,7 @@ int gv_get_decomp(gv_ctx* c, gv_decomp_info* out4) {
 }
 int gv_set_decomp(gv_ctx* c, int cls, const gv_decomp_info* in) {
     REFUSE_DOSAGE(c, "gv_set_decomp", "no tunable decomposition (derived from N, M and the CU count)");
-    NEED(c, !c->have_dense, "gv_set_decomp: methylation data has no tunable decomposition (derived from N, M and the CU count)");
+    NEED(c, !c->dense.resident, "gv_set_decomp: methylation data has no tunable decomposition (derived from N, M and the CU count)");
     NEED(c, cls >= 0 && cls <= 3 && in != nullptr, "gv_set_decomp: class 0..3 and a decomposition are required");
     NEED(c, c->have_stripes, "gv_set_decomp: no re-encoded layout resident yet (call it after the ingest)");
     gvm::Decomp d;

@@ -250,6 +250,74 @@ def test_option_off_reserved_codes_are_values_and_the_setting_is_pinned_while_co
         assert sh.dosage_info() == dict(bits=0, scale=0.0, missing=True, reserved=0, na_kernels=False)
 
 
+# ---- one context through every kind: the allocation an upload of the same width reuses, and the state it must not inherit -------------
+def test_one_context_through_a_sequence_of_uploads_equals_a_fresh_context_after_each(monkeypatch):
+    """Eight uploads into ONE context -- two of them (2 and 5) of the width already held, which keep the allocation -- and after each
+    one gv_dosage_info, gv_get_layout, the resident bytes of gv_ingest_info2, the marker statistics, the counts and both products
+    are those of a fresh context given that upload alone, bit for bit.  N = 1203: one whole 1024-column step and a partial one, N no
+    multiple of 4; M = 450: no multiple of the 32- or 16-row wave groups."""
+    monkeypatch.delenv(SWITCH, raising=False)
+    N, M = 1203, 450
+    pitch = (N + 63) // 64 * 64
+    s1, s2 = 1.0 / 127.0, 2.0 ** -6
+    m4, _na, nonas = na_mask(N, True)
+    rng = np.random.default_rng(N + M)
+    x = rng.standard_normal(M)
+    p = np.zeros(4 * ((N + 3) // 4))
+    p[:N] = rng.standard_normal(N)
+    b8a, b8b = synth.synth_dosage(N, M, 11, 8), synth.synth_dosage(N, M, 12, 8)
+    n8a, _rows = codes_with_missing(N, M, 8, 13)
+    n8b = synth.synth_dosage_na(N, M, 14, 8, 30000)
+    n16 = synth.synth_dosage_na(N, M, 15, 16, 0)
+    b16 = synth.synth_dosage(N, M, 16, 16)
+    b8a[0, 0], b16[0, 0] = 255, 65535                          # option off: the all-ones code is a value
+    assert not np.any(n16 == 65535) and np.any(n8a == 255) and np.any(n8b == 255) and not np.array_equal(n8a, n8b)
+    bed, meth = synth.synth_bed(N, M, seed=3, miss_ppm=5000), synth.synth_meth(N, M, 7)
+    none = dict(bits=0, scale=0.0, reserved=0, na_kernels=False)
+
+    def codes(B, scale, missing):
+        R = dr.reserved(8 * B.dtype.itemsize)
+        res = int((B == R).sum()) if missing else 0
+        info = dict(bits=8 * B.dtype.itemsize, scale=scale, missing=missing, reserved=res, na_kernels=res != 0)
+        return (lambda sh: sh.upload_dosage(B, scale, missing=missing)), info, 3 + B.dtype.itemsize, B.dtype.itemsize
+
+    steps = [codes(b8a, s1, False),
+             codes(b8b, s2, False),                              # the width held: the allocation is kept
+             ((lambda sh: sh.upload_bed(bed)), dict(none, missing=False), 2, None),
+             codes(n8a, s1, True),
+             codes(n8b, s2, True),                               # the width held, with the state of missing entries to reset
+             codes(n16, TEST_SCALE[16], True),                   # option on, no reserved code: the plain kernels
+             ((lambda sh: sh.upload_meth(meth)), dict(none, missing=True), 3, 8),
+             codes(b16, TEST_SCALE[16], False)]
+
+    def observe(sh, is_codes):
+        sh.compute_markers_statistics()
+        out = list(sh.marker_stats()) + [sh.Ax(x), sh.ATx(p)]
+        return out + ([sh.marker_counts()] if is_codes else [])
+
+    with capi.Shard(N, M) as one:
+        one.set_mask(m4, nonas)
+        for k, (upload, info, layout, esz) in enumerate(steps, 1):
+            upload(one)
+            with capi.Shard(N, M) as fresh:
+                fresh.set_mask(m4, nonas)
+                if info["missing"] and not info["bits"]:
+                    fresh.set_dosage_missing(True)               # (the setting outlives the dataset)
+                upload(fresh)
+                for sh in (one, fresh):
+                    assert sh.dosage_info() == info, (k, sh.dosage_info())
+                    assert sh.get_layout() == layout, (k, sh.get_layout())
+                    if esz:
+                        assert sh.ingest_stats()["resident_GB"] == esz * M * pitch / 1e9, (k, sh.ingest_stats())
+                assert one.ingest_stats()["resident_GB"] == fresh.ingest_stats()["resident_GB"], k
+                got, ref = observe(one, info["bits"] != 0), observe(fresh, info["bits"] != 0)
+            assert len(got) == len(ref) and all(np.all(np.isfinite(a)) for a in ref[2:]), k
+            for a, b in zip(got, ref):
+                assert np.array_equal(a, b), k
+            if info["bits"]:
+                assert np.any(got[-1] != nonas) == info["na_kernels"], k
+
+
 # ---- bed parity: a bed file with missing genotypes, written as codes with the reserved code --------------------------------------
 _VAMP_KW = dict(iterations=6, CG_max_iter=30, rho=0.5, seed=7, gam1=1e-8, gamw=2.0)
 
