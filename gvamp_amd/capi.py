@@ -29,6 +29,7 @@ EXPORTS = [
     "gv_set_cg_precond", "gv_precond_info", "gv_precond_window_gram", "gv_precond_apply",
     "gv_assoc_loo", "gv_assoc_loco",
     "gv_set_dosage_missing", "gv_synth_dosage_na", "gv_dosage_info", "gv_marker_counts",
+    "gv_set_dosage_route", "gv_get_dosage_route",
 ]
 
 
@@ -141,6 +142,8 @@ def load():
     L.gv_synth_dosage_na.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint32]
     L.gv_dosage_info.argtypes = [vp, C.POINTER(DosageStats)]
     L.gv_marker_counts.argtypes = [vp, dp]
+    L.gv_set_dosage_route.argtypes = [vp, C.c_int]
+    L.gv_get_dosage_route.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.gv_set_mask.argtypes = [vp, up, i64]
     L.gv_marker_stats.argtypes = [vp, C.c_double]
     L.gv_get_marker_stats.argtypes = [vp, dp, dp]
@@ -371,6 +374,17 @@ class Shard:
         st = DosageStats()
         self._ck(self.L.gv_dosage_info(self.h, C.byref(st)))
         return dict(bits=st.bits, scale=st.scale, missing=bool(st.missing), reserved=int(st.reserved), na_kernels=bool(st.na_kernels))
+
+    def set_dosage_route(self, route):
+        """gv_set_dosage_route: 0 = the VALU kernels of the dosage kind (default), 1 = fixed-point i8 MFMA (8-bit codes without missing
+        entries; a request, kept where it does not apply)"""
+        self._ck(self.L.gv_set_dosage_route(self.h, int(route)))
+
+    def dosage_route(self):
+        """gv_get_dosage_route: (requested, in_force)"""
+        req, inf = C.c_int(0), C.c_int(0)
+        self._ck(self.L.gv_get_dosage_route(self.h, C.byref(req), C.byref(inf)))
+        return req.value, inf.value
 
     def marker_counts(self):
         """gv_marker_counts: the M per-marker counts sum b na after compute_markers_statistics (dosage data)"""

@@ -157,6 +157,7 @@ void dense_release(gv_ctx* c, bool keep_alloc) {
     if (keep_alloc) return;
     for (void** q : {&d.rows, (void**)&d.mu, (void**)&d.cnt, (void**)&d.rcount, (void**)&d.rpart, (void**)&d.part})
         if (*q) { (void)hipFree(*q); *q = nullptr; }
+    gvdm::release(d.fx);
     d.bits = 0;
     d.part_cap = 0;
 }
@@ -277,6 +278,18 @@ int gv_create(int device, gv_ctx** out) {
     // GV_DOSAGE_NA_KERNELS=1 (development, read per context as GV_DEAL is): the missing-aware dosage kernels whenever gv_set_dosage_missing
     // is on, also for a shard without a reserved code
     if (const char* nk = getenv("GV_DOSAGE_NA_KERNELS")) c->force_na_kernels = atoi(nk) != 0;
+    // GV_DOSAGE_MFMA_SEG=<k> (development, read per context): most K-entries per int32 segment of the fixed-point dosage route, rounded
+    // down to the kernel's K-step (at least one step).  It changes no bit; a value beyond the int32 bound is refused.
+    if (const char* sg = getenv("GV_DOSAGE_MFMA_SEG")) {
+        const long long k = atoll(sg);
+        if (k < 1 || k > gvdm::SEG_MAX) {
+            g_create_err = "gv_create: GV_DOSAGE_MFMA_SEG=" + std::string(sg) + ": a segment of the fixed-point dosage route holds 1.." +
+                           std::to_string((long long)gvdm::SEG_MAX) + " K-entries (an int32 column sum gains up to 16384 per entry)";
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->dosage_seg = k;
+    }
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)

@@ -512,6 +512,18 @@ int gv_set_dosage_missing(gv_ctx* c, int on) {
     return 0;
 }
 
+int gv_set_dosage_route(gv_ctx* c, int route) {
+    NEED(c, route == 0 || route == 1, "gv_set_dosage_route: route must be 0 (VALU kernels) or 1 (fixed-point i8 MFMA)");
+    c->dosage_route = route;
+    return 0;
+}
+
+int gv_get_dosage_route(const gv_ctx* c, int* requested, int* in_force) {
+    if (requested) *requested = c->dosage_route;
+    if (in_force) *in_force = dosage_mfma_route(c) ? 1 : 0;
+    return 0;
+}
+
 int gv_dosage_info(gv_ctx* c, gv_dosage_stats* out) {
     NEED(c, out != nullptr, "gv_dosage_info: out is NULL");
     const DenseData& d = c->dense;

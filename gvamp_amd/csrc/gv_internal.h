@@ -21,6 +21,33 @@ struct gv_vec {
     bool owns = true;   // false: d points into another vector's allocation (w_n2 behind w_n)
 };
 
+// ---- fixed-point i8 MFMA route for 8-bit dosage codes (gv_dense_mfma.hip; gv_set_dosage_route) -----------------------------------
+namespace gvdm {
+// THE int32 invariant of the route: a K-entry adds at most 128 * 128 = 16 384 in magnitude to an int32 column sum of a streaming
+// kernel, so no int32 accumulation spans more than SEG_MAX = (2^31 - 1) / 16 384 K-entries -- over the individuals in ATx, over the
+// markers in Ax.  Longer sums are cut into segments whose int32 partials the epilogues add in int64 (cut() in gv_dense_mfma.hip).
+constexpr int64_t SEG_MAX = 131071;
+constexpr int ATX_KSTEP = 128, AX_KSTEP = 64;       // K-entries per step of the streaming kernels: a segment is a whole number of steps
+constexpr int64_t PITCH_MAX = (int64_t)1 << 26;     // the Ax kernel keeps a lane's offset within 64 rows in 32 bits
+constexpr int BLOCKS = 1024;                        // most blocks of a quantisation launch
+// per-pass scratch, owned by DenseData: digits (16 bytes per K-entry), int32 partials, block maxima | limb sums | scalars
+struct Scratch {
+    void* dig = nullptr;
+    size_t dig_cap = 0;
+    int32_t* part = nullptr;
+    size_t part_cap = 0;
+    double* pmax = nullptr;
+    long long* limb = nullptr;
+    double* scal = nullptr;
+};
+struct Shape {
+    int64_t blocks = 1;             // blocks of 128 rows (ATx: markers, Ax: individuals), one wave each
+    int64_t steps = 1;              // K-steps in all
+    int64_t seg_steps = 1;          // K-steps per segment
+    int segs = 1;
+};
+}  // namespace gvdm
+
 // The resident dense matrix of the dense kinds (gv_dense.hip): fp64 values of methylation data (gv_upload_meth / gv_upload_meth_file /
 // gv_synth_meth; bits == 0) or unsigned 8- / 16-bit codes of compact dense data, X = scale * B (gv_upload_dosage /
 // gv_upload_dosage_file / gv_synth_dosage).  One owner of the rows whatever the width; freed and reset by gvi::dense_release alone.
@@ -40,6 +67,7 @@ struct DenseData {
     double* part = nullptr;         // Ax partial vectors: 2 * segs * npad doubles
     size_t part_cap = 0;
     int cus = 0;                    // CU count of the device (the Ax decomposition's only input beyond N and M)
+    gvdm::Scratch fx;               // 8-bit codes on the fixed-point route: digits and integer partials of a pass
     size_t elem_bytes() const { return bits ? (size_t)bits / 8 : sizeof(double); }
     size_t bytes(int64_t M) const { return elem_bytes() * (size_t)M * (size_t)pitch; }
 };
@@ -91,6 +119,10 @@ struct gv_ctx {
     // the missing-aware kernels run when dosage_na_kernels(c) says so.
     bool dosage_missing = false;
     bool force_na_kernels = false;  // GV_DOSAGE_NA_KERNELS=1 (development, read by gv_create per context)
+    // gv_set_dosage_route: the request (0 = the k_dosage_* VALU kernels, 1 = fixed-point i8 MFMA); it outlives the dataset.  What runs:
+    // dosage_mfma_route(c).  dosage_seg: most K-entries per int32 segment of that route (GV_DOSAGE_MFMA_SEG, development, per context)
+    int dosage_route = 0;
+    int64_t dosage_seg = gvdm::SEG_MAX;
     double tune_seconds = 0.0;      // wall time the pick cost (0 when it came from the cache)
     int tune_source = 0;            // 0 model's first candidate, 1 measured, 2 cache, 3 fixed by an override / nothing to tune
 
@@ -329,6 +361,20 @@ void assoc(hipStream_t s, const View& v, const int64_t* rows, int64_t nrows, con
            double nonas, const double* xself, double self_scale, double* beta, double* se, double* tstat, double* pval);
 }  // namespace gvd
 
+// ---- the fixed-point route of 8-bit codes (gv_dense_mfma.hip): NA = false views only ---------------------------------------------
+namespace gvdm {
+Shape atx_shape(int64_t N, int64_t M, int cus, int64_t cap);      // cap: most K-entries per int32 segment (<= SEG_MAX)
+Shape ax_shape(int64_t N, int64_t M, int cus, int64_t cap);
+hipError_t reserve(Scratch& w, int64_t N, int64_t M, int cus, int64_t cap);      // scratch for both products of this shape
+void release(Scratch& w);
+// gvd::atx / gvd::ax_partial + ax_reduce with the same arguments and meaning; ev0 / ev1 (may be NULL) are recorded around the
+// streaming kernel
+void atx(hipStream_t s, int nv, const gvd::View& v, const Scratch& w, const Shape& sh, const double* pa, const double* pb, double scale,
+         double* outa, double* outb, const double* addxa, const double* addxb, double tau, double gam2, hipEvent_t ev0, hipEvent_t ev1);
+void ax(hipStream_t s, int nv, const gvd::View& v, const Scratch& w, const Shape& sh, const double* xa, const double* xb, int64_t npad,
+        double post, double* outa, double* outb, hipEvent_t ev0, hipEvent_t ev1);
+}  // namespace gvdm
+
 // ---- LD-block preconditioner (gv_precond.hip) --------------------------------------------------------------------------------
 namespace gvp {
 int64_t first_window(int64_t S, int W);             // first half-grid window u overlapping the shard [S, S+M)
@@ -390,6 +436,11 @@ void pc_invalidate(gv_ctx* c, bool free_mem);
 // compact dense data: the missing-aware kernels run when the codes were uploaded with gv_set_dosage_missing on AND the ingest counted a
 // reserved code in this shard (a shard without one gets the same bits from the plain kernels) or GV_DOSAGE_NA_KERNELS=1 forces them
 inline bool dosage_na_kernels(const gv_ctx* c) { return c->dense.na && (c->dense.reserved != 0 || c->force_na_kernels); }
+// the fixed-point route is in force: requested, 8-bit codes resident, the NA = false kernels would run (and the pitch within the Ax
+// kernel's 32-bit lane offsets); otherwise the k_dosage_* kernels run
+inline bool dosage_mfma_route(const gv_ctx* c) {
+    return c->dosage_route == 1 && c->dense.resident && c->dense.bits == 8 && !dosage_na_kernels(c) && c->dense.pitch <= gvdm::PITCH_MAX;
+}
 // the resident dense matrix as the gvd:: launchers take it
 inline gvd::View dense_view(const gv_ctx* c) {
     const DenseData& d = c->dense;

@@ -146,7 +146,10 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
     } else {
         const bool mfma = !dense && c->kernel_mode != 0;
         gvd::AxShape sh;
-        if (dense) {
+        const bool fixed = dense && dosage_mfma_route(c);      // 8-bit codes on the fixed-point route (gv_set_dosage_route)
+        if (fixed)
+            HIPCHK(c, gvdm::reserve(c->dense.fx, c->N, c->M, c->dense.cus, c->dosage_seg));
+        else if (dense) {
             DenseData& d = c->dense;
             sh = gvd::ax_shape(c->N, c->M, d.cus, gvd::ax_cols(d.bits));
             const size_t need = (size_t)2 * sh.segs * c->npad;
@@ -165,7 +168,10 @@ int ax_pass(gv_ctx* c, int nv, const double* xa, const double* xb, double* outa,
             NEED(c, c->have_raw, "Ax: kernel mode 0 needs the raw row layout (not the default: gv_set_layout(ctx, 1, ..) before ingest)");
         Timer t(c, &c->cnt.ms_ax);
         gv_ctx::EvRec* er = ev_next(c, 0);     // timing == 2: around the streaming kernel (the MFMA family records the pair itself)
-        if (dense) {
+        if (fixed)
+            gvdm::ax(c->stream, nv, dense_view(c), c->dense.fx, gvdm::ax_shape(c->N, c->M, c->dense.cus, c->dosage_seg), xa, nv == 2 ? xb : xa,
+                     c->npad, multi ? 1.0 : scale, outa, nv == 2 ? outb : outa, er ? er->a : nullptr, er ? er->b : nullptr);
+        else if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
             gvd::ax_partial(c->stream, nv, sh, dense_view(c), xa, nv == 2 ? xb : xa, c->dense.part, c->npad);
             if (er) (void)hipEventRecord(er->b, c->stream);
@@ -224,9 +230,15 @@ int atx_pass(gv_ctx* c, int nv, const double* pa, const double* pb, double* outa
             if (!c->ks_tuned && autotune_ks(c)) return 1;
         } else if (!dense)
             NEED(c, c->have_raw, "ATx: kernel mode 0 needs the raw row layout (not the default: gv_set_layout(ctx, 1, ..) before ingest)");
+        const bool fixed = dense && dosage_mfma_route(c);      // 8-bit codes on the fixed-point route (gv_set_dosage_route)
+        if (fixed) HIPCHK(c, gvdm::reserve(c->dense.fx, c->N, c->M, c->dense.cus, c->dosage_seg));
         Timer t(c, &c->cnt.ms_atx);
         gv_ctx::EvRec* er = ev_next(c, 1);
-        if (dense) {
+        if (fixed)
+            gvdm::atx(c->stream, nv, dense_view(c), c->dense.fx, gvdm::atx_shape(c->N, c->M, c->dense.cus, c->dosage_seg), pa, nv == 2 ? pb : pa,
+                      scale, outa, nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa, tau, gam2, er ? er->a : nullptr,
+                      er ? er->b : nullptr);
+        else if (dense) {
             if (er) (void)hipEventRecord(er->a, c->stream);
             gvd::atx(c->stream, nv, dense_view(c), pa, nv == 2 ? pb : pa, scale, outa, nv == 2 ? outb : outa, addxa, nv == 2 ? addxb : addxa,
                      tau, gam2);

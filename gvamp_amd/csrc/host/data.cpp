@@ -126,9 +126,9 @@ void data::push_mask() { ck(ctx, gv_set_mask(ctx, mask4.data(), nonas), "gv_set_
 
 data::data(std::vector<double> y, std::string genofp, const int N, const int M, const int Mt, const int S,
            const int rank, std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode,
-           double dosage_scale, int dosage_missing)
+           double dosage_scale, int dosage_missing, int dosage_route)
     : bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), phen_data(y), alpha_scale(alpha_scale),
-      dosage_scale(dosage_scale), dosage_missing(dosage_missing) {
+      dosage_scale(dosage_scale), dosage_missing(dosage_missing), dosage_route(dosage_route) {
     check_type_data(type_data);
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
@@ -155,9 +155,9 @@ data::data(std::vector<double> y, std::string genofp, const int N, const int M, 
 
 data::data(std::string fp, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
            std::string type_data, double alpha_scale, std::string bimfp, int device, int kernel_mode, double dosage_scale,
-           int dosage_missing)
+           int dosage_missing, int dosage_route)
     : phenfp(fp), bimfp(bimfp), type_data(type_data), N(N), M(M), Mt(Mt), S(S), rank(rank), alpha_scale(alpha_scale),
-      dosage_scale(dosage_scale), dosage_missing(dosage_missing) {
+      dosage_scale(dosage_scale), dosage_missing(dosage_missing), dosage_route(dosage_route) {
     check_type_data(type_data);
     mbytes = (N % 4) ? (size_t)N / 4 + 1 : (size_t)N / 4;
     im4 = (int)mbytes;
@@ -292,6 +292,14 @@ void data::read_dosage_data() {
     const auto t0 = std::chrono::steady_clock::now();
     ck(ctx, gv_upload_dosage_file(ctx, methfp.c_str(), (int64_t)(size_t(S) * size_t(N) * size_t(bits / 8)), bits, dosage_scale),
        "gv_upload_dosage_file");
+    // the route of the products: a request; what is in force depends on the codes now resident (8 bits, no missing entry in this shard)
+    ck(ctx, gv_set_dosage_route(ctx, dosage_route), "gv_set_dosage_route");
+    int route_req = 0, route_on = 0;
+    ck(ctx, gv_get_dosage_route(ctx, &route_req, &route_on), "gv_get_dosage_route");
+    if (rank == 0)
+        std::cout << "dosage kernels: " << (route_on ? "fixed-point i8 MFMA route" : "fp64 VALU kernels")
+                  << (route_req && !route_on ? " (--dosage-kernels mfma is not in force: it needs 8-bit codes without missing entries)" : "")
+                  << std::endl;
     if (rank == 0)
         std::cout << "reading dosage data took "
                   << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " seconds." << std::endl;

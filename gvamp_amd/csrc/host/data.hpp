@@ -25,6 +25,7 @@ private:
     double intercept = 0, scale = 1, alpha_scale = 1;
     double dosage_scale = 0;           // [ext] type_data "dosage8" / "dosage16": value = scale * code; <= 0 = 1/127, 1/16384
     int dosage_missing = 0;            // [ext] ... 1: the all-ones code is a missing entry (gv_set_dosage_missing)
+    int dosage_route = 0;              // [ext] ... 1: the products on the fixed-point i8 MFMA route where it applies (gv_set_dosage_route)
     gv_ctx* ctx = nullptr;
     bool owns_ctx = true;
 
@@ -35,11 +36,11 @@ public:
     // data.cpp:69-113 -- phenotype given as a vector, every individual present
     data(std::vector<double> y, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
          std::string type_data = "bed", double alpha_scale = 1, std::string bimfp = "", int device = -1,
-         int kernel_mode = 1, double dosage_scale = 0, int dosage_missing = 0);
+         int kernel_mode = 1, double dosage_scale = 0, int dosage_missing = 0, int dosage_route = 0);
     // data.cpp:30-61 -- phenotype file (.phen) with NA handling
     data(std::string fp, std::string genofp, const int N, const int M, const int Mt, const int S, const int rank,
          std::string type_data = "bed", double alpha_scale = 1, std::string bimfp = "", int device = -1,
-         int kernel_mode = 1, double dosage_scale = 0, int dosage_missing = 0);
+         int kernel_mode = 1, double dosage_scale = 0, int dosage_missing = 0, int dosage_route = 0);
     // [ext] adopt a context whose genotype shard is already resident (synthetic shards, bench, tests).
     // The context's mask is replaced by the full mask unless mask4 is given.
     data(gv_ctx* resident, std::vector<double> y, const int N, const int M, const int Mt, const int S, const int rank,

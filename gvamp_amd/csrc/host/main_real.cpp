@@ -50,6 +50,9 @@ int main(int argc, char** argv) {
     const int dmiss = opt.get_dosage_missing();               // [ext] --dosage-missing: the all-ones code is a missing entry
     if (dmiss && type_data == "bed" && rank == 0)
         std::cout << "WARNING: --dosage-missing is ignored for --geno-format bed (PLINK rows carry their own missing code)" << std::endl;
+    const int droute = opt.get_dosage_kernels() == "mfma" ? 1 : 0;      // [ext] --dosage-kernels: the route of the dosage products
+    if (droute && type_data == "bed" && rank == 0)
+        std::cout << "WARNING: --dosage-kernels is ignored for --geno-format bed (gv_set_kernel_mode selects the bed kernels)" << std::endl;
     const double alpha_scale = opt.get_alpha_scale();
     const std::string bimfp = opt.get_bim_file();
     const int dev = opt.get_device(), km = opt.get_kernel_mode();
@@ -65,7 +68,7 @@ int main(int argc, char** argv) {
         std::vector<double> MS = divide_work(Mt);
         const int M = (int)MS[0], S = (int)MS[1];
         need_phen(opt.get_phen_files(), "--phen-files");
-        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss);
+        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
         // infere: gam1 = 1e-6, gamw from --h2 (:64-69); restart: both from --gam1-init / --gamw-init (:381-382), r1 is
         // reloaded from --estimate-file inside infere_linear (vamp.cpp:226-233)
         const double gam1 = (mode == "restart") ? opt.get_gam1_init() : 1e-6;
@@ -78,7 +81,7 @@ int main(int argc, char** argv) {
         const int M_test = (int)MS[0], S_test = (int)MS[1];
         need_phen(opt.get_phen_files_test(), "--phen-files-test");
         data dataset_test(opt.get_phen_files_test()[0], opt.get_bed_file_test(), N_test, M_test, Mt_test, S_test, rank,
-                          type_data, alpha_scale, bimfp, dev, km, dscale, dmiss);
+                          type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
         std::vector<double> y_test = dataset_test.get_phen();
         const std::string est = opt.get_estimate_file();
         const size_t dot = est.find("."), pos_it = est.rfind("it");
@@ -119,7 +122,7 @@ int main(int argc, char** argv) {
         std::vector<double> x_est;
         double intercept, scale;
         {
-            data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss);
+            data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
             vamp emvamp(M, 1e-6, initial_gamw(opt), std::vector<double>(M, 0.0), rank, opt);
             x_est = infere_or_exit(emvamp, &dataset);
             intercept = dataset.get_intercept();
@@ -128,7 +131,7 @@ int main(int argc, char** argv) {
         if (rank == 0) std::cout << "intercept = " << intercept << std::endl << "scale = " << scale << std::endl;
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         data dataset_test(opt.get_phen_files_test()[0], opt.get_bed_file_test(), N_test, M, Mt_test, S, rank, type_data,
-                          alpha_scale, bimfp, dev, km, dscale, dmiss);
+                          alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
         std::vector<double> y_test = dataset_test.get_phen();
         double err2 = 0;
         const double R2 = test_r2(dataset_test, x_est, N_test, y_test, &err2, intercept, scale);   // :262-272
@@ -143,7 +146,7 @@ int main(int argc, char** argv) {
         std::vector<double> MS = divide_work(Mt);
         const int M = (int)MS[0], S = (int)MS[1];
         need_phen(opt.get_phen_files(), "--phen-files");
-        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss);
+        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
         const std::string est = opt.get_estimate_file();
         const size_t dot = est.rfind("."), pos_it = est.rfind("it");
         const std::string ext = est.substr(dot + 1);
@@ -174,7 +177,7 @@ int main(int argc, char** argv) {
         std::vector<double> MS = divide_work(Mt_test);
         const int M_test = (int)MS[0], S_test = (int)MS[1];
         data dataset_test(std::vector<double>(N_test, 0.0), opt.get_bed_file_test(), N_test, M_test, Mt_test, S_test, rank,
-                          type_data, alpha_scale, bimfp, dev, km, dscale, dmiss);
+                          type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
         const std::string est = opt.get_estimate_file();
         const std::string ext = est.substr(est.find(".") + 1);
         const std::string pre = opt.get_out_dir() + opt.get_out_name();

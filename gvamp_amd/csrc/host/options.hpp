@@ -44,13 +44,16 @@
        --dosage-scale s: value = s * code (default 1/127 for dosage8, 1/16384 for dosage16);                            \
        --dosage-missing 0|1 (default 0): 1 = the all-ones code (255 / 65535) is a missing entry (gv_set_dosage_missing); \
        ignored with one warning line for --geno-format bed;                                                            \
+       --dosage-kernels valu|mfma (default valu): the products of dosage8 codes on the fp64 VALU kernels or on the        \
+       fixed-point i8 MFMA route (gv_set_dosage_route; in force for 8-bit codes without missing entries, the line         \
+       "dosage kernels: ..." names what runs); ignored with one warning line for --geno-format bed;                      \
        --store-assoc 0|1 (default 0): after the loop write the whole per-marker association test -- effect, standard  \
        error, t and p, LOO and (with a .bim file) LOCO -- for bed and dosage data */            \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
     X(int, cg_precond_window, 128) X(std::string, geno_format, "bed") X(double, dosage_scale, 0) \
-    X(unsigned int, store_assoc, 0) X(int, dosage_missing, 0)
+    X(unsigned int, store_assoc, 0) X(int, dosage_missing, 0) X(std::string, dosage_kernels, "valu")
 
 class Options {
 public:

@@ -153,6 +153,24 @@ typedef struct {
     int pad_;
 } gv_dosage_stats;
 int gv_dosage_info(gv_ctx* ctx, gv_dosage_stats* out);
+/* ---- fixed-point i8 MFMA route for 8-bit dosage codes (additions only: GV_ABI_VERSION stays 4) ------------------------------------
+ * gv_set_dosage_route(ctx, route): 0 (default) = the fp64 VALU kernels of the dosage kind, 1 = the products gv_ax / gv_atx, their
+ * two-vector forms and everything built on them (gv_lmmse_mult, the CG solvers, the fused solves) run in fixed point on the i8 matrix
+ * pipe, on the SAME resident rows (no second copy of the codes).  Any other value is refused.  A request, per context; it may be made
+ * before or after an upload and outlives the dataset.  It is IN FORCE only while 8-bit codes are resident and the plain (not the
+ * missing-aware) kernels would run (and N <= 2^26: a lane offset of the Ax kernel is 32 bits wide); on 16-bit codes, on a shard with reserved codes under gv_set_dosage_missing, under
+ * GV_DOSAGE_NA_KERNELS=1, on bed and on methylation data the request is kept and nothing changes by a bit.  Statistics, gv_assoc_* and
+ * the ingest keep their kernels on either route.  gv_get_dosage_route reports both (either pointer may be NULL).
+ * Accuracy contract of route 1: that of kernel mode 1 (above) scaled by the code range.  A vector enters a product in fixed point with
+ * ONE exponent (|q| < 2^54 relative to its largest entry: per-entry error 2^-55 max|v|), an entry of the matrix is |b - mu'| <= 255
+ * codes, everything after the quantisation is exact integer arithmetic with one final rounding.  With the factor-16 slack of mode 1:
+ *   Ax : |out[n] - exact[n]| <= M * 2^-50 * (255 * scale / 2) * max_i |msig[i] x[i]| / sqrt(N),
+ *   ATx: |out[m] - exact[m]| <= N * 2^-50 * (255 * scale / 2) * msig[m] * max_n |p[n]| / sqrt(N)
+ * -- an ABSOLUTE error relative to the vector's largest entry, not relative to each output entry.  Results are bit-reproducible,
+ * independent of the work decomposition (every sum is an integer: no order enters), each slot of a two-vector call is bit-identical to
+ * the one-vector call, pad slots of gv_ax are exact zeros, no atomics -- but they are not bit-equal to route 0. */
+int gv_set_dosage_route(gv_ctx* ctx, int route);
+int gv_get_dosage_route(const gv_ctx* ctx, int* requested, int* in_force);
 /* cnt: M host doubles, the per-marker counts cnt_k after gv_marker_stats -- nonas for every marker when nothing is missing.
  * Compact dosage data only. */
 int gv_marker_counts(gv_ctx* ctx, double* cnt);

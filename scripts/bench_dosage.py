@@ -1,7 +1,7 @@
 """Compact dense data (8- / 16-bit dosage codes) products on one GPU, beside the dense fp64 kernels at the same shape: prints ONE
 JSON line and, with --out, writes it to a file (profiles/dosage_bench_<shape>.json).
 
-  python scripts/bench_dosage.py [--N 20000] [--M 800000] [--kinds u8,u16,f64] [--reps 10] [--rounds 3] [--seed 2026] [--out FILE]
+  python scripts/bench_dosage.py [--N 20000] [--M 800000] [--kinds u8,u16,f64,u8_mfma] [--reps 10] [--rounds 3] [--seed 2026] [--out FILE]
                                  [--miss-ppm P]
 
 Every kind asked for is resident at once (one context each; u8 + u16 + f64 at 20 000 x 800 000 are 16 + 32 + 128 GB) and the timed
@@ -17,7 +17,11 @@ per pass (the padding and the vectors not counted); `share` is against 8 TB/s; `
 --miss-ppm P (missing entries, gv_set_dosage_missing): every code kind k runs twice in the same alternation -- `k`, the plain kernels,
 on gv_synth_dosage_na(seed, bits, 0) in a context that takes the shortcut (no reserved code counted), and `k_na`, the missing-aware
 kernels forced by GV_DOSAGE_NA_KERNELS=1, on gv_synth_dosage_na(seed, bits, P).  With P = 0 the two hold the same codes, read the same
-bytes and give the same bits, so `<product>_x_plain` = time(k_na) / time(k) is the cost of the compare and select alone."""
+bytes and give the same bits, so `<product>_x_plain` = time(k_na) / time(k) is the cost of the compare and select alone.
+
+Kind u8_mfma: the codes of u8 in a context of its own on the fixed-point i8 MFMA route (gv_set_dosage_route(ctx, 1)), timed in the same
+alternation; with u8 among the kinds `<product>_x_u8` = time(u8) / time(u8_mfma) -- above 1 the route is faster -- and
+`<product>_spread` the largest relative deviation of a round from the median over both kinds, the resolution of that ratio."""
 import argparse
 import json
 import os
@@ -30,7 +34,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gvamp_amd import capi, synth  # noqa: E402
 
 PEAK_TBS = 8.0
-BYTES = {"u8": 1, "u16": 2, "f64": 8}
+BYTES = {"u8": 1, "u16": 2, "f64": 8, "u8_mfma": 1}
+BITS = {"u8": 8, "u16": 16, "u8_mfma": 8}
 PRODUCTS = ("Ax", "ATx", "Ax2", "ATx2")
 
 
@@ -49,9 +54,9 @@ def main():
     kinds = [k for k in a.kinds.split(",") if k]
     assert kinds and all(k in BYTES for k in kinds), a.kinds
     if a.miss_ppm is not None:
-        kinds = [kk for k in kinds for kk in ((k, k + "_na") if k != "f64" else (k,))]
-        for k in list(BYTES):
-            BYTES[k + "_na"] = BYTES[k]
+        kinds = [kk for k in kinds for kk in ((k, k + "_na") if k in ("u8", "u16") else (k,))]
+        for k in ("u8", "u16"):
+            BYTES[k + "_na"], BITS[k + "_na"] = BYTES[k], BITS[k]
     rng = np.random.default_rng(a.seed)
     xs = [rng.standard_normal(M), rng.standard_normal(M)]
     res = {"metric": "dosage_products", "N": N, "M": M, "reps": a.reps, "rounds": a.rounds, "peak_TBs": PEAK_TBS, "kinds": {}}
@@ -68,15 +73,17 @@ def main():
                 os.environ.pop("GV_DOSAGE_NA_KERNELS", None)
             sh = capi.Shard(N, M)
             shards[k] = sh
+            if k == "u8_mfma":
+                sh.set_dosage_route(1)
             t0 = time.perf_counter()
             if k == "f64" and same_values:
                 sh.upload_meth(synth.synth_dosage(N, M, a.seed, 8).astype(np.float64) / 127.0)
             elif k == "f64":
                 sh.synth_meth(a.seed)
             elif a.miss_ppm is not None:
-                sh.synth_dosage_na(a.seed, 8 * BYTES[k], a.miss_ppm if k.endswith("_na") else 0)
+                sh.synth_dosage_na(a.seed, BITS[k], a.miss_ppm if k.endswith("_na") else 0)
             else:
-                sh.synth_dosage(a.seed, 8 * BYTES[k])
+                sh.synth_dosage(a.seed, BITS[k])
             ingest = time.perf_counter() - t0
             t0 = time.perf_counter()
             sh.compute_markers_statistics()
@@ -84,6 +91,8 @@ def main():
                     "layout": sh.get_layout()}
             if k != "f64":
                 info["dosage_info"] = sh.dosage_info()
+                info["dosage_route"] = list(sh.dosage_route())
+                assert info["dosage_route"][1] == (1 if k == "u8_mfma" else 0), (k, info["dosage_route"])
             res["kinds"][k] = info
             x, x2 = sh.vecM(xs[0]), sh.vecM(xs[1])
             pn = np.zeros(4 * sh.mbytes)
@@ -121,6 +130,12 @@ def main():
             for k in kinds:
                 for pr in PRODUCTS:
                     res["kinds"][k][pr + "_x_f64"] = res["kinds"]["f64"][pr + "_ms"] / res["kinds"][k][pr + "_ms"]
+        if "u8_mfma" in kinds and "u8" in kinds:
+            for pr in PRODUCTS:
+                d = res["kinds"]["u8_mfma"]
+                d[pr + "_x_u8"] = res["kinds"]["u8"][pr + "_ms"] / d[pr + "_ms"]
+                d[pr + "_spread"] = max(abs(t - res["kinds"][k][pr + "_ms"]) / res["kinds"][k][pr + "_ms"]
+                                        for k in ("u8", "u8_mfma") for t in times[k][pr])
         for k in kinds:
             if k.endswith("_na"):
                 for pr in PRODUCTS:
