@@ -30,6 +30,7 @@ EXPORTS = [
     "gv_assoc_loo", "gv_assoc_loco",
     "gv_set_dosage_missing", "gv_synth_dosage_na", "gv_dosage_info", "gv_marker_counts",
     "gv_set_dosage_route", "gv_get_dosage_route",
+    "gv_ld_scores", "gv_ld_band", "gv_ld_info",
 ]
 
 
@@ -92,6 +93,10 @@ class PrecondStats(C.Structure):     # gv_precond_stats
     _fields_ = [("kind", C.c_int), ("window", C.c_int), ("windows", C.c_int64 * 2), ("first_window", C.c_int64 * 2),
                 ("resident_bytes", C.c_double), ("build_seconds", C.c_double), ("factorisations", C.c_int64),
                 ("fallback_windows", C.c_int64), ("last_tau", C.c_double), ("last_gam2", C.c_double)]
+
+
+class LdStats(C.Structure):          # gv_ld_stats
+    _fields_ = [("seconds", C.c_double), ("block_pairs", C.c_int64), ("useful_macs", C.c_double), ("scratch_bytes", C.c_double)]
 
 
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_size_t)
@@ -191,6 +196,9 @@ def load():
     L.gv_precond_info.argtypes = [vp, C.POINTER(PrecondStats)]
     L.gv_precond_window_gram.argtypes = [vp, C.c_int, i64, dp]
     L.gv_precond_apply.argtypes = [vp, C.c_double, C.c_double, vp, vp]
+    L.gv_ld_scores.argtypes = [vp, i64, C.POINTER(C.c_int), C.c_int, dp, dp]
+    L.gv_ld_band.argtypes = [vp, i64, C.POINTER(C.c_int), i64, i64, dp]
+    L.gv_ld_info.argtypes = [vp, C.POINTER(LdStats)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
     L.gv_cg_solve_aat.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(CgStats), dp]
     L.gv_cg_solve_aat2.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.POINTER(CgStats),
@@ -523,6 +531,35 @@ class Shard:
 
     def precond_apply(self, tau, gam2, r, z):
         self._ck(self.L.gv_precond_apply(self.h, tau, gam2, r.h, z.h))
+
+    def _chrom(self, chrom):
+        if chrom is None:
+            return None, None
+        ch = np.ascontiguousarray(chrom, dtype=np.int32)
+        assert ch.size == self.M
+        return ch, ch.ctypes.data_as(C.POINTER(C.c_int))
+
+    def ld_scores(self, window, chrom=None, adjusted=False):
+        """gv_ld_scores: (l2[M], npairs[M]) -- l_j = 1 + sum of f(r_jk^2) over the band of `window` markers on each side (clipped
+        to the shard and, with chrom, to the chromosome), NaN / 0 for a monomorphic marker; adjusted: the LDSC estimator"""
+        l2, n = np.zeros(max(self.M, 1)), np.zeros(max(self.M, 1))
+        ch, chp = self._chrom(chrom)
+        self._ck(self.L.gv_ld_scores(self.h, int(window), chp, int(bool(adjusted)), _dp(l2), _dp(n)))
+        return l2[:self.M].copy(), n[:self.M].copy()
+
+    def ld_band(self, window, j0, nj, chrom=None):
+        """gv_ld_band: nj x (2 * window + 1) correlations of the local markers [j0, j0 + nj); column window + d is r[j][j + d],
+        0 outside the band"""
+        nj_ = int(nj)
+        out = np.zeros((max(nj_, 1), 2 * int(window) + 1))
+        ch, chp = self._chrom(chrom)
+        self._ck(self.L.gv_ld_band(self.h, int(window), chp, int(j0), nj_, _dp(out)))
+        return out[:max(nj_, 0)]
+
+    def ld_info(self):
+        st = LdStats()
+        self._ck(self.L.gv_ld_info(self.h, C.byref(st)))
+        return {"seconds": st.seconds, "block_pairs": st.block_pairs, "useful_macs": st.useful_macs, "scratch_bytes": st.scratch_bytes}
 
     def ax2_dev(self, xa, xb, outa, outb):
         self._ck(self.L.gv_ax2_dev(self.h, xa.h, xb.h, outa.h, outb.h))

@@ -180,6 +180,7 @@ struct gv_ctx {
     bool pc_have_gram = false, pc_have_inv = false;
     double pc_tau = 0.0, pc_gam2 = 0.0, pc_build_s = 0.0;
     int64_t pc_factorisations = 0, pc_fallback = 0;
+    gv_ld_stats ld_last{};          // gv_ld_info: the last gv_ld_scores / gv_ld_band call (gv_ld.hip)
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;

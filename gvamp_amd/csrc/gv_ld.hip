@@ -1,0 +1,465 @@
+// gv_ld.hip -- LD scores and banded LD correlations of the resident genotypes (gv_ld_scores, gv_ld_band).
+//
+// C = A^T A restricted to a band of B markers on each side, from the resident 2-bit re-encoding: the exact integer sums VV, VP, PV, PP
+// of the planes P = b na, V = a P with v_mfma_i32_16x16x64_i8, then the fixed fp64 combination of section 13 and r = C_jk / sqrt(C_jj C_kk).
+//   k_ld_diag    C_jj of every marker from popcounts of the same planes (the same integers an MFMA would sum), one workgroup per
+//                64-marker row group
+//   k_ld_block   one workgroup per pair of row groups (I, J = I + d), d <= D = (B + 63) / 64: the 64 x 64 block of the four products
+//                over all individuals.  Every thread expands the words of one 16-byte load per half K-block into the i8 planes ONCE
+//                and shares them through LDS; each of the 4 waves multiplies a 32 x 32 quarter of the block (16 MFMAs per K-step).
+//                Epilogue: r, and either the band rows (band mode) or the block's row and column sums of f(r^2) (scores mode)
+//   k_ld_finish  l_j = 1 + the 2D + 1 block partials of marker j in ascending block order
+// Integer sums, then a fixed fp64 order, no atomics: the results do not depend on the layout, the kernel mode or the launch.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+
+#include "gv_internal.h"
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+// THE int32 invariant of this file: one individual adds at most 2 * 2 = 4 to an int32 sum (VV of two a = 2 genotypes), so a sum over
+// all N individuals stays below 2^31 for N <= 2^29 - 1 and no accumulation is cut into segments.  gv_ld_* refuse a larger N.
+constexpr int64_t LD_N_MAX = ((int64_t)1 << 29) - 1;
+constexpr int64_t LD_WINDOW_MAX = 8192;
+constexpr int LD_PITCH = 65;     // doubles per row of the scores epilogue's 64 x 64 LDS image (odd: row and column walks spread over the banks)
+
+// The two integer planes of 16 entries as i8 MFMA operands (VGPR s, byte t = entry 4t + s): P = present and phenotyped, V = a P.
+// (The bit recipe of pc_planes in gv_precond.hip; w holds r' = 2, 1, 0 for a = 2, 1, 0 and 3 for a missing genotype.)
+__device__ __forceinline__ void ld_planes(uint32_t w, uint32_t na, v4i& V, v4i& P) {
+    const uint32_t pm = ~(w & (w >> 1)) & na & 0x55555555u;
+    const uint32_t vb = w & (pm | (pm << 1));
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        V[s] = (int)((vb >> (2 * s)) & 0x03030303u);
+        P[s] = (int)((pm >> (2 * s)) & 0x03030303u);
+    }
+}
+
+// One 16-byte load of the (row group, K-block) image -- 64 markers x 256 individuals in 256 pieces -- and the four 16-entry words it
+// brings.  x in [0, 128) names the piece within half h of the K-block (K-steps 2h and 2h + 1 of 64 individuals); word q belongs to
+// marker 16 b[q] + r[q] of the row group and the 16 individuals 16 (4 (2h + sl) + g[q]) + [0, 16) of the K-block.
+template <int LAYOUT>
+struct Piece {
+    // tile layout: piece (s, quad, jj) at s * 64 + quad * 4 + jj holds byte d of marker t of the quad in byte t of dword d: all four
+    // markers of the quad, individuals 16 (4 s + jj) + [0, 16)
+    // stripes_m:   piece (i, s, r) at i * 64 + s * 16 + r holds marker 16 i + r, individuals 64 s + [0, 64): dword d = 16 of them
+    static __device__ __forceinline__ int index(int h, int x) {
+        return LAYOUT == 1 ? 128 * h + x : (x >> 5) * 64 + (2 * h + ((x >> 4) & 1)) * 16 + (x & 15);
+    }
+    static __device__ __forceinline__ int sl(int x) { return LAYOUT == 1 ? x >> 6 : (x >> 4) & 1; }
+    static __device__ __forceinline__ int b(int x, int q) { return LAYOUT == 1 ? (x >> 4) & 3 : x >> 5; }
+    static __device__ __forceinline__ int r(int x, int q) { return LAYOUT == 1 ? 4 * ((x >> 2) & 3) + q : x & 15; }
+    static __device__ __forceinline__ int g(int x, int q) { return LAYOUT == 1 ? x & 3 : q; }
+    static __device__ __forceinline__ uint32_t word(const uint4& o, int q) {
+        if (LAYOUT == 1) {
+            const int sh = 8 * q;
+            return ((o.x >> sh) & 0xFFu) | (((o.y >> sh) & 0xFFu) << 8) | (((o.z >> sh) & 0xFFu) << 16) | (((o.w >> sh) & 0xFFu) << 24);
+        }
+        return q == 0 ? o.x : (q == 1 ? o.y : (q == 2 ? o.z : o.w));
+    }
+};
+
+// C_jk from the four integer sums, j < k: vp = sum V_nj P_nk, pv = sum P_nj V_nk (the order of k_pc_gram)
+__device__ __forceinline__ double ld_c(int vv, int vp, int pv, int pp, double mj, double mk, double sj, double sk, double inv_n) {
+    const double s = (double)vv - mk * (double)vp - mj * (double)pv + mj * mk * (double)pp;
+    return sj * sk * inv_n * s;
+}
+
+// C_jj of the markers of row group blockIdx.x: VV = sum a^2 P, VP = PV = sum a P, PP = sum P by popcount, summed over the threads that
+// hold a marker in a fixed order (integers: any order gives the same)
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_ld_diag(const uint4* __restrict__ lay, int64_t nkb, const uint32_t* __restrict__ mask2, int64_t P4,
+                                                 int64_t N, int64_t M, const double* __restrict__ mave, const double* __restrict__ msig,
+                                                 double* __restrict__ cdiag) {
+    __shared__ int red[3][64][16];      // [sum][marker of the row group][slot]
+    const int tid = threadIdx.x, h = tid >> 7, x = tid & 127;
+    const int64_t rg = blockIdx.x, nJ = (N + 15) / 16, nkbn = (nJ + 15) / 16;
+    int vv[4] = {0, 0, 0, 0}, vp[4] = {0, 0, 0, 0}, pp[4] = {0, 0, 0, 0};
+    const uint4* p = lay + rg * nkb * 256 + Piece<LAYOUT>::index(h, x);
+    for (int64_t kb = 0; kb < nkbn; kb++) {
+        const uint4 o = p[kb * 256];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int64_t J = kb * 16 + 4 * (2 * h + Piece<LAYOUT>::sl(x)) + Piece<LAYOUT>::g(x, q);
+            const uint32_t na = J < nJ && J < P4 ? mask2[J] : 0u;
+            const uint32_t w = Piece<LAYOUT>::word(o, q);
+            const uint32_t pm = ~(w & (w >> 1)) & na & 0x55555555u;
+            const uint32_t vb = w & (pm | (pm << 1));
+            const int lo = __popc(vb & 0x55555555u), hi = __popc(vb & 0xAAAAAAAAu);
+            vv[q] += lo + 4 * hi;
+            vp[q] += lo + 2 * hi;
+            pp[q] += __popc(pm);
+        }
+    }
+    // marker ml of the row group is held by 16 (tile layout: 2 h x 2 sl x 4 jj, word q = ml % 4) or 4 x 4 (stripes: 2 h x 2 sl threads,
+    // all four words) partial sums: slot = the holder's index among them
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int ml = 16 * Piece<LAYOUT>::b(x, q) + Piece<LAYOUT>::r(x, q);
+        const int slot = LAYOUT == 1 ? (h * 2 + Piece<LAYOUT>::sl(x)) * 4 + (x & 3) : (h * 2 + Piece<LAYOUT>::sl(x)) * 4 + q;
+        red[0][ml][slot] = vv[q];
+        red[1][ml][slot] = vp[q];
+        red[2][ml][slot] = pp[q];
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int64_t j = rg * 64 + tid;
+        int s[3] = {0, 0, 0};
+#pragma unroll
+        for (int t = 0; t < 3; t++)
+            for (int e = 0; e < 16; e++) s[t] += red[t][tid][e];
+        if (j < M) cdiag[j] = ld_c(s[0], s[1], s[1], s[2], mave[j], mave[j], msig[j], msig[j], 1.0 / (double)N);
+    }
+}
+
+struct LdArgs {
+    const uint4* lay;
+    int64_t nkb;
+    const uint32_t* mask2;
+    int64_t P4, N, M, B;
+    int64_t nrg, I0;                // row groups in all; the first row group of this launch (band mode starts at the requested rows)
+    const double *mave, *msig, *cdiag;
+    const int* chrom;               // M device ints or NULL
+    int adjusted;
+    double nm2;                     // nonas - 2
+    int D;                          // (B + 63) / 64
+    int64_t Mp;                     // scores: markers per slot of the partials, 64 nrg
+    double* part;                   // scores: (2D + 1) x Mp partial sums, slot D + (other row group - own row group)
+    int* pcnt;                      // scores: ... and the number of terms in each
+    int64_t j0, nj;                 // band: the requested rows
+    double* band;                   // band: nj x (2B + 1)
+};
+
+// f(r^2) of the LD score
+__device__ __forceinline__ double ld_f(double r, int adjusted, double nm2) {
+    const double x = r * r;
+    return adjusted ? x - (1.0 - x) / nm2 : x;
+}
+
+// block (I = I0 + blockIdx.x, J = I + blockIdx.y).  BAND: store r of the requested rows; else the block's row / column sums.
+template <int LAYOUT, bool BAND>
+__global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
+    // operand images of one half K-block: [side: I, J][16-marker tile][K-step of the half][plane V, P][lane] x 16 bytes = 32 KiB;
+    // the scores epilogue reuses the space for the block's 64 x 64 values of f(r^2)
+    constexpr int OP_BYTES = 2 * 4 * 2 * 2 * 64 * 16, EP_BYTES = 64 * LD_PITCH * 8;
+    __shared__ __attribute__((aligned(16))) char lds[BAND ? OP_BYTES : (EP_BYTES > OP_BYTES ? EP_BYTES : OP_BYTES)];
+    v4i* op = reinterpret_cast<v4i*>(lds);
+    const int64_t I = a.I0 + blockIdx.x, J = I + blockIdx.y;
+    if (I >= a.nrg || J >= a.nrg) return;       // (uniform over the workgroup)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int side = tid >> 7, x = tid & 127;
+    const int64_t nJ = (a.N + 15) / 16, nkbn = (nJ + 15) / 16;
+    v4i acc[4][2][2];
+#pragma unroll
+    for (int p = 0; p < 4; p++)
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int j = 0; j < 2; j++) acc[p][i][j] = v4i{0, 0, 0, 0};
+    const uint4* src = a.lay + (side ? J : I) * a.nkb * 256;
+    const int psl = Piece<LAYOUT>::sl(x);
+    const int64_t steps = 2 * nkbn;              // half K-blocks
+    // this thread's piece of half K-block st and the mask words of its four words, loaded one step ahead of their use
+    uint4 o;
+    uint32_t na[4];
+    auto fetch = [&](int64_t st) {
+        const int64_t kb = st >> 1;
+        const int h = (int)(st & 1);
+        o = src[kb * 256 + Piece<LAYOUT>::index(h, x)];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int64_t Jn = kb * 16 + 4 * (2 * h + psl) + Piece<LAYOUT>::g(x, q);
+            na[q] = Jn < nJ && Jn < a.P4 ? a.mask2[Jn] : 0u;
+        }
+    };
+    fetch(0);
+    for (int64_t st = 0; st < steps; st++) {
+        // expand the four words once, for the whole workgroup
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            v4i V, P;
+            ld_planes(Piece<LAYOUT>::word(o, q), na[q], V, P);
+            const int slot = (((side * 4 + Piece<LAYOUT>::b(x, q)) * 2 + psl) * 2) * 64 + Piece<LAYOUT>::g(x, q) * 16 + Piece<LAYOUT>::r(x, q);
+            op[slot] = V;
+            op[slot + 64] = P;
+        }
+        if (st + 1 < steps) fetch(st + 1);
+        __syncthreads();
+#pragma unroll
+        for (int sl = 0; sl < 2; sl++) {
+            v4i Vi[2], Pi[2], Vj[2], Pj[2];
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                const int si = (((0 * 4 + 2 * wr + t) * 2 + sl) * 2) * 64 + lane, sj = (((1 * 4 + 2 * wc + t) * 2 + sl) * 2) * 64 + lane;
+                Vi[t] = op[si];
+                Pi[t] = op[si + 64];
+                Vj[t] = op[sj];
+                Pj[t] = op[sj + 64];
+            }
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    acc[0][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vi[i], Vj[j], acc[0][i][j], 0, 0, 0);   // VV
+                    acc[1][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vi[i], Pj[j], acc[1][i][j], 0, 0, 0);   // VP_ik = sum V_ni P_nk
+                    acc[2][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Pi[i], Vj[j], acc[2][i][j], 0, 0, 0);   // VP_ki
+                    acc[3][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Pi[i], Pj[j], acc[3][i][j], 0, 0, 0);   // PP
+                }
+        }
+        __syncthreads();
+    }
+    // Epilogue.  Register v of tile (i, j) of this lane is the entry of row 16 (2 wr + i) + 4 (lane >> 4) + v, column
+    // 16 (2 wc + j) + (lane & 15) of the block.
+    const double inv_n = 1.0 / (double)a.N;
+    double* fl = reinterpret_cast<double*>(lds);
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+        const int kl = 16 * (2 * wc + j) + (lane & 15);
+        const int64_t k = J * 64 + kl;
+        const bool kin = k < a.M;
+        const double mk = kin ? a.mave[k] : 0.0, sk = kin ? a.msig[k] : 0.0, ck = kin ? a.cdiag[k] : 0.0;
+        const int chk = kin && a.chrom ? a.chrom[k] : 0;
+#pragma unroll
+        for (int i = 0; i < 2; i++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const int il = 16 * (2 * wr + i) + 4 * (lane >> 4) + v;
+                const int64_t m = I * 64 + il;
+                const bool min_ = m < a.M;
+                const double mi = min_ ? a.mave[m] : 0.0, si = min_ ? a.msig[m] : 0.0, ci = min_ ? a.cdiag[m] : 0.0;
+                const int chi = min_ && a.chrom ? a.chrom[m] : 0;
+                const int64_t dist = k - m;
+                const bool inband = min_ && kin && dist <= a.B && -dist <= a.B && chi == chk;
+                const bool poly = ci != 0.0 && ck != 0.0;
+                double r = 0.0;
+                if (inband && poly) {
+                    if (m == k) r = 1.0;
+                    else {
+                        // once per unordered pair: the lower marker takes the role of j (only the diagonal block holds m > k)
+                        const double c = m < k ? ld_c(acc[0][i][j][v], acc[1][i][j][v], acc[2][i][j][v], acc[3][i][j][v], mi, mk, si, sk, inv_n)
+                                               : ld_c(acc[0][i][j][v], acc[2][i][j][v], acc[1][i][j][v], acc[3][i][j][v], mk, mi, sk, si, inv_n);
+                        r = c / sqrt(m < k ? ci * ck : ck * ci);
+                    }
+                }
+                if (BAND) {
+                    if (inband) {
+                        const int64_t w = 2 * a.B + 1;
+                        if (m >= a.j0 && m < a.j0 + a.nj) a.band[(m - a.j0) * w + a.B + dist] = r;
+                        if (I != J && k >= a.j0 && k < a.j0 + a.nj) a.band[(k - a.j0) * w + a.B - dist] = r;     // the mirror image
+                    }
+                } else {
+                    // a term of l_m (and, mirrored, of l_k): in the band, not the marker itself, both polymorphic; NaN = no term
+                    fl[il * LD_PITCH + kl] = inband && poly && m != k ? ld_f(r, a.adjusted, a.nm2) : __builtin_nan("");
+                }
+            }
+    }
+    if (BAND) return;
+    __syncthreads();
+    // rows of I summed over the columns in ascending k (threads 0..63); columns of J over the rows in ascending order (64..127, I < J)
+    if (tid < 128 && (tid < 64 || I != J)) {
+        const bool col = tid >= 64;
+        const int e = tid & 63;
+        double s = 0.0;
+        int n = 0;
+        for (int t = 0; t < 64; t++) {
+            const double f = col ? fl[t * LD_PITCH + e] : fl[e * LD_PITCH + t];
+            if (f == f) {
+                s += f;
+                n++;
+            }
+        }
+        const int64_t m = (col ? J : I) * 64 + e;
+        const int64_t slot = col ? a.D - (J - I) : a.D + (J - I);
+        a.part[slot * a.Mp + m] = s;          // (m < Mp = 64 nrg: the rows past M hold 0 terms)
+        a.pcnt[slot * a.Mp + m] = n;
+    }
+}
+
+// l_j = 1 + the block partials of marker j in ascending block order (slots whose block does not exist were zeroed)
+__global__ __launch_bounds__(256) void k_ld_finish(const double* __restrict__ part, const int* __restrict__ pcnt, int nslots, int64_t Mp,
+                                                   int64_t M, const double* __restrict__ cdiag, double* __restrict__ l2,
+                                                   double* __restrict__ npairs) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    if (cdiag[j] == 0.0) {
+        l2[j] = __builtin_nan("");
+        npairs[j] = 0.0;
+        return;
+    }
+    double s = 0.0;
+    int64_t n = 0;
+    for (int t = 0; t < nslots; t++) {
+        s += part[(int64_t)t * Mp + j];
+        n += pcnt[(int64_t)t * Mp + j];
+    }
+    l2[j] = 1.0 + s;
+    npairs[j] = (double)(1 + n);
+}
+
+// device scratch of one call: freed when the call returns, however it returns
+struct Scratch {
+    std::vector<void*> ptrs;
+    size_t bytes = 0;
+    ~Scratch() {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    template <class T>
+    hipError_t get(T** out, size_t n) {
+        void* p = nullptr;
+        const size_t b = sizeof(T) * (n ? n : 1);
+        const hipError_t e = hipMalloc(&p, b);
+        if (e != hipSuccess) return e;
+        ptrs.push_back(p);
+        bytes += b;
+        *out = (T*)p;
+        return hipSuccess;
+    }
+};
+
+}  // namespace
+
+using namespace gvi;
+
+// what both entry points check, next to pc_build_gram's checks of the same data (gv_precond.hip)
+static int ld_check(gv_ctx* c, const char* who, int64_t window) {
+    REFUSE_DOSAGE(c, who, "LD is computed from 2-bit genotypes only");
+    if (c->dense.resident) return fail(c, "%s: refused for dense (meth) data -- LD is computed from 2-bit genotypes only", who);
+    if (!c->have_stripes)
+        return fail(c, "%s: needs a re-encoded genotype layout resident (tile layout or two stripe sets); raw rows alone are not supported", who);
+    if (!c->have_stats || !c->mask2) return fail(c, "%s: marker statistics must be computed first", who);
+    if (window < 1 || window > LD_WINDOW_MAX) return fail(c, "%s: window must be in [1, %lld] markers (%lld was passed)", who, (long long)LD_WINDOW_MAX, (long long)window);
+    if (c->N > LD_N_MAX)
+        return fail(c, "%s: N = %lld exceeds %lld, the most individuals whose products fit the int32 accumulators (4 per individual)", who,
+                    (long long)c->N, (long long)LD_N_MAX);
+    return 0;
+}
+
+// the (j, k) entries of the band of rows [j0, j0 + nj), self included, chromosomes ignored
+static double ld_entries(int64_t M, int64_t B, int64_t j0, int64_t nj) {
+    double e = 0.0;
+    for (int64_t j = j0; j < j0 + nj; j++) e += (double)(std::min(j + B, M - 1) - std::max(j - B, (int64_t)0) + 1);
+    return e;
+}
+
+// scores (band == NULL) or the band rows [j0, j0 + nj)
+static int ld_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int adjusted, double* l2, double* npairs, int64_t j0, int64_t nj,
+                  double* band) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const gvm::Plan& pl = c->plan;
+    const int64_t M = c->M, nrg = (M + 63) / 64;
+    const int D = (int)((B + 63) / 64);
+    Scratch w;
+    LdArgs a{};
+    a.lay = reinterpret_cast<const uint4*>(pl.layout == 1 ? pl.tiles : pl.stripes_m);
+    a.nkb = pl.nkb_m;
+    a.mask2 = c->mask2;
+    a.P4 = c->pitch / 4;
+    a.N = c->N;
+    a.M = M;
+    a.B = B;
+    a.nrg = nrg;
+    a.mave = c->mave;
+    a.msig = c->msig;
+    a.adjusted = adjusted;
+    a.nm2 = (double)c->nonas - 2.0;
+    a.D = D;
+    a.Mp = nrg * 64;
+    a.j0 = j0;
+    a.nj = nj;
+    double* cdiag = nullptr;
+    int* dchrom = nullptr;
+    double *dl2 = nullptr, *dnp = nullptr;
+    const size_t nband = band ? (size_t)nj * (size_t)(2 * B + 1) : 0, nslots = (size_t)(2 * D + 1);
+#define LDALLOC(p, n)                                                                                                          \
+    do {                                                                                                                       \
+        if (w.get(&p, n) != hipSuccess) {                                                                                      \
+            (void)hipGetLastError();                                                                                           \
+            return fail(c, "%s: cannot allocate %zu bytes of device scratch (%zu already held by this call)", who, sizeof(*p) * (size_t)(n), w.bytes); \
+        }                                                                                                                      \
+    } while (0)
+    LDALLOC(cdiag, (size_t)M);
+    if (chrom) LDALLOC(dchrom, (size_t)M);
+    if (band) LDALLOC(a.band, nband);
+    else {
+        LDALLOC(a.part, nslots * (size_t)a.Mp);
+        LDALLOC(a.pcnt, nslots * (size_t)a.Mp);
+        LDALLOC(dl2, (size_t)M);
+        LDALLOC(dnp, (size_t)M);
+    }
+#undef LDALLOC
+    a.cdiag = cdiag;
+    a.chrom = dchrom;
+    if (chrom) HIPCHK(c, hipMemcpyAsync(dchrom, chrom, sizeof(int) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    if (band) HIPCHK(c, hipMemsetAsync(a.band, 0, sizeof(double) * nband, c->stream));
+    else {
+        HIPCHK(c, hipMemsetAsync(a.part, 0, sizeof(double) * nslots * (size_t)a.Mp, c->stream));
+        HIPCHK(c, hipMemsetAsync(a.pcnt, 0, sizeof(int) * nslots * (size_t)a.Mp, c->stream));
+    }
+    int64_t blocks = 0;
+    if (M > 0 && (!band || nj > 0)) {
+        if (pl.layout == 1)
+            hipLaunchKernelGGL(k_ld_diag<1>, dim3((unsigned)nrg), dim3(256), 0, c->stream, a.lay, a.nkb, a.mask2, a.P4, a.N, M, a.mave, a.msig, cdiag);
+        else
+            hipLaunchKernelGGL(k_ld_diag<2>, dim3((unsigned)nrg), dim3(256), 0, c->stream, a.lay, a.nkb, a.mask2, a.P4, a.N, M, a.mave, a.msig, cdiag);
+        KCHK(c);
+        // band mode: the row groups I that hold a requested row, or whose blocks (I, I + d) mirror into one
+        const int64_t Ia = band ? std::max<int64_t>(j0 / 64 - D, 0) : 0, Ib = band ? (j0 + nj - 1) / 64 : nrg - 1;
+        a.I0 = Ia;
+        const dim3 grid((unsigned)(Ib - Ia + 1), (unsigned)(D + 1));
+        for (int64_t I = Ia; I <= Ib; I++) blocks += std::min<int64_t>(D, nrg - 1 - I) + 1;
+        if (band) {
+            if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, true>), grid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_ld_block<2, true>), grid, dim3(256), 0, c->stream, a);
+        } else {
+            if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, false>), grid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_ld_block<2, false>), grid, dim3(256), 0, c->stream, a);
+        }
+        KCHK(c);
+        if (!band) {
+            hipLaunchKernelGGL(k_ld_finish, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, a.part, a.pcnt, (int)nslots, a.Mp, M,
+                               cdiag, dl2, dnp);
+            KCHK(c);
+        }
+    }
+    if (band) {
+        if (nband) HIPCHK(c, hipMemcpyAsync(band, a.band, sizeof(double) * nband, hipMemcpyDeviceToHost, c->stream));
+    } else if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(l2, dl2, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+        if (npairs) HIPCHK(c, hipMemcpyAsync(npairs, dnp, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ld_last.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c->ld_last.block_pairs = blocks;
+    c->ld_last.useful_macs = 4.0 * (double)c->N * (band ? ld_entries(M, B, j0, nj) : ld_entries(M, B, 0, M));
+    c->ld_last.scratch_bytes = (double)w.bytes;
+    return 0;
+}
+
+extern "C" {
+
+int gv_ld_scores(gv_ctx* c, int64_t window, const int* chrom, int adjusted, double* l2, double* npairs) {
+    if (ld_check(c, "gv_ld_scores", window)) return 1;
+    NEED(c, l2, "gv_ld_scores: l2 is NULL");
+    NEED(c, adjusted == 0 || adjusted == 1, "gv_ld_scores: adjusted must be 0 or 1");
+    NEED(c, adjusted == 0 || c->nonas >= 3, "gv_ld_scores: the adjusted estimator r^2 - (1 - r^2) / (n - 2) needs at least 3 phenotyped individuals");
+    return ld_run(c, "gv_ld_scores", window, chrom, adjusted, l2, npairs, 0, c->M, nullptr);
+}
+
+int gv_ld_band(gv_ctx* c, int64_t window, const int* chrom, int64_t j0, int64_t nj, double* r) {
+    if (ld_check(c, "gv_ld_band", window)) return 1;
+    NEED(c, r, "gv_ld_band: r is NULL");
+    if (j0 < 0 || nj < 0 || j0 > c->M || nj > c->M - j0)
+        return fail(c, "gv_ld_band: rows [%lld, %lld) are outside the shard's markers [0, %lld)", (long long)j0, (long long)(j0 + nj), (long long)c->M);
+    return ld_run(c, "gv_ld_band", window, chrom, 0, nullptr, nullptr, j0, nj, r);
+}
+
+int gv_ld_info(gv_ctx* c, gv_ld_stats* info) {
+    NEED(c, info, "gv_ld_info: info is NULL");
+    *info = c->ld_last;
+    return 0;
+}
+
+}  // extern "C"

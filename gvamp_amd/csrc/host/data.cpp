@@ -385,6 +385,18 @@ std::vector<std::vector<double>> data::assoc_calc_dev(gv_vec* z1, gv_vec* y, gv_
     return res;
 }
 
+std::vector<std::vector<double>> data::ld_scores_dev(int window, bool adjusted) {
+    std::vector<std::vector<double>> res(2, std::vector<double>(M > 0 ? M : 1, 0.0));
+    std::vector<int> ch_info;
+    if (bimfp != "") {
+        ch_info = read_chromosome_info(bimfp);
+        ch_info.resize(M > 0 ? M : 1, 0);
+    }
+    ck(ctx, gv_ld_scores(ctx, window, ch_info.empty() ? nullptr : ch_info.data(), adjusted ? 1 : 0, res[0].data(), res[1].data()), "gv_ld_scores");
+    for (auto& v : res) v.resize(M > 0 ? M : 0);
+    return res;
+}
+
 static std::vector<std::vector<double>> pvals_host(data* d, gv_ctx* ctx, int M, size_t mbytes,
                                                    std::vector<std::vector<double>>& z1, std::vector<double>& y,
                                                    std::vector<std::vector<double>>& x1_hat, bool loco,

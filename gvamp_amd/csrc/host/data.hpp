@@ -95,4 +95,6 @@ public:
     std::vector<double> pvals_calc_dev(gv_vec* z1, gv_vec* y, gv_vec* x1_hat, bool loco, const std::string& pred_prefix = std::string());
     // [ext] the whole test of gv_assoc_loo / gv_assoc_loco: {beta, se, t, p}, M values each (bed and compact dosage data)
     std::vector<std::vector<double>> assoc_calc_dev(gv_vec* z1, gv_vec* y, gv_vec* x1_hat, bool loco, const std::string& pred_prefix = std::string());
+    // [ext] gv_ld_scores over `window` markers on each side: {l2, npairs}, M values each; per chromosome when a .bim file was given
+    std::vector<std::vector<double>> ld_scores_dev(int window, bool adjusted);
 };

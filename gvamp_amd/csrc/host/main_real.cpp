@@ -1,6 +1,6 @@
 // main_real.cpp -- real-data driver mirroring the reference's main_real.cpp:13-599, all run modes:
 //   infere (:34-128), test (:129-213), both (:214-283), pvals-calc (:284-368), restart (:369-385),
-//   predict (:386-437), predict_single (:438-594).
+//   predict (:386-437), predict_single (:438-594); [ext] ldscore (gv_ld_scores).
 // Every mode is "load data, maybe run vamp::infere, one or more data::Ax, a reduction, a file": the matvecs are HIP
 // kernels behind libgvamp, the rest is host code.  One process per GPU (RANK / WORLD_SIZE from the launcher).
 #include <cmath>
@@ -172,6 +172,28 @@ int main(int argc, char** argv) {
         const int sp = (int)opt.get_store_pvals();   // 0 = LOO and LOCO, 1 = only LOO, 2 = only LOCO (:313)
         if (sp == 0 || sp == 1) dataset.pvals_calc(z1_hats, y, x1_hats, out_loo);
         if (dataset.get_bimfp() != "" && (sp == 0 || sp == 2)) dataset.pvals_calc_LOCO(z1_hats, y, x1_hats, out_loco);
+    } else if (mode == "ldscore") {                                                    // [ext] DESIGN.md section 16
+        // LD scores of the markers over --ld-window markers on each side, among the individuals with a phenotype
+        if (type_data != "bed") {
+            std::cout << "FATAL: --run-mode ldscore works on 2-bit genotypes only, not on --geno-format " << type_data << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (gv_env_nranks() > 1) {
+            std::cout << "FATAL: --run-mode ldscore runs on one rank: the band stops at a shard's edges, so the scores of a sharded job "
+                         "would miss their neighbours across them" << std::endl;
+            return EXIT_FAILURE;
+        }
+        const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
+        need_phen(opt.get_phen_files(), "--phen-files");
+        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, Mt, Mt, 0, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
+        const std::vector<std::vector<double>> res = dataset.ld_scores_dev(opt.get_ld_window(), opt.get_ld_adjust() == 1);
+        gv_ld_stats st;
+        gv_ld_info(dataset.get_ctx(), &st);
+        const std::string pre = opt.get_out_dir() + opt.get_out_name();
+        mpi_store_vec_to_file(pre + "_ldscore.bin", res[0], 0, Mt);
+        mpi_store_vec_to_file(pre + "_ldscore_n.bin", res[1], 0, Mt);
+        std::cout << "LD scores: window " << opt.get_ld_window() << (opt.get_ld_adjust() ? " (adjusted)" : "") << ", " << Mt << " markers, "
+                  << st.seconds << " seconds" << std::endl;
     } else if (mode == "predict" || mode == "predict_single") {                        // :386-594
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);

@@ -158,6 +158,16 @@ void Options::read_command_line_options(int argc, char** argv) {
             fatal(std::string("FATAL  : option --store-assoc has to be 0 or 1! (") + a + " was passed)");
         store_assoc = (unsigned int)atoi(a);
     };
+    H["--ld-window"] = [&](const char* a) {
+        if (atoi(a) < 1 || atoi(a) > 8192)
+            fatal(std::string("FATAL  : option --ld-window has to be within 1..8192! (") + a + " was passed)");
+        ld_window = atoi(a);
+    };
+    H["--ld-adjust"] = [&](const char* a) {
+        if (strcmp(a, "0") && strcmp(a, "1"))
+            fatal(std::string("FATAL  : option --ld-adjust has to be 0 or 1! (") + a + " was passed)");
+        ld_adjust = atoi(a);
+    };
     H["--resident-layout"] = [&](const char* a) {      // read by data::open_device (every data object of the run)
         resident_layout = atoi(a);
         setenv("GVAMP_RESIDENT_LAYOUT", a, 1);

@@ -638,6 +638,36 @@ int gv_precond_window_gram(gv_ctx* ctx, int grid, int64_t k, double* out);
 /* z = M^-1 r for (tau, gam2) (factorises when they differ from the last factorisation) */
 int gv_precond_apply(gv_ctx* ctx, double tau, double gam2, const gv_vec* r, gv_vec* z);
 
+/* ---- LD scores and banded LD correlations of the resident genotypes (additions only: GV_ABI_VERSION stays 4) ---
+ * Data: bed data with a re-encoded layout resident (the tile layout or two stripe sets), marker statistics computed; the phenotype
+ * mask applies as everywhere else.  With A_nj = (a_nj - mave_j) msig_j b_nj na_n / sqrt(N), the operator of gv_ax / gv_atx,
+ *   C_jk = sum_n A_nj A_nk = msig_j msig_k / N * (VV_jk - mave_k VP_jk - mave_j VP_kj + mave_j mave_k PP_jk)
+ * from the exact integer sums VV = V^T V, VP = V^T P, PP = P^T P of the planes P = b na, V = a P, in that fixed fp64 order, evaluated
+ * once per unordered pair (j < k) and mirrored: r_jk and r_kj are the same bits.  A marker is monomorphic if C_jj == 0 (constant among
+ * the phenotyped individuals, or missing everywhere).
+ *   r_jk = C_jk / sqrt(C_jj C_kk);  r_jj = 1 exactly for a polymorphic marker;  r_jk = 0 if either marker is monomorphic
+ * (missing genotypes count as the mean, as the operator treats them).
+ * Band: `window` = B >= 1 markers on each side in global marker order, clipped to this shard [S, S+M): the band STOPS at the shard's
+ * edges (as the preconditioner's windows do), so a sharded job misses the neighbours across them.  chrom (M ints, as gv_assoc_loco
+ * takes them; NULL = one chromosome): pairs on different chromosomes are outside the band.
+ *   l_j = 1 + sum over k != j in the band, k polymorphic, of f(r_jk^2);  f(x) = x (adjusted == 0) or x - (1 - x) / (n - 2) with
+ *   n = nonas (adjusted == 1, the LDSC estimator; needs nonas >= 3);  l_j = NaN for a monomorphic j
+ *   npairs_j = the number of terms, self included (0 for a monomorphic j)
+ * Row sums run in ascending k through per-block partials added in a fixed order, no atomics: two calls, both layouts and every kernel
+ * mode give the same bits.  One individual adds at most 4 to an int32 sum, so N <= 2^29 - 1 needs no segmenting; a larger N is refused.
+ * 1 <= window <= 8192.  Scratch is allocated for the call and released after it.  Refused with a message: methylation data, compact
+ * dosage data, a context with raw rows only, statistics not computed, arguments out of range. */
+int gv_ld_scores(gv_ctx* ctx, int64_t window, const int* chrom, int adjusted, double* l2 /* M */, double* npairs /* M or NULL */);
+/* r: nj x (2 * window + 1) doubles, row-major, for the local markers [j0, j0 + nj): column window + d is r[j][j + d], 0 outside the band */
+int gv_ld_band(gv_ctx* ctx, int64_t window, const int* chrom, int64_t j0, int64_t nj, double* r);
+typedef struct gv_ld_stats {
+    double seconds;              /* wall time of the last gv_ld_scores / gv_ld_band call */
+    int64_t block_pairs;         /* pairs of 64-marker row groups it computed */
+    double useful_macs;          /* 4 products x N x the (j, k) entries of the band it delivered, self included */
+    double scratch_bytes;        /* device scratch it allocated and released */
+} gv_ld_stats;
+int gv_ld_info(gv_ctx* ctx, gv_ld_stats* info);
+
 #ifdef __cplusplus
 }
 #endif
