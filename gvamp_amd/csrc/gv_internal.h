@@ -376,10 +376,11 @@ void ax(hipStream_t s, int nv, const gvd::View& v, const Scratch& w, const Shape
         double post, double* outa, double* outb, hipEvent_t ev0, hipEvent_t ev1);
 }  // namespace gvdm
 
-// ---- LD-block preconditioner (gv_precond.hip) --------------------------------------------------------------------------------
+// ---- LD-block preconditioner (gv_precond.hip; the window Grams are an epilogue of the LD block kernel, gv_ld.hip) --------------
 namespace gvp {
 int64_t first_window(int64_t S, int W);             // first half-grid window u overlapping the shard [S, S+M)
 int64_t num_windows(int64_t S, int64_t M, int W);
+// out[u - first_window] = the W x W Gram of every window, zero beyond its clipped length (memset and one kernel on s)
 void gram(hipStream_t s, const void* lay, int layout, int64_t nkb, const uint32_t* mask2, int64_t P4, int64_t N, int64_t S, int64_t M,
           int W, const double* mave, const double* msig, double* out);
 int factor(hipStream_t s, const double* gram, int W, int64_t S, int64_t M, double tau, double gam2, double diag, double* inv, int* fail);
@@ -434,6 +435,9 @@ void ev_resolve(gv_ctx* c);     // timing == 2: the pending event pairs into the
 int pc_prepare(gv_ctx* c, double tau, double gam2);
 void pc_apply(gv_ctx* c, const double* r, double* z);
 void pc_invalidate(gv_ctx* c, bool free_mem);
+// what the exact blocks of A^T A need (gv_ld.hip): not compact dosage data, not dense, a re-encoded layout, marker statistics and mask
+// words, N within the int32 sums -- refused by message under the caller's name `who`, `why` being its reason for wanting genotypes
+int planes_check(gv_ctx* c, const char* who, const char* why);
 // compact dense data: the missing-aware kernels run when the codes were uploaded with gv_set_dosage_missing on AND the ingest counted a
 // reserved code in this shard (a shard without one gets the same bits from the plain kernels) or GV_DOSAGE_NA_KERNELS=1 forces them
 inline bool dosage_na_kernels(const gv_ctx* c) { return c->dense.na && (c->dense.reserved != 0 || c->force_na_kernels); }

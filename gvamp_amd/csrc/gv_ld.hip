@@ -1,4 +1,5 @@
-// gv_ld.hip -- LD scores and banded LD correlations of the resident genotypes (gv_ld_scores, gv_ld_band).
+// gv_ld.hip -- LD scores and banded LD correlations of the resident genotypes (gv_ld_scores, gv_ld_band), and the
+// window Grams of the LD-block preconditioner (gvp::gram; section 13): every exact block of A^T A comes from this file.
 //
 // C = A^T A restricted to a band of B markers on each side, from the resident 2-bit re-encoding: the exact integer sums VV, VP, PV, PP
 // of the planes P = b na, V = a P with v_mfma_i32_16x16x64_i8, then the fixed fp64 combination of section 13 and r = C_jk / sqrt(C_jj C_kk).
@@ -7,7 +8,8 @@
 //   k_ld_block   one workgroup per pair of row groups (I, J = I + d), d <= D = (B + 63) / 64: the 64 x 64 block of the four products
 //                over all individuals.  Every thread expands the words of one 16-byte load per half K-block into the i8 planes ONCE
 //                and shares them through LDS; each of the 4 waves multiplies a 32 x 32 quarter of the block (16 MFMAs per K-step).
-//                Epilogue: r, and either the band rows (band mode) or the block's row and column sums of f(r^2) (scores mode)
+//                Epilogue: r, and either the band rows (band mode) or the block's row and column sums of f(r^2) (scores mode); or
+//                the block's entries of the preconditioner's window Grams (Gram mode: d only as far as one window reaches, no k_ld_diag)
 //   k_ld_finish  l_j = 1 + the 2D + 1 block partials of marker j in ascending block order
 // Integer sums, then a fixed fp64 order, no atomics: the results do not depend on the layout, the kernel mode or the launch.
 #include <algorithm>
@@ -21,16 +23,23 @@ namespace {
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 // THE int32 invariant of this file: one individual adds at most 2 * 2 = 4 to an int32 sum (VV of two a = 2 genotypes), so a sum over
-// all N individuals stays below 2^31 for N <= 2^29 - 1 and no accumulation is cut into segments.  gv_ld_* refuse a larger N.
+// all N individuals stays below 2^31 for N <= 2^29 - 1 and no accumulation is cut into segments.  gv_ld_* and the preconditioner's
+// Gram build refuse a larger N (planes_check).
 constexpr int64_t LD_N_MAX = ((int64_t)1 << 29) - 1;
 constexpr int64_t LD_WINDOW_MAX = 8192;
 constexpr int LD_PITCH = 65;     // doubles per row of the scores epilogue's 64 x 64 LDS image (odd: row and column walks spread over the banks)
 
-// The two integer planes of 16 entries as i8 MFMA operands (VGPR s, byte t = entry 4t + s): P = present and phenotyped, V = a P.
-// (The bit recipe of pc_planes in gv_precond.hip; w holds r' = 2, 1, 0 for a = 2, 1, 0 and 3 for a missing genotype.)
+// THE bit recipe of the two integer planes of 16 entries, P = present and phenotyped, V = a P.  w holds r' = 2, 1, 0 for a = 2, 1, 0 and
+// 3 for a missing genotype (0 at pad): bit 2q of pm is P of entry q, bits 2q + 1 and 2q of vb are its V.
+__device__ __forceinline__ void ld_bits(uint32_t w, uint32_t na, uint32_t& pm, uint32_t& vb) {
+    pm = ~(w & (w >> 1)) & na & 0x55555555u;
+    vb = w & (pm | (pm << 1));
+}
+
+// ... as i8 MFMA operands (VGPR s, byte t = entry 4t + s)
 __device__ __forceinline__ void ld_planes(uint32_t w, uint32_t na, v4i& V, v4i& P) {
-    const uint32_t pm = ~(w & (w >> 1)) & na & 0x55555555u;
-    const uint32_t vb = w & (pm | (pm << 1));
+    uint32_t pm, vb;
+    ld_bits(w, na, pm, vb);
 #pragma unroll
     for (int s = 0; s < 4; s++) {
         V[s] = (int)((vb >> (2 * s)) & 0x03030303u);
@@ -62,7 +71,8 @@ struct Piece {
     }
 };
 
-// C_jk from the four integer sums, j < k: vp = sum V_nj P_nk, pv = sum P_nj V_nk (the order of k_pc_gram)
+// C_jk from the four integer sums: vp = sum V_nj P_nk, pv = sum P_nj V_nk.  THE combination of sections 13 and 16: the LD epilogues call it
+// with the lower marker as j, the Gram epilogue with j = the entry's row (the lower triangle of a Gram is what k_pc_factor reads)
 __device__ __forceinline__ double ld_c(int vv, int vp, int pv, int pp, double mj, double mk, double sj, double sk, double inv_n) {
     const double s = (double)vv - mk * (double)vp - mj * (double)pv + mj * mk * (double)pp;
     return sj * sk * inv_n * s;
@@ -85,9 +95,8 @@ __global__ __launch_bounds__(256) void k_ld_diag(const uint4* __restrict__ lay, 
         for (int q = 0; q < 4; q++) {
             const int64_t J = kb * 16 + 4 * (2 * h + Piece<LAYOUT>::sl(x)) + Piece<LAYOUT>::g(x, q);
             const uint32_t na = J < nJ && J < P4 ? mask2[J] : 0u;
-            const uint32_t w = Piece<LAYOUT>::word(o, q);
-            const uint32_t pm = ~(w & (w >> 1)) & na & 0x55555555u;
-            const uint32_t vb = w & (pm | (pm << 1));
+            uint32_t pm, vb;
+            ld_bits(Piece<LAYOUT>::word(o, q), na, pm, vb);
             const int lo = __popc(vb & 0x55555555u), hi = __popc(vb & 0xAAAAAAAAu);
             vv[q] += lo + 4 * hi;
             vp[q] += lo + 2 * hi;
@@ -131,7 +140,12 @@ struct LdArgs {
     int* pcnt;                      // scores: ... and the number of terms in each
     int64_t j0, nj;                 // band: the requested rows
     double* band;                   // band: nj x (2B + 1)
+    int64_t S, u0, nu;              // Gram: the shard's first global marker; the half-grid windows [u0, u0 + nu) that overlap it
+    int W, hs;                      // Gram: the window length and log2 of its half H
+    double* gram;                   // Gram: nu x W x W, zeroed before the launch
 };
+
+enum { EP_SCORES, EP_BAND, EP_GRAM };     // the epilogues of k_ld_block
 
 // f(r^2) of the LD score
 __device__ __forceinline__ double ld_f(double r, int adjusted, double nm2) {
@@ -139,13 +153,30 @@ __device__ __forceinline__ double ld_f(double r, int adjusted, double nm2) {
     return adjusted ? x - (1.0 - x) / nm2 : x;
 }
 
-// block (I = I0 + blockIdx.x, J = I + blockIdx.y).  BAND: store r of the requested rows; else the block's row / column sums.
-template <int LAYOUT, bool BAND>
+// G_u[m - lo_u][k - lo_u] = g and, if mirror, G_u[k - lo_u][m - lo_u] = gt in every half-grid window u = [(u - 1) H, (u + 1) H) that holds
+// the local markers m and k: with am = (S + m) / H and ak = (S + k) / H, u = am and am + 1 if am == ak, the larger if they differ by 1.
+// (lo_u <= m, k < lo_u + W because both markers lie in the window; u0 <= am and ak + 1 < u0 + nu for m, k < M.)
+__device__ __forceinline__ void ld_gram_store(const LdArgs& a, int64_t m, int64_t k, double g, bool mirror, double gt) {
+    const int64_t am = (a.S + m) >> a.hs, ak = (a.S + k) >> a.hs;
+    for (int64_t u = max(am, ak); u <= min(am, ak) + 1; u++) {
+        if (u < a.u0 || u >= a.u0 + a.nu) continue;
+        const int64_t lo = max((u - 1) * ((int64_t)1 << a.hs), a.S) - a.S;
+        double* G = a.gram + (u - a.u0) * a.W * a.W;
+        const int r = (int)(m - lo), c = (int)(k - lo);
+        G[r * a.W + c] = g;
+        if (mirror) G[c * a.W + r] = gt;
+    }
+}
+
+// block (I = I0 + blockIdx.x, J = I + blockIdx.y).  EP_BAND: store r of the requested rows; EP_SCORES: the block's row / column sums;
+// EP_GRAM: the block's entries of the window Grams.
+template <int LAYOUT, int EP>
 __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
     // operand images of one half K-block: [side: I, J][16-marker tile][K-step of the half][plane V, P][lane] x 16 bytes = 32 KiB;
     // the scores epilogue reuses the space for the block's 64 x 64 values of f(r^2)
     constexpr int OP_BYTES = 2 * 4 * 2 * 2 * 64 * 16, EP_BYTES = 64 * LD_PITCH * 8;
-    __shared__ __attribute__((aligned(16))) char lds[BAND ? OP_BYTES : (EP_BYTES > OP_BYTES ? EP_BYTES : OP_BYTES)];
+    constexpr bool LD = EP != EP_GRAM;      // r needs the diagonal and the chromosomes; a Gram entry neither
+    __shared__ __attribute__((aligned(16))) char lds[EP == EP_SCORES && EP_BYTES > OP_BYTES ? EP_BYTES : OP_BYTES];
     v4i* op = reinterpret_cast<v4i*>(lds);
     const int64_t I = a.I0 + blockIdx.x, J = I + blockIdx.y;
     if (I >= a.nrg || J >= a.nrg) return;       // (uniform over the workgroup)
@@ -220,8 +251,8 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
         const int kl = 16 * (2 * wc + j) + (lane & 15);
         const int64_t k = J * 64 + kl;
         const bool kin = k < a.M;
-        const double mk = kin ? a.mave[k] : 0.0, sk = kin ? a.msig[k] : 0.0, ck = kin ? a.cdiag[k] : 0.0;
-        const int chk = kin && a.chrom ? a.chrom[k] : 0;
+        const double mk = kin ? a.mave[k] : 0.0, sk = kin ? a.msig[k] : 0.0, ck = LD && kin ? a.cdiag[k] : 0.0;
+        const int chk = LD && kin && a.chrom ? a.chrom[k] : 0;
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -229,8 +260,16 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                 const int il = 16 * (2 * wr + i) + 4 * (lane >> 4) + v;
                 const int64_t m = I * 64 + il;
                 const bool min_ = m < a.M;
-                const double mi = min_ ? a.mave[m] : 0.0, si = min_ ? a.msig[m] : 0.0, ci = min_ ? a.cdiag[m] : 0.0;
-                const int chi = min_ && a.chrom ? a.chrom[m] : 0;
+                const double mi = min_ ? a.mave[m] : 0.0, si = min_ ? a.msig[m] : 0.0, ci = LD && min_ ? a.cdiag[m] : 0.0;
+                const int chi = LD && min_ && a.chrom ? a.chrom[m] : 0;
+                if (EP == EP_GRAM) {
+                    // the roles go by the entry's row and column (G[row][col] takes mave_col with sum V_row P_col), so the mirror
+                    // image swaps them.  A diagonal block holds both orders itself.
+                    if (min_ && kin)
+                        ld_gram_store(a, m, k, ld_c(acc[0][i][j][v], acc[1][i][j][v], acc[2][i][j][v], acc[3][i][j][v], mi, mk, si, sk, inv_n), I != J,
+                                      ld_c(acc[0][i][j][v], acc[2][i][j][v], acc[1][i][j][v], acc[3][i][j][v], mk, mi, sk, si, inv_n));
+                    continue;
+                }
                 const int64_t dist = k - m;
                 const bool inband = min_ && kin && dist <= a.B && -dist <= a.B && chi == chk;
                 const bool poly = ci != 0.0 && ck != 0.0;
@@ -244,7 +283,7 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                         r = c / sqrt(m < k ? ci * ck : ck * ci);
                     }
                 }
-                if (BAND) {
+                if (EP == EP_BAND) {
                     if (inband) {
                         const int64_t w = 2 * a.B + 1;
                         if (m >= a.j0 && m < a.j0 + a.nj) a.band[(m - a.j0) * w + a.B + dist] = r;
@@ -256,7 +295,7 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                 }
             }
     }
-    if (BAND) return;
+    if (EP != EP_SCORES) return;
     __syncthreads();
     // rows of I summed over the columns in ascending k (threads 0..63); columns of J over the rows in ascending order (64..127, I < J)
     if (tid < 128 && (tid < 64 || I != J)) {
@@ -323,17 +362,57 @@ struct Scratch {
 
 using namespace gvi;
 
-// what both entry points check, next to pc_build_gram's checks of the same data (gv_precond.hip)
-static int ld_check(gv_ctx* c, const char* who, int64_t window) {
-    REFUSE_DOSAGE(c, who, "LD is computed from 2-bit genotypes only");
-    if (c->dense.resident) return fail(c, "%s: refused for dense (meth) data -- LD is computed from 2-bit genotypes only", who);
+// what every user of k_ld_block needs resident: 2-bit genotypes in a re-encoded layout, the marker statistics and the mask words, and an
+// N within the int32 invariant.  who: the caller's name; why: its reason for wanting genotypes
+int gvi::planes_check(gv_ctx* c, const char* who, const char* why) {
+    REFUSE_DOSAGE(c, who, why);
+    if (c->dense.resident) return fail(c, "%s: refused for dense (meth) data -- %s", who, why);
     if (!c->have_stripes)
         return fail(c, "%s: needs a re-encoded genotype layout resident (tile layout or two stripe sets); raw rows alone are not supported", who);
     if (!c->have_stats || !c->mask2) return fail(c, "%s: marker statistics must be computed first", who);
-    if (window < 1 || window > LD_WINDOW_MAX) return fail(c, "%s: window must be in [1, %lld] markers (%lld was passed)", who, (long long)LD_WINDOW_MAX, (long long)window);
     if (c->N > LD_N_MAX)
         return fail(c, "%s: N = %lld exceeds %lld, the most individuals whose products fit the int32 accumulators (4 per individual)", who,
                     (long long)c->N, (long long)LD_N_MAX);
+    return 0;
+}
+
+// the window Grams of section 13: G_u of every half-grid window that overlaps the shard, W x W each and zero beyond its clipped length
+void gvp::gram(hipStream_t s, const void* lay, int layout, int64_t nkb, const uint32_t* mask2, int64_t P4, int64_t N, int64_t S, int64_t M,
+               int W, const double* mave, const double* msig, double* out) {
+    LdArgs a{};
+    a.lay = reinterpret_cast<const uint4*>(lay);
+    a.nkb = nkb;
+    a.mask2 = mask2;
+    a.P4 = P4;
+    a.N = N;
+    a.M = M;
+    a.nrg = (M + 63) / 64;
+    a.mave = mave;
+    a.msig = msig;
+    a.S = S;
+    a.u0 = first_window(S, W);
+    a.nu = num_windows(S, M, W);
+    a.W = W;
+    a.hs = W == 32 ? 4 : (W == 64 ? 5 : 6);
+    a.gram = out;
+    if (a.nu == 0) return;
+    (void)hipMemsetAsync(out, 0, sizeof(double) * (size_t)a.nu * W * W, s);      // (an error stays for the caller's hipGetLastError)
+    // blocks (I, I + d) up to the most row groups that one window's markers [lo, hi) straddle
+    const int64_t H = W / 2;
+    int64_t D = 0;
+    for (int64_t u = a.u0; u < a.u0 + a.nu; u++) {
+        const int64_t lo = std::max((u - 1) * H, S) - S, hi = std::min((u + 1) * H, S + M) - S;
+        D = std::max(D, (hi - 1) / 64 - lo / 64);
+    }
+    const dim3 grid((unsigned)a.nrg, (unsigned)(D + 1));
+    if (layout == 1) hipLaunchKernelGGL((k_ld_block<1, EP_GRAM>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_ld_block<2, EP_GRAM>), grid, dim3(256), 0, s, a);
+}
+
+// what both entry points check
+static int ld_check(gv_ctx* c, const char* who, int64_t window) {
+    if (planes_check(c, who, "LD is computed from 2-bit genotypes only")) return 1;
+    if (window < 1 || window > LD_WINDOW_MAX) return fail(c, "%s: window must be in [1, %lld] markers (%lld was passed)", who, (long long)LD_WINDOW_MAX, (long long)window);
     return 0;
 }
 
@@ -411,11 +490,11 @@ static int ld_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int a
         const dim3 grid((unsigned)(Ib - Ia + 1), (unsigned)(D + 1));
         for (int64_t I = Ia; I <= Ib; I++) blocks += std::min<int64_t>(D, nrg - 1 - I) + 1;
         if (band) {
-            if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, true>), grid, dim3(256), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_ld_block<2, true>), grid, dim3(256), 0, c->stream, a);
+            if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, EP_BAND>), grid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_ld_block<2, EP_BAND>), grid, dim3(256), 0, c->stream, a);
         } else {
-            if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, false>), grid, dim3(256), 0, c->stream, a);
-            else hipLaunchKernelGGL((k_ld_block<2, false>), grid, dim3(256), 0, c->stream, a);
+            if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, EP_SCORES>), grid, dim3(256), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_ld_block<2, EP_SCORES>), grid, dim3(256), 0, c->stream, a);
         }
         KCHK(c);
         if (!band) {

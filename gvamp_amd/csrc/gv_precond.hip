@@ -3,7 +3,8 @@
 // Windows of W markers on GLOBAL marker indices, two grids staggered by h = W/2: window u >= 0 covers [(u-1)h, (u+1)h), clipped
 // to [0, Mt) and to the shard [S, S+M).  Odd u is grid 0 (window k = (u-1)/2 = [kW, kW+W)), even u is grid 1 (window k = u/2 =
 // [kW-h, kW+h), the first one clipped at 0).  Every marker lies in exactly one window of each grid: u = g/h and g/h + 1.
-//   Gram      G_u = the window's exact diagonal block of A^T A, from the resident 2-bit re-encoding with i8 MFMA (k_pc_gram)
+//   Gram      G_u = the window's exact diagonal block of A^T A, from the resident 2-bit re-encoding with i8 MFMA: the Gram epilogue of
+//             k_ld_block (gvp::gram, gv_ld.hip)
 //   factor    B_u = tau G_u + gam2 I, Cholesky in LDS and the explicit inverse L^-T L^-1, one workgroup per window (k_pc_factor)
 //   apply     z = 1/2 sum over both grids of blockdiag(B_u^-1) r (k_pc_apply)
 // Integer Grams, then a fixed fp64 order everywhere, no atomics: the results do not depend on the layout or the launch.
@@ -13,110 +14,6 @@
 #include "gv_internal.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-// 16 recoded 2-bit entries (r' = 2, 1, 0 for a = 2, 1, 0; 3 missing; 0 at pad) of local marker m, individuals [16J, 16J+16)
-__device__ __forceinline__ uint32_t pc_word(const void* lay, int layout, int64_t nkb, int64_t m, int64_t J) {
-    const int64_t rg = m >> 6, kb = J >> 4;
-    const int Jl = (int)(J & 15);
-    if (layout == 1) {     // tile layout: piece tau = (Jl/4)*64 + quad*4 + Jl%4, byte d of marker t of the quad is byte t of dword d
-        const int ml = (int)(m & 63), ql = ml >> 2, t = ml & 3;
-        const uint4 o = reinterpret_cast<const uint4*>(lay)[(rg * nkb + kb) * 256 + (Jl >> 2) * 64 + ql * 4 + (Jl & 3)];
-        const int sh = 8 * t;
-        return ((o.x >> sh) & 0xFFu) | (((o.y >> sh) & 0xFFu) << 8) | (((o.z >> sh) & 0xFFu) << 16) | (((o.w >> sh) & 0xFFu) << 24);
-    }
-    // stripes_m: piece t = i*64 + g*16 + r (marker 16i + r of the row group, individuals 64g + [0, 64)), dword d = 16 of them
-    const int mi = (int)(m & 63);
-    const int64_t piece = (rg * nkb + kb) * 256 + (mi >> 4) * 64 + (Jl >> 2) * 16 + (mi & 15);
-    return reinterpret_cast<const uint32_t*>(lay)[piece * 4 + (Jl & 3)];
-}
-
-// The two integer planes of 16 entries as i8 MFMA operands (VGPR s, byte t = entry 4t + s): P = present and phenotyped, V = a P
-__device__ __forceinline__ void pc_planes(uint32_t w, uint32_t na, v4i& V, v4i& P) {
-    const uint32_t pm = ~(w & (w >> 1)) & na & 0x55555555u;     // bit 2q: entry q is present and has a phenotype
-    const uint32_t vb = w & (pm | (pm << 1));
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        V[s] = (int)((vb >> (2 * s)) & 0x03030303u);
-        P[s] = (int)((pm >> (2 * s)) & 0x03030303u);
-    }
-}
-
-// block (window ul, row block bi): rows [16 bi, 16 bi + 16) x all W columns of the window's Gram; the 4 waves split the individuals
-template <int NB>
-__global__ __launch_bounds__(256) void k_pc_gram(const void* __restrict__ lay, int layout, int64_t nkb, const uint32_t* __restrict__ mask2,
-                                                 int64_t P4, int64_t N, int64_t S, int64_t M, int64_t u0, const double* __restrict__ mave,
-                                                 const double* __restrict__ msig, double* __restrict__ gram) {
-    constexpr int W = NB * 16, H = W / 2;
-    __shared__ int red[NB * 256];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, g = lane >> 4;
-    const int bi = blockIdx.y;
-    const int64_t u = u0 + blockIdx.x;
-    const int64_t glo = max((u - 1) * H, S), ghi = min((u + 1) * H, S + M);
-    const int64_t lo = glo - S, len = ghi - glo;
-    v4i acc[4][NB];
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int b = 0; b < NB; b++) acc[p][b] = v4i{0, 0, 0, 0};
-    const int64_t nJ = (N + 15) / 16;
-    for (int64_t c = wave; c * 4 < nJ; c += 4) {
-        const int64_t J = c * 4 + g;
-        const uint32_t na = J < nJ && J < P4 ? mask2[J] : 0u;
-        v4i V[NB], P[NB];
-#pragma unroll
-        for (int b = 0; b < NB; b++) {
-            const int row = b * 16 + r;
-            const uint32_t w = (na && row < len) ? pc_word(lay, layout, nkb, lo + row, J) : 0u;
-            pc_planes(w, row < len ? na : 0u, V[b], P[b]);
-        }
-        v4i Vi = V[0], Pi = P[0];
-#pragma unroll
-        for (int b = 0; b < NB; b++)
-            if (b == bi) { Vi = V[b]; Pi = P[b]; }
-#pragma unroll
-        for (int b = 0; b < NB; b++) {
-            acc[0][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vi, V[b], acc[0][b], 0, 0, 0);   // VV
-            acc[1][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vi, P[b], acc[1][b], 0, 0, 0);   // VP_ij = sum V_ni P_nj
-            acc[2][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Pi, V[b], acc[2][b], 0, 0, 0);   // VP_ji
-            acc[3][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Pi, P[b], acc[3][b], 0, 0, 0);   // PP
-        }
-    }
-    // the four waves' integer sums (exact, so any order gives the same), one product at a time through LDS
-    int tot[4][NB];
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-        for (int w = 0; w < 4; w++) {
-            if (wave == w)
-#pragma unroll
-                for (int b = 0; b < NB; b++)
-#pragma unroll
-                    for (int v = 0; v < 4; v++) red[b * 256 + lane * 4 + v] = (w == 0 ? 0 : red[b * 256 + lane * 4 + v]) + acc[p][b][v];
-            __syncthreads();
-        }
-#pragma unroll
-        for (int b = 0; b < NB; b++) tot[p][b] = red[b * 256 + threadIdx.x];
-        __syncthreads();
-    }
-    // entry e = b * 256 + threadIdx.x holds C[row][col] of lane e/4 % 64, register e % 4: row = 4 (lane >> 4) + reg, col = lane & 15
-    const int el = threadIdx.x >> 2, ev = threadIdx.x & 3;
-    const int i = bi * 16 + 4 * (el >> 4) + ev;
-    const double inv_n = 1.0 / (double)N;
-    const double mi = i < len ? mave[lo + i] : 0.0, si = i < len ? msig[lo + i] : 0.0;
-    double* out = gram + ((int64_t)blockIdx.x * W + i) * W;
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        const int j = b * 16 + (el & 15);
-        double gij = 0.0;
-        if (i < len && j < len) {
-            const double mj = mave[lo + j], sj = msig[lo + j];
-            const double s = (double)tot[0][b] - mj * (double)tot[1][b] - mi * (double)tot[2][b] + mi * mj * (double)tot[3][b];
-            gij = si * sj * inv_n * s;
-        }
-        out[j] = gij;
-    }
-}
 
 // one workgroup per window: B = tau G + gam2 I in LDS, Cholesky B = L L^T (L strictly below the diagonal of a, its diagonal in dl),
 // X = L^-1 by column-wise forward substitution (X^T on and above the diagonal of a), then B^-1 = X^T X -- symmetric and positive
@@ -213,16 +110,6 @@ namespace gvp {
 int64_t first_window(int64_t S, int W) { return S / (W / 2); }
 int64_t num_windows(int64_t S, int64_t M, int W) { return M > 0 ? (S + M - 1) / (W / 2) + 2 - S / (W / 2) : 0; }
 
-void gram(hipStream_t s, const void* lay, int layout, int64_t nkb, const uint32_t* mask2, int64_t P4, int64_t N, int64_t S, int64_t M,
-          int W, const double* mave, const double* msig, double* out) {
-    const int64_t u0 = first_window(S, W), nu = num_windows(S, M, W);
-    if (nu == 0) return;
-    const dim3 grid((unsigned)nu, (unsigned)(W / 16));
-    if (W == 32) hipLaunchKernelGGL(k_pc_gram<2>, grid, dim3(256), 0, s, lay, layout, nkb, mask2, P4, N, S, M, u0, mave, msig, out);
-    else if (W == 64) hipLaunchKernelGGL(k_pc_gram<4>, grid, dim3(256), 0, s, lay, layout, nkb, mask2, P4, N, S, M, u0, mave, msig, out);
-    else hipLaunchKernelGGL(k_pc_gram<8>, grid, dim3(256), 0, s, lay, layout, nkb, mask2, P4, N, S, M, u0, mave, msig, out);
-}
-
 size_t factor_lds(int W) { return sizeof(double) * ((size_t)W * W + W); }
 
 int factor(hipStream_t s, const double* gram, int W, int64_t S, int64_t M, double tau, double gam2, double diag, double* inv, int* fail) {
@@ -258,11 +145,7 @@ void pc_invalidate(gv_ctx* c, bool free_mem) {
 // the window Grams of the resident data set (once per data set, mask and marker statistics)
 static int pc_build_gram(gv_ctx* c) {
     NEED(c, c->pc_kind == 1, "LD preconditioner: not enabled (gv_set_cg_precond(ctx, 1, window))");
-    REFUSE_DOSAGE(c, "LD preconditioner", "genotype windows only");
-    NEED(c, !c->dense.resident, "LD preconditioner: refused for dense (meth) data -- genotype windows only");
-    NEED(c, c->have_stripes, "LD preconditioner: needs a re-encoded genotype layout resident (tile layout or two stripe sets); "
-                             "raw rows alone are not supported");
-    NEED(c, c->have_stats && c->mask2, "LD preconditioner: marker statistics must be computed first");
+    if (planes_check(c, "LD preconditioner", "genotype windows only")) return 1;
     const int W = c->pc_W;
     if (!c->pc_have_gram) {
         const int64_t u0 = gvp::first_window(c->S, W), nu = gvp::num_windows(c->S, c->M, W);

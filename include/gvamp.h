@@ -620,7 +620,8 @@ int gv_read_bandwidth(gv_ctx* ctx, size_t nbytes, int reps, double* gbps);
  * Grams come from the resident re-encoded layout (a context with raw rows only is refused, so are dense (meth) data); they are built
  * at the first solve (or gv_precond_window_gram) and dropped on a new ingest, gv_set_mask and gv_marker_stats; kind 0 releases them.  A window whose pivot is <= 1e-12 x its largest
  * diagonal, or not finite, takes the scalar rule on its markers.  With kind 1 the M-space solves run the host-driven loop, and the
- * N-space solvers gv_cg_solve_aat* are refused. */
+ * N-space solvers gv_cg_solve_aat* are refused.  The Grams are exact int32 sums over all individuals (at most 4 per individual), so
+ * kind 1 is refused above N = 2^29 - 1 where they are built, with the message of gv_ld_scores / gv_ld_band under its own name. */
 int gv_set_cg_precond(gv_ctx* ctx, int kind, int window);
 typedef struct gv_precond_stats {
     int kind, window;

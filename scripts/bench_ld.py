@@ -1,6 +1,7 @@
-"""The LD-score pass (gv_ld_scores) against the preconditioner's Gram build (k_pc_gram, section 13) on
-gv_synth_bed_ld genotypes, in one process: seconds and useful integer MAC/s of both -- 4 products x N x the (j, k) entries
-delivered (the in-band entries of the scores, the clipped window squares of the Grams).  Writes one JSON file.
+"""Two epilogues of one kernel, k_ld_block: the LD-score pass (gv_ld_scores) against the preconditioner's Gram
+build (gvp::gram, section 13; gv_precond_info.build_seconds) on gv_synth_bed_ld genotypes, in one process.  Seconds and useful integer
+MAC/s of both -- 4 products x N x the (j, k) entries delivered (the in-band entries of the scores, the clipped window squares of the
+Grams); ratio_to_gram is the scores' rate over the Gram build's, i.e. how much of a block each epilogue delivers.  Writes one JSON file.
 
     python scripts/bench_ld.py --N 400000 --M 125000 --out profiles/ld_bench_400k_125k.json
 """

@@ -37,7 +37,17 @@ def _host(bed, N, M, S, na=None):
     return a, b, na, mave, msig
 
 
-@pytest.mark.parametrize("N,S,M,W,masked", [(2001, 37, 650, 128, False), (1203, 37, 333, 64, True), (998, 5, 200, 32, False)])
+# The Grams are an epilogue of the LD block kernel (64-marker row groups, K-blocks of 256 individuals).  After the three larger
+# shapes, the smallest at which that epilogue can go wrong:
+#   (100, 0, 40, 128)    one row group, one K-block whose second half is all mask-zero, a window longer than the shard
+#   (257, 64, 130, 128)  the shard offset on a row-group and window edge, a partly filled last row group, one individual in the
+#                        second K-block
+#   (300, 37, 200, 128)  windows that straddle three row groups: blocks (I, I + 2)
+#   (300, 5, 70, 32)     h = 16: several windows per row group and one across the edge at local marker 64
+#   (130, 3, 1, 64)      a single marker
+@pytest.mark.parametrize("N,S,M,W,masked", [(2001, 37, 650, 128, False), (1203, 37, 333, 64, True), (998, 5, 200, 32, False),
+                                            (100, 0, 40, 128, False), (257, 64, 130, 128, True), (300, 37, 200, 128, False),
+                                            (300, 5, 70, 32, False), (130, 3, 1, 64, False)])
 def test_window_grams_match_restatement_on_both_layouts_and_modes(N, S, M, W, masked):
     bed = synth.synth_bed(N, M, seed=3, miss_ppm=20000, S=S, ld_block=48, ld_ppm=900000)
     na = None
@@ -66,6 +76,29 @@ def test_window_grams_match_restatement_on_both_layouts_and_modes(N, S, M, W, ma
             assert info["build_seconds"] > 0 and info["resident_bytes"] == 2 * 8 * len(wins) * W * W
     for key, gs in grams.items():      # layouts and kernel modes agree bit for bit
         assert all(np.array_equal(gs[0], g) for g in gs[1:]), key
+
+
+def test_ld_band_and_window_grams_give_the_same_correlations():
+    """the two users of the block kernel: r_jk of gv_ld_band against G_jk / sqrt(G_jj G_kk) of every window that holds both markers.
+    Both are held to 1e-12 against the same restatement and the diagonal of r is 1, hence 1e-12."""
+    N, S, M, W = 300, 37, 200, 128
+    bed = synth.synth_bed(N, M, seed=3, miss_ppm=20000, S=S, ld_block=48, ld_ppm=900000)
+    with _shard(bed, N, M, S=S, W=W) as sh:
+        r = sh.ld_band(W, 0, M)
+        pairs = 0
+        for grid, k, lo, hi in pr.windows(S, M, W):
+            n, j0 = hi - lo, lo - S
+            G = sh.precond_window_gram(grid, k)[:n, :n]
+            d = np.diag(G)
+            poly = d != 0
+            assert poly.sum() >= 2
+            jj, kk = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+            rb = r[j0 + jj, W + kk - jj]
+            rg = G / np.sqrt(np.outer(d, d), where=np.outer(poly, poly), out=np.ones((n, n)))
+            both = np.outer(poly, poly)
+            assert np.max(np.abs(rb - rg)[both]) <= 1e-12, (grid, k)
+            pairs += int(both.sum())
+        assert pairs > M * W // 2
 
 
 def test_apply_matches_restatement_and_counts_singular_windows():
