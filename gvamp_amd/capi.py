@@ -31,6 +31,7 @@ EXPORTS = [
     "gv_set_dosage_missing", "gv_synth_dosage_na", "gv_dosage_info", "gv_marker_counts",
     "gv_set_dosage_route", "gv_get_dosage_route",
     "gv_ld_scores", "gv_ld_band", "gv_ld_info",
+    "gv_set_ld_dosage", "gv_get_ld_dosage",
 ]
 
 
@@ -199,6 +200,8 @@ def load():
     L.gv_ld_scores.argtypes = [vp, i64, C.POINTER(C.c_int), C.c_int, dp, dp]
     L.gv_ld_band.argtypes = [vp, i64, C.POINTER(C.c_int), i64, i64, dp]
     L.gv_ld_info.argtypes = [vp, C.POINTER(LdStats)]
+    L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
+    L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
     L.gv_cg_solve_aat.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(CgStats), dp]
     L.gv_cg_solve_aat2.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.POINTER(CgStats),
@@ -555,6 +558,15 @@ class Shard:
         ch, chp = self._chrom(chrom)
         self._ck(self.L.gv_ld_band(self.h, int(window), chp, int(j0), nj_, _dp(out)))
         return out[:max(nj_, 0)]
+
+    def set_ld_dosage(self, on):
+        """gv_set_ld_dosage: 1 = ld_scores / ld_band / ld_info accept resident 8-bit dosage codes with the mask set (default 0)"""
+        self._ck(self.L.gv_set_ld_dosage(self.h, int(on)))
+
+    def get_ld_dosage(self):
+        on = C.c_int(0)
+        self._ck(self.L.gv_get_ld_dosage(self.h, C.byref(on)))
+        return on.value
 
     def ld_info(self):
         st = LdStats()

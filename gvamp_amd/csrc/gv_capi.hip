@@ -290,6 +290,16 @@ int gv_create(int device, gv_ctx** out) {
         }
         c->dosage_seg = k;
     }
+    // GV_LD_DOSAGE_EDGE=64|128 (development, read per context): the block edge of the one-product LD kernel of 8-bit dosage codes
+    // (gv_set_ld_dosage).  It changes no bit.
+    if (const char* ed = getenv("GV_LD_DOSAGE_EDGE")) {
+        if (atoi(ed) != 64 && atoi(ed) != 128) {
+            g_create_err = "gv_create: GV_LD_DOSAGE_EDGE=" + std::string(ed) + ": the block edge is 64 or 128 markers";
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->ld_dosage_edge = atoi(ed);
+    }
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)

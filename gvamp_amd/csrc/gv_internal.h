@@ -181,6 +181,10 @@ struct gv_ctx {
     double pc_tau = 0.0, pc_gam2 = 0.0, pc_build_s = 0.0;
     int64_t pc_factorisations = 0, pc_fallback = 0;
     gv_ld_stats ld_last{};          // gv_ld_info: the last gv_ld_scores / gv_ld_band call (gv_ld.hip)
+    // gv_set_ld_dosage: gv_ld_scores / gv_ld_band accept resident 8-bit dosage codes; it outlives the dataset.
+    // ld_dosage_edge: markers per side of a block of the one-product kernel, 64 or 128 (GV_LD_DOSAGE_EDGE, development, per context)
+    int ld_dosage = 0;
+    int ld_dosage_edge = 128;
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;

@@ -12,6 +12,8 @@
 //                the block's entries of the preconditioner's window Grams (Gram mode: d only as far as one window reaches, no k_ld_diag)
 //   k_ld_finish  l_j = 1 + the 2D + 1 block partials of marker j in ascending block order
 // Integer sums, then a fixed fp64 order, no atomics: the results do not depend on the layout, the kernel mode or the launch.
+// Second part (k_ldd_*, ldd_run): the same two entry points on resident 8-bit dosage codes, opt-in (gv_set_ld_dosage; section 17) -- the
+// centred product of two markers in exact 128-bit integers, one correctly rounded conversion.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -26,6 +28,12 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 // all N individuals stays below 2^31 for N <= 2^29 - 1 and no accumulation is cut into segments.  gv_ld_* and the preconditioner's
 // Gram build refuse a larger N (planes_check).
 constexpr int64_t LD_N_MAX = ((int64_t)1 << 29) - 1;
+// ... and of the dosage kernels (k_ldd_block): an individual adds at most 128 * 128 = 16 384 in magnitude to an int32 sum, so no int32
+// accumulation spans more than c->dosage_seg <= gvdm::SEG_MAX = 131 071 individuals (GV_DOSAGE_MFMA_SEG lowers it), rounded down to
+// whole K-steps of LDD_KSTEP individuals, at least one (ldd_run is the one place that cuts).  The segment sums are added in int64; a
+// data set of one segment runs the instantiation without them.  The 128-bit epilogue (ldd_x) holds for N <= LD_N_MAX.
+constexpr int LDD_KSTEP = 128;
+static_assert((gvdm::SEG_MAX / LDD_KSTEP) * LDD_KSTEP * 128 * 128 <= 2147483647LL, "an int32 sum over one segment must fit");
 constexpr int64_t LD_WINDOW_MAX = 8192;
 constexpr int LD_PITCH = 65;     // doubles per row of the scores epilogue's 64 x 64 LDS image (odd: row and column walks spread over the banks)
 
@@ -338,6 +346,335 @@ __global__ __launch_bounds__(256) void k_ld_finish(const double* __restrict__ pa
     npairs[j] = (double)(1 + n);
 }
 
+// =====================================================================================================================================
+// 8-bit dosage codes (gv_set_ld_dosage).  The operands are the resident pitched rows as they are: byte code ^ 0x80
+// is the i8 value code - 128, and 16 consecutive bytes of a row are a lane's share of an MFMA operand on either side.
+//   k_ldd_mask   the phenotype mask as one byte per individual (0xFF / 0), zero from N up to the padded length: what the J side is
+//                ANDed with.  na is 0 or 1, so masking ONE side masks every product; pad bytes (code 0, -128 after the bias) and whatever
+//                a clamped load brings on the other side multiply zeros.
+//   k_ldd_diag   c_j = sum P_j, T_j = sum V_j, VV_jj and fl(X_jj) per marker in one streaming read, one wave per marker
+//   k_ldd_block  one workgroup per pair of groups of EDGE markers (I, I + d): K-steps of 128 individuals staged once per workgroup in LDS
+//                in operand order; wave (wr, wc) multiplies the EDGE/2 x EDGE/2 quarter.  UNIFORM (every marker has P_j = na): one
+//                product, VV; otherwise the four products of the bed kernel.  Both feed ldd_x, the ONE epilogue function.
+// The epilogue works per 64 x 64 sub-block (Is, Js) of the block, so the partials layout [2D + 1][64 row groups], the summation order and
+// k_ld_finish are those of the bed kernel whatever EDGE is.
+constexpr uint32_t LDD_BIAS = 0x80808080u;
+
+// 0xFF in every byte of x that is not the reserved code 255
+__device__ __forceinline__ uint32_t ldd_present(uint32_t x) {
+    const uint32_t miss = ((x & 0x7F7F7F7Fu) + 0x01010101u) & x & 0x80808080u;      // bit 7 of every byte that is 0xFF
+    return ~((miss >> 7) * 0xFFu);
+}
+
+// a 128-bit integer to fp64, correctly rounded: the top 64 bits with a sticky bit ORed into bit 0 (53 kept bits and the rounding bit
+// lie above it), converted as uint64 (one rounding), then scaled by a power of two
+__device__ __forceinline__ double ldd_to_double(__int128 x) {
+    const bool neg = x < 0;
+    const unsigned __int128 u = neg ? -(unsigned __int128)x : (unsigned __int128)x;
+    const uint64_t hi = (uint64_t)(u >> 64), lo = (uint64_t)u;
+    double d;
+    if (hi == 0) d = (double)lo;
+    else {
+        const int sh = 64 - __builtin_clzll(hi);        // 1 .. 64 bits dropped
+        const uint64_t top = sh == 64 ? hi : (hi << (64 - sh)) | (lo >> sh);
+        const bool sticky = sh == 64 ? lo != 0 : (lo << (64 - sh)) != 0;
+        d = ldexp((double)(top | (uint64_t)sticky), sh);
+    }
+    return neg ? -d : d;
+}
+
+// THE epilogue function of section 17: fl(X_jk), X_jk = c_j c_k VV - c_j T_k VP_jk - c_k T_j VP_kj + T_j T_k PP in exact integers
+// (|X| < 2^103 for N <= LD_N_MAX: every factor pair and every sum fits 128 bits).  X_jk = X_kj exactly: no role of j and k enters.
+__device__ __forceinline__ double ldd_x(int64_t cj, int64_t ck, int64_t tj, int64_t tk, int64_t vv, int64_t vpjk, int64_t vpkj, int64_t pp) {
+    typedef __int128 i128;
+    const i128 x = (i128)cj * ck * vv - (i128)cj * tk * vpjk - (i128)ck * tj * vpkj + (i128)tj * tk * pp;
+    return ldd_to_double(x);
+}
+
+// nab[w]: the mask bytes of the individuals 4 w + [0, 4)
+__global__ __launch_bounds__(256) void k_ldd_mask(const uint32_t* __restrict__ mask2, int64_t P4, int64_t N, int64_t nwords,
+                                                  uint32_t* __restrict__ nab) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= nwords) return;
+    uint32_t out = 0;
+    const int64_t Jn = w >> 2;
+    if (Jn < P4) {
+        const uint32_t m = mask2[Jn] >> (8 * (w & 3));
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+            if (4 * w + t < N && ((m >> (2 * t)) & 1u)) out |= 0xFFu << (8 * t);
+    }
+    nab[w] = out;
+}
+
+__device__ __forceinline__ int64_t ldd_wave_sum(int64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor((long long)v, off, 64);
+    return v;
+}
+
+// one wave per marker; a lane adds the 16 bytes of a load in int32 (at most 16 * 16384) and keeps its running sums in int64
+template <bool NA>
+__global__ __launch_bounds__(256) void k_ldd_diag(const uint8_t* __restrict__ rows, int64_t pitch, const uint4* __restrict__ nab, int64_t M,
+                                                  int64_t* __restrict__ cnt, int64_t* __restrict__ tsum, int64_t* __restrict__ vvd,
+                                                  double* __restrict__ xd) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= M) return;
+    const uint4* row = reinterpret_cast<const uint4*>(rows + j * pitch);
+    int64_t c = 0, t = 0, vv = 0;
+    for (int64_t q = lane; q < pitch / 16; q += 64) {
+        const uint4 o = row[q], nm = nab[q];
+        const uint32_t ow[4] = {o.x, o.y, o.z, o.w}, mw[4] = {nm.x, nm.y, nm.z, nm.w};
+        int c1 = 0, t1 = 0, v1 = 0;
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const uint32_t m = NA ? mw[d] & ldd_present(ow[d]) : mw[d];
+            const uint32_t v = (ow[d] ^ LDD_BIAS) & m;
+            c1 += __popc(m & 0x01010101u);
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int s = (int)(signed char)(v >> (8 * b));
+                t1 += s;
+                v1 += s * s;
+            }
+        }
+        c += c1;
+        t += t1;
+        vv += v1;
+    }
+    c = ldd_wave_sum(c);
+    t = ldd_wave_sum(t);
+    vv = ldd_wave_sum(vv);
+    if (lane == 0) {
+        cnt[j] = c;
+        tsum[j] = t;
+        vvd[j] = vv;
+        xd[j] = ldd_x(c, c, t, t, vv, t, t, c);        // VP_jj = sum V_j P_j = T_j, PP_jj = c_j
+    }
+}
+
+struct LddArgs {
+    const uint8_t* rows;
+    int64_t pitch;
+    const uint4* nab;               // mask bytes, 16 individuals per element, steps * 8 elements
+    int64_t N, M, B, nonas;
+    int64_t steps, seg_steps;       // K-steps of 128 individuals in all; per int32 segment (SEGMENTED only)
+    int64_t nrg, nrge, I0;          // 64-marker row groups; groups of EDGE markers; the first of those of this launch
+    const int64_t *cnt, *tsum;
+    const double* xd;               // fl(X_jj): 0 = monomorphic
+    const int* chrom;
+    int adjusted;
+    double nm2;
+    int D;
+    int64_t Mp;
+    double* part;
+    int* pcnt;
+    int64_t j0, nj;
+    double* band;
+};
+
+template <bool UNIFORM, int EDGE, int EP, bool SEGMENTED>
+__global__ __launch_bounds__(256) void k_ldd_block(const LddArgs a) {
+    constexpr int T = EDGE / 16;                    // 16-marker tiles per side
+    constexpr int TW = EDGE / 32;                   // ... per wave and side
+    constexpr int F = EDGE / 64;                    // 64-marker row groups per side
+    constexpr int NPL = UNIFORM ? 1 : 2;            // planes per side: V (and P)
+    constexpr int NP = UNIFORM ? 1 : 4;             // products
+    constexpr int PIECES = 2 * EDGE * 8 / 256;      // 16-byte pieces per thread and K-step: the first half of them of side I
+    // operand images of one K-step: [side: I, J][plane V, P][half of 64 individuals][16-marker tile][lane] x 16 bytes; the scores
+    // epilogue reuses the space for a sub-block's 64 x 64 values of f(r^2)
+    constexpr int OP_BYTES = 2 * NPL * 2 * T * 64 * 16, EP_BYTES = 64 * LD_PITCH * 8;
+    __shared__ __attribute__((aligned(16))) char lds[EP == EP_SCORES && EP_BYTES > OP_BYTES ? EP_BYTES : OP_BYTES];
+    v4i* op = reinterpret_cast<v4i*>(lds);
+    const int64_t I = a.I0 + blockIdx.x, J = I + blockIdx.y;
+    if (I >= a.nrge || J >= a.nrge) return;         // (uniform over the workgroup)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int kp = tid & 7;                         // this thread's 16 individuals of a K-step: half kp >> 2, lane group kp & 3
+    v4i acc[NP][TW][TW];
+    int64_t tot[SEGMENTED ? NP : 1][SEGMENTED ? TW : 1][SEGMENTED ? TW : 1][4];
+#pragma unroll
+    for (int p = 0; p < NP; p++)
+#pragma unroll
+        for (int i = 0; i < TW; i++)
+#pragma unroll
+            for (int j = 0; j < TW; j++) {
+                acc[p][i][j] = v4i{0, 0, 0, 0};
+                if (SEGMENTED)
+#pragma unroll
+                    for (int v = 0; v < 4; v++) tot[p][i][j][v] = 0;
+            }
+    // piece i of this thread: side i / (PIECES / 2), marker (tid >> 3) + 32 (i % (PIECES / 2)) of the side's group.  A marker past the
+    // last re-reads it: its sums are never used.
+    const uint8_t* src[PIECES];
+    int dst[PIECES];
+#pragma unroll
+    for (int i = 0; i < PIECES; i++) {
+        const int side = i / (PIECES / 2), row = (tid >> 3) + 32 * (i % (PIECES / 2));
+        int64_t m = (side ? J : I) * EDGE + row;
+        if (m >= a.M) m = a.M - 1;
+        src[i] = a.rows + m * a.pitch + 16 * kp;
+        dst[i] = ((side * NPL * 2 + (kp >> 2)) * T + (row >> 4)) * 64 + (row & 15) + 16 * (kp & 3);
+    }
+    uint4 o[PIECES], nm;
+    // the pitch is a multiple of 64, not of 128: the second half of the last K-step may lie past the row (a piece is inside or outside
+    // as a whole).  Zeros stand in; the mask bytes there are zeros too.
+    auto fetch = [&](int64_t st) {
+        const int64_t k0 = st * 128;
+        const bool in = k0 + 16 * kp < a.pitch;
+#pragma unroll
+        for (int i = 0; i < PIECES; i++) o[i] = in ? *reinterpret_cast<const uint4*>(src[i] + k0) : uint4{0u, 0u, 0u, 0u};
+        nm = a.nab[st * 8 + kp];
+    };
+    auto flush = [&]() {
+#pragma unroll
+        for (int p = 0; p < NP; p++)
+#pragma unroll
+            for (int i = 0; i < TW; i++)
+#pragma unroll
+                for (int j = 0; j < TW; j++)
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        tot[SEGMENTED ? p : 0][SEGMENTED ? i : 0][SEGMENTED ? j : 0][v] += acc[p][i][j][v];
+                        acc[p][i][j][v] = 0;
+                    }
+    };
+    fetch(0);
+    int64_t left = a.seg_steps;                      // K-steps until the int32 sums are flushed (SEGMENTED)
+    for (int64_t st = 0; st < a.steps; st++) {
+#pragma unroll
+        for (int i = 0; i < PIECES; i++) {
+            const bool jside = i >= PIECES / 2;
+            const uint32_t ow[4] = {o[i].x, o[i].y, o[i].z, o[i].w}, mw[4] = {nm.x, nm.y, nm.z, nm.w};
+            v4i V, P;
+#pragma unroll
+            for (int d = 0; d < 4; d++) {
+                const uint32_t x = ow[d] ^ LDD_BIAS;
+                if (UNIFORM) V[d] = (int)(jside ? x & mw[d] : x);
+                else {
+                    const uint32_t pm = jside ? ldd_present(ow[d]) & mw[d] : ldd_present(ow[d]);
+                    V[d] = (int)(x & pm);
+                    P[d] = (int)(pm & 0x01010101u);
+                }
+            }
+            op[dst[i]] = V;
+            if constexpr (!UNIFORM) op[dst[i] + 2 * T * 64] = P;
+        }
+        if (st + 1 < a.steps) fetch(st + 1);
+        __syncthreads();
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            v4i Vi[TW], Vj[TW], Pi[UNIFORM ? 1 : TW], Pj[UNIFORM ? 1 : TW];
+#pragma unroll
+            for (int t = 0; t < TW; t++) {
+                const int si = ((0 * NPL * 2 + h) * T + wr * TW + t) * 64 + lane, sj = ((1 * NPL * 2 + h) * T + wc * TW + t) * 64 + lane;
+                Vi[t] = op[si];
+                Vj[t] = op[sj];
+                if constexpr (!UNIFORM) {
+                    Pi[t] = op[si + 2 * T * 64];
+                    Pj[t] = op[sj + 2 * T * 64];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < TW; i++)
+#pragma unroll
+                for (int j = 0; j < TW; j++) {
+                    acc[0][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vi[i], Vj[j], acc[0][i][j], 0, 0, 0);               // VV
+                    if constexpr (!UNIFORM) {
+                        acc[1][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Vi[i], Pj[j], acc[1][i][j], 0, 0, 0);   // VP_ik = sum V_ni P_nk
+                        acc[2][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Pi[i], Vj[j], acc[2][i][j], 0, 0, 0);   // VP_ki
+                        acc[3][i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(Pi[i], Pj[j], acc[3][i][j], 0, 0, 0);   // PP
+                    }
+                }
+        }
+        if (SEGMENTED && --left == 0) {
+            flush();
+            left = a.seg_steps;
+        }
+        __syncthreads();
+    }
+    if (SEGMENTED) flush();
+    // Epilogue, one 64 x 64 sub-block (Is, Js) at a time.  Register v of tile (i, j) of this lane is the entry of row
+    // 16 (TW wr + i) + 4 (lane >> 4) + v, column 16 (TW wc + j) + (lane & 15) of the block: with EDGE = 128 wave 2 sa + sb holds the whole
+    // sub-block (sa, sb), with EDGE = 64 the four waves share the one there is.
+    double* fl = reinterpret_cast<double*>(lds);
+    for (int sb = 0; sb < F * F; sb++) {
+        const int64_t Is = I * F + sb / F, Js = J * F + sb % F;
+        if (Js < Is || Js - Is > a.D || Js >= a.nrg) continue;       // (uniform over the workgroup; Js < Is: the mirror image holds it)
+        if (F == 1 || wave == sb) {
+            // (rows outside, columns inside: a row's c, T, X and chromosome are loaded once, those of the TW columns stay in registers)
+#pragma unroll
+            for (int i = 0; i < TW; i++)
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    const int il = (16 * (TW * wr + i) + 4 * (lane >> 4) + v) & 63;
+                    const int64_t m = Is * 64 + il;
+                    const bool min_ = m < a.M;
+                    const int64_t cm = min_ ? a.cnt[m] : 0, tm = min_ ? a.tsum[m] : 0;
+                    const double xm = min_ ? a.xd[m] : 0.0;
+                    const int chi = min_ && a.chrom ? a.chrom[m] : 0;
+#pragma unroll
+                    for (int j = 0; j < TW; j++) {
+                        const int kl = (16 * (TW * wc + j) + (lane & 15)) & 63;
+                        const int64_t k = Js * 64 + kl;
+                        const bool kin = k < a.M;
+                        const int64_t ck = kin ? a.cnt[k] : 0, tk = kin ? a.tsum[k] : 0;
+                        const double xk = kin ? a.xd[k] : 0.0;
+                        const int chk = kin && a.chrom ? a.chrom[k] : 0;
+                        const int64_t dist = k - m;
+                        const bool inband = min_ && kin && dist <= a.B && -dist <= a.B && chi == chk;
+                        const bool poly = xm != 0.0 && xk != 0.0;
+                        double r = 0.0;
+                        if (inband && poly) {
+                            if (m == k) r = 1.0;
+                            else {
+                                int64_t s[4];
+#pragma unroll
+                                for (int p = 0; p < NP; p++)
+                                    s[p] = SEGMENTED ? tot[SEGMENTED ? p : 0][SEGMENTED ? i : 0][SEGMENTED ? j : 0][v] : (int64_t)acc[p][i][j][v];
+                                // UNIFORM: P_j = na for every marker, so VP_jk = T_j, VP_kj = T_k and PP = nonas
+                                double x;
+                                if constexpr (UNIFORM) x = ldd_x(cm, ck, tm, tk, s[0], tm, tk, a.nonas);
+                                else x = ldd_x(cm, ck, tm, tk, s[0], s[1], s[2], s[3]);
+                                r = x / sqrt(xm * xk);
+                            }
+                        }
+                        if (EP == EP_BAND) {
+                            if (inband) {
+                                const int64_t w = 2 * a.B + 1;
+                                if (m >= a.j0 && m < a.j0 + a.nj) a.band[(m - a.j0) * w + a.B + dist] = r;
+                                if (Is != Js && k >= a.j0 && k < a.j0 + a.nj) a.band[(k - a.j0) * w + a.B - dist] = r;     // the mirror image
+                            }
+                        } else {
+                            fl[il * LD_PITCH + kl] = inband && poly && m != k ? ld_f(r, a.adjusted, a.nm2) : __builtin_nan("");
+                        }
+                    }
+                }
+        }
+        if (EP != EP_SCORES) continue;
+        __syncthreads();
+        // rows of Is summed over the columns in ascending k (threads 0..63); columns of Js over the rows in ascending order (64..127)
+        if (tid < 128 && (tid < 64 || Is != Js)) {
+            const bool col = tid >= 64;
+            const int e = tid & 63;
+            double s = 0.0;
+            int n = 0;
+            for (int t = 0; t < 64; t++) {
+                const double f = col ? fl[t * LD_PITCH + e] : fl[e * LD_PITCH + t];
+                if (f == f) {
+                    s += f;
+                    n++;
+                }
+            }
+            const int64_t m = (col ? Js : Is) * 64 + e;
+            const int64_t slot = col ? a.D - (Js - Is) : a.D + (Js - Is);
+            a.part[slot * a.Mp + m] = s;
+            a.pcnt[slot * a.Mp + m] = n;
+        }
+        __syncthreads();
+    }
+}
+
 // device scratch of one call: freed when the call returns, however it returns
 struct Scratch {
     std::vector<void*> ptrs;
@@ -409,8 +746,22 @@ void gvp::gram(hipStream_t s, const void* lay, int layout, int64_t nkb, const ui
     else hipLaunchKernelGGL((k_ld_block<2, EP_GRAM>), grid, dim3(256), 0, s, a);
 }
 
+// gv_set_ld_dosage is on and compact dosage data are resident: the section-17 kernels answer (8-bit codes) or refuse (16-bit codes)
+static bool ld_dosage(const gv_ctx* c) { return c->ld_dosage && c->dense.resident && c->dense.bits != 0; }
+
 // what both entry points check
 static int ld_check(gv_ctx* c, const char* who, int64_t window) {
+    if (ld_dosage(c)) {
+        if (c->dense.bits != 8)
+            return fail(c, "%s: gv_set_ld_dosage covers 8-bit codes only: the resident data are 16-bit codes (their hi / lo byte split is not built)", who);
+        if (!c->mask2) return fail(c, "%s: the phenotype mask must be set first (gv_set_mask)", who);
+        if (c->N > LD_N_MAX)
+            return fail(c, "%s: N = %lld exceeds %lld, the most individuals whose centred products fit the 128-bit integers", who, (long long)c->N,
+                        (long long)LD_N_MAX);
+        if (window < 1 || window > LD_WINDOW_MAX)
+            return fail(c, "%s: window must be in [1, %lld] markers (%lld was passed)", who, (long long)LD_WINDOW_MAX, (long long)window);
+        return 0;
+    }
     if (planes_check(c, who, "LD is computed from 2-bit genotypes only")) return 1;
     if (window < 1 || window > LD_WINDOW_MAX) return fail(c, "%s: window must be in [1, %lld] markers (%lld was passed)", who, (long long)LD_WINDOW_MAX, (long long)window);
     return 0;
@@ -423,9 +774,126 @@ static double ld_entries(int64_t M, int64_t B, int64_t j0, int64_t nj) {
     return e;
 }
 
+// ld_run for 8-bit dosage codes (section 17)
+template <bool UNIFORM, int EDGE>
+static void ldd_launch(hipStream_t s, dim3 grid, const LddArgs& a, bool band, bool seg) {
+    if (band) {
+        if (seg) hipLaunchKernelGGL((k_ldd_block<UNIFORM, EDGE, EP_BAND, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_ldd_block<UNIFORM, EDGE, EP_BAND, false>), grid, dim3(256), 0, s, a);
+    } else {
+        if (seg) hipLaunchKernelGGL((k_ldd_block<UNIFORM, EDGE, EP_SCORES, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_ldd_block<UNIFORM, EDGE, EP_SCORES, false>), grid, dim3(256), 0, s, a);
+    }
+}
+
+static int ldd_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int adjusted, double* l2, double* npairs, int64_t j0, int64_t nj,
+                   double* band) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int64_t M = c->M, nrg = (M + 63) / 64;
+    const int D = (int)((B + 63) / 64);
+    const bool uniform = !dosage_na_kernels(c);
+    const int edge = uniform ? c->ld_dosage_edge : 64, F = edge / 64;
+    Scratch w;
+    LddArgs a{};
+    a.rows = reinterpret_cast<const uint8_t*>(c->dense.rows);
+    a.pitch = c->dense.pitch;
+    a.N = c->N;
+    a.M = M;
+    a.B = B;
+    a.nonas = c->nonas;
+    // THE place that cuts the K-segments of k_ldd_block (the invariant: next to LD_N_MAX)
+    a.steps = (c->N + LDD_KSTEP - 1) / LDD_KSTEP;
+    a.seg_steps = std::max<int64_t>(std::min<int64_t>(c->dosage_seg, gvdm::SEG_MAX) / LDD_KSTEP, 1);
+    const bool seg = a.steps > a.seg_steps;
+    a.nrg = nrg;
+    a.nrge = (M + edge - 1) / edge;
+    a.adjusted = adjusted;
+    a.nm2 = (double)c->nonas - 2.0;
+    a.D = D;
+    a.Mp = nrg * 64;
+    a.j0 = j0;
+    a.nj = nj;
+    uint32_t* nab = nullptr;
+    int64_t *cnt = nullptr, *tsum = nullptr, *vvd = nullptr;
+    double* xd = nullptr;
+    int* dchrom = nullptr;
+    double *dl2 = nullptr, *dnp = nullptr;
+    const size_t nband = band ? (size_t)nj * (size_t)(2 * B + 1) : 0, nslots = (size_t)(2 * D + 1);
+    const int64_t nwords = std::max<int64_t>(a.steps, 1) * (LDD_KSTEP / 4);
+#define LDALLOC(p, n)                                                                                                          \
+    do {                                                                                                                       \
+        if (w.get(&p, n) != hipSuccess) {                                                                                      \
+            (void)hipGetLastError();                                                                                           \
+            return fail(c, "%s: cannot allocate %zu bytes of device scratch (%zu already held by this call)", who, sizeof(*p) * (size_t)(n), w.bytes); \
+        }                                                                                                                      \
+    } while (0)
+    LDALLOC(nab, (size_t)nwords);
+    LDALLOC(cnt, (size_t)M);
+    LDALLOC(tsum, (size_t)M);
+    LDALLOC(vvd, (size_t)M);
+    LDALLOC(xd, (size_t)M);
+    if (chrom) LDALLOC(dchrom, (size_t)M);
+    if (band) LDALLOC(a.band, nband);
+    else {
+        LDALLOC(a.part, nslots * (size_t)a.Mp);
+        LDALLOC(a.pcnt, nslots * (size_t)a.Mp);
+        LDALLOC(dl2, (size_t)M);
+        LDALLOC(dnp, (size_t)M);
+    }
+#undef LDALLOC
+    a.nab = reinterpret_cast<const uint4*>(nab);
+    a.cnt = cnt;
+    a.tsum = tsum;
+    a.xd = xd;
+    a.chrom = dchrom;
+    if (chrom) HIPCHK(c, hipMemcpyAsync(dchrom, chrom, sizeof(int) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    if (band) HIPCHK(c, hipMemsetAsync(a.band, 0, sizeof(double) * nband, c->stream));
+    else {
+        HIPCHK(c, hipMemsetAsync(a.part, 0, sizeof(double) * nslots * (size_t)a.Mp, c->stream));
+        HIPCHK(c, hipMemsetAsync(a.pcnt, 0, sizeof(int) * nslots * (size_t)a.Mp, c->stream));
+    }
+    int64_t blocks = 0;
+    if (M > 0 && (!band || nj > 0)) {
+        hipLaunchKernelGGL(k_ldd_mask, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, c->stream, c->mask2, c->pitch / 4, c->N, nwords, nab);
+        KCHK(c);
+        if (uniform) hipLaunchKernelGGL(k_ldd_diag<false>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, c->stream, a.rows, a.pitch, a.nab, M, cnt, tsum, vvd, xd);
+        else hipLaunchKernelGGL(k_ldd_diag<true>, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, c->stream, a.rows, a.pitch, a.nab, M, cnt, tsum, vvd, xd);
+        KCHK(c);
+        // groups of `edge` markers: (I, I + d) holds the sub-blocks of 64-marker row groups at distances F d - (F - 1) .. F d + (F - 1);
+        // band mode: the groups that hold a requested row, or whose blocks mirror into one
+        const int64_t De = (D + F - 1) / F;
+        const int64_t Ia = band ? std::max<int64_t>(j0 / 64 - D, 0) / F : 0, Ib = band ? (j0 + nj - 1) / 64 / F : a.nrge - 1;
+        a.I0 = Ia;
+        const dim3 grid((unsigned)(Ib - Ia + 1), (unsigned)(De + 1));
+        for (int64_t I = Ia; I <= Ib; I++) blocks += (std::min<int64_t>(De, a.nrge - 1 - I) + 1) * F * F;
+        if (!uniform) ldd_launch<false, 64>(c->stream, grid, a, band != nullptr, seg);
+        else if (edge == 64) ldd_launch<true, 64>(c->stream, grid, a, band != nullptr, seg);
+        else ldd_launch<true, 128>(c->stream, grid, a, band != nullptr, seg);
+        KCHK(c);
+        if (!band) {
+            hipLaunchKernelGGL(k_ld_finish, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, a.part, a.pcnt, (int)nslots, a.Mp, M, xd,
+                               dl2, dnp);
+            KCHK(c);
+        }
+    }
+    if (band) {
+        if (nband) HIPCHK(c, hipMemcpyAsync(band, a.band, sizeof(double) * nband, hipMemcpyDeviceToHost, c->stream));
+    } else if (M > 0) {
+        HIPCHK(c, hipMemcpyAsync(l2, dl2, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+        if (npairs) HIPCHK(c, hipMemcpyAsync(npairs, dnp, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ld_last.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c->ld_last.block_pairs = blocks;
+    c->ld_last.useful_macs = (uniform ? 1.0 : 4.0) * (double)c->N * (band ? ld_entries(M, B, j0, nj) : ld_entries(M, B, 0, M));
+    c->ld_last.scratch_bytes = (double)w.bytes;
+    return 0;
+}
+
 // scores (band == NULL) or the band rows [j0, j0 + nj)
 static int ld_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int adjusted, double* l2, double* npairs, int64_t j0, int64_t nj,
                   double* band) {
+    if (ld_dosage(c)) return ldd_run(c, who, B, chrom, adjusted, l2, npairs, j0, nj, band);
     const auto t0 = std::chrono::steady_clock::now();
     const gvm::Plan& pl = c->plan;
     const int64_t M = c->M, nrg = (M + 63) / 64;
@@ -533,6 +1001,17 @@ int gv_ld_band(gv_ctx* c, int64_t window, const int* chrom, int64_t j0, int64_t 
     if (j0 < 0 || nj < 0 || j0 > c->M || nj > c->M - j0)
         return fail(c, "gv_ld_band: rows [%lld, %lld) are outside the shard's markers [0, %lld)", (long long)j0, (long long)(j0 + nj), (long long)c->M);
     return ld_run(c, "gv_ld_band", window, chrom, 0, nullptr, nullptr, j0, nj, r);
+}
+
+int gv_set_ld_dosage(gv_ctx* c, int on) {
+    NEED(c, on == 0 || on == 1, "gv_set_ld_dosage: on must be 0 or 1");
+    c->ld_dosage = on;
+    return 0;
+}
+
+int gv_get_ld_dosage(const gv_ctx* c, int* on) {
+    if (on) *on = c->ld_dosage;
+    return 0;
 }
 
 int gv_ld_info(gv_ctx* c, gv_ld_stats* info) {

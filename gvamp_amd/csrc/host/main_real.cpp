@@ -174,7 +174,8 @@ int main(int argc, char** argv) {
         if (dataset.get_bimfp() != "" && (sp == 0 || sp == 2)) dataset.pvals_calc_LOCO(z1_hats, y, x1_hats, out_loco);
     } else if (mode == "ldscore") {                                                    // [ext] DESIGN.md section 16
         // LD scores of the markers over --ld-window markers on each side, among the individuals with a phenotype
-        if (type_data != "bed") {
+        const bool ldd = type_data == "dosage8" && opt.get_ld_dosage() == 1;      // [ext] --ld-dosage 1: DESIGN.md section 17
+        if (type_data != "bed" && !ldd) {
             std::cout << "FATAL: --run-mode ldscore works on 2-bit genotypes only, not on --geno-format " << type_data << std::endl;
             return EXIT_FAILURE;
         }
@@ -186,6 +187,10 @@ int main(int argc, char** argv) {
         const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
         need_phen(opt.get_phen_files(), "--phen-files");
         data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, Mt, Mt, 0, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
+        if (ldd && gv_set_ld_dosage(dataset.get_ctx(), 1)) {
+            std::cout << "FATAL: gv_set_ld_dosage: " << gv_last_error(dataset.get_ctx()) << std::endl;
+            return EXIT_FAILURE;
+        }
         const std::vector<std::vector<double>> res = dataset.ld_scores_dev(opt.get_ld_window(), opt.get_ld_adjust() == 1);
         gv_ld_stats st;
         gv_ld_info(dataset.get_ctx(), &st);

@@ -168,6 +168,11 @@ void Options::read_command_line_options(int argc, char** argv) {
             fatal(std::string("FATAL  : option --ld-adjust has to be 0 or 1! (") + a + " was passed)");
         ld_adjust = atoi(a);
     };
+    H["--ld-dosage"] = [&](const char* a) {
+        if (strcmp(a, "0") && strcmp(a, "1"))
+            fatal(std::string("FATAL  : option --ld-dosage has to be 0 or 1! (") + a + " was passed)");
+        ld_dosage = atoi(a);
+    };
     H["--resident-layout"] = [&](const char* a) {      // read by data::open_device (every data object of the run)
         resident_layout = atoi(a);
         setenv("GVAMP_RESIDENT_LAYOUT", a, 1);

@@ -50,13 +50,15 @@
        --store-assoc 0|1 (default 0): after the loop write the whole per-marker association test -- effect, standard  \
        error, t and p, LOO and (with a .bim file) LOCO -- for bed and dosage data;              \
        --run-mode ldscore with --ld-window B (1..8192, default 200) and --ld-adjust 0|1 (default 0): the LD scores of    \
-       the markers over B markers on each side, per chromosome with a .bim file */              \
+       the markers over B markers on each side, per chromosome with a .bim file;                \
+       --ld-dosage 0|1 (default 0): 1 = --run-mode ldscore also accepts --geno-format dosage8 (gv_set_ld_dosage,         \
+       DESIGN.md section 17; with --dosage-missing 1 the code 255 is a missing entry) */                                 \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
     X(int, cg_precond_window, 128) X(std::string, geno_format, "bed") X(double, dosage_scale, 0) \
     X(unsigned int, store_assoc, 0) X(int, dosage_missing, 0) X(std::string, dosage_kernels, "valu")       \
-    X(int, ld_window, 200) X(int, ld_adjust, 0)
+    X(int, ld_window, 200) X(int, ld_adjust, 0) X(int, ld_dosage, 0)
 
 class Options {
 public:

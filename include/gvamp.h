@@ -668,6 +668,24 @@ typedef struct gv_ld_stats {
     double scratch_bytes;        /* device scratch it allocated and released */
 } gv_ld_stats;
 int gv_ld_info(gv_ctx* ctx, gv_ld_stats* info);
+/* ---- LD of 8-bit dosage codes (additions only: GV_ABI_VERSION stays 4) ----------------------------------------
+ * gv_set_ld_dosage(ctx, 1): gv_ld_scores, gv_ld_band and gv_ld_info accept a context whose resident data are 8-bit dosage codes and
+ * whose mask is set.  Per context, default 0, it outlives the dataset; with 0 nothing changes by a bit or by a message.  Marker
+ * statistics are not needed (mave and msig do not enter).  Still refused, each by its own message: 16-bit codes ("16-bit codes"),
+ * methylation data, no mask, and the window / adjusted / band-row checks above.
+ * Definition, in exact integers up to one rounding per quantity.  b_jn = 0 at the reserved code 255 when the codes were uploaded under
+ * gv_set_dosage_missing, 1 otherwise (with the option off 255 is the value 255); P_jn = b_jn na_n, V_jn = (code_jn - 128) P_jn;
+ *   VV_jk = sum V_j V_k, VP_jk = sum V_j P_k, PP_jk = sum P_j P_k, c_j = sum P_j, T_j = sum V_j            (sums over the individuals)
+ *   X_jk = c_j c_k VV_jk - c_j T_k VP_jk - c_k T_j VP_kj + T_j T_k PP_jk     = c_j c_k sum_n (code_j - mu'_j)(code_k - mu'_k) P_j P_k
+ * formed in 128-bit integers and converted to fp64 correctly rounded (a missing entry counts as the mean);
+ *   r_jk = fl(X_jk) / sqrt(fl(X_jj) fl(X_kk)) for j < k, mirrored;  monomorphic iff X_jj == 0 (exact for a constant and for an
+ *   all-missing row);  r_jj = 1 for a polymorphic marker, r_jk = 0 if either marker is monomorphic.
+ * Band, chromosomes, l_j, npairs_j, the adjusted estimator with n = nonas, NaN and 0 for a monomorphic j: as above.  The sums are int32
+ * MFMA sums over at most 131 071 individuals (GV_DOSAGE_MFMA_SEG lowers it) added in int64: no bit depends on the segment length, the
+ * kernel instantiation or the call.  gv_ld_stats.useful_macs counts 1 product where every marker shares the presence pattern na (no
+ * reserved code in the shard), 4 otherwise (or under GV_DOSAGE_NA_KERNELS=1).  N <= 2^29 - 1. */
+int gv_set_ld_dosage(gv_ctx* ctx, int on);
+int gv_get_ld_dosage(const gv_ctx* ctx, int* on);
 
 #ifdef __cplusplus
 }

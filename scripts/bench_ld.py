@@ -4,6 +4,14 @@ MAC/s of both -- 4 products x N x the (j, k) entries delivered (the in-band entr
 Grams); ratio_to_gram is the scores' rate over the Gram build's, i.e. how much of a block each epilogue delivers.  Writes one JSON file.
 
     python scripts/bench_ld.py --N 400000 --M 125000 --out profiles/ld_bench_400k_125k.json
+
+--kind dosage8: gv_ld_scores on 8-bit dosage codes (gv_set_ld_dosage), three contexts holding the same
+gv_synth_dosage_na(seed, 8, 0) codes -- no reserved code among them -- timed alternately in one process: the one-product kernel with a
+block edge of 128 and of 64 markers (GV_LD_DOSAGE_EDGE), and the four-product kernel forced by GV_DOSAGE_NA_KERNELS=1.  Per leg: seconds,
+useful and computed integer MAC/s (computed: every 64 x 64 sub-block the launch multiplied, over the K-steps of 128 individuals) and the
+implied load rate, 2 * EDGE * N bytes per block.
+
+    python scripts/bench_ld.py --kind dosage8 --N 20000 --M 800000 --out profiles/ld_dosage_bench_20000x800000.json
 """
 import argparse
 import json
@@ -20,8 +28,47 @@ def gram_entries(M, W):
     return sum((min((u + 1) * h, M) - max((u - 1) * h, 0)) ** 2 for u in range(0, (M - 1) // h + 2))
 
 
+DOSAGE_LEGS = (("uniform128", dict(GV_LD_DOSAGE_EDGE="128"), 128, 1), ("uniform64", dict(GV_LD_DOSAGE_EDGE="64"), 64, 1),
+               ("forced4", dict(GV_DOSAGE_NA_KERNELS="1"), 64, 4))
+
+
+def dosage8(a):
+    shards = {}
+    for name, env, _, _ in DOSAGE_LEGS:          # the switches are read by gv_create, per context
+        os.environ.update(env)
+        sh = capi.Shard(a.N, a.M)
+        for k in env:
+            del os.environ[k]
+        sh.synth_dosage_na(77, 8, 0)
+        sh.set_ld_dosage(1)
+        assert sh.dosage_info()["na_kernels"] == (name == "forced4")
+        shards[name] = sh
+    rounds = []
+    kpad = (a.N + 127) // 128 * 128
+    for rd in range(a.rounds):
+        row = {"round": rd, "ld": []}
+        for B in a.windows:
+            for name, _, edge, products in DOSAGE_LEGS:
+                shards[name].ld_scores(B)
+                st = shards[name].ld_info()
+                blocks = st["block_pairs"] // (edge // 64) ** 2
+                row["ld"].append(dict(leg=name, window=B, seconds=st["seconds"], products=products, useful_macs=st["useful_macs"],
+                                      useful_macs_per_s=st["useful_macs"] / st["seconds"],
+                                      computed_macs_per_s=products * 4096.0 * st["block_pairs"] * kpad / st["seconds"],
+                                      blocks=blocks, load_bytes_per_s=blocks * 2.0 * edge * a.N / st["seconds"],
+                                      scratch_bytes=st["scratch_bytes"]))
+        rounds.append(row)
+        print(json.dumps(row), flush=True)
+    for sh in shards.values():
+        sh.close()
+    with open(a.out, "w") as f:
+        json.dump(dict(kind="dosage8", N=a.N, M=a.M, rounds=rounds), f)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kind", choices=["bed", "dosage8"], default="bed")
     ap.add_argument("--N", type=int, default=400000)
     ap.add_argument("--M", type=int, default=125000)
     ap.add_argument("--ld-block", type=int, default=64)
@@ -30,6 +77,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
+    if a.kind == "dosage8":
+        return dosage8(a)
     rounds = []
     with capi.Shard(a.N, a.M) as sh:
         sh.synth_bed(77, 5000, ld_block=a.ld_block, ld_ppm=900000)
