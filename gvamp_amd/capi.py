@@ -32,6 +32,7 @@ EXPORTS = [
     "gv_set_dosage_route", "gv_get_dosage_route",
     "gv_ld_scores", "gv_ld_band", "gv_ld_info",
     "gv_set_ld_dosage", "gv_get_ld_dosage",
+    "gv_synth_dosage_ld",
 ]
 
 
@@ -146,6 +147,7 @@ def load():
     L.gv_synth_dosage.argtypes = [vp, C.c_uint64, C.c_int]
     L.gv_set_dosage_missing.argtypes = [vp, C.c_int]
     L.gv_synth_dosage_na.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint32]
+    L.gv_synth_dosage_ld.argtypes = [vp, C.c_uint64, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32]
     L.gv_dosage_info.argtypes = [vp, C.POINTER(DosageStats)]
     L.gv_marker_counts.argtypes = [vp, dp]
     L.gv_set_dosage_route.argtypes = [vp, C.c_int]
@@ -379,6 +381,11 @@ class Shard:
         """the device-generated codes with missing entries that synth.synth_dosage_na(N, M, seed, bits, miss_ppm, S) reproduces on the
         host; turns the missing option on"""
         self._ck(self.L.gv_synth_dosage_na(self.h, seed, bits, miss_ppm))
+
+    def synth_dosage_ld(self, seed, bits, ld_block, ld_ppm, miss_ppm=0):
+        """the device-generated block-correlated codes that synth.synth_dosage_ld(N, M, seed, bits, ld_block, ld_ppm, miss_ppm, S)
+        reproduces on the host; miss_ppm > 0 turns the missing option on"""
+        self._ck(self.L.gv_synth_dosage_ld(self.h, seed, bits, miss_ppm, ld_block, ld_ppm))
 
     def dosage_info(self):
         """gv_dosage_info as a dict: bits, scale, missing (option on), reserved (codes counted at ingest), na_kernels (in use)"""

@@ -307,6 +307,40 @@ __global__ void k_synth_dosage(T* __restrict__ A, int64_t M, int64_t S, int64_t 
     }
 }
 
+// gv_synth_dosage_ld: k_synth_dosage's codes with k_synth_bed's block latent.  The markers of a block of ld_block consecutive markers
+// share, per individual, one latent hash lat; an entry takes its two allele draws (the two low 16-bit fields) from lat with probability
+// ld_thr / 2^32 -- decided by the high half of rs, a second hash of the entry -- and from its own hash r otherwise, and pushes them through
+// the marker's own frequency: co-monotone genotypes inside a block, independent blocks.  The jitter always comes from the high half of
+// r.  The code is clamped one below the reserved code; a THIRD hash below miss_thr replaces it by the reserved code, so that
+// missingness is independent of the LD draw.  Integer arithmetic only (gvamp_amd/synth.py:synth_dosage_ld, bit for bit).
+template <typename T>
+__global__ void k_synth_dosage_ld(T* __restrict__ A, int64_t M, int64_t S, int64_t N, int64_t pitch, uint64_t seed, uint64_t miss_thr,
+                                  uint64_t ld_block, uint64_t ld_thr) {
+    constexpr int BITS = 8 * (int)sizeof(T);
+    for (int64_t m = blockIdx.x; m < M; m += gridDim.x) {
+        const uint64_t g = (uint64_t)(S + m);
+        const uint64_t hm = splitmix64(seed ^ (g * 0xD1342543DE82EF95ull));
+        const uint64_t base = splitmix64(hm + 0x632BE59BD9B4E019ull);
+        const uint64_t maf = 655ull + hm % 32113ull;
+        const uint64_t lbase = splitmix64(seed ^ ((g / ld_block) * 0xA24BAED4963EE407ull) ^ 0x5851F42D4C957F2Dull);
+        T* row = A + m * pitch;
+        for (int64_t j = threadIdx.x; j < pitch; j += blockDim.x) {
+            uint64_t v = 0;
+            if (j < N) {
+                const uint64_t r = splitmix64(base + (uint64_t)j);
+                const uint64_t rs = splitmix64(r ^ 0x9FB21C651E98DF25ull);
+                const uint64_t al = (rs >> 32) < ld_thr ? splitmix64(lbase + (uint64_t)j) : r;
+                const uint64_t geno = ((al & 0xFFFFull) < maf ? 1ull : 0ull) + (((al >> 16) & 0xFFFFull) < maf ? 1ull : 0ull);
+                const uint64_t jit = (((r >> 32) & 0xFFFFull) * (r >> 48)) >> 16;
+                v = geno * (3ull << (BITS - 3)) + (jit >> (18 - BITS));
+                if (v >= Code<T>::RESERVED) v = Code<T>::RESERVED - 1;
+                if ((splitmix64(rs ^ 0x2545F4914F6CDD1Dull) >> 32) < miss_thr) v = Code<T>::RESERVED;
+            }
+            row[j] = (T)v;
+        }
+    }
+}
+
 // ---- marker statistics in code units: mu' = (sum_present b) / nonas with the integer sum exact, q = sum_present (b - mu')^2 in a
 // second pass; mave = scale mu', msig = 1 if q == 0 else (scale sqrt(q / (nonas - 1)))^-alpha_scale.  mu' is kept for the products.
 // NA: b = 0 at the reserved code.  A second integer sum cnt = sum b na rides the butterfly of the first; mu' = (sum code b na) / cnt, 0
@@ -752,6 +786,15 @@ void synth(hipStream_t s, const View& v, int64_t S, uint64_t seed, uint64_t miss
         typedef typename decltype(kind)::type T;
         hipLaunchKernelGGL((k_synth_dosage<T, decltype(kind)::na>), g, dim3(256), 0, s, (T*)v.rows, M, S, N, pitch, seed, miss_thr);
     });
+}
+
+void synth_ld(hipStream_t s, const View& v, int64_t S, uint64_t seed, uint64_t miss_thr, uint64_t ld_block, uint64_t ld_thr) {
+    if (v.M <= 0) return;
+    const dim3 g((unsigned)(v.M < 16384 ? v.M : 16384));
+    if (v.bits == 8)
+        hipLaunchKernelGGL(k_synth_dosage_ld<uint8_t>, g, dim3(256), 0, s, (uint8_t*)v.rows, v.M, S, v.N, v.pitch, seed, miss_thr, ld_block, ld_thr);
+    else
+        hipLaunchKernelGGL(k_synth_dosage_ld<uint16_t>, g, dim3(256), 0, s, (uint16_t*)v.rows, v.M, S, v.N, v.pitch, seed, miss_thr, ld_block, ld_thr);
 }
 
 void stats(hipStream_t s, const View& v, const uint32_t* mask2, double nonas, double alpha_scale, double* mave) {

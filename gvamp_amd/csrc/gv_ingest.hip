@@ -319,6 +319,7 @@ static int dense_begin(gv_ctx* c, int bits, double scale, DenseClock* clk) {
     free_layouts(c);
     if (c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
     c->have_raw = c->have_stripes = c->have_stats = false;
+    pc_invalidate(c, false);        // (window Grams belong to the data set they were built from)
     c->ingest_bytes = 0;
     DenseData& d = c->dense;
     dense_release(c, bits == d.bits && d.rows);      // rows of this width are held: their allocation is used again
@@ -480,12 +481,13 @@ int gv_upload_dosage_file(gv_ctx* c, const char* path, int64_t offset, int bits,
     return dense_upload_file(c, "gv_upload_dosage_file", path, offset, bits, scale);
 }
 
-static int synth_dosage(gv_ctx* c, uint64_t seed, int bits, bool na, uint64_t miss_thr) {
+static int synth_dosage(gv_ctx* c, uint64_t seed, int bits, bool na, uint64_t miss_thr, uint64_t ld_block = 0, uint64_t ld_thr = 0) {
     DenseClock clk;
     if (dense_begin(c, bits, bits == 8 ? 1.0 / 127.0 : 1.0 / 16384.0, &clk)) return 1;
     gvd::View v = dense_view(c);
     v.na = na;      // (of the generator: nothing is resident yet)
-    gvd::synth(c->stream, v, c->S, seed, miss_thr);
+    if (ld_block) gvd::synth_ld(c->stream, v, c->S, seed, miss_thr, ld_block, ld_thr);
+    else gvd::synth(c->stream, v, c->S, seed, miss_thr);
     count_reserved(c, 0, c->M);
     KCHK(c);
     return dense_finish(c, clk);
@@ -503,11 +505,22 @@ int gv_synth_dosage_na(gv_ctx* c, uint64_t seed, int bits, uint32_t miss_ppm) {
     return synth_dosage(c, seed, bits, true, ((uint64_t)miss_ppm << 32) / 1000000ull);
 }
 
+int gv_synth_dosage_ld(gv_ctx* c, uint64_t seed, int bits, uint32_t miss_ppm, uint32_t ld_block, uint32_t ld_ppm) {
+    if (dosage_args(c, "gv_synth_dosage_ld", bits, 1.0)) return 1;
+    NEED(c, miss_ppm <= 1000000u, "gv_synth_dosage_ld: miss_ppm above 1000000");
+    NEED(c, ld_ppm <= 1000000u, "gv_synth_dosage_ld: ld_ppm is a probability in 1e-6");
+    NEED(c, ld_block >= 1, "gv_synth_dosage_ld: ld_block must be at least 1 marker");
+    if (miss_ppm) c->dosage_missing = true;      // (reserved codes are written: they are missing entries, as gv_synth_dosage_na's)
+    const uint64_t lt = ((uint64_t)ld_ppm << 32) / 1000000ull;
+    return synth_dosage(c, seed, bits, false, ((uint64_t)miss_ppm << 32) / 1000000ull, ld_block, lt > 0xFFFFFFFFull ? 0xFFFFFFFFull : lt);
+}
+
 int gv_set_dosage_missing(gv_ctx* c, int on) {
     const bool want = on != 0;
     if (c->dense.resident && c->dense.bits && want != c->dense.na)
         return fail(c, "gv_set_dosage_missing: %d-bit codes are resident and were uploaded with the option %s; their statistics would be "
                        "stale -- set it before the upload", c->dense.bits, c->dense.na ? "on" : "off");
+    if (want != c->dosage_missing) pc_invalidate(c, false);
     c->dosage_missing = want;
     return 0;
 }

@@ -344,6 +344,8 @@ struct View {
 };
 // the device-generated matrix of the rows [S, S + M); miss_thr: codes with na set only (gv_synth_dosage_na)
 void synth(hipStream_t s, const View& v, int64_t S, uint64_t seed, uint64_t miss_thr = 0);
+// gv_synth_dosage_ld (codes only): block-correlated columns, ld_block >= 1 markers per block, ld_thr = ld_ppm 2^32 / 10^6
+void synth_ld(hipStream_t s, const View& v, int64_t S, uint64_t seed, uint64_t miss_thr, uint64_t ld_block, uint64_t ld_thr);
 // marker statistics: mave, v.msig (codes: v.centre and, with na, v.cnt beside them; fp64: mave is v.centre)
 void stats(hipStream_t s, const View& v, const uint32_t* mask2, double nonas, double alpha_scale, double* mave);
 // out[m] = msig[m] sum_j (x[m][j] - mave[m]) p[j] * scale, then tau * out + gam2 * addx when addx != NULL (nv = 1 or 2 vectors)
@@ -387,6 +389,9 @@ int64_t num_windows(int64_t S, int64_t M, int W);
 // out[u - first_window] = the W x W Gram of every window, zero beyond its clipped length (memset and one kernel on s)
 void gram(hipStream_t s, const void* lay, int layout, int64_t nkb, const uint32_t* mask2, int64_t P4, int64_t N, int64_t S, int64_t M,
           int W, const double* mave, const double* msig, double* out);
+// the same for resident 8-bit dosage codes under gv_set_ld_dosage: out = c's pc_nu x W x W device buffer, W = pc_W;
+// scratch of its own, freed on return; returns after the kernels have run
+int gram_dosage(gv_ctx* c, double* out);
 int factor(hipStream_t s, const double* gram, int W, int64_t S, int64_t M, double tau, double gam2, double diag, double* inv, int* fail);
 void apply(hipStream_t s, const double* inv, int W, int64_t S, int64_t M, const double* r, double* z);
 }  // namespace gvp
@@ -442,6 +447,10 @@ void pc_invalidate(gv_ctx* c, bool free_mem);
 // what the exact blocks of A^T A need (gv_ld.hip): not compact dosage data, not dense, a re-encoded layout, marker statistics and mask
 // words, N within the int32 sums -- refused by message under the caller's name `who`, `why` being its reason for wanting genotypes
 int planes_check(gv_ctx* c, const char* who, const char* why);
+// gv_set_ld_dosage is on and compact dosage data are resident: the section-17 / 18 kernels answer (8-bit codes) or refuse (16-bit codes)
+inline bool ld_dosage(const gv_ctx* c) { return c->ld_dosage && c->dense.resident && c->dense.bits != 0; }
+// ... and what the Gram build needs of them: 8-bit codes, the mask, marker statistics, N within the 128-bit epilogue
+int gram_dosage_check(gv_ctx* c, const char* who);
 // compact dense data: the missing-aware kernels run when the codes were uploaded with gv_set_dosage_missing on AND the ingest counted a
 // reserved code in this shard (a shard without one gets the same bits from the plain kernels) or GV_DOSAGE_NA_KERNELS=1 forces them
 inline bool dosage_na_kernels(const gv_ctx* c) { return c->dense.na && (c->dense.reserved != 0 || c->force_na_kernels); }

@@ -13,7 +13,8 @@
 //   k_ld_finish  l_j = 1 + the 2D + 1 block partials of marker j in ascending block order
 // Integer sums, then a fixed fp64 order, no atomics: the results do not depend on the layout, the kernel mode or the launch.
 // Second part (k_ldd_*, ldd_run): the same two entry points on resident 8-bit dosage codes, opt-in (gv_set_ld_dosage; section 17) -- the
-// centred product of two markers in exact 128-bit integers, one correctly rounded conversion.
+// centred product of two markers in exact 128-bit integers, one correctly rounded conversion.  The same block kernel with a Gram epilogue
+// builds the preconditioner's window Grams of 8-bit codes (gvp::gram_dosage; section 18).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -164,7 +165,9 @@ __device__ __forceinline__ double ld_f(double r, int adjusted, double nm2) {
 // G_u[m - lo_u][k - lo_u] = g and, if mirror, G_u[k - lo_u][m - lo_u] = gt in every half-grid window u = [(u - 1) H, (u + 1) H) that holds
 // the local markers m and k: with am = (S + m) / H and ak = (S + k) / H, u = am and am + 1 if am == ak, the larger if they differ by 1.
 // (lo_u <= m, k < lo_u + W because both markers lie in the window; u0 <= am and ak + 1 < u0 + nu for m, k < M.)
-__device__ __forceinline__ void ld_gram_store(const LdArgs& a, int64_t m, int64_t k, double g, bool mirror, double gt) {
+// (A: LdArgs or LddArgs -- the window fields S, u0, nu, W, hs, gram of either)
+template <class A>
+__device__ __forceinline__ void ld_gram_store(const A& a, int64_t m, int64_t k, double g, bool mirror, double gt) {
     const int64_t am = (a.S + m) >> a.hs, ak = (a.S + k) >> a.hs;
     for (int64_t u = max(am, ak); u <= min(am, ak) + 1; u++) {
         if (u < a.u0 || u >= a.u0 + a.nu) continue;
@@ -472,7 +475,18 @@ struct LddArgs {
     int* pcnt;
     int64_t j0, nj;
     double* band;
+    const double* msig;             // Gram: the marker statistics; s_j = msig_j * wscale
+    double wscale, inv_n;           // Gram: the factor between codes and values; 1 / N
+    int64_t S, u0, nu;              // Gram: as LdArgs
+    int W, hs;
+    double* gram;
 };
+
+// THE Gram entry of section 18 from fl(X_jk): G_jk = ((s_j s_k) / N) (fl(X_jk) / (c_j c_k)), s = msig * scale, every operation in fp64 in
+// this order.  Each product is commutative and X_jk = X_kj exactly, so G_jk and G_kj are the same bits whichever marker is named first.
+__device__ __forceinline__ double ldd_g(double x, int64_t cj, int64_t ck, double sj, double sk, double inv_n) {
+    return ((sj * sk) * inv_n) * (x / ((double)cj * (double)ck));
+}
 
 template <bool UNIFORM, int EDGE, int EP, bool SEGMENTED>
 __global__ __launch_bounds__(256) void k_ldd_block(const LddArgs a) {
@@ -619,6 +633,22 @@ __global__ __launch_bounds__(256) void k_ldd_block(const LddArgs a) {
                         const int64_t k = Js * 64 + kl;
                         const bool kin = k < a.M;
                         const int64_t ck = kin ? a.cnt[k] : 0, tk = kin ? a.tsum[k] : 0;
+                        if constexpr (EP == EP_GRAM) {
+                            // every entry of the sub-block, the diagonal included (a diagonal block holds both orders itself); a marker
+                            // without a present individual keeps the zeros the Grams were cleared to
+                            if (min_ && kin && cm != 0 && ck != 0) {
+                                int64_t s[4];
+#pragma unroll
+                                for (int p = 0; p < NP; p++)
+                                    s[p] = SEGMENTED ? tot[SEGMENTED ? p : 0][SEGMENTED ? i : 0][SEGMENTED ? j : 0][v] : (int64_t)acc[p][i][j][v];
+                                double x;
+                                if constexpr (UNIFORM) x = ldd_x(cm, ck, tm, tk, s[0], tm, tk, a.nonas);
+                                else x = ldd_x(cm, ck, tm, tk, s[0], s[1], s[2], s[3]);
+                                const double g = ldd_g(x, cm, ck, a.msig[m] * a.wscale, a.msig[k] * a.wscale, a.inv_n);
+                                ld_gram_store(a, m, k, g, Is != Js, g);
+                            }
+                            continue;
+                        }
                         const double xk = kin ? a.xd[k] : 0.0;
                         const int chk = kin && a.chrom ? a.chrom[k] : 0;
                         const int64_t dist = k - m;
@@ -746,9 +776,6 @@ void gvp::gram(hipStream_t s, const void* lay, int layout, int64_t nkb, const ui
     else hipLaunchKernelGGL((k_ld_block<2, EP_GRAM>), grid, dim3(256), 0, s, a);
 }
 
-// gv_set_ld_dosage is on and compact dosage data are resident: the section-17 kernels answer (8-bit codes) or refuse (16-bit codes)
-static bool ld_dosage(const gv_ctx* c) { return c->ld_dosage && c->dense.resident && c->dense.bits != 0; }
-
 // what both entry points check
 static int ld_check(gv_ctx* c, const char* who, int64_t window) {
     if (ld_dosage(c)) {
@@ -776,8 +803,13 @@ static double ld_entries(int64_t M, int64_t B, int64_t j0, int64_t nj) {
 
 // ld_run for 8-bit dosage codes (section 17)
 template <bool UNIFORM, int EDGE>
-static void ldd_launch(hipStream_t s, dim3 grid, const LddArgs& a, bool band, bool seg) {
-    if (band) {
+static void ldd_launch(hipStream_t s, dim3 grid, const LddArgs& a, int ep, bool seg) {
+    if (ep == EP_GRAM) {        // (EDGE = 64 only: the build runs once per data set and reaches d <= 2 row groups)
+        if constexpr (EDGE == 64) {
+            if (seg) hipLaunchKernelGGL((k_ldd_block<UNIFORM, 64, EP_GRAM, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_ldd_block<UNIFORM, 64, EP_GRAM, false>), grid, dim3(256), 0, s, a);
+        }
+    } else if (ep == EP_BAND) {
         if (seg) hipLaunchKernelGGL((k_ldd_block<UNIFORM, EDGE, EP_BAND, true>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_ldd_block<UNIFORM, EDGE, EP_BAND, false>), grid, dim3(256), 0, s, a);
     } else {
@@ -786,13 +818,24 @@ static void ldd_launch(hipStream_t s, dim3 grid, const LddArgs& a, bool band, bo
     }
 }
 
+// gram != NULL (the preconditioner's build, gvp::gram_dosage): the W x W Grams of the pc_nu half-grid windows into that DEVICE buffer
+// instead -- no band, no scores, no copy to the host, gv_ld_info untouched
 static int ldd_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int adjusted, double* l2, double* npairs, int64_t j0, int64_t nj,
-                   double* band) {
+                   double* band, double* gram = nullptr) {
     const auto t0 = std::chrono::steady_clock::now();
     const int64_t M = c->M, nrg = (M + 63) / 64;
-    const int D = (int)((B + 63) / 64);
+    const int W = c->pc_W;
+    const int64_t u0 = gvp::first_window(c->S, W), nu = gvp::num_windows(c->S, M, W);
+    int D = (int)((B + 63) / 64);
+    if (gram) {     // blocks (I, I + d) up to the most row groups that one window's markers [lo, hi) straddle, as gvp::gram
+        D = 0;
+        for (int64_t u = u0; u < u0 + nu; u++) {
+            const int64_t lo = std::max((u - 1) * (W / 2), c->S) - c->S, hi = std::min((u + 1) * (W / 2), c->S + M) - c->S;
+            D = std::max(D, (int)((hi - 1) / 64 - lo / 64));
+        }
+    }
     const bool uniform = !dosage_na_kernels(c);
-    const int edge = uniform ? c->ld_dosage_edge : 64, F = edge / 64;
+    const int edge = uniform && !gram ? c->ld_dosage_edge : 64, F = edge / 64;
     Scratch w;
     LddArgs a{};
     a.rows = reinterpret_cast<const uint8_t*>(c->dense.rows);
@@ -833,7 +876,17 @@ static int ldd_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int 
     LDALLOC(vvd, (size_t)M);
     LDALLOC(xd, (size_t)M);
     if (chrom) LDALLOC(dchrom, (size_t)M);
-    if (band) LDALLOC(a.band, nband);
+    if (gram) {
+        a.msig = c->msig;
+        a.wscale = c->dense.scale;
+        a.inv_n = 1.0 / (double)c->N;
+        a.S = c->S;
+        a.u0 = u0;
+        a.nu = nu;
+        a.W = W;
+        a.hs = W == 32 ? 4 : (W == 64 ? 5 : 6);
+        a.gram = gram;
+    } else if (band) LDALLOC(a.band, nband);
     else {
         LDALLOC(a.part, nslots * (size_t)a.Mp);
         LDALLOC(a.pcnt, nslots * (size_t)a.Mp);
@@ -847,7 +900,9 @@ static int ldd_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int 
     a.xd = xd;
     a.chrom = dchrom;
     if (chrom) HIPCHK(c, hipMemcpyAsync(dchrom, chrom, sizeof(int) * (size_t)M, hipMemcpyHostToDevice, c->stream));
-    if (band) HIPCHK(c, hipMemsetAsync(a.band, 0, sizeof(double) * nband, c->stream));
+    if (gram) {
+        if (nu > 0) HIPCHK(c, hipMemsetAsync(gram, 0, sizeof(double) * (size_t)nu * W * W, c->stream));
+    } else if (band) HIPCHK(c, hipMemsetAsync(a.band, 0, sizeof(double) * nband, c->stream));
     else {
         HIPCHK(c, hipMemsetAsync(a.part, 0, sizeof(double) * nslots * (size_t)a.Mp, c->stream));
         HIPCHK(c, hipMemsetAsync(a.pcnt, 0, sizeof(int) * nslots * (size_t)a.Mp, c->stream));
@@ -866,15 +921,20 @@ static int ldd_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int 
         a.I0 = Ia;
         const dim3 grid((unsigned)(Ib - Ia + 1), (unsigned)(De + 1));
         for (int64_t I = Ia; I <= Ib; I++) blocks += (std::min<int64_t>(De, a.nrge - 1 - I) + 1) * F * F;
-        if (!uniform) ldd_launch<false, 64>(c->stream, grid, a, band != nullptr, seg);
-        else if (edge == 64) ldd_launch<true, 64>(c->stream, grid, a, band != nullptr, seg);
-        else ldd_launch<true, 128>(c->stream, grid, a, band != nullptr, seg);
+        const int ep = gram ? EP_GRAM : (band ? EP_BAND : EP_SCORES);
+        if (!uniform) ldd_launch<false, 64>(c->stream, grid, a, ep, seg);
+        else if (edge == 64) ldd_launch<true, 64>(c->stream, grid, a, ep, seg);
+        else ldd_launch<true, 128>(c->stream, grid, a, ep, seg);
         KCHK(c);
-        if (!band) {
+        if (!band && !gram) {
             hipLaunchKernelGGL(k_ld_finish, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, a.part, a.pcnt, (int)nslots, a.Mp, M, xd,
                                dl2, dnp);
             KCHK(c);
         }
+    }
+    if (gram) {      // (the scratch is freed on return: the kernels that read it must have run)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return 0;
     }
     if (band) {
         if (nband) HIPCHK(c, hipMemcpyAsync(band, a.band, sizeof(double) * nband, hipMemcpyDeviceToHost, c->stream));
@@ -888,6 +948,27 @@ static int ldd_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int 
     c->ld_last.useful_macs = (uniform ? 1.0 : 4.0) * (double)c->N * (band ? ld_entries(M, B, j0, nj) : ld_entries(M, B, 0, M));
     c->ld_last.scratch_bytes = (double)w.bytes;
     return 0;
+}
+
+// what the Gram build of 8-bit codes needs (the dosage side of planes_check): gv_set_ld_dosage on, 8-bit codes, the mask, the marker
+// statistics (unlike the LD calls: msig enters the Grams) and an N within the 128-bit epilogue
+int gvi::gram_dosage_check(gv_ctx* c, const char* who) {
+    // (the option was switched off after kind 1 was accepted, or codes replaced a bed under kind 1: never the bed kernel on dosage rows)
+    if (!ld_dosage(c)) REFUSE_DOSAGE(c, who, "genotype windows only, unless gv_set_ld_dosage(ctx, 1) is in force (it is off)");
+    if (!ld_dosage(c)) return fail(c, "%s: no compact dosage data resident", who);
+    if (c->dense.bits != 8)
+        return fail(c, "%s: gv_set_ld_dosage covers 8-bit codes only: the resident data are 16-bit codes (their hi / lo byte split is not built)", who);
+    if (!c->mask2) return fail(c, "%s: the phenotype mask must be set first (gv_set_mask)", who);
+    if (!c->have_stats) return fail(c, "%s: marker statistics must be computed first", who);
+    if (c->N > LD_N_MAX)
+        return fail(c, "%s: N = %lld exceeds %lld, the most individuals whose centred products fit the 128-bit integers", who, (long long)c->N,
+                    (long long)LD_N_MAX);
+    return 0;
+}
+
+// the window Grams of section 18 into out (device, pc_nu x W x W, W = pc_W): zeroed, then the Gram epilogue of k_ldd_block
+int gvp::gram_dosage(gv_ctx* c, double* out) {
+    return ldd_run(c, "LD preconditioner", 0, nullptr, 0, nullptr, nullptr, 0, c->M, nullptr, out);
 }
 
 // scores (band == NULL) or the band rows [j0, j0 + nj)
@@ -1005,6 +1086,7 @@ int gv_ld_band(gv_ctx* c, int64_t window, const int* chrom, int64_t j0, int64_t 
 
 int gv_set_ld_dosage(gv_ctx* c, int on) {
     NEED(c, on == 0 || on == 1, "gv_set_ld_dosage: on must be 0 or 1");
+    if (on != c->ld_dosage) pc_invalidate(c, false);      // (the Grams of dosage codes belong to the option)
     c->ld_dosage = on;
     return 0;
 }

@@ -4,7 +4,8 @@
 // to [0, Mt) and to the shard [S, S+M).  Odd u is grid 0 (window k = (u-1)/2 = [kW, kW+W)), even u is grid 1 (window k = u/2 =
 // [kW-h, kW+h), the first one clipped at 0).  Every marker lies in exactly one window of each grid: u = g/h and g/h + 1.
 //   Gram      G_u = the window's exact diagonal block of A^T A, from the resident 2-bit re-encoding with i8 MFMA: the Gram epilogue of
-//             k_ld_block (gvp::gram, gv_ld.hip)
+//             k_ld_block (gvp::gram, gv_ld.hip); of resident 8-bit dosage codes under gv_set_ld_dosage: the Gram epilogue of k_ldd_block
+//             (gvp::gram_dosage; section 18)
 //   factor    B_u = tau G_u + gam2 I, Cholesky in LDS and the explicit inverse L^-T L^-1, one workgroup per window (k_pc_factor)
 //   apply     z = 1/2 sum over both grids of blockdiag(B_u^-1) r (k_pc_apply)
 // Integer Grams, then a fixed fp64 order everywhere, no atomics: the results do not depend on the layout or the launch.
@@ -145,7 +146,8 @@ void pc_invalidate(gv_ctx* c, bool free_mem) {
 // the window Grams of the resident data set (once per data set, mask and marker statistics)
 static int pc_build_gram(gv_ctx* c) {
     NEED(c, c->pc_kind == 1, "LD preconditioner: not enabled (gv_set_cg_precond(ctx, 1, window))");
-    if (planes_check(c, "LD preconditioner", "genotype windows only")) return 1;
+    const bool codes = c->dense.resident && c->dense.bits;      // compact dosage data: the Gram epilogue of k_ldd_block, or a refusal
+    if (codes ? gram_dosage_check(c, "LD preconditioner") : planes_check(c, "LD preconditioner", "genotype windows only")) return 1;
     const int W = c->pc_W;
     if (!c->pc_have_gram) {
         const int64_t u0 = gvp::first_window(c->S, W), nu = gvp::num_windows(c->S, c->M, W);
@@ -161,8 +163,11 @@ static int pc_build_gram(gv_ctx* c) {
         const gvm::Plan& pl = c->plan;
         HIPCHK(c, hipStreamSynchronize(c->stream));
         const auto t0 = std::chrono::steady_clock::now();
-        gvp::gram(c->stream, pl.layout == 1 ? pl.tiles : pl.stripes_m, pl.layout, pl.nkb_m, c->mask2, c->pitch / 4, c->N, c->S, c->M, W,
-                  c->mave, c->msig, c->pc_gram);
+        if (codes) {
+            if (gvp::gram_dosage(c, c->pc_gram)) return 1;
+        } else
+            gvp::gram(c->stream, pl.layout == 1 ? pl.tiles : pl.stripes_m, pl.layout, pl.nkb_m, c->mask2, c->pitch / 4, c->N, c->S, c->M, W,
+                      c->mave, c->msig, c->pc_gram);
         KCHK(c);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->pc_build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -201,8 +206,15 @@ extern "C" {
 int gv_set_cg_precond(gv_ctx* c, int kind, int window) {
     NEED(c, kind == 0 || kind == 1, "gv_set_cg_precond: kind must be 0 (scalar, the default) or 1 (ld)");
     NEED(c, kind == 0 || window == 32 || window == 64 || window == 128, "gv_set_cg_precond: window must be 32, 64 or 128");
-    if (kind != 0) REFUSE_DOSAGE(c, "gv_set_cg_precond", "the LD preconditioner works on genotype windows only");
-    NEED(c, kind == 0 || !c->dense.resident, "gv_set_cg_precond: the LD preconditioner is refused for dense (meth) data");
+    // compact dosage data: accepted while gv_set_ld_dosage is on and the codes are 8 bits wide
+    if (kind != 0 && ld_dosage(c)) {
+        if (c->dense.bits != 8)
+            return fail(c, "gv_set_cg_precond: gv_set_ld_dosage covers 8-bit codes only: the resident data are 16-bit codes (their hi / lo byte "
+                           "split is not built)");
+    } else if (kind != 0) {
+        REFUSE_DOSAGE(c, "gv_set_cg_precond", "the LD preconditioner works on genotype windows only");
+        NEED(c, !c->dense.resident, "gv_set_cg_precond: the LD preconditioner is refused for dense (meth) data");
+    }
     if (kind == 0 || window != c->pc_W) pc_invalidate(c, true);     // (kind 0 releases the Grams and inverses)
     c->pc_kind = kind;
     if (kind == 1) c->pc_W = window;

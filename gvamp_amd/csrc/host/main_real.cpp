@@ -63,6 +63,20 @@ int main(int argc, char** argv) {
         }
     };
 
+    // [ext] --ld-dosage 1 with --cg-precond ld: the data object's context accepts the LD preconditioner on 8-bit codes (DESIGN.md
+    // section 18).  Without the flag vamp::infere's refusal stands.
+    const bool pcd = opt.get_ld_dosage() == 1 && opt.get_cg_precond() == "ld" && type_data != "bed";
+    if (pcd && (mode == "infere" || mode == "restart" || mode == "both") && type_data != "dosage8") {
+        std::cout << "FATAL: --cg-precond ld with --ld-dosage 1 covers --geno-format dosage8 only, not --geno-format " << type_data << std::endl;
+        return EXIT_FAILURE;
+    }
+    auto opt_in_ld_dosage = [&](data& ds) {
+        if (pcd && gv_set_ld_dosage(ds.get_ctx(), 1)) {
+            std::cout << "FATAL: gv_set_ld_dosage: " << gv_last_error(ds.get_ctx()) << std::endl;
+            exit(EXIT_FAILURE);
+        }
+    };
+
     if (mode == "infere" || mode == "restart") {
         const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
         std::vector<double> MS = divide_work(Mt);
@@ -74,6 +88,7 @@ int main(int argc, char** argv) {
         const double gam1 = (mode == "restart") ? opt.get_gam1_init() : 1e-6;
         const double gamw = (mode == "restart") ? opt.get_gamw_init() : initial_gamw(opt);
         vamp emvamp(M, gam1, gamw, std::vector<double>(M, 0.0), rank, opt);
+        opt_in_ld_dosage(dataset);
         infere_or_exit(emvamp, &dataset);
     } else if (mode == "test") {
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
@@ -124,6 +139,7 @@ int main(int argc, char** argv) {
         {
             data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
             vamp emvamp(M, 1e-6, initial_gamw(opt), std::vector<double>(M, 0.0), rank, opt);
+            opt_in_ld_dosage(dataset);
             x_est = infere_or_exit(emvamp, &dataset);
             intercept = dataset.get_intercept();
             scale = dataset.get_scale();

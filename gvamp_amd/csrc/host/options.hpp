@@ -52,7 +52,8 @@
        --run-mode ldscore with --ld-window B (1..8192, default 200) and --ld-adjust 0|1 (default 0): the LD scores of    \
        the markers over B markers on each side, per chromosome with a .bim file;                \
        --ld-dosage 0|1 (default 0): 1 = --run-mode ldscore also accepts --geno-format dosage8 (gv_set_ld_dosage,         \
-       DESIGN.md section 17; with --dosage-missing 1 the code 255 is a missing entry) */                                 \
+       DESIGN.md section 17; with --dosage-missing 1 the code 255 is a missing entry), and --cg-precond ld accepts it   \
+       in the infere / restart / both modes (section 18) */                                                           \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \

@@ -129,7 +129,10 @@ std::vector<double> vamp::infere(data* dataset) {
     ctx = dataset->get_ctx();
     if (cg_precond == 1 && reverse == 1)
         throw std::invalid_argument("--cg-precond ld is not available with --use-XXT-denoiser 1 (the N-space solve has no LD preconditioner)");
-    if (cg_precond == 1 && gv_get_layout(ctx) >= 3)
+    // (8-bit dosage codes pass while the context's gv_set_ld_dosage is on: DESIGN.md section 18)
+    int ld_dosage_on = 0;
+    gv_get_ld_dosage(ctx, &ld_dosage_on);
+    if (cg_precond == 1 && gv_get_layout(ctx) >= 3 && !(gv_get_layout(ctx) == 4 && ld_dosage_on == 1))
         throw std::invalid_argument(std::string("--cg-precond ld is not available for ") + dense_kind_name(gv_get_layout(ctx)) +
                                     " (genotype windows only)");
     if (gv_set_cg_precond(ctx, cg_precond, cg_precond_window)) throw std::runtime_error(gv_last_error(ctx));

@@ -107,6 +107,46 @@ def synth_dosage(N, M, seed, bits, S=0):
     return out
 
 
+def synth_dosage_ld(N, M, seed, bits, ld_block, ld_ppm, miss_ppm=0, S=0):
+    """Host twin of gv_synth_dosage_ld: synth_dosage's constants with synth_bed's block latent.  The two allele draws (the two low
+    16-bit fields) read the block's latent hash lat = splitmix64(lbase + n) where rs >> 32 < ld_ppm * 2^32 / 10^6, rs a second hash of
+    the entry, and the entry's own hash r elsewhere; the jitter always comes from the high 32 bits of r; a code equal to the reserved
+    one is clamped one below it; a third hash below miss_ppm * 2^32 / 10^6 puts the reserved code.  Integer arithmetic only: the two
+    agree bit for bit."""
+    if bits not in (8, 16):
+        raise ValueError("synth_dosage_ld: bits must be 8 or 16")
+    if not 0 <= miss_ppm <= 1000000 or not 0 <= ld_ppm <= 1000000 or ld_block < 1:
+        raise ValueError("synth_dosage_ld: miss_ppm and ld_ppm must be within 0..1000000, ld_block at least 1")
+    out = np.empty((M, N), dtype=np.uint8 if bits == 8 else np.uint16)
+    reserved = np.uint64((1 << bits) - 1)
+    miss_thr = np.uint64((miss_ppm << 32) // 1000000)
+    ld_thr = np.uint64(min((ld_ppm << 32) // 1000000, 0xFFFFFFFF))
+    with np.errstate(over="ignore"):
+        g = np.arange(S, S + M, dtype=np.uint64)
+        hm = _splitmix64(np.uint64(seed) ^ (g * np.uint64(0xD1342543DE82EF95)))
+        base = _splitmix64(hm + np.uint64(0x632BE59BD9B4E019))
+        maf = np.uint64(655) + hm % np.uint64(32113)
+        lbase = _splitmix64(np.uint64(seed) ^ ((g // np.uint64(ld_block)) * np.uint64(0xA24BAED4963EE407)) ^
+                            np.uint64(0x5851F42D4C957F2D))
+        n = np.arange(N, dtype=np.uint64)
+        f = np.uint64(0xFFFF)
+        step = max(1, (1 << 22) // max(N, 1))
+        for m0 in range(0, M, step):
+            m1 = min(M, m0 + step)
+            r = _splitmix64(base[m0:m1, None] + n[None, :])
+            rs = _splitmix64(r ^ np.uint64(0x9FB21C651E98DF25))
+            lat = _splitmix64(lbase[m0:m1, None] + n[None, :])
+            al = np.where((rs >> np.uint64(32)) < ld_thr, lat, r)
+            q = maf[m0:m1, None]
+            geno = ((al & f) < q).astype(np.uint64) + (((al >> np.uint64(16)) & f) < q).astype(np.uint64)
+            jit = (((r >> np.uint64(32)) & f) * (r >> np.uint64(48))) >> np.uint64(16)
+            code = geno * np.uint64(3 << (bits - 3)) + (jit >> np.uint64(18 - bits))
+            code = np.minimum(code, reserved - np.uint64(1))
+            code[(_splitmix64(rs ^ np.uint64(0x2545F4914F6CDD1D)) >> np.uint64(32)) < miss_thr] = reserved
+            out[m0:m1] = code.astype(out.dtype)
+    return out
+
+
 def synth_dosage_na(N, M, seed, bits, miss_ppm, S=0):
     """Host twin of gv_synth_dosage_na: the codes of synth_dosage clamped one below the reserved code (255 / 65535), then, per entry,
     an independent draw -- the high 32 bits of a second hash of the entry below miss_ppm * 2^32 / 10^6 -- replaces the code by the

@@ -105,6 +105,8 @@ int gv_synth_meth(gv_ctx* ctx, uint64_t seed);
  * it behind rounding).  The products form (b - mu') per entry and carry msig * scale in the per-marker weight.
  * Not available (non-zero return, the message names compact dosage data): everything the dense fp64 kind refuses --
  * gv_download_bed, gv_people_stats, gv_cg_solve_aat*, gv_pvals_*, gv_set_decomp -- and gv_set_cg_precond kind 1.
+ * The one exception: while gv_set_ld_dosage(ctx, 1) is in force and the resident codes are 8 bits wide, gv_set_cg_precond kind 1 is
+ * accepted (the LD-block preconditioner of 8-bit dosage codes, at the end of this header).
  * bits other than 8 or 16 and a scale that is not positive and finite are refused. */
 /* codes: M*N codes of this shard, marker-major: uint8_t when bits == 8, uint16_t (host byte order) when bits == 16. */
 int gv_upload_dosage(gv_ctx* ctx, const void* codes, size_t n, int bits, double scale);
@@ -143,6 +145,17 @@ int gv_set_dosage_missing(gv_ctx* ctx, int on);
  * a second hash of the entry below miss_ppm * 2^32 / 10^6 -- replaces it by the reserved code.  miss_ppm <= 1000000.
  * gvamp_amd.synth.synth_dosage_na(N, M, seed, bits, miss_ppm, S) reproduces it bit for bit. */
 int gv_synth_dosage_na(gv_ctx* ctx, uint64_t seed, int bits, uint32_t miss_ppm);
+/* Block-correlated synthetic codes: gv_synth_dosage's columns are independent, so nothing that exploits LD can be shown on them.
+ * Integer only, gv_synth_dosage's constants (hm, base, maf and the entry hash r) and gv_synth_bed_ld's block latent
+ * (lbase from the global marker index / ld_block; ld_block >= 1, ld_ppm <= 1000000):
+ *   rs = splitmix64(r ^ 0x9FB21C651E98DF25), lat = splitmix64(lbase + n);
+ *   the two allele draws read the low 32 bits of lat where rs >> 32 < ld_ppm * 2^32 / 10^6, of r elsewhere; the jitter always comes
+ *   from the high 32 bits of r; a code equal to the reserved one is clamped one below it (also with miss_ppm == 0);
+ *   where splitmix64(rs ^ 0x2545F4914F6CDD1D) >> 32 < miss_ppm * 2^32 / 10^6 the reserved code replaces the code -- a third hash, so
+ *   that missingness is independent of the LD draw.
+ * miss_ppm > 0 implies gv_set_dosage_missing(ctx, 1); with miss_ppm == 0 the setting is left as it is (no reserved code is written).
+ * gvamp_amd.synth.synth_dosage_ld(N, M, seed, bits, ld_block, ld_ppm, miss_ppm, S) reproduces it bit for bit. */
+int gv_synth_dosage_ld(gv_ctx* ctx, uint64_t seed, int bits, uint32_t miss_ppm, uint32_t ld_block, uint32_t ld_ppm);
 typedef struct {
     double scale;          /* of the resident codes; 0 when none are resident */
     uint64_t reserved;     /* reserved codes found at the last ingest of this shard: counted on the device behind the copy into the
@@ -686,6 +699,26 @@ int gv_ld_info(gv_ctx* ctx, gv_ld_stats* info);
  * reserved code in the shard), 4 otherwise (or under GV_DOSAGE_NA_KERNELS=1).  N <= 2^29 - 1. */
 int gv_set_ld_dosage(gv_ctx* ctx, int on);
 int gv_get_ld_dosage(const gv_ctx* ctx, int* on);
+/* ---- LD-block preconditioner of 8-bit dosage codes (additions only: GV_ABI_VERSION stays 4) ------------------
+ * While gv_set_ld_dosage(ctx, 1) is in force and 8-bit codes are resident, gv_set_cg_precond(ctx, 1, window) is accepted, and
+ * gv_precond_info, gv_precond_window_gram, gv_precond_apply and every M-space solve work as on bed data.  With the option off (the
+ * default) every call and every message is what it was.  Windows, the two grids, clipping to the shard, B = tau G + gam2 I, the
+ * pivot rule and the apply are those of gv_set_cg_precond above; only the Gram differs.
+ * Definition.  A_nj = (code_nj - mu'_j) s_j b_nj na_n / sqrt(N) with s_j = msig_j * scale is the matrix gv_ax / gv_atx apply to
+ * compact data.  G is the window's exact diagonal block of A^T A,
+ *   G_jk = s_j s_k / N * X_jk / (c_j c_k)
+ * with the integers X_jk, c_j, T_j of gv_set_ld_dosage above: X formed in 128 bits, converted to fp64 correctly rounded.  The ONE
+ * fp64 evaluation order, symmetric in j and k:
+ *   G_jk = ((s_j * s_k) * (1 / N)) * (fl(X_jk) / (fl(c_j) * fl(c_k))),    s_j = msig_j * scale,  1 / N one division
+ * so G_jk and G_kj are the same bits (every product is commutative and X_jk = X_kj exactly) and the mirror image of a block is a
+ * copy.  A row with c_j = 0 (no present individual) contributes exact zeros; a constant row has X_jj = 0, hence G_jj = 0, exactly.
+ * Needs the mask and the marker statistics (msig enters).  The Grams are built at the first solve or gv_precond_window_gram and
+ * dropped where the bed Grams are and also by a new dosage upload or synthesis, gv_set_dosage_missing and gv_set_ld_dosage.  The sums
+ * are int32 MFMA sums over at most 131 071 individuals added in int64: the Grams are the same bits for every segment length, for the
+ * one-product and the four-product kernel on data without a reserved code, and across calls.
+ * Still refused, each by a message that names its reason: 16-bit codes ("16-bit codes"), methylation data, the N-space solvers and
+ * gv_cg_warm::ata_v_b under kind 1, N > 2^29 - 1.  If kind 1 was accepted and the option is then switched off, the next solve,
+ * gv_precond_apply or gv_precond_window_gram refuses with a message that names gv_set_ld_dosage. */
 
 #ifdef __cplusplus
 }
