@@ -30,7 +30,7 @@ EXPORTS = [
     "gv_assoc_loo", "gv_assoc_loco",
     "gv_set_dosage_missing", "gv_synth_dosage_na", "gv_dosage_info", "gv_marker_counts",
     "gv_set_dosage_route", "gv_get_dosage_route",
-    "gv_ld_scores", "gv_ld_band", "gv_ld_info",
+    "gv_ld_scores", "gv_ld_band", "gv_ld_info", "gv_ld_scores_pos", "gv_ld_last_passes",
     "gv_set_ld_dosage", "gv_get_ld_dosage",
     "gv_synth_dosage_ld",
 ]
@@ -202,6 +202,8 @@ def load():
     L.gv_ld_scores.argtypes = [vp, i64, C.POINTER(C.c_int), C.c_int, dp, dp]
     L.gv_ld_band.argtypes = [vp, i64, C.POINTER(C.c_int), i64, i64, dp]
     L.gv_ld_info.argtypes = [vp, C.POINTER(LdStats)]
+    L.gv_ld_scores_pos.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, dp]
+    L.gv_ld_last_passes.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
     L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
@@ -556,6 +558,31 @@ class Shard:
         ch, chp = self._chrom(chrom)
         self._ck(self.L.gv_ld_scores(self.h, int(window), chp, int(bool(adjusted)), _dp(l2), _dp(n)))
         return l2[:self.M].copy(), n[:self.M].copy()
+
+    def ld_scores_pos(self, pos, radius, chrom=None, adjusted=False, annot=None):
+        """gv_ld_scores_pos: (l2, npairs[M]) over the band |pos_k - pos_j| <= radius on the same chromosome; l2 has shape (M,) without
+        annot and (M, C) with the M x C annotation matrix: l(j, c) = a_jc + sum of f(r_jk^2) a_kc.  pos=None passes NULL (refused)."""
+        M = self.M
+        p = None if pos is None else np.ascontiguousarray(pos, dtype=np.float64)
+        assert p is None or p.size == M
+        C_ = 1
+        an = None
+        if annot is not None:
+            an = np.ascontiguousarray(annot, dtype=np.float64)
+            assert an.ndim == 2 and an.shape[0] == M
+            C_ = an.shape[1]
+        l2, n = np.zeros(max(M, 1) * max(C_, 1)), np.zeros(max(M, 1))
+        ch, chp = self._chrom(chrom)
+        self._ck(self.L.gv_ld_scores_pos(self.h, None if p is None else _dp(p), float(radius), chp, int(bool(adjusted)),
+                                         None if an is None else _dp(an), C_, _dp(l2), _dp(n)))
+        l2 = l2[:M * C_].copy()
+        return (l2 if annot is None else l2.reshape(M, C_)), n[:M].copy()
+
+    def ld_last_passes(self):
+        """gv_ld_last_passes: the passes over row groups the last LD call took (more than 1 only for ld_scores_pos over its budget)"""
+        k = C.c_int(0)
+        self._ck(self.L.gv_ld_last_passes(self.h, C.byref(k)))
+        return k.value
 
     def ld_band(self, window, j0, nj, chrom=None):
         """gv_ld_band: nj x (2 * window + 1) correlations of the local markers [j0, j0 + nj); column window + d is r[j][j + d],

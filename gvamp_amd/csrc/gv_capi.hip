@@ -300,6 +300,18 @@ int gv_create(int device, gv_ctx** out) {
         }
         c->ld_dosage_edge = atoi(ed);
     }
+    // GV_LD_PART_MB=<x> (development, read per context): the budget of gv_ld_scores_pos for the per-block partial sums of one pass, in MiB
+    // (fractions allowed; default 2048).  It changes no bit, only the number of passes; a call whose single row group does not fit refuses.
+    if (const char* pm = getenv("GV_LD_PART_MB")) {
+        char* end = nullptr;
+        const double mb = strtod(pm, &end);
+        if (end == pm || *end != 0 || !(mb > 0.0) || !std::isfinite(mb)) {
+            g_create_err = "gv_create: GV_LD_PART_MB=" + std::string(pm) + ": the budget of the LD partial sums is a positive number of MiB";
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->ld_part_bytes = mb * 1048576.0;
+    }
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)

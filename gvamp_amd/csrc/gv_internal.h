@@ -185,6 +185,10 @@ struct gv_ctx {
     // ld_dosage_edge: markers per side of a block of the one-product kernel, 64 or 128 (GV_LD_DOSAGE_EDGE, development, per context)
     int ld_dosage = 0;
     int ld_dosage_edge = 128;
+    // gv_ld_scores_pos: the most bytes of per-block partial sums one pass may hold (GV_LD_PART_MB, development,
+    // per context; a memory budget, not a tuned number) and the passes the last LD call took (gv_ld_last_passes)
+    double ld_part_bytes = 2147483648.0;
+    int ld_last_passes = 0;
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;

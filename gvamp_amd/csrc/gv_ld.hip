@@ -11,6 +11,8 @@
 //                Epilogue: r, and either the band rows (band mode) or the block's row and column sums of f(r^2) (scores mode); or
 //                the block's entries of the preconditioner's window Grams (Gram mode: d only as far as one window reaches, no k_ld_diag)
 //   k_ld_finish  l_j = 1 + the 2D + 1 block partials of marker j in ascending block order
+// gv_ld_scores_pos (section 19): the band of a marker from its position (hi[], gv_ld_window.h) and scores per annotation category -- the
+// EP_POS epilogue of k_ld_block and k_ld_finish_pos, in passes over row groups that keep the partials within a memory budget.
 // Integer sums, then a fixed fp64 order, no atomics: the results do not depend on the layout, the kernel mode or the launch.
 // Second part (k_ldd_*, ldd_run): the same two entry points on resident 8-bit dosage codes, opt-in (gv_set_ld_dosage; section 17) -- the
 // centred product of two markers in exact 128-bit integers, one correctly rounded conversion.  The same block kernel with a Gram epilogue
@@ -20,6 +22,7 @@
 #include <cmath>
 
 #include "gv_internal.h"
+#include "gv_ld_window.h"
 
 namespace {
 
@@ -152,14 +155,64 @@ struct LdArgs {
     int64_t S, u0, nu;              // Gram: the shard's first global marker; the half-grid windows [u0, u0 + nu) that overlap it
     int W, hs;                      // Gram: the window length and log2 of its half H
     double* gram;                   // Gram: nu x W x W, zeroed before the launch
+    // positional scores (EP_POS, section 19).  The launch covers the row groups of one pass, the first of them I0; its partials are laid
+    // out by the block that writes them: row sums [I - I0][d = J - I in 0..dmax][64][ncat] in part / pcnt (pcnt without ncat), column
+    // sums (the terms the block owes the markers of J, d >= 1) [I - I0][d - 1][64][ncat] in cpart / ccnt
+    const int64_t* hi;              // M: the last in-band index of every marker (gv_ld_window.h)
+    const double* annot;            // M x ncat row-major or NULL (one category, a = 1)
+    int ncat, dmax;
+    double* cpart;
+    int* ccnt;
+    const int* pairs;               // the blocks of the launch, (I, J) of block blockIdx.x: a 1-D grid over the blocks that hold an in-band pair
 };
 
-enum { EP_SCORES, EP_BAND, EP_GRAM };     // the epilogues of k_ld_block
+enum { EP_SCORES, EP_BAND, EP_GRAM, EP_POS };     // the epilogues of k_ld_block
 
 // f(r^2) of the LD score
 __device__ __forceinline__ double ld_f(double r, int adjusted, double nm2) {
     const double x = r * r;
     return adjusted ? x - (1.0 - x) / nm2 : x;
+}
+
+// s + f a of the positional scores: the plain product, then the sum (the contract of gv_ld_scores_pos: never contracted into an fma)
+__device__ __forceinline__ double ld_term_add(double s, double f, double a) {
+#pragma clang fp contract(off)
+    const double p = f * a;
+    return s + p;
+}
+
+// The EP_POS epilogue after the block's 64 x 64 image of f(r^2) (NaN = no term) is in LDS: for every category c the rows of I times the
+// annotation rows of J, out[e][c] = sum_t f[e][t] a[64 J + t][c] in ascending t, and for I < J the columns times the annotation rows of
+// I.  The (row or column, e, c) triples are dealt to the 256 threads with c fastest: the annotation reads and the store coalesce along c,
+// the LDS reads are broadcasts.  With one category these are the 128 threads of the EP_SCORES epilogue.  An annotation row past M is
+// never read: t stops at M.  The annotation value of every t < tn is loaded whether its f is a term or not, so that the loads do not
+// hang on the NaN test and the compiler can issue a batch of them ahead of the sums (eight, the unroll); the sum takes the terms alone,
+// in order.  The term counts are written once per marker, by the thread of c = 0.
+__device__ __forceinline__ void ld_pos_sums(const LdArgs& a, const double* fl, int64_t I, int64_t J, int tid) {
+    const int C = a.ncat, d = (int)(J - I);
+    const int64_t Il = I - a.I0;
+    const int nq = (I == J ? 64 : 128) * C;
+    for (int q = tid; q < nq; q += 256) {
+        const bool col = q >= 64 * C;
+        const int p = col ? q - 64 * C : q;
+        const int e = p / C, c = p - e * C;
+        const int64_t other = (col ? I : J) * 64;
+        const int tn = (int)min((int64_t)64, a.M - other);
+        const double* an = a.annot ? a.annot + other * C + c : nullptr;
+        double s = 0.0;
+        int n = 0;
+#pragma unroll 8
+        for (int t = 0; t < tn; t++) {
+            const double f = col ? fl[t * LD_PITCH + e] : fl[e * LD_PITCH + t];
+            const double av = an ? an[(int64_t)t * C] : 1.0;
+            const bool term = f == f;
+            s = term ? ld_term_add(s, f, av) : s;
+            n += term;
+        }
+        const int64_t slot = (col ? Il * a.dmax + (d - 1) : Il * (a.dmax + 1) + d) * 64;
+        (col ? a.cpart : a.part)[slot * C + p] = s;
+        if (c == 0) (col ? a.ccnt : a.pcnt)[slot + e] = n;
+    }
 }
 
 // G_u[m - lo_u][k - lo_u] = g and, if mirror, G_u[k - lo_u][m - lo_u] = gt in every half-grid window u = [(u - 1) H, (u + 1) H) that holds
@@ -180,16 +233,22 @@ __device__ __forceinline__ void ld_gram_store(const A& a, int64_t m, int64_t k, 
 }
 
 // block (I = I0 + blockIdx.x, J = I + blockIdx.y).  EP_BAND: store r of the requested rows; EP_SCORES: the block's row / column sums;
-// EP_GRAM: the block's entries of the window Grams.
+// EP_GRAM: the block's entries of the window Grams; EP_POS: the band is k <= hi[m] (section 19), the block's row / column sums per
+// annotation category; the launch is a 1-D grid over a host-built list of the blocks that hold an in-band pair.
 template <int LAYOUT, int EP>
 __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
     // operand images of one half K-block: [side: I, J][16-marker tile][K-step of the half][plane V, P][lane] x 16 bytes = 32 KiB;
     // the scores epilogue reuses the space for the block's 64 x 64 values of f(r^2)
     constexpr int OP_BYTES = 2 * 4 * 2 * 2 * 64 * 16, EP_BYTES = 64 * LD_PITCH * 8;
     constexpr bool LD = EP != EP_GRAM;      // r needs the diagonal and the chromosomes; a Gram entry neither
-    __shared__ __attribute__((aligned(16))) char lds[EP == EP_SCORES && EP_BYTES > OP_BYTES ? EP_BYTES : OP_BYTES];
+    constexpr bool CH = LD && EP != EP_POS;     // (the positional band has the chromosomes folded into hi)
+    __shared__ __attribute__((aligned(16))) char lds[(EP == EP_SCORES || EP == EP_POS) && EP_BYTES > OP_BYTES ? EP_BYTES : OP_BYTES];
     v4i* op = reinterpret_cast<v4i*>(lds);
-    const int64_t I = a.I0 + blockIdx.x, J = I + blockIdx.y;
+    int64_t I = a.I0 + blockIdx.x, J = I + blockIdx.y;
+    if constexpr (EP == EP_POS) {
+        I = a.pairs[2 * blockIdx.x];
+        J = a.pairs[2 * blockIdx.x + 1];
+    }
     if (I >= a.nrg || J >= a.nrg) return;       // (uniform over the workgroup)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
     const int side = tid >> 7, x = tid & 127;
@@ -263,7 +322,9 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
         const int64_t k = J * 64 + kl;
         const bool kin = k < a.M;
         const double mk = kin ? a.mave[k] : 0.0, sk = kin ? a.msig[k] : 0.0, ck = LD && kin ? a.cdiag[k] : 0.0;
-        const int chk = LD && kin && a.chrom ? a.chrom[k] : 0;
+        const int chk = CH && kin && a.chrom ? a.chrom[k] : 0;
+        int64_t hik = 0;
+        if constexpr (EP == EP_POS) hik = kin ? a.hi[k] : 0;
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -272,7 +333,7 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                 const int64_t m = I * 64 + il;
                 const bool min_ = m < a.M;
                 const double mi = min_ ? a.mave[m] : 0.0, si = min_ ? a.msig[m] : 0.0, ci = LD && min_ ? a.cdiag[m] : 0.0;
-                const int chi = LD && min_ && a.chrom ? a.chrom[m] : 0;
+                const int chi = CH && min_ && a.chrom ? a.chrom[m] : 0;
                 if (EP == EP_GRAM) {
                     // the roles go by the entry's row and column (G[row][col] takes mave_col with sum V_row P_col), so the mirror
                     // image swaps them.  A diagonal block holds both orders itself.
@@ -282,7 +343,12 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                     continue;
                 }
                 const int64_t dist = k - m;
-                const bool inband = min_ && kin && dist <= a.B && -dist <= a.B && chi == chk;
+                bool inband;
+                if constexpr (EP == EP_POS) {
+                    const int64_t him = min_ ? a.hi[m] : 0;
+                    inband = min_ && kin && (m <= k ? k <= him : m <= hik);      // (k <= hi_m <=> m >= lo_k)
+                }
+                else inband = min_ && kin && dist <= a.B && -dist <= a.B && chi == chk;
                 const bool poly = ci != 0.0 && ck != 0.0;
                 double r = 0.0;
                 if (inband && poly) {
@@ -305,6 +371,11 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                     fl[il * LD_PITCH + kl] = inband && poly && m != k ? ld_f(r, a.adjusted, a.nm2) : __builtin_nan("");
                 }
             }
+    }
+    if constexpr (EP == EP_POS) {
+        __syncthreads();
+        ld_pos_sums(a, fl, I, J, tid);
+        return;
     }
     if (EP != EP_SCORES) return;
     __syncthreads();
@@ -347,6 +418,49 @@ __global__ __launch_bounds__(256) void k_ld_finish(const double* __restrict__ pa
     }
     l2[j] = 1.0 + s;
     npairs[j] = (double)(1 + n);
+}
+
+// The finish of one pass [Ia, Ib] of the positional scores, thread (j, c) with c fastest over the markers of the row groups
+// [Ia, min(Ib + dmax, nrg - 1)]: the running sum run[j][c] (zero before the first pass) takes the pass's partials of marker j in
+// ascending block order -- the column sums of the blocks (I, R), I < R, then the row sums of (R, R + d) -- and a marker whose own row
+// group R lies in the pass has seen every block: the self term a_jc is added last, as k_ld_finish adds the 1.  A marker of a later row
+// group is taken up again by the next pass where this one stopped, so the order of the additions does not depend on the passes.
+__global__ __launch_bounds__(256) void k_ld_finish_pos(const double* __restrict__ part, const int* __restrict__ pcnt,
+                                                       const double* __restrict__ cpart, const int* __restrict__ ccnt, int dmax, int C,
+                                                       int64_t Ia, int64_t Ib, int64_t nrg, int64_t M, const double* __restrict__ cdiag,
+                                                       const double* __restrict__ annot, double* __restrict__ run, double* __restrict__ nrun) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, jl = t / C;
+    const int c = (int)(t - jl * C);
+    const int64_t j = Ia * 64 + jl, R = j >> 6;
+    if (j >= M || R > Ib + dmax) return;
+    const int e = (int)(j & 63);
+    const bool last = R <= Ib;
+    if (cdiag[j] == 0.0) {
+        if (last) {
+            run[j * C + c] = __builtin_nan("");
+            if (c == 0) nrun[j] = 0.0;
+        }
+        return;
+    }
+    double s = run[j * C + c];
+    int64_t n = 0;
+    for (int64_t I = max(Ia, R - dmax); I <= min(R - 1, Ib); I++) {
+        const int64_t slot = ((I - Ia) * dmax + (R - I - 1)) * 64 + e;
+        s += cpart[slot * C + c];
+        n += ccnt[slot];
+    }
+    if (last)
+        for (int d = 0; d <= dmax; d++) {
+            const int64_t slot = ((R - Ia) * (dmax + 1) + d) * 64 + e;
+            s += part[slot * C + c];
+            n += pcnt[slot];
+        }
+    if (last) {
+        s = (annot ? annot[j * C + c] : 1.0) + s;
+        n++;
+    }
+    run[j * C + c] = s;
+    if (c == 0) nrun[j] += (double)n;
 }
 
 // =====================================================================================================================================
@@ -947,6 +1061,7 @@ static int ldd_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int 
     c->ld_last.block_pairs = blocks;
     c->ld_last.useful_macs = (uniform ? 1.0 : 4.0) * (double)c->N * (band ? ld_entries(M, B, j0, nj) : ld_entries(M, B, 0, M));
     c->ld_last.scratch_bytes = (double)w.bytes;
+    c->ld_last_passes = 1;
     return 0;
 }
 
@@ -1063,10 +1178,160 @@ static int ld_run(gv_ctx* c, const char* who, int64_t B, const int* chrom, int a
     c->ld_last.block_pairs = blocks;
     c->ld_last.useful_macs = 4.0 * (double)c->N * (band ? ld_entries(M, B, j0, nj) : ld_entries(M, B, 0, M));
     c->ld_last.scratch_bytes = (double)w.bytes;
+    c->ld_last_passes = 1;
+    return 0;
+}
+
+// gv_ld_scores_pos (section 19): the band of every marker from its position, scores per annotation category.  The block kernel's EP_POS
+// epilogue over the list of the blocks that hold an in-band pair, in as many passes over consecutive row groups as keep the partials within c->ld_part_bytes.
+static int ld_pos_run(gv_ctx* c, const char* who, const gvw::Window& win, int adjusted, const double* annot, int C, double* l2, double* npairs) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const gvm::Plan& pl = c->plan;
+    const int64_t M = c->M, nrg = (M + 63) / 64;
+    const int dmax = (int)win.dmax;
+    // one row group's worth of slots: 2 dmax + 1 blocks x 64 markers x (C sums and a count)
+    const double per_rg = (double)(2 * dmax + 1) * 64.0 * (8.0 * C + 4.0);
+    if (per_rg > c->ld_part_bytes)
+        return fail(c, "%s: the budget of the partial sums, %.0f bytes (GV_LD_PART_MB), cannot hold one row group's worth of slots: (2 * %d + 1) blocks "
+                       "x 64 markers x (8 * %d + 4) bytes = %.0f bytes", who, c->ld_part_bytes, dmax, C, per_rg);
+    const int64_t rgp = std::max<int64_t>(std::min<int64_t>(nrg, (int64_t)(c->ld_part_bytes / per_rg)), 1);      // row groups per pass
+    const int64_t passes = (nrg + rgp - 1) / rgp;
+    Scratch w;
+    LdArgs a{};
+    a.lay = reinterpret_cast<const uint4*>(pl.layout == 1 ? pl.tiles : pl.stripes_m);
+    a.nkb = pl.nkb_m;
+    a.mask2 = c->mask2;
+    a.P4 = c->pitch / 4;
+    a.N = c->N;
+    a.M = M;
+    a.nrg = nrg;
+    a.mave = c->mave;
+    a.msig = c->msig;
+    a.adjusted = adjusted;
+    a.nm2 = (double)c->nonas - 2.0;
+    a.ncat = C;
+    a.dmax = dmax;
+    double *cdiag = nullptr, *dannot = nullptr, *dl2 = nullptr, *dnp = nullptr;
+    int64_t* dhi = nullptr;
+    int* dpairs = nullptr;
+    std::vector<std::vector<int>> lists;       // (the host side of an asynchronous copy: alive until the call's synchronise)
+    const size_t nrow = (size_t)rgp * (size_t)(dmax + 1) * 64, ncol = (size_t)rgp * (size_t)dmax * 64;
+#define LDALLOC(p, n)                                                                                                          \
+    do {                                                                                                                       \
+        if (w.get(&p, n) != hipSuccess) {                                                                                      \
+            (void)hipGetLastError();                                                                                           \
+            return fail(c, "%s: cannot allocate %zu bytes of device scratch (%zu already held by this call)", who, sizeof(*p) * (size_t)(n), w.bytes); \
+        }                                                                                                                      \
+    } while (0)
+    LDALLOC(cdiag, (size_t)M);
+    LDALLOC(dhi, (size_t)M);
+    if (annot) LDALLOC(dannot, (size_t)M * (size_t)C);
+    LDALLOC(a.part, nrow * (size_t)C);
+    LDALLOC(a.pcnt, nrow);
+    LDALLOC(a.cpart, ncol * (size_t)C);
+    LDALLOC(a.ccnt, ncol);
+    LDALLOC(dl2, (size_t)M * (size_t)C);
+    LDALLOC(dnp, (size_t)M);
+    LDALLOC(dpairs, 2 * (size_t)rgp * (size_t)(dmax + 1));
+#undef LDALLOC
+    a.cdiag = cdiag;
+    a.hi = dhi;
+    a.pairs = dpairs;
+    a.annot = dannot;
+    HIPCHK(c, hipMemcpyAsync(dhi, win.hi.data(), sizeof(int64_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    if (annot) HIPCHK(c, hipMemcpyAsync(dannot, annot, sizeof(double) * (size_t)M * (size_t)C, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dl2, 0, sizeof(double) * (size_t)M * (size_t)C, c->stream));
+    HIPCHK(c, hipMemsetAsync(dnp, 0, sizeof(double) * (size_t)M, c->stream));
+    if (pl.layout == 1)
+        hipLaunchKernelGGL(k_ld_diag<1>, dim3((unsigned)nrg), dim3(256), 0, c->stream, a.lay, a.nkb, a.mask2, a.P4, a.N, M, a.mave, a.msig, cdiag);
+    else
+        hipLaunchKernelGGL(k_ld_diag<2>, dim3((unsigned)nrg), dim3(256), 0, c->stream, a.lay, a.nkb, a.mask2, a.P4, a.N, M, a.mave, a.msig, cdiag);
+    KCHK(c);
+    int64_t blocks = 0;
+    for (int64_t I = 0; I < nrg; I++) blocks += win.hi[(size_t)std::min(I * 64 + 63, M - 1)] / 64 - I + 1;
+    for (int64_t Ia = 0; Ia < nrg; Ia += rgp) {
+        const int64_t Ib = std::min(Ia + rgp, nrg) - 1;
+        // (the slots of the blocks that are not launched read as zero)
+        HIPCHK(c, hipMemsetAsync(a.part, 0, sizeof(double) * nrow * (size_t)C, c->stream));
+        HIPCHK(c, hipMemsetAsync(a.pcnt, 0, sizeof(int) * nrow, c->stream));
+        if (ncol) {
+            HIPCHK(c, hipMemsetAsync(a.cpart, 0, sizeof(double) * ncol * (size_t)C, c->stream));
+            HIPCHK(c, hipMemsetAsync(a.ccnt, 0, sizeof(int) * ncol, c->stream));
+        }
+        a.I0 = Ia;
+        // the blocks (I, I + d) that hold an in-band pair -- hi does not decrease, so the last marker of I reaches furthest -- with d
+        // outermost, the order in which the index window's grid (row groups, D + 1) dispatches its blocks
+        lists.emplace_back();
+        std::vector<int>& L = lists.back();
+        for (int d = 0; d <= dmax; d++)
+            for (int64_t I = Ia; I <= Ib; I++)
+                if (win.hi[(size_t)std::min(I * 64 + 63, M - 1)] / 64 - I >= d) {
+                    L.push_back((int)I);
+                    L.push_back((int)(I + d));
+                }
+        HIPCHK(c, hipMemcpyAsync(dpairs, L.data(), sizeof(int) * L.size(), hipMemcpyHostToDevice, c->stream));
+        const dim3 grid((unsigned)(L.size() / 2));
+        if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, EP_POS>), grid, dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_ld_block<2, EP_POS>), grid, dim3(256), 0, c->stream, a);
+        KCHK(c);
+        const int64_t span = (std::min<int64_t>(Ib + dmax, nrg - 1) - Ia + 1) * 64 * C;
+        hipLaunchKernelGGL(k_ld_finish_pos, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, c->stream, a.part, a.pcnt, a.cpart, a.ccnt, dmax, C, Ia,
+                           Ib, nrg, M, cdiag, dannot, dl2, dnp);
+        KCHK(c);
+    }
+    HIPCHK(c, hipMemcpyAsync(l2, dl2, sizeof(double) * (size_t)M * (size_t)C, hipMemcpyDeviceToHost, c->stream));
+    if (npairs) HIPCHK(c, hipMemcpyAsync(npairs, dnp, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ld_last.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    c->ld_last.block_pairs = blocks;
+    c->ld_last.useful_macs = 4.0 * (double)c->N * win.entries;
+    c->ld_last.scratch_bytes = (double)w.bytes;
+    c->ld_last_passes = (int)passes;
     return 0;
 }
 
 extern "C" {
+
+int gv_ld_scores_pos(gv_ctx* c, const double* pos, double radius, const int* chrom, int adjusted, const double* annot, int ncat, double* l2,
+                     double* npairs) {
+    const char* who = "gv_ld_scores_pos";
+    if (c->dense.resident && c->dense.bits)
+        return fail(c, "%s: bed data only for now: compact dosage data (%d-bit codes) are not served by this entry point, with or without "
+                       "gv_set_ld_dosage", who, c->dense.bits);
+    if (planes_check(c, who, "LD is computed from 2-bit genotypes only")) return 1;
+    NEED(c, pos, "gv_ld_scores_pos: pos is NULL");
+    NEED(c, l2, "gv_ld_scores_pos: l2 is NULL");
+    NEED(c, adjusted == 0 || adjusted == 1, "gv_ld_scores_pos: adjusted must be 0 or 1");
+    NEED(c, adjusted == 0 || c->nonas >= 3, "gv_ld_scores_pos: the adjusted estimator r^2 - (1 - r^2) / (n - 2) needs at least 3 phenotyped individuals");
+    if (!std::isfinite(radius) || radius < 0.0) return fail(c, "%s: radius must be finite and >= 0 (%g was passed)", who, radius);
+    if (annot && (ncat < 1 || ncat > 512)) return fail(c, "%s: ncat must be in [1, 512] when annot is given (%d was passed)", who, ncat);
+    const gvw::Window win = gvw::make_window(pos, chrom, radius, c->M, LD_WINDOW_MAX);
+    const long long at = (long long)win.at;
+    switch (win.verdict) {
+        case gvw::OK: break;
+        case gvw::POS_NOT_FINITE: return fail(c, "%s: pos[%lld] is not finite", who, at);
+        case gvw::POS_DECREASES:
+            return fail(c, "%s: pos[%lld] = %.17g is below pos[%lld] = %.17g on the same chromosome: positions must not decrease", who, at, pos[at],
+                        at - 1, pos[at - 1]);
+        case gvw::CHROM_REAPPEARS:
+            return fail(c, "%s: chromosome id %d reappears at marker %lld after its run has ended: every chromosome must be one contiguous run", who,
+                        chrom[at], at);
+        case gvw::REACH_TOO_LONG:
+            return fail(c, "%s: marker %lld reaches %lld markers ahead, more than the %lld a band may (a smaller radius, or gv_ld_scores)", who, at,
+                        (long long)win.reach, (long long)LD_WINDOW_MAX);
+    }
+    if (c->M == 0) {
+        c->ld_last = gv_ld_stats{};
+        c->ld_last_passes = 0;
+        return 0;
+    }
+    return ld_pos_run(c, who, win, adjusted, annot, annot ? ncat : 1, l2, npairs);
+}
+
+int gv_ld_last_passes(const gv_ctx* c, int* passes) {
+    if (passes) *passes = c->ld_last_passes;
+    return 0;
+}
 
 int gv_ld_scores(gv_ctx* c, int64_t window, const int* chrom, int adjusted, double* l2, double* npairs) {
     if (ld_check(c, "gv_ld_scores", window)) return 1;

@@ -397,6 +397,102 @@ std::vector<std::vector<double>> data::ld_scores_dev(int window, bool adjusted) 
     return res;
 }
 
+namespace {
+// a whole token as a finite-or-not double; false if it is none
+bool parse_double(const std::string& tok, double* out) {
+    if (tok.empty()) return false;
+    char* end = nullptr;
+    *out = strtod(tok.c_str(), &end);
+    return *end == 0;
+}
+}  // namespace
+
+std::vector<double> data::read_positions(std::string bim_file, const std::string& unit) {
+    const size_t col = unit == "cm" ? 2 : 3;
+    std::vector<double> pos;
+    std::ifstream infile(bim_file);
+    if (!infile.is_open()) die("FATAL: could not open bim file: " + bim_file);
+    std::string line;
+    for (int line_n = 0; getline(infile, line); line_n++) {
+        if (line_n < S || line_n >= S + M) continue;
+        const std::vector<std::string> tokens = split_ws(line);
+        double v = 0.0;
+        if (tokens.size() <= col)
+            die("FATAL: line " + std::to_string(line_n + 1) + " of bim file " + bim_file + " has no column " + std::to_string(col + 1) +
+                " (the " + (col == 2 ? "cM" : "base-pair") + " position)");
+        if (!parse_double(tokens[col], &v))
+            die("FATAL: line " + std::to_string(line_n + 1) + " of bim file " + bim_file + ": \"" + tokens[col] + "\" in column " +
+                std::to_string(col + 1) + " is not a number");
+        pos.push_back(v);
+    }
+    if ((int)pos.size() != M)
+        die("FATAL: bim file " + bim_file + " holds " + std::to_string(S + (int)pos.size()) + " lines, fewer than the " + std::to_string(S + M) +
+            " markers");
+    return pos;
+}
+
+std::vector<double> data::read_annot(std::string path, int M_, std::vector<std::string>* names) {
+    std::ifstream infile(path);
+    if (!infile.is_open()) die("FATAL: could not open annotation file: " + path);
+    std::string line;
+    if (!getline(infile, line)) die("FATAL: annotation file " + path + " is empty (line 1 must be the header)");
+    std::vector<std::string> head = split_ws(line);
+    if (!head.empty() && head[0].empty()) head.erase(head.begin());
+    std::vector<size_t> cols;
+    std::vector<std::string> cats;
+    for (size_t i = 0; i < head.size(); i++)
+        if (head[i] != "CHR" && head[i] != "BP" && head[i] != "SNP" && head[i] != "CM") {
+            cols.push_back(i);
+            cats.push_back(head[i]);
+        }
+    if (cols.empty()) die("FATAL: line 1 of annotation file " + path + " names no category (every column is CHR, BP, SNP or CM)");
+    std::vector<double> out;
+    out.reserve((size_t)M_ * cols.size());
+    int rows = 0, last_line = 1;
+    for (int line_n = 2; getline(infile, line); line_n++) {
+        last_line = line_n;
+        std::vector<std::string> tokens = split_ws(line);
+        if (!tokens.empty() && tokens[0].empty()) tokens.erase(tokens.begin());
+        if (tokens.empty()) continue;          // (a blank line, as at the end of the file)
+        if (rows == M_)
+            die("FATAL: line " + std::to_string(line_n) + " of annotation file " + path + " is row " + std::to_string(rows + 1) + ", but there are " +
+                std::to_string(M_) + " markers");
+        if (tokens.size() != head.size())
+            die("FATAL: line " + std::to_string(line_n) + " of annotation file " + path + " has " + std::to_string(tokens.size()) + " fields, the header " +
+                std::to_string(head.size()));
+        for (size_t i : cols) {
+            double v = 0.0;
+            if (!parse_double(tokens[i], &v))
+                die("FATAL: line " + std::to_string(line_n) + " of annotation file " + path + ": \"" + tokens[i] + "\" is not a number");
+            if (!std::isfinite(v))
+                die("FATAL: line " + std::to_string(line_n) + " of annotation file " + path + ": \"" + tokens[i] + "\" is not finite");
+            out.push_back(v);
+        }
+        rows++;
+    }
+    if (rows != M_)
+        die("FATAL: annotation file " + path + " ends after line " + std::to_string(last_line) + ": " + std::to_string(rows) + " rows for " +
+            std::to_string(M_) + " markers");
+    if (names) *names = cats;
+    return out;
+}
+
+std::vector<std::vector<double>> data::ld_scores_pos_dev(const std::vector<double>& pos, double radius, bool adjusted,
+                                                         const std::vector<double>& annot, int ncat) {
+    const size_t C = annot.empty() ? 1 : (size_t)ncat, Mp = M > 0 ? M : 1;
+    std::vector<std::vector<double>> res{std::vector<double>(Mp * C, 0.0), std::vector<double>(Mp, 0.0)};
+    std::vector<int> ch_info;
+    if (bimfp != "") {
+        ch_info = read_chromosome_info(bimfp);
+        ch_info.resize(Mp, 0);
+    }
+    ck(ctx, gv_ld_scores_pos(ctx, pos.data(), radius, ch_info.empty() ? nullptr : ch_info.data(), adjusted ? 1 : 0,
+                             annot.empty() ? nullptr : annot.data(), ncat, res[0].data(), res[1].data()), "gv_ld_scores_pos");
+    res[0].resize((size_t)(M > 0 ? M : 0) * C);
+    res[1].resize(M > 0 ? M : 0);
+    return res;
+}
+
 static std::vector<std::vector<double>> pvals_host(data* d, gv_ctx* ctx, int M, size_t mbytes,
                                                    std::vector<std::vector<double>>& z1, std::vector<double>& y,
                                                    std::vector<std::vector<double>>& x1_hat, bool loco,

@@ -97,4 +97,13 @@ public:
     std::vector<std::vector<double>> assoc_calc_dev(gv_vec* z1, gv_vec* y, gv_vec* x1_hat, bool loco, const std::string& pred_prefix = std::string());
     // [ext] gv_ld_scores over `window` markers on each side: {l2, npairs}, M values each; per chromosome when a .bim file was given
     std::vector<std::vector<double>> ld_scores_dev(int window, bool adjusted);
+    // [ext] the positions of this shard's markers from a .bim file: unit "cm" = column 3, "bp" = column 4
+    std::vector<double> read_positions(std::string bim_file, const std::string& unit);
+    // [ext] an annotation file: one header line, then one row per marker in marker order, M rows; the columns headed CHR, BP, SNP or CM
+    // are skipped, every other column is a category.  Returns M x C row-major and the C names.
+    std::vector<double> read_annot(std::string path, int M, std::vector<std::string>* names);
+    // [ext] gv_ld_scores_pos: {l2 (M x max(ncat, 1) row-major), npairs (M)}; annot empty = no annotation; per chromosome when a .bim
+    // file was given
+    std::vector<std::vector<double>> ld_scores_pos_dev(const std::vector<double>& pos, double radius, bool adjusted,
+                                                       const std::vector<double>& annot, int ncat);
 };

@@ -4,6 +4,7 @@
 // Every mode is "load data, maybe run vamp::infere, one or more data::Ax, a reduction, a file": the matvecs are HIP
 // kernels behind libgvamp, the rest is host code.  One process per GPU (RANK / WORLD_SIZE from the launcher).
 #include <cmath>
+#include <fstream>
 #include <iostream>
 
 #include "data.hpp"
@@ -200,6 +201,17 @@ int main(int argc, char** argv) {
                          "would miss their neighbours across them" << std::endl;
             return EXIT_FAILURE;
         }
+        // [ext] DESIGN.md section 19: the window by distance (--ld-wind-kb / --ld-wind-cm) and the annotation categories (--ld-annot)
+        const bool by_kb = opt.get_ld_wind_kb() >= 0, by_cm = opt.get_ld_wind_cm() >= 0, positional = by_kb || by_cm || opt.get_ld_annot() != "";
+        if (opt.count_ld_windows() > 1) {
+            std::cout << "FATAL: exactly one of --ld-window, --ld-wind-kb and --ld-wind-cm may be given" << std::endl;
+            return EXIT_FAILURE;
+        }
+        if ((by_kb || by_cm) && bimfp == "") {
+            std::cout << "FATAL: " << (by_kb ? "--ld-wind-kb" : "--ld-wind-cm") << " needs --bim-file: the positions are its "
+                      << (by_kb ? "base-pair" : "cM") << " column" << std::endl;
+            return EXIT_FAILURE;
+        }
         const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
         need_phen(opt.get_phen_files(), "--phen-files");
         data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, Mt, Mt, 0, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
@@ -207,14 +219,67 @@ int main(int argc, char** argv) {
             std::cout << "FATAL: gv_set_ld_dosage: " << gv_last_error(dataset.get_ctx()) << std::endl;
             return EXIT_FAILURE;
         }
-        const std::vector<std::vector<double>> res = dataset.ld_scores_dev(opt.get_ld_window(), opt.get_ld_adjust() == 1);
-        gv_ld_stats st;
-        gv_ld_info(dataset.get_ctx(), &st);
         const std::string pre = opt.get_out_dir() + opt.get_out_name();
-        mpi_store_vec_to_file(pre + "_ldscore.bin", res[0], 0, Mt);
-        mpi_store_vec_to_file(pre + "_ldscore_n.bin", res[1], 0, Mt);
-        std::cout << "LD scores: window " << opt.get_ld_window() << (opt.get_ld_adjust() ? " (adjusted)" : "") << ", " << Mt << " markers, "
-                  << st.seconds << " seconds" << std::endl;
+        gv_ld_stats st;
+        if (!positional) {
+            const std::vector<std::vector<double>> res = dataset.ld_scores_dev(opt.get_ld_window(), opt.get_ld_adjust() == 1);
+            gv_ld_info(dataset.get_ctx(), &st);
+            mpi_store_vec_to_file(pre + "_ldscore.bin", res[0], 0, Mt);
+            mpi_store_vec_to_file(pre + "_ldscore_n.bin", res[1], 0, Mt);
+            std::cout << "LD scores: window " << opt.get_ld_window() << (opt.get_ld_adjust() ? " (adjusted)" : "") << ", " << Mt << " markers, "
+                      << st.seconds << " seconds" << std::endl;
+        } else {
+            // the positions and the radius: kb of the base-pair column, cM of the cM column, or (an annotation with --ld-window) the indices
+            std::vector<double> pos;
+            double radius = (double)opt.get_ld_window();
+            if (by_kb) {
+                pos = dataset.read_positions(bimfp, "bp");
+                radius = 1000.0 * opt.get_ld_wind_kb();
+            } else if (by_cm) {
+                pos = dataset.read_positions(bimfp, "cm");
+                radius = opt.get_ld_wind_cm();
+            } else
+                for (int j = 0; j < Mt; j++) pos.push_back((double)j);
+            std::vector<std::string> cats;
+            std::vector<double> annot;
+            if (opt.get_ld_annot() != "") annot = dataset.read_annot(opt.get_ld_annot(), Mt, &cats);
+            const int C = annot.empty() ? 1 : (int)cats.size();
+            const std::vector<std::vector<double>> res = dataset.ld_scores_pos_dev(pos, radius, opt.get_ld_adjust() == 1, annot, C);
+            gv_ld_info(dataset.get_ctx(), &st);
+            mpi_store_vec_to_file(pre + "_ldscore.bin", res[0], 0, Mt * C);
+            mpi_store_vec_to_file(pre + "_ldscore_n.bin", res[1], 0, Mt);
+            if (!annot.empty()) {
+                // the category sums over the polymorphic markers, and over those whose minor-allele frequency (mave / 2, folded to at
+                // most 0.5) is above 0.05: what LD-score regression divides the heritability of a category by
+                std::vector<double> tot(C, 0.0), tot5(C, 0.0);
+                const double* mave = dataset.get_mave();
+                for (int j = 0; j < Mt; j++) {
+                    if (res[1][j] == 0.0) continue;
+                    const double f = mave[j] / 2.0, maf = f > 0.5 ? 1.0 - f : f;
+                    for (int c = 0; c < C; c++) {
+                        tot[c] += annot[(size_t)j * C + c];
+                        if (maf > 0.05) tot5[c] += annot[(size_t)j * C + c];
+                    }
+                }
+                std::ofstream fm(pre + "_ldscore_M.txt"), fc(pre + "_ldscore_cats.txt");
+                fm.precision(17);
+                for (const std::vector<double>* t : {&tot, &tot5}) {
+                    for (int c = 0; c < C; c++) fm << (c ? " " : "") << (*t)[c];
+                    fm << "\n";
+                }
+                for (const std::string& nm : cats) fc << nm << "\n";
+                if (!fm.good() || !fc.good()) {
+                    std::cout << "FATAL: cannot write " << pre << "_ldscore_M.txt / _ldscore_cats.txt" << std::endl;
+                    return EXIT_FAILURE;
+                }
+            }
+            std::cout << "LD scores: window ";
+            if (by_kb) std::cout << opt.get_ld_wind_kb() << " kb";
+            else if (by_cm) std::cout << opt.get_ld_wind_cm() << " cM";
+            else std::cout << opt.get_ld_window();
+            std::cout << (opt.get_ld_adjust() ? " (adjusted)" : "") << ", " << Mt << " markers, " << C << (C == 1 ? " category, " : " categories, ")
+                      << st.seconds << " seconds" << std::endl;
+        }
     } else if (mode == "predict" || mode == "predict_single") {                        // :386-594
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);

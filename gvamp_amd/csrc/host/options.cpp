@@ -162,7 +162,22 @@ void Options::read_command_line_options(int argc, char** argv) {
         if (atoi(a) < 1 || atoi(a) > 8192)
             fatal(std::string("FATAL  : option --ld-window has to be within 1..8192! (") + a + " was passed)");
         ld_window = atoi(a);
+        ld_windows_given++;
     };
+    auto wind = [&](const char* f, double& dst) {
+        std::string flag = f;
+        H[f] = [&dst, flag, this](const char* a) {
+            char* end = nullptr;
+            const double v = strtod(a, &end);
+            if (end == a || *end != 0 || !(v >= 0) || v > 1e300)
+                fatal("FATAL  : option " + flag + " has to be a non-negative number! (" + a + " was passed)");
+            dst = v;
+            ld_windows_given++;
+        };
+    };
+    wind("--ld-wind-kb", ld_wind_kb);
+    wind("--ld-wind-cm", ld_wind_cm);
+    str("--ld-annot", ld_annot);
     H["--ld-adjust"] = [&](const char* a) {
         if (strcmp(a, "0") && strcmp(a, "1"))
             fatal(std::string("FATAL  : option --ld-adjust has to be 0 or 1! (") + a + " was passed)");

@@ -53,13 +53,20 @@
        the markers over B markers on each side, per chromosome with a .bim file;                \
        --ld-dosage 0|1 (default 0): 1 = --run-mode ldscore also accepts --geno-format dosage8 (gv_set_ld_dosage,         \
        DESIGN.md section 17; with --dosage-missing 1 the code 255 is a missing entry), and --cg-precond ld accepts it   \
-       in the infere / restart / both modes (section 18) */                                                           \
+       in the infere / restart / both modes (section 18);                                                              \
+       --ld-wind-kb X / --ld-wind-cm X (instead of --ld-window; need --bim-file): the window of --run-mode ldscore by    \
+       distance, X kb of the .bim file's base-pair column (radius 1000 X) or X cM of its cM column, at most 8192 markers \
+       ahead (gv_ld_scores_pos); --ld-annot FILE: one header line, one row per marker, the columns \
+       CHR / BP / SNP / CM skipped and every other column an annotation category -- partitioned LD scores, M x C, with    \
+       <out>_ldscore_M.txt (the category sums over the polymorphic markers and over those of MAF > 0.05) and            \
+       <out>_ldscore_cats.txt (the names); without a kb / cM window the positions are the marker indices */             \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
     X(int, cg_precond_window, 128) X(std::string, geno_format, "bed") X(double, dosage_scale, 0) \
     X(unsigned int, store_assoc, 0) X(int, dosage_missing, 0) X(std::string, dosage_kernels, "valu")       \
-    X(int, ld_window, 200) X(int, ld_adjust, 0) X(int, ld_dosage, 0)
+    X(int, ld_window, 200) X(int, ld_adjust, 0) X(int, ld_dosage, 0)                                                   \
+    X(double, ld_wind_kb, -1) X(double, ld_wind_cm, -1) X(std::string, ld_annot, "")
 
 class Options {
 public:
@@ -82,6 +89,7 @@ public:
     const std::vector<std::string>& get_true_signal_files() const { return true_signal_files; }
     int count_phen_files() const { return (int)phen_files.size(); }
     int count_phen_files_test() const { return (int)phen_files_test.size(); }
+    int count_ld_windows() const { return ld_windows_given; }      // [ext] how many of --ld-window / --ld-wind-kb / --ld-wind-cm were given
     void list_phen_files() const;
 
     void set_probit_var(double v) { probit_var = v; }
@@ -108,6 +116,7 @@ private:
     std::vector<double> vars, probs;
     std::vector<int> test_iter_range = std::vector<int>(2, -1);
     std::vector<std::string> phen_files, phen_files_test, true_signal_files;
+    int ld_windows_given = 0;
 
     void fail_if_last(char** argv, const int i);
     void check_options();

@@ -681,6 +681,34 @@ typedef struct gv_ld_stats {
     double scratch_bytes;        /* device scratch it allocated and released */
 } gv_ld_stats;
 int gv_ld_info(gv_ctx* ctx, gv_ld_stats* info);
+/* ---- LD scores over a window of positions, per annotation category (additions only: GV_ABI_VERSION stays 4) ----
+ * The data, the planes, C_jk, r_jk, the monomorphic rule, f, and adjusted with n = nonas >= 3 are exactly those of gv_ld_scores.
+ * Band: k is in the band of j iff chrom_j == chrom_k (chrom NULL: one chromosome) and |pos_k - pos_j| <= radius; the comparison is the
+ * fp64 expression pos_k - pos_j <= radius for j <= k, so equal positions are always in each other's band.  pos (M doubles: bp, cM, any
+ * unit radius is given in) must be finite and non-decreasing inside each maximal run of equal chrom, and each chromosome id must form a
+ * single contiguous run: the band of j is then an index interval [lo_j, hi_j] with lo and hi non-decreasing and k <= hi_j <=> j >= lo_k,
+ * which lets each unordered pair be evaluated once and mirrored.  The band is clipped to the shard, as above.  Reach limit:
+ * hi_j - j <= 8192 for every j, the reach of gv_ld_scores' largest window.
+ *   l(j, c) = a_jc + sum over k != j in the band, k polymorphic, of f(r_jk^2) * a_kc        (annot: M x ncat row-major, 1 <= ncat <= 512)
+ * With annot == NULL ncat is ignored, there is one category and a = 1.  l(j, .) = NaN and npairs_j = 0 for a monomorphic j; npairs_j
+ * counts the terms, self included, whatever the annotation values are (zeros and negative values are legal).
+ * Summation order: per (j, c) the terms are added in ascending k, through per-block partials added in ascending block order; each term
+ * is formed as the plain product f * a and then added (no fused multiply-add); the self term a_jc is added last.  No atomics: two
+ * calls, both layouts and kernel modes 1 and 2 give the same bits, and so does any number of passes (below).  With pos[j] = S + j,
+ * radius = B and annot == NULL the output is bit-identical to gv_ld_scores(ctx, B, chrom, adjusted, ...) (a chromosome layout with
+ * non-contiguous ids is refused here, although that call serves it); an annotation of one all-ones column gives the bits of annot == NULL.
+ * The per-block partial sums take (2 dmax + 1) * 64 * row groups * (8 ncat + 4) bytes, dmax the most 64-marker row groups a row group
+ * reaches ahead; above a budget (2 GiB; GV_LD_PART_MB, read by gv_create) the call runs in passes over consecutive row groups, each
+ * within the budget.  gv_ld_info after the call: block_pairs counts the blocks actually computed (a block that no marker reaches is
+ * skipped), useful_macs = 4 N sum_j (hi_j - lo_j + 1); gv_ld_last_passes: the passes of the last LD call (1 for gv_ld_scores / band).
+ * Refused with a message that names the reason: everything gv_ld_scores refuses; compact dosage data of either width, also under
+ * gv_set_ld_dosage(ctx, 1) (this entry point is bed-only for now); pos == NULL; a non-finite or decreasing position and a chromosome id
+ * that reappears after its run has ended (naming the first offending local marker); radius negative or not finite; a reach above 8192
+ * (naming the marker and its reach); ncat outside [1, 512] when annot is given; a budget that cannot hold one row group's slots. */
+int gv_ld_scores_pos(gv_ctx* ctx, const double* pos /* M */, double radius, const int* chrom /* M or NULL */, int adjusted,
+                     const double* annot /* M x ncat row-major, or NULL */, int ncat,
+                     double* l2 /* M x max(ncat, 1) row-major */, double* npairs /* M or NULL */);
+int gv_ld_last_passes(const gv_ctx* ctx, int* passes);
 /* ---- LD of 8-bit dosage codes (additions only: GV_ABI_VERSION stays 4) ----------------------------------------
  * gv_set_ld_dosage(ctx, 1): gv_ld_scores, gv_ld_band and gv_ld_info accept a context whose resident data are 8-bit dosage codes and
  * whose mask is set.  Per context, default 0, it outlives the dataset; with 0 nothing changes by a bit or by a message.  Marker

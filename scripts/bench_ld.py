@@ -12,6 +12,14 @@ useful and computed integer MAC/s (computed: every 64 x 64 sub-block the launch 
 implied load rate, 2 * EDGE * N bytes per block.
 
     python scripts/bench_ld.py --kind dosage8 --N 20000 --M 800000 --out profiles/ld_dosage_bench_20000x800000.json
+
+--kind pos: gv_ld_scores_pos on synthetic base-pair positions, 1 kb between neighbours (so --wind-kb X reaches X
+markers on each side and the index window of gv_ld_scores at B = X computes the same blocks: both are timed in the same process), or
+with --pos-cluster alternating stretches of 2048 markers 0.25 kb and 4 kb apart (no index window equals that band).  --ncat C ...: a
+random 0 / 1 annotation of C categories at the first --wind-kb (0 = no annotation).  One JSON line per call with seconds, block_pairs,
+useful_macs, scratch_bytes and the pass count.
+
+    python scripts/bench_ld.py --kind pos --wind-kb 512 2048 --ncat 1 16 64 97 --out profiles/ld_pos_400k_125k.json
 """
 import argparse
 import json
@@ -66,9 +74,60 @@ def dosage8(a):
         f.write("\n")
 
 
+def positional(a):
+    import numpy as np
+    j = np.arange(a.M)
+    if a.pos_cluster:
+        gaps = np.where((j // 2048) % 2 == 0, 250.0, 4000.0)
+        gaps[0] = 0.0
+        pos = np.cumsum(gaps)
+    else:
+        pos = 1000.0 * j
+    rng = np.random.default_rng(5)
+    annots = {C_: (rng.random((a.M, C_)) < 0.3).astype(np.float64) for C_ in a.ncat if C_ > 0}
+    rows = []
+
+    def leg(sh, rd, what, call, **kw):
+        res = call()
+        st = sh.ld_info()
+        if rd < 0:                           # the warm-up round: every shape of the timed rounds, not recorded
+            return res
+        row = dict(round=rd, call=what, seconds=st["seconds"], block_pairs=st["block_pairs"], useful_macs=st["useful_macs"],
+                   useful_macs_per_s=st["useful_macs"] / st["seconds"], seconds_per_block=st["seconds"] / max(st["block_pairs"], 1),
+                   scratch_bytes=st["scratch_bytes"], passes=sh.ld_last_passes(), **kw)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        return res
+
+    with capi.Shard(a.N, a.M) as sh:
+        sh.synth_bed(77, 5000, ld_block=a.ld_block, ld_ppm=900000)
+        sh.compute_markers_statistics()
+        for rd in range(-1, a.rounds):
+            for X in a.wind_kb:
+                # the two legs in an order that alternates with the round: what runs first is not always the same call
+                legs = [("index", lambda: leg(sh, rd, "gv_ld_scores", lambda: sh.ld_scores(int(X)), window=int(X))),
+                        ("pos", lambda: leg(sh, rd, "gv_ld_scores_pos", lambda: sh.ld_scores_pos(pos, 1000.0 * X), wind_kb=X, ncat=0))]
+                if a.pos_cluster:
+                    legs = legs[1:]
+                k = (rd + 1) % len(legs)
+                res = {name: run() for name, run in legs[k:] + legs[:k]}
+                if rd >= 0 and "index" in res:          # the same band: the same bits, at the size that is timed
+                    eq = all(np.array_equal(res["pos"][i], res["index"][i], equal_nan=True) for i in (0, 1))
+                    rows.append(dict(round=rd, wind_kb=X, bits_equal_index_window=bool(eq)))
+                    print(json.dumps(rows[-1]), flush=True)
+            for C_, an in annots.items():
+                leg(sh, rd, "gv_ld_scores_pos", lambda: sh.ld_scores_pos(pos, 1000.0 * a.wind_kb[0], annot=an), wind_kb=a.wind_kb[0], ncat=C_)
+    with open(a.out, "w") as f:
+        json.dump(dict(kind="pos", N=a.N, M=a.M, ld_block=a.ld_block, layout="default", pos_cluster=bool(a.pos_cluster), calls=rows), f)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", choices=["bed", "dosage8"], default="bed")
+    ap.add_argument("--kind", choices=["bed", "dosage8", "pos"], default="bed")
+    ap.add_argument("--wind-kb", type=float, nargs="+", default=[512.0])
+    ap.add_argument("--pos-cluster", action="store_true")
+    ap.add_argument("--ncat", type=int, nargs="*", default=[])
     ap.add_argument("--N", type=int, default=400000)
     ap.add_argument("--M", type=int, default=125000)
     ap.add_argument("--ld-block", type=int, default=64)
@@ -79,6 +138,8 @@ def main():
     a = ap.parse_args()
     if a.kind == "dosage8":
         return dosage8(a)
+    if a.kind == "pos":
+        return positional(a)
     rounds = []
     with capi.Shard(a.N, a.M) as sh:
         sh.synth_bed(77, 5000, ld_block=a.ld_block, ld_ppm=900000)
