@@ -7,7 +7,10 @@
 //   v (fp64)  ->  q = rint(v * 2^(54-e)),  2^(e-1) <= max|v| < 2^e      (absolute error <= 2^-55 max|v| per entry)
 //             ->  7 balanced base-256 digits d_l in [-128,127]          (q = sum_l d_l 256^l, exact)
 //   per 16x64 genotype tile:  acc[row][l] += sum_k g[row][k] * d_l[k]   v_mfma_i32_16x16x64_i8, exact int32
-//   result = (sum_l acc_l 256^l) * 2^(e-54)                             exact int64 limbs -> one fp64 rounding
+//   result = (sum_l acc_l 256^l) * 2^(e-54)                             exact int64 limbs (hi, lo) -> fl(fl(hi) 2^32 + fl(lo)):
+//                                                                       one fp64 rounding while |lo| <= 2^53 (always, short of an
+//                                                                       adversarial vector over > 1e6 K-entries: DESIGN.md section 4)
+// and the epilogue adds its own short, fixed sequence of roundings (k_fin_*; restated step by step in tests/bed_fixed_restatement.py).
 //
 // All sums are integer: results do not depend on tile order, K-split count or wave scheduling (bitwise
 // reproducible), and the error is that of the input quantisation only -- below fp64 summation error.

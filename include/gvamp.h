@@ -220,7 +220,10 @@ int gv_get_layout(const gv_ctx* ctx);   /* resident now: 0 none, 1 two stripe se
  * results within 2e-14 of fp64 sums, bit-reproducible); 0 = fp64 VALU kernels on the raw rows (parity anchor, 4-9 % of the
  * roofline; needs gv_set_layout(ctx, 1, ..) before ingest); 2 = two-level fixed point on the re-encoded layout (below). */
 /* Accuracy contract of kernel mode 1.  A vector enters a product in fixed point with ONE exponent for the whole vector
- * (|q| < 2^54 relative to its largest entry); the product itself is exact integer arithmetic with one final rounding.  Hence
+ * (|q| < 2^54 relative to its largest entry); the product itself is exact integer arithmetic with one final rounding (the integer
+ * sum to fp64: as fl(fl(hi) 2^32 + fl(lo)), which is ONE rounding while |lo| <= 2^53 -- any vector up to N = 2 088 960 individuals /
+ * M = 1 044 480 markers of a shard, and all but adversarial vectors beyond), followed by the few fixed roundings of the epilogue
+ * (mean correction, msig, 1/sqrt(N)); DESIGN.md section 4 lists the sequence, tests/bed_fixed_restatement.py restates it.  Hence
  *   Ax : |out[n] - exact[n]| <= M * 2^-50 * max_i |msig[i] x[i]| / sqrt(N),
  *   ATx: |out[m] - exact[m]| <= N * 2^-50 * msig[m] * max_n |p[n]| / sqrt(N)
  * (worst case; typical errors are sqrt(M) resp. sqrt(N) times smaller), i.e. an ABSOLUTE error relative to the vector's largest
