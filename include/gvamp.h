@@ -179,7 +179,10 @@ int gv_dosage_info(gv_ctx* ctx, gv_dosage_stats* out);
  * codes, everything after the quantisation is exact integer arithmetic with one final rounding.  With the factor-16 slack of mode 1:
  *   Ax : |out[n] - exact[n]| <= M * 2^-50 * (255 * scale / 2) * max_i |msig[i] x[i]| / sqrt(N),
  *   ATx: |out[m] - exact[m]| <= N * 2^-50 * (255 * scale / 2) * msig[m] * max_n |p[n]| / sqrt(N)
- * -- an ABSOLUTE error relative to the vector's largest entry, not relative to each output entry.  Results are bit-reproducible,
+ * -- an ABSOLUTE error relative to the vector's largest entry, not relative to each output entry.  The multiplier 2^(54-e) of the
+ * quantisation is at most 2^1000: where the largest entry of the quantised vector (p; msig[i] scale x[i] in Ax) is below 2^-946 the
+ * per-entry error is 2^-1001 and the bounds hold with that largest entry replaced by 2^-946.  A zero vector gives zeros; one entry
+ * that is not finite gives NaN in every output entry of that vector (pad slots of gv_ax stay zero).  Results are bit-reproducible,
  * independent of the work decomposition (every sum is an integer: no order enters), each slot of a two-vector call is bit-identical to
  * the one-vector call, pad slots of gv_ax are exact zeros, no atomics -- but they are not bit-equal to route 0. */
 int gv_set_dosage_route(gv_ctx* ctx, int route);

@@ -10,7 +10,10 @@ integers and numpy, kept apart from the library's code: quantisation, digits, th
          T[n] = sum_l 256^l sum_m (b_mn - 128) dc_l[m],  E = sum_m qe_m
          out[n] = (T[n] - 128 E) 2^(ec-54) / sqrt(N)              the subtraction in integers, one rounding
 
-The digit-plane sums are int64 matrix products (exact); everything above them is Python integers."""
+The multiplier 2^(54-e) is at most 2^1000 (E_MIN); a vector with an entry that is not finite gives NaN everywhere.
+
+The digit-plane sums are int64 matrix products (exact); everything above them is Python integers.  tests/test_dosage_fixed_cpu.py
+replaces quantise, plane_sums, total, centre_weights and centre_term by subtly wrong ones to show what the GPU test would see."""
 import math
 from fractions import Fraction
 
@@ -20,14 +23,22 @@ SEG_MAX = (2 ** 31 - 1) // (128 * 128)          # K-entries an int32 column sum 
 INT32_MAX = 2 ** 31 - 1
 
 
+SHIFT_MAX = 1000                                 # k_dm_quant: the multiplier 2^(54-e) stays representable -- at most 2^1000
+E_MIN = 54 - SHIFT_MAX                           # so a vector with max|v| < 2^-946 is quantised as if its exponent were -946
+
+
 def exponent(v):
-    """e with 2^(e-1) <= max|v| < 2^e (0 for a zero vector)"""
+    """e with 2^(e-1) <= max|v| < 2^e, but at least E_MIN (fewer bits below it, the same formulas); 0 for a zero vector -- every q is
+    zero then, whatever e -- and None when an entry is not finite: every output of the product is NaN then"""
+    v = np.asarray(v, dtype=np.float64)
+    if not np.all(np.isfinite(v)):
+        return None
     amax = float(np.max(np.abs(v))) if len(v) else 0.0
-    return math.frexp(amax)[1] if amax > 0 else 0
+    return max(math.frexp(amax)[1], E_MIN) if amax > 0 else 0
 
 
 def quantise(v, e):
-    """q = rint(v 2^(54-e)) as Python integers (the product by a power of two is exact)"""
+    """q = rint(v 2^(54-e)) as Python integers (the product by a power of two is exact), ties to even"""
     return [int(t) for t in np.rint(np.asarray(v, dtype=np.float64) * math.ldexp(1.0, 54 - e))]
 
 
@@ -65,17 +76,34 @@ def code_mean(B, na=None):
     return (B.astype(np.int64) * nai[None, :]).sum(axis=1).astype(np.float64) / float(nai.sum())
 
 
+def total(q):
+    """the pass's one integer sum_k q_k (the limb sums of k_dm_quant, added in integers)"""
+    return sum(q)
+
+
+def centre_weights(mu, c, ec):
+    """qe: e = (mu' - 128) c quantised on the grid 2^7 coarser than that of c"""
+    return quantise((np.asarray(mu, dtype=np.float64) - 128.0) * c, ec + 7)
+
+
+def centre_term(qe):
+    """what the Ax epilogue subtracts from T[n], in units of the grid of c: 128 E"""
+    return 128 * total(qe)
+
+
 def atx(B, mu, msig, scale, p, planes_out=None):
     """route 1's ATx in float64: B M x N uint8, mu / msig float64 per marker, p the first N entries"""
     B = np.asarray(B)
     M, N = B.shape
     p = np.asarray(p, dtype=np.float64)[:N]
     e = exponent(p)
+    if e is None:
+        return np.full(M, np.nan)
     q = quantise(p, e)
     planes = plane_sums(B.astype(np.int64) - 128, digits(q))
     if planes_out is not None:
         planes_out.append(planes)
-    S1, Q = recombine(planes), sum(q)
+    S1, Q = recombine(planes), total(q)
     Qd, inv, isn = float(Q), math.ldexp(1.0, e - 54), 1.0 / math.sqrt(float(N))
     out = np.empty(M)
     for m in range(M):
@@ -88,26 +116,45 @@ def ax(B, mu, msig, scale, x, planes_out=None):
     """route 1's Ax in float64 at the N individuals"""
     B = np.asarray(B)
     M, N = B.shape
-    c = np.asarray(msig, dtype=np.float64) * scale * np.asarray(x, dtype=np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        c = np.asarray(msig, dtype=np.float64) * scale * np.asarray(x, dtype=np.float64)
     ec = exponent(c)
+    if ec is None:
+        return np.full(N, np.nan)
     qc = quantise(c, ec)
-    qe = quantise((np.asarray(mu, dtype=np.float64) - 128.0) * c, ec + 7)
+    qe = centre_weights(mu, c, ec)
     planes = plane_sums((B.astype(np.int64) - 128).T.copy(), digits(qc))
     if planes_out is not None:
         planes_out.append(planes)
-    T, E = recombine(planes), sum(qe)
+    T, E128 = recombine(planes), centre_term(qe)
     inv, isn = math.ldexp(1.0, ec - 54), 1.0 / math.sqrt(float(N))
-    return np.array([float(t - 128 * E) * inv * isn for t in T])
+    return np.array([float(t - E128) * inv * isn for t in T])
+
+
+def lmmse(B, mu, msig, scale, x, tau, gam2):
+    """gv_lmmse_mult on route 1: z = Ax(x) (zeros at the pad slots, which ATx does not read), w = ATx(z), out = fma(tau, w, gam2 x) as the
+    ATx epilogue k_dm_fin_atx forms it"""
+    x = np.asarray(x, dtype=np.float64)
+    w = atx(B, mu, msig, scale, ax(B, mu, msig, scale, x))
+    return np.array([fma(tau, float(w[m]), gam2 * float(x[m])) for m in range(len(x))])
+
+
+FLOOR = math.ldexp(1.0, E_MIN)      # the bounds are relative to the largest entry of the QUANTISED vector, but not below 2^E_MIN: under it
+                                    # the per-entry error is 2^-55 2^E_MIN (SHIFT_MAX), not 2^-55 max|v|
 
 
 def atx_bound(N, scale, msig, p):
-    """the contract: N 2^-50 (255 scale / 2) msig[m] max|p| / sqrt(N)"""
-    return N * 2.0 ** -50 * (255.0 * scale / 2.0) * np.asarray(msig, dtype=np.float64) * float(np.max(np.abs(p))) / math.sqrt(N)
+    """the contract: N 2^-50 (255 scale / 2) msig[m] max|p| / sqrt(N), max|p| not below 2^E_MIN"""
+    amax = max(float(np.max(np.abs(p))), FLOOR)
+    return N * 2.0 ** -50 * (255.0 * scale / 2.0) * np.asarray(msig, dtype=np.float64) * amax / math.sqrt(N)
 
 
 def ax_bound(N, M, scale, msig, x):
-    """the contract: M 2^-50 (255 scale / 2) max|msig x| / sqrt(N)"""
-    return M * 2.0 ** -50 * (255.0 * scale / 2.0) * float(np.max(np.abs(np.asarray(msig, dtype=np.float64) * x))) / math.sqrt(N)
+    """the contract: M 2^-50 (255 scale / 2) max|msig x| / sqrt(N), the weight scale max|msig x| not below 2^E_MIN"""
+    amax = float(np.max(np.abs(np.asarray(msig, dtype=np.float64) * x)))
+    if scale * amax < FLOOR:
+        amax = FLOOR / scale
+    return M * 2.0 ** -50 * (255.0 * scale / 2.0) * amax / math.sqrt(N)
 
 
 # ---- inputs of the int32-bound tests: one digit plane is -128 at EVERY K-entry, so a row of code 0 (operand byte -128) gains +16 384

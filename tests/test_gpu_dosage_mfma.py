@@ -237,7 +237,7 @@ def test_atx_past_the_int32_bound_flushes_its_accumulators():
             sh.upload_dosage(B, SCALE)
             sh.compute_markers_statistics()
             assert sh.dosage_route() == (1, 1)
-            msig = sh.marker_stats()[1]
+            mave, msig = sh.marker_stats()
             pp = np.zeros(4 * sh.mbytes)
             pp[:N] = p
             outs.append(sh.ATx(pp))
@@ -247,6 +247,9 @@ def test_atx_past_the_int32_bound_flushes_its_accumulators():
           % (gd.rel(w, rw), float(np.max(ew / bw)), w[3], w[5]))
     assert np.all(ew <= bw) and gd.rel(w, rw) < 1e-13
     assert np.array_equal(outs[0], outs[1])
+    # and bit for bit what the integer restatement (unsegmented, exact) gives
+    assert np.array_equal(mave, SCALE * fx.code_mean(B))
+    assert np.array_equal(w, fx.atx(B, fx.code_mean(B), msig, SCALE, p))
 
 
 def test_ax_past_the_int32_bound_flushes_its_accumulators():
@@ -262,7 +265,7 @@ def test_ax_past_the_int32_bound_flushes_its_accumulators():
             sh.upload_dosage(B, SCALE)
             sh.compute_markers_statistics()
             assert sh.dosage_route() == (1, 1)
-            msig = sh.marker_stats()[1]
+            mave, msig = sh.marker_stats()
             assert np.all(msig[~ordinary] == 1.0)
             x = c / (msig * SCALE)
             outs.append(sh.Ax(x))
@@ -277,6 +280,9 @@ def test_ax_past_the_int32_bound_flushes_its_accumulators():
     print("Ax rel %.3e  worst error %.3e  bound %.3e" % (gd.rel(z, rz), float(ez.max()), bz))
     assert np.all(ez <= bz) and gd.rel(z, rz) < 1e-13 and np.all(z[N:] == 0.0)
     assert np.array_equal(outs[0], outs[1])
+    # and bit for bit what the integer restatement (unsegmented, exact) gives
+    assert np.array_equal(mave, SCALE * fx.code_mean(B))
+    assert np.array_equal(z[:N], fx.ax(B, fx.code_mean(B), msig, SCALE, x))
 
 
 # ---- 5. fallbacks -----------------------------------------------------------------------------------------------------------------
