@@ -31,6 +31,7 @@ EXPORTS = [
     "gv_set_dosage_missing", "gv_synth_dosage_na", "gv_dosage_info", "gv_marker_counts",
     "gv_set_dosage_route", "gv_get_dosage_route",
     "gv_ld_scores", "gv_ld_band", "gv_ld_info", "gv_ld_scores_pos", "gv_ld_last_passes",
+    "gv_ld_clump", "gv_ld_clump_last", "gv_ld_clump_seconds",
     "gv_set_ld_dosage", "gv_get_ld_dosage",
     "gv_synth_dosage_ld",
 ]
@@ -204,6 +205,9 @@ def load():
     L.gv_ld_info.argtypes = [vp, C.POINTER(LdStats)]
     L.gv_ld_scores_pos.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, dp]
     L.gv_ld_last_passes.argtypes = [vp, C.POINTER(C.c_int)]
+    L.gv_ld_clump.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), dp, C.c_double, C.c_double, C.c_double, C.POINTER(i64), C.POINTER(i64)]
+    L.gv_ld_clump_last.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]
+    L.gv_ld_clump_seconds.argtypes = [vp, dp, dp]
     L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
     L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
@@ -583,6 +587,30 @@ class Shard:
         k = C.c_int(0)
         self._ck(self.L.gv_ld_last_passes(self.h, C.byref(k)))
         return k.value
+
+    def ld_clump(self, pos, radius, p, p1, p2, r2, chrom=None):
+        """gv_ld_clump: (index_of int64[M], n_index) -- the index marker of every marker's clump (itself for an index marker, -1 for a
+        marker in no clump) over the band |pos_k - pos_j| <= radius on the same chromosome: index candidates p <= p1, members p <= p2,
+        adjacency r^2 >= r2.  pos=None / p=None pass NULL (refused)."""
+        M = self.M
+        ps = None if pos is None else np.ascontiguousarray(pos, dtype=np.float64)
+        pv = None if p is None else np.ascontiguousarray(p, dtype=np.float64)
+        assert (ps is None or ps.size == M) and (pv is None or pv.size == M)
+        out = np.full(max(M, 1), -1, dtype=np.int64)
+        n = C.c_int64(0)
+        ch, chp = self._chrom(chrom)
+        self._ck(self.L.gv_ld_clump(self.h, None if ps is None else _dp(ps), float(radius), chp, None if pv is None else _dp(pv), float(p1),
+                                    float(p2), float(r2), out.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n)))
+        return out[:M].copy(), n.value
+
+    def ld_clump_last(self):
+        """gv_ld_clump_last and gv_ld_clump_seconds of the last ld_clump: the rounds of the selection, |E1|, |E2|, and the seconds of the
+        block pass and of the selection"""
+        k, n1, n2 = C.c_int(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.gv_ld_clump_last(self.h, C.byref(k), C.byref(n1), C.byref(n2)))
+        tb, ts = C.c_double(0.0), C.c_double(0.0)
+        self._ck(self.L.gv_ld_clump_seconds(self.h, C.byref(tb), C.byref(ts)))
+        return {"rounds": k.value, "n_e1": n1.value, "n_e2": n2.value, "block_seconds": tb.value, "select_seconds": ts.value}
 
     def ld_band(self, window, j0, nj, chrom=None):
         """gv_ld_band: nj x (2 * window + 1) correlations of the local markers [j0, j0 + nj); column window + d is r[j][j + d],

@@ -189,6 +189,11 @@ struct gv_ctx {
     // per context; a memory budget, not a tuned number) and the passes the last LD call took (gv_ld_last_passes)
     double ld_part_bytes = 2147483648.0;
     int ld_last_passes = 0;
+    // gv_ld_clump: the rounds of the selection, |E1| and |E2| of the last call (gv_ld_clump_last), and the
+    // seconds of its block pass and of its selection (gv_ld_clump_seconds)
+    int clump_rounds = 0;
+    int64_t clump_n_e1 = 0, clump_n_e2 = 0;
+    double clump_block_s = 0.0, clump_select_s = 0.0;
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;

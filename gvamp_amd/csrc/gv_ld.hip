@@ -13,6 +13,9 @@
 //   k_ld_finish  l_j = 1 + the 2D + 1 block partials of marker j in ascending block order
 // gv_ld_scores_pos (section 19): the band of a marker from its position (hi[], gv_ld_window.h) and scores per annotation category -- the
 // EP_POS epilogue of k_ld_block and k_ld_finish_pos, in passes over row groups that keep the partials within a memory budget.
+// gv_ld_clump (section 20): LD clumping of association results over the same band -- the EP_ADJ epilogue of k_ld_block thresholds r * r
+// into bit words over a list of blocks filtered by eligibility (gv_ld_clump.h), k_clump_round picks the index markers in rounds that
+// decide only what is certain, k_clump_assign names every marker's index.
 // Integer sums, then a fixed fp64 order, no atomics: the results do not depend on the layout, the kernel mode or the launch.
 // Second part (k_ldd_*, ldd_run): the same two entry points on resident 8-bit dosage codes, opt-in (gv_set_ld_dosage; section 17) -- the
 // centred product of two markers in exact 128-bit integers, one correctly rounded conversion.  The same block kernel with a Gram epilogue
@@ -22,6 +25,7 @@
 #include <cmath>
 
 #include "gv_internal.h"
+#include "gv_ld_clump.h"
 #include "gv_ld_window.h"
 
 namespace {
@@ -40,6 +44,7 @@ constexpr int LDD_KSTEP = 128;
 static_assert((gvdm::SEG_MAX / LDD_KSTEP) * LDD_KSTEP * 128 * 128 <= 2147483647LL, "an int32 sum over one segment must fit");
 constexpr int64_t LD_WINDOW_MAX = 8192;
 constexpr int LD_PITCH = 65;     // doubles per row of the scores epilogue's 64 x 64 LDS image (odd: row and column walks spread over the banks)
+constexpr int ADJ_PITCH = 68;    // bytes per row of the clumping epilogue's 64 x 64 predicate image (17 dwords: a column walk spreads over the banks)
 
 // THE bit recipe of the two integer planes of 16 entries, P = present and phenotyped, V = a P.  w holds r' = 2, 1, 0 for a = 2, 1, 0 and
 // 3 for a missing genotype (0 at pad): bit 2q of pm is P of entry q, bits 2q + 1 and 2q of vb are its V.
@@ -164,9 +169,13 @@ struct LdArgs {
     double* cpart;
     int* ccnt;
     const int* pairs;               // the blocks of the launch, (I, J) of block blockIdx.x: a 1-D grid over the blocks that hold an in-band pair
+    // clumping (EP_ADJ, section 20): hi, dmax and pairs as above
+    const int* crank;               // M: the rank of a marker of E2 in the order of (p, index), -1 outside E2 (gv_ld_clump.h)
+    double r2;                      // the threshold on r * r
+    uint64_t* adjw;                 // [nrg][2 dmax + 1][64] adjacency words, slot dmax + (other row group - own), zeroed before the launch
 };
 
-enum { EP_SCORES, EP_BAND, EP_GRAM, EP_POS };     // the epilogues of k_ld_block
+enum { EP_SCORES, EP_BAND, EP_GRAM, EP_POS, EP_ADJ };     // the epilogues of k_ld_block
 
 // f(r^2) of the LD score
 __device__ __forceinline__ double ld_f(double r, int adjusted, double nm2) {
@@ -234,18 +243,20 @@ __device__ __forceinline__ void ld_gram_store(const A& a, int64_t m, int64_t k, 
 
 // block (I = I0 + blockIdx.x, J = I + blockIdx.y).  EP_BAND: store r of the requested rows; EP_SCORES: the block's row / column sums;
 // EP_GRAM: the block's entries of the window Grams; EP_POS: the band is k <= hi[m] (section 19), the block's row / column sums per
-// annotation category; the launch is a 1-D grid over a host-built list of the blocks that hold an in-band pair.
+// annotation category; the launch is a 1-D grid over a host-built list of the blocks that hold an in-band pair.  EP_ADJ (section 20): the
+// band and the list of EP_POS, r of EP_BAND; the block's 64 x 64 adjacency predicate as 64 row words and, for I < J, 64 column words.
 template <int LAYOUT, int EP>
 __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
     // operand images of one half K-block: [side: I, J][16-marker tile][K-step of the half][plane V, P][lane] x 16 bytes = 32 KiB;
     // the scores epilogue reuses the space for the block's 64 x 64 values of f(r^2)
     constexpr int OP_BYTES = 2 * 4 * 2 * 2 * 64 * 16, EP_BYTES = 64 * LD_PITCH * 8;
     constexpr bool LD = EP != EP_GRAM;      // r needs the diagonal and the chromosomes; a Gram entry neither
-    constexpr bool CH = LD && EP != EP_POS;     // (the positional band has the chromosomes folded into hi)
+    constexpr bool POSW = EP == EP_POS || EP == EP_ADJ;     // the band by hi[] over the list of blocks
+    constexpr bool CH = LD && !POSW;            // (the positional band has the chromosomes folded into hi)
     __shared__ __attribute__((aligned(16))) char lds[(EP == EP_SCORES || EP == EP_POS) && EP_BYTES > OP_BYTES ? EP_BYTES : OP_BYTES];
     v4i* op = reinterpret_cast<v4i*>(lds);
     int64_t I = a.I0 + blockIdx.x, J = I + blockIdx.y;
-    if constexpr (EP == EP_POS) {
+    if constexpr (POSW) {
         I = a.pairs[2 * blockIdx.x];
         J = a.pairs[2 * blockIdx.x + 1];
     }
@@ -324,7 +335,9 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
         const double mk = kin ? a.mave[k] : 0.0, sk = kin ? a.msig[k] : 0.0, ck = LD && kin ? a.cdiag[k] : 0.0;
         const int chk = CH && kin && a.chrom ? a.chrom[k] : 0;
         int64_t hik = 0;
-        if constexpr (EP == EP_POS) hik = kin ? a.hi[k] : 0;
+        if constexpr (POSW) hik = kin ? a.hi[k] : 0;
+        bool ek = false;
+        if constexpr (EP == EP_ADJ) ek = kin && a.crank[k] >= 0;
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
@@ -344,7 +357,7 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                 }
                 const int64_t dist = k - m;
                 bool inband;
-                if constexpr (EP == EP_POS) {
+                if constexpr (POSW) {
                     const int64_t him = min_ ? a.hi[m] : 0;
                     inband = min_ && kin && (m <= k ? k <= him : m <= hik);      // (k <= hi_m <=> m >= lo_k)
                 }
@@ -366,6 +379,10 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
                         if (m >= a.j0 && m < a.j0 + a.nj) a.band[(m - a.j0) * w + a.B + dist] = r;
                         if (I != J && k >= a.j0 && k < a.j0 + a.nj) a.band[(k - a.j0) * w + a.B - dist] = r;     // the mirror image
                     }
+                } else if constexpr (EP == EP_ADJ) {
+                    // adj(m, k): in the band, not the marker itself, both polymorphic, both in E2, r * r >= r2 on the bits of EP_BAND
+                    const bool em = min_ && a.crank[m] >= 0;
+                    reinterpret_cast<unsigned char*>(lds)[il * ADJ_PITCH + kl] = inband && poly && m != k && em && ek && r * r >= a.r2;
                 } else {
                     // a term of l_m (and, mirrored, of l_k): in the band, not the marker itself, both polymorphic; NaN = no term
                     fl[il * LD_PITCH + kl] = inband && poly && m != k ? ld_f(r, a.adjusted, a.nm2) : __builtin_nan("");
@@ -375,6 +392,24 @@ __global__ __launch_bounds__(256) void k_ld_block(const LdArgs a) {
     if constexpr (EP == EP_POS) {
         __syncthreads();
         ld_pos_sums(a, fl, I, J, tid);
+        return;
+    }
+    if constexpr (EP == EP_ADJ) {
+        __syncthreads();
+        // wave w forms the words of the rows and of the columns 16 w + [0, 16): one wave64 ballot per word, lane t voting bit t.  Lane i
+        // keeps row word i, lane 16 + i column word i, and the 16 (or 32) lanes store them side by side.
+        const unsigned char* pb = reinterpret_cast<const unsigned char*>(lds);
+        uint64_t word = 0;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int e = 16 * wave + i;
+            const uint64_t rw = __ballot(pb[e * ADJ_PITCH + lane] != 0), cw = __ballot(pb[lane * ADJ_PITCH + e] != 0);
+            if (lane == i) word = rw;
+            if (lane == 16 + i) word = cw;
+        }
+        const int64_t nsl = 2 * a.dmax + 1, d = J - I;
+        if (lane < 16) a.adjw[((I * nsl + a.dmax + d) * 64) + 16 * wave + lane] = word;
+        else if (lane < 32 && I != J) a.adjw[((J * nsl + a.dmax - d) * 64) + 16 * wave + lane - 16] = word;
         return;
     }
     if (EP != EP_SCORES) return;
@@ -461,6 +496,78 @@ __global__ __launch_bounds__(256) void k_ld_finish_pos(const double* __restrict_
     }
     run[j * C + c] = s;
     if (c == 0) nrun[j] += (double)n;
+}
+
+// The selection of the index markers (section 20).  state[j]: UNDECIDED, INDEX or CLAIMED, written once.  The words of marker j are the
+// 2 dmax + 1 slots adjw[j / 64][.][j % 64]; bit t of slot s names marker 64 (j / 64 + s - dmax) + t (a slot whose row group does not
+// exist was never written: zero).
+enum { CL_UNDECIDED = 0, CL_INDEX = 1, CL_CLAIMED = 2 };
+
+// One round, thread q for the marker of rank q (the markers of E1 are the ranks [0, n_e1)): still undecided, it becomes claimed if a
+// neighbour of lower rank is an index, an index if every neighbour of lower rank is claimed, and waits otherwise -- a decision is taken
+// only when no later state of a neighbour can change it, so a neighbour's state read while its thread writes it gives the same end.  (A
+// neighbour of lower rank is in E1 itself.)  left counts the markers that wait.
+__global__ __launch_bounds__(256) void k_clump_round(const uint64_t* __restrict__ adjw, const int* __restrict__ order, const int* __restrict__ crank,
+                                                     int64_t n_e1, int dmax, int64_t nrg, int* state, int* __restrict__ left) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_e1) return;
+    const int64_t j = order[q], R = j >> 6;
+    if (__atomic_load_n(&state[j], __ATOMIC_RELAXED) != CL_UNDECIDED) return;
+    const int nsl = 2 * dmax + 1;
+    const uint64_t* w = adjw + (R * nsl) * 64 + (j & 63);
+    bool wait = false;
+    for (int s = 0; s < nsl; s++) {
+        const int64_t Rk = R + s - dmax;
+        if (Rk < 0 || Rk >= nrg) continue;
+        uint64_t bits = w[(int64_t)s * 64];
+        while (bits) {
+            const int t = __builtin_ctzll(bits);
+            bits &= bits - 1;
+            const int64_t k = Rk * 64 + t;
+            if (crank[k] >= q) continue;
+            const int st = __atomic_load_n(&state[k], __ATOMIC_RELAXED);
+            if (st == CL_INDEX) {
+                __atomic_store_n(&state[j], (int)CL_CLAIMED, __ATOMIC_RELAXED);
+                return;
+            }
+            wait |= st == CL_UNDECIDED;
+        }
+    }
+    if (wait) atomicAdd(left, 1);
+    else __atomic_store_n(&state[j], (int)CL_INDEX, __ATOMIC_RELAXED);
+}
+
+// index_of of every marker once no marker of E1 is undecided: -1 outside E2, itself for an index, else the index of the lowest rank
+// among its neighbours, else -1
+__global__ __launch_bounds__(256) void k_clump_assign(const uint64_t* __restrict__ adjw, const int* __restrict__ crank, const int* __restrict__ state,
+                                                      int dmax, int64_t nrg, int64_t M, int64_t* __restrict__ index_of) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    int64_t out = -1;
+    if (crank[j] >= 0) {
+        if (state[j] == CL_INDEX) out = j;
+        else {
+            const int nsl = 2 * dmax + 1;
+            const int64_t R = j >> 6;
+            const uint64_t* w = adjw + (R * nsl) * 64 + (j & 63);
+            int best = 0x7FFFFFFF;
+            for (int s = 0; s < nsl; s++) {
+                const int64_t Rk = R + s - dmax;
+                if (Rk < 0 || Rk >= nrg) continue;
+                uint64_t bits = w[(int64_t)s * 64];
+                while (bits) {
+                    const int t = __builtin_ctzll(bits);
+                    bits &= bits - 1;
+                    const int64_t k = Rk * 64 + t;
+                    if (state[k] == CL_INDEX && crank[k] < best) {
+                        best = crank[k];
+                        out = k;
+                    }
+                }
+            }
+        }
+    }
+    index_of[j] = out;
 }
 
 // =====================================================================================================================================
@@ -1290,7 +1397,173 @@ static int ld_pos_run(gv_ctx* c, const char* who, const gvw::Window& win, int ad
     return 0;
 }
 
+// gv_ld_clump (section 20): the EP_ADJ epilogue over the filtered list of blocks, then the selection in rounds of k_clump_round, then
+// k_clump_assign.  index_of: M host int64.
+static int ld_clump_run(gv_ctx* c, const char* who, const gvw::Window& win, const gvc::Plan& cp, double r2, int64_t* index_of) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const gvm::Plan& pl = c->plan;
+    const int64_t M = c->M, nrg = (M + 63) / 64;
+    const int dmax = (int)win.dmax;
+    constexpr int BATCH = 16;        // rounds between two reads of the undecided counters
+    Scratch w;
+    LdArgs a{};
+    a.lay = reinterpret_cast<const uint4*>(pl.layout == 1 ? pl.tiles : pl.stripes_m);
+    a.nkb = pl.nkb_m;
+    a.mask2 = c->mask2;
+    a.P4 = c->pitch / 4;
+    a.N = c->N;
+    a.M = M;
+    a.nrg = nrg;
+    a.mave = c->mave;
+    a.msig = c->msig;
+    a.dmax = dmax;
+    a.r2 = r2;
+    double* cdiag = nullptr;
+    int64_t *dhi = nullptr, *dindex = nullptr;
+    int *dpairs = nullptr, *drank = nullptr, *dorder = nullptr, *dstate = nullptr, *dleft = nullptr;
+    const size_t nwords = (size_t)nrg * (size_t)(2 * dmax + 1) * 64;
+#define LDALLOC(p, n)                                                                                                          \
+    do {                                                                                                                       \
+        if (w.get(&p, n) != hipSuccess) {                                                                                      \
+            (void)hipGetLastError();                                                                                           \
+            return fail(c, "%s: cannot allocate %zu bytes of device scratch (%zu already held by this call)", who, sizeof(*p) * (size_t)(n), w.bytes); \
+        }                                                                                                                      \
+    } while (0)
+    LDALLOC(cdiag, (size_t)M);
+    LDALLOC(dhi, (size_t)M);
+    LDALLOC(drank, (size_t)M);
+    LDALLOC(dorder, (size_t)cp.n_e1);
+    LDALLOC(dstate, (size_t)M);
+    LDALLOC(dleft, (size_t)BATCH);
+    LDALLOC(dindex, (size_t)M);
+    LDALLOC(dpairs, cp.pairs.size());
+    LDALLOC(a.adjw, nwords);
+#undef LDALLOC
+    a.cdiag = cdiag;
+    a.hi = dhi;
+    a.pairs = dpairs;
+    a.crank = drank;
+    HIPCHK(c, hipMemcpyAsync(dhi, win.hi.data(), sizeof(int64_t) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(drank, cp.rank.data(), sizeof(int) * (size_t)M, hipMemcpyHostToDevice, c->stream));
+    if (cp.n_e1) HIPCHK(c, hipMemcpyAsync(dorder, cp.order.data(), sizeof(int) * (size_t)cp.n_e1, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dstate, 0, sizeof(int) * (size_t)M, c->stream));
+    // (the words of the blocks that are not launched read as no edge)
+    HIPCHK(c, hipMemsetAsync(a.adjw, 0, sizeof(uint64_t) * nwords, c->stream));
+    const int64_t blocks = (int64_t)(cp.pairs.size() / 2);
+    if (blocks) {
+        if (pl.layout == 1)
+            hipLaunchKernelGGL(k_ld_diag<1>, dim3((unsigned)nrg), dim3(256), 0, c->stream, a.lay, a.nkb, a.mask2, a.P4, a.N, M, a.mave, a.msig, cdiag);
+        else
+            hipLaunchKernelGGL(k_ld_diag<2>, dim3((unsigned)nrg), dim3(256), 0, c->stream, a.lay, a.nkb, a.mask2, a.P4, a.N, M, a.mave, a.msig, cdiag);
+        KCHK(c);
+        HIPCHK(c, hipMemcpyAsync(dpairs, cp.pairs.data(), sizeof(int) * cp.pairs.size(), hipMemcpyHostToDevice, c->stream));
+        if (pl.layout == 1) hipLaunchKernelGGL((k_ld_block<1, EP_ADJ>), dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_ld_block<2, EP_ADJ>), dim3((unsigned)blocks), dim3(256), 0, c->stream, a);
+        KCHK(c);
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const auto t1 = std::chrono::steady_clock::now();
+    // the rounds: the undecided marker of the lowest rank is decided in every round, so |E1| rounds decide them all
+    int64_t rounds = 0;
+    int left[BATCH] = {0};
+    bool open = cp.n_e1 > 0;
+    while (open) {
+        if (rounds > cp.n_e1)
+            return fail(c, "%s: the selection has not finished after %lld rounds over %lld index candidates (%d still undecided): this cannot "
+                           "happen", who, (long long)rounds, (long long)cp.n_e1, left[BATCH - 1]);
+        HIPCHK(c, hipMemsetAsync(dleft, 0, sizeof(int) * BATCH, c->stream));
+        for (int b = 0; b < BATCH; b++) {
+            hipLaunchKernelGGL(k_clump_round, dim3((unsigned)((cp.n_e1 + 255) / 256)), dim3(256), 0, c->stream, a.adjw, dorder, drank, cp.n_e1, dmax, nrg,
+                               dstate, dleft + b);
+            KCHK(c);
+        }
+        HIPCHK(c, hipMemcpyAsync(left, dleft, sizeof(int) * BATCH, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int b = 0; b < BATCH && open; b++) {
+            rounds++;
+            open = left[b] != 0;
+        }
+    }
+    hipLaunchKernelGGL(k_clump_assign, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, a.adjw, drank, dstate, dmax, nrg, M, dindex);
+    KCHK(c);
+    HIPCHK(c, hipMemcpyAsync(index_of, dindex, sizeof(int64_t) * (size_t)M, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const auto t2 = std::chrono::steady_clock::now();
+    c->ld_last.seconds = std::chrono::duration<double>(t2 - t0).count();
+    c->ld_last.block_pairs = blocks;
+    c->ld_last.useful_macs = 4.0 * (double)c->N * cp.pairs_e2;
+    c->ld_last.scratch_bytes = (double)w.bytes;
+    c->ld_last_passes = 1;
+    c->clump_rounds = (int)rounds;
+    c->clump_n_e1 = cp.n_e1;
+    c->clump_n_e2 = cp.n_e2;
+    c->clump_block_s = std::chrono::duration<double>(t1 - t0).count();
+    c->clump_select_s = std::chrono::duration<double>(t2 - t1).count();
+    return 0;
+}
+
+// the refusals of a positional window (gv_ld_scores_pos, gv_ld_clump)
+static int ld_window_check(gv_ctx* c, const char* who, const gvw::Window& win, const double* pos, const int* chrom) {
+    const long long at = (long long)win.at;
+    switch (win.verdict) {
+        case gvw::OK: break;
+        case gvw::POS_NOT_FINITE: return fail(c, "%s: pos[%lld] is not finite", who, at);
+        case gvw::POS_DECREASES:
+            return fail(c, "%s: pos[%lld] = %.17g is below pos[%lld] = %.17g on the same chromosome: positions must not decrease", who, at, pos[at],
+                        at - 1, pos[at - 1]);
+        case gvw::CHROM_REAPPEARS:
+            return fail(c, "%s: chromosome id %d reappears at marker %lld after its run has ended: every chromosome must be one contiguous run", who,
+                        chrom[at], at);
+        case gvw::REACH_TOO_LONG:
+            return fail(c, "%s: marker %lld reaches %lld markers ahead, more than the %lld a band may (a smaller radius, or gv_ld_scores)", who, at,
+                        (long long)win.reach, (long long)LD_WINDOW_MAX);
+    }
+    return 0;
+}
+
 extern "C" {
+
+int gv_ld_clump(gv_ctx* c, const double* pos, double radius, const int* chrom, const double* p, double p1, double p2, double r2,
+                int64_t* index_of, int64_t* n_index) {
+    const char* who = "gv_ld_clump";
+    if (c->dense.resident && c->dense.bits)
+        return fail(c, "%s: bed data only for now: compact dosage data (%d-bit codes) are not served by this entry point, with or without "
+                       "gv_set_ld_dosage", who, c->dense.bits);
+    if (planes_check(c, who, "LD is computed from 2-bit genotypes only")) return 1;
+    NEED(c, pos, "gv_ld_clump: pos is NULL");
+    NEED(c, p, "gv_ld_clump: p is NULL");
+    NEED(c, index_of, "gv_ld_clump: index_of is NULL");
+    if (!std::isfinite(radius) || radius < 0.0) return fail(c, "%s: radius must be finite and >= 0 (%g was passed)", who, radius);
+    if (!std::isfinite(p1) || !std::isfinite(p2)) return fail(c, "%s: p1 and p2 must be finite (%g and %g were passed)", who, p1, p2);
+    if (!std::isfinite(r2)) return fail(c, "%s: r2 must be finite (%g was passed)", who, r2);
+    if (p1 > p2) return fail(c, "%s: p1 must not exceed p2 (%g > %g): an index marker is a member too", who, p1, p2);
+    if (p1 < 0.0) return fail(c, "%s: p1 must be >= 0 (%g was passed)", who, p1);
+    if (r2 < 0.0 || r2 > 1.0) return fail(c, "%s: r2 must be in [0, 1] (%g was passed)", who, r2);
+    const gvw::Window win = gvw::make_window(pos, chrom, radius, c->M, LD_WINDOW_MAX);
+    if (ld_window_check(c, who, win, pos, chrom)) return 1;
+    if (c->M == 0) return 0;
+    const gvc::Plan cp = gvc::make_plan(p, p1, p2, win.hi.data(), win.dmax, c->M);
+    if (ld_clump_run(c, who, win, cp, r2, index_of)) return 1;
+    if (n_index) {
+        int64_t n = 0;
+        for (int64_t j = 0; j < c->M; j++) n += index_of[j] == j;
+        *n_index = n;
+    }
+    return 0;
+}
+
+int gv_ld_clump_last(const gv_ctx* c, int* rounds, int64_t* n_e1, int64_t* n_e2) {
+    if (rounds) *rounds = c->clump_rounds;
+    if (n_e1) *n_e1 = c->clump_n_e1;
+    if (n_e2) *n_e2 = c->clump_n_e2;
+    return 0;
+}
+
+int gv_ld_clump_seconds(const gv_ctx* c, double* block_pass, double* selection) {
+    if (block_pass) *block_pass = c->clump_block_s;
+    if (selection) *selection = c->clump_select_s;
+    return 0;
+}
 
 int gv_ld_scores_pos(gv_ctx* c, const double* pos, double radius, const int* chrom, int adjusted, const double* annot, int ncat, double* l2,
                      double* npairs) {
@@ -1306,20 +1579,7 @@ int gv_ld_scores_pos(gv_ctx* c, const double* pos, double radius, const int* chr
     if (!std::isfinite(radius) || radius < 0.0) return fail(c, "%s: radius must be finite and >= 0 (%g was passed)", who, radius);
     if (annot && (ncat < 1 || ncat > 512)) return fail(c, "%s: ncat must be in [1, 512] when annot is given (%d was passed)", who, ncat);
     const gvw::Window win = gvw::make_window(pos, chrom, radius, c->M, LD_WINDOW_MAX);
-    const long long at = (long long)win.at;
-    switch (win.verdict) {
-        case gvw::OK: break;
-        case gvw::POS_NOT_FINITE: return fail(c, "%s: pos[%lld] is not finite", who, at);
-        case gvw::POS_DECREASES:
-            return fail(c, "%s: pos[%lld] = %.17g is below pos[%lld] = %.17g on the same chromosome: positions must not decrease", who, at, pos[at],
-                        at - 1, pos[at - 1]);
-        case gvw::CHROM_REAPPEARS:
-            return fail(c, "%s: chromosome id %d reappears at marker %lld after its run has ended: every chromosome must be one contiguous run", who,
-                        chrom[at], at);
-        case gvw::REACH_TOO_LONG:
-            return fail(c, "%s: marker %lld reaches %lld markers ahead, more than the %lld a band may (a smaller radius, or gv_ld_scores)", who, at,
-                        (long long)win.reach, (long long)LD_WINDOW_MAX);
-    }
+    if (ld_window_check(c, who, win, pos, chrom)) return 1;
     if (c->M == 0) {
         c->ld_last = gv_ld_stats{};
         c->ld_last_passes = 0;

@@ -493,6 +493,21 @@ std::vector<std::vector<double>> data::ld_scores_pos_dev(const std::vector<doubl
     return res;
 }
 
+std::vector<int64_t> data::ld_clump_dev(const std::vector<double>& pos, double radius, const std::vector<double>& p, double p1, double p2,
+                                        double r2, int64_t* n_index) {
+    const size_t Mp = M > 0 ? M : 1;
+    std::vector<int64_t> index_of(Mp, -1);
+    std::vector<int> ch_info;
+    if (bimfp != "") {
+        ch_info = read_chromosome_info(bimfp);
+        ch_info.resize(Mp, 0);
+    }
+    ck(ctx, gv_ld_clump(ctx, pos.data(), radius, ch_info.empty() ? nullptr : ch_info.data(), p.data(), p1, p2, r2, index_of.data(), n_index),
+       "gv_ld_clump");
+    index_of.resize(M > 0 ? M : 0);
+    return index_of;
+}
+
 static std::vector<std::vector<double>> pvals_host(data* d, gv_ctx* ctx, int M, size_t mbytes,
                                                    std::vector<std::vector<double>>& z1, std::vector<double>& y,
                                                    std::vector<std::vector<double>>& x1_hat, bool loco,

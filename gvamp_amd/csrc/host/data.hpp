@@ -104,6 +104,10 @@ public:
     std::vector<double> read_annot(std::string path, int M, std::vector<std::string>* names);
     // [ext] gv_ld_scores_pos: {l2 (M x max(ncat, 1) row-major), npairs (M)}; annot empty = no annotation; per chromosome when a .bim
     // file was given
+    // [ext] gv_ld_clump: index_of of every marker (local indices, -1 = in no clump) and the number of index
+    // markers; per chromosome when a .bim file was given
+    std::vector<int64_t> ld_clump_dev(const std::vector<double>& pos, double radius, const std::vector<double>& p, double p1, double p2,
+                                      double r2, int64_t* n_index);
     std::vector<std::vector<double>> ld_scores_pos_dev(const std::vector<double>& pos, double radius, bool adjusted,
                                                        const std::vector<double>& annot, int ncat);
 };

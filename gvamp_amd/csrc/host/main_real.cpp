@@ -1,11 +1,13 @@
 // main_real.cpp -- real-data driver mirroring the reference's main_real.cpp:13-599, all run modes:
 //   infere (:34-128), test (:129-213), both (:214-283), pvals-calc (:284-368), restart (:369-385),
-//   predict (:386-437), predict_single (:438-594); [ext] ldscore (gv_ld_scores).
+//   predict (:386-437), predict_single (:438-594); [ext] ldscore (gv_ld_scores), clump (gv_ld_clump, section 20).
 // Every mode is "load data, maybe run vamp::infere, one or more data::Ax, a reduction, a file": the matvecs are HIP
 // kernels behind libgvamp, the rest is host code.  One process per GPU (RANK / WORLD_SIZE from the launcher).
+#include <algorithm>
 #include <cmath>
 #include <fstream>
 #include <iostream>
+#include <sstream>
 
 #include "data.hpp"
 #include "options.hpp"
@@ -280,6 +282,118 @@ int main(int argc, char** argv) {
             std::cout << (opt.get_ld_adjust() ? " (adjusted)" : "") << ", " << Mt << " markers, " << C << (C == 1 ? " category, " : " categories, ")
                       << st.seconds << " seconds" << std::endl;
         }
+    } else if (mode == "clump") {                                                      // [ext] DESIGN.md section 20
+        // LD clumping of association results: the markers of p <= --clump-p1 in ascending p become index markers unless an earlier one
+        // has claimed them; an index marker claims the markers of p <= --clump-p2 in its window with r^2 >= --clump-r2
+        if (type_data != "bed") {
+            std::cout << "FATAL: --run-mode clump works on 2-bit genotypes only, not on --geno-format " << type_data << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (gv_env_nranks() > 1) {
+            std::cout << "FATAL: --run-mode clump runs on one rank: the band stops at a shard's edges, so the clumps of a sharded job "
+                         "would miss their members across them" << std::endl;
+            return EXIT_FAILURE;
+        }
+        const bool given_kb = opt.get_clump_kb() >= 0 || opt.get_ld_wind_kb() >= 0, by_cm = opt.get_ld_wind_cm() >= 0;
+        const int windows = opt.count_ld_windows() + (opt.get_clump_kb() >= 0 ? 1 : 0);
+        if (windows > 1) {
+            std::cout << "FATAL: exactly one of --clump-kb, --ld-wind-cm and --ld-window may be given" << std::endl;
+            return EXIT_FAILURE;
+        }
+        const bool by_kb = given_kb || windows == 0;            // (no window given: --clump-kb 250)
+        const double kb = opt.get_clump_kb() >= 0 ? opt.get_clump_kb() : (opt.get_ld_wind_kb() >= 0 ? opt.get_ld_wind_kb() : 250.0);
+        if ((by_kb || by_cm) && bimfp == "") {
+            std::cout << "FATAL: " << (by_kb ? "--clump-kb" : "--ld-wind-cm") << " needs --bim-file: the positions are its "
+                      << (by_kb ? "base-pair" : "cM") << " column" << std::endl;
+            return EXIT_FAILURE;
+        }
+        const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
+        const std::string pfile = opt.get_clump_p_file();
+        if (pfile == "") {
+            std::cout << "FATAL: --run-mode clump needs --clump-p-file: " << Mt << " raw float64 p-values, the format of <out>_assoc_p.bin" << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::vector<double> p((size_t)Mt, 0.0);
+        {
+            std::ifstream fp(pfile, std::ios::binary | std::ios::ate);
+            if (!fp.is_open()) {
+                std::cout << "FATAL: cannot open the p file " << pfile << std::endl;
+                return EXIT_FAILURE;
+            }
+            const long long bytes = (long long)fp.tellg();
+            if (bytes < 8LL * Mt) {
+                std::cout << "FATAL: the p file " << pfile << " holds " << bytes << " bytes, fewer than the " << 8LL * Mt << " of " << Mt
+                          << " float64 values" << std::endl;
+                return EXIT_FAILURE;
+            }
+            fp.seekg(0);
+            fp.read(reinterpret_cast<char*>(p.data()), 8LL * Mt);
+        }
+        need_phen(opt.get_phen_files(), "--phen-files");
+        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, Mt, Mt, 0, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
+        std::vector<double> pos;
+        double radius = (double)opt.get_ld_window();
+        if (by_kb) {
+            pos = dataset.read_positions(bimfp, "bp");
+            radius = 1000.0 * kb;
+        } else if (by_cm) {
+            pos = dataset.read_positions(bimfp, "cm");
+            radius = opt.get_ld_wind_cm();
+        } else
+            for (int j = 0; j < Mt; j++) pos.push_back((double)j);
+        // the marker ids and chromosomes of the report: columns 2 and 1 of the .bim file, or m<j> and 0 without one
+        std::vector<std::string> ids, chr;
+        if (bimfp != "") {
+            std::ifstream fb(bimfp);
+            std::string c1, c2, line;
+            while ((int)ids.size() < Mt && getline(fb, line)) {
+                std::istringstream ls(line);
+                ls >> c1 >> c2;
+                chr.push_back(c1);
+                ids.push_back(c2);
+            }
+        }
+        for (int j = (int)ids.size(); j < Mt; j++) {
+            ids.push_back("m" + std::to_string(j));
+            chr.push_back("0");
+        }
+        int64_t n_index = 0;
+        const std::vector<int64_t> index_of =
+            dataset.ld_clump_dev(pos, radius, p, opt.get_clump_p1(), opt.get_clump_p2(), opt.get_clump_r2(), &n_index);
+        gv_ld_stats st;
+        gv_ld_info(dataset.get_ctx(), &st);
+        int rounds = 0;
+        gv_ld_clump_last(dataset.get_ctx(), &rounds, nullptr, nullptr);
+        const std::string pre = opt.get_out_dir() + opt.get_out_name();
+        mpi_store_vec_to_file(pre + "_clump_index.bin", std::vector<double>(index_of.begin(), index_of.end()), 0, Mt);
+        // one line per clump, in the order the index markers were chosen (ascending p, ties by index): the index marker's id, chromosome,
+        // position and p, the number of markers it claimed and their ids
+        std::vector<int> lead;
+        std::vector<std::vector<int>> members((size_t)Mt);
+        for (int j = 0; j < Mt; j++) {
+            if (index_of[j] == j) lead.push_back(j);
+            else if (index_of[j] >= 0) members[(size_t)index_of[j]].push_back(j);
+        }
+        std::stable_sort(lead.begin(), lead.end(), [&](int x, int y) { return p[x] < p[y]; });
+        std::ofstream fc(pre + "_clumps.txt");
+        fc.precision(17);
+        for (int j : lead) {
+            fc << ids[j] << " " << chr[j] << " " << pos[j] << " " << p[j] << " " << members[j].size();
+            for (size_t t = 0; t < members[j].size(); t++) fc << (t ? "," : " ") << ids[members[j][t]];
+            fc << "\n";
+        }
+        fc.close();
+        if (!fc.good()) {
+            std::cout << "FATAL: cannot write " << pre << "_clumps.txt" << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::cout << "LD clumping: window ";
+        if (by_kb) std::cout << kb << " kb";
+        else if (by_cm) std::cout << opt.get_ld_wind_cm() << " cM";
+        else std::cout << opt.get_ld_window();
+        std::cout << ", p1 " << opt.get_clump_p1() << ", p2 " << opt.get_clump_p2() << ", r2 " << opt.get_clump_r2() << ", " << Mt << " markers, "
+                  << st.seconds << " seconds, " << n_index << " clumps, " << rounds << " rounds, " << st.block_pairs << " blocks launched"
+                  << std::endl;
     } else if (mode == "predict" || mode == "predict_single") {                        // :386-594
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);

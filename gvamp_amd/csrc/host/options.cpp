@@ -178,6 +178,26 @@ void Options::read_command_line_options(int argc, char** argv) {
     wind("--ld-wind-kb", ld_wind_kb);
     wind("--ld-wind-cm", ld_wind_cm);
     str("--ld-annot", ld_annot);
+    str("--clump-p-file", clump_p_file);
+    auto num = [&](const char* f, double& dst) {          // a whole token as a number (NaN and infinities are the library's to refuse)
+        std::string flag = f;
+        H[f] = [&dst, flag](const char* a) {
+            char* end = nullptr;
+            const double v = strtod(a, &end);
+            if (end == a || *end != 0) fatal("FATAL  : option " + flag + " has to be a number! (" + a + " was passed)");
+            dst = v;
+        };
+    };
+    num("--clump-p1", clump_p1);
+    num("--clump-p2", clump_p2);
+    num("--clump-r2", clump_r2);
+    H["--clump-kb"] = [&](const char* a) {
+        char* end = nullptr;
+        const double v = strtod(a, &end);
+        if (end == a || *end != 0 || !(v >= 0) || v > 1e300)
+            fatal(std::string("FATAL  : option --clump-kb has to be a non-negative number! (") + a + " was passed)");
+        clump_kb = v;
+    };
     H["--ld-adjust"] = [&](const char* a) {
         if (strcmp(a, "0") && strcmp(a, "1"))
             fatal(std::string("FATAL  : option --ld-adjust has to be 0 or 1! (") + a + " was passed)");

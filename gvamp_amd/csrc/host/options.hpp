@@ -59,14 +59,20 @@
        ahead (gv_ld_scores_pos); --ld-annot FILE: one header line, one row per marker, the columns \
        CHR / BP / SNP / CM skipped and every other column an annotation category -- partitioned LD scores, M x C, with    \
        <out>_ldscore_M.txt (the category sums over the polymorphic markers and over those of MAF > 0.05) and            \
-       <out>_ldscore_cats.txt (the names); without a kb / cM window the positions are the marker indices */             \
+       <out>_ldscore_cats.txt (the names); without a kb / cM window the positions are the marker indices;              \
+       --run-mode clump (gv_ld_clump) with --clump-p-file FILE (Mt raw float64, the format of      \
+       <out>_assoc_p.bin), --clump-p1 (default 1e-4: index markers), --clump-p2 (default 1e-2: members), --clump-r2      \
+       (default 0.5) and exactly one window: --clump-kb X (default 250; needs --bim-file), --ld-wind-cm X or --ld-window B \
+       -- LD clumping of association results: <out>_clump_index.bin and <out>_clumps.txt */                             \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
     X(int, cg_precond_window, 128) X(std::string, geno_format, "bed") X(double, dosage_scale, 0) \
     X(unsigned int, store_assoc, 0) X(int, dosage_missing, 0) X(std::string, dosage_kernels, "valu")       \
     X(int, ld_window, 200) X(int, ld_adjust, 0) X(int, ld_dosage, 0)                                                   \
-    X(double, ld_wind_kb, -1) X(double, ld_wind_cm, -1) X(std::string, ld_annot, "")
+    X(double, ld_wind_kb, -1) X(double, ld_wind_cm, -1) X(std::string, ld_annot, "")                                   \
+    X(std::string, clump_p_file, "") X(double, clump_p1, 1e-4) X(double, clump_p2, 1e-2) X(double, clump_r2, 0.5)      \
+    X(double, clump_kb, -1)
 
 class Options {
 public:

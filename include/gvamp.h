@@ -715,6 +715,34 @@ int gv_ld_scores_pos(gv_ctx* ctx, const double* pos /* M */, double radius, cons
                      const double* annot /* M x ncat row-major, or NULL */, int ncat,
                      double* l2 /* M x max(ncat, 1) row-major */, double* npairs /* M or NULL */);
 int gv_ld_last_passes(const gv_ctx* ctx, int* passes);
+/* ---- LD clumping of association results (additions only: GV_ABI_VERSION stays 4) --------------------------------
+ * The data, the planes, C_jk, r_jk and the monomorphic rule are exactly those of gv_ld_scores_pos (a missing genotype counts as the
+ * mean); so are the band (k is in the band of j iff same chromosome and pos_k - pos_j <= radius for j <= k), the conditions on pos and
+ * chrom and the reach limit of 8192.
+ * p: M host doubles (the p-values of the markers); p1 <= p2, finite and >= 0; r2 in [0, 1].
+ *   E2 = { j : p_j <= p2 } may be a member of a clump, E1 = { j : p_j <= p1 } may be its index marker; a NaN p_j is in neither set.
+ *   adj(j, k) iff j != k, k is in the band of j, both markers are polymorphic, both are in E2, and r_jk * r_jk >= r2 -- the product and
+ *   the comparison in fp64 on the very bits gv_ld_band returns for the pair; r_jk and r_kj are the same bits, so adj is symmetric.
+ *   Order: ascending p, equal p by ascending marker index.
+ * Result, the sequential definition: walk E1 in that order; a marker not yet assigned becomes an index marker, index_of[j] = j, and claims
+ * every still unassigned k of E2 with adj(j, k), index_of[k] = j.  Everything else -- the markers outside E2 and those of E2 \ E1 that no
+ * index marker reaches -- gets index_of = -1.  A monomorphic marker of E1 is a clump of one.  n_index (may be NULL) is the number of index
+ * markers.  Indices are local to the shard and the band stops at the shard's edges, as everywhere above.  The result is a function of the
+ * inputs alone: two calls, both layouts and kernel modes 1 and 2 give the same values.
+ * The adjacency is held as bit words, 8 * 64 * (2 dmax + 1) * row groups bytes (dmax as above), allocated for the call and released
+ * after it; only the blocks that hold an in-band pair AND a marker of E2 in both row groups are computed.  gv_ld_info after the call:
+ * seconds, block_pairs = the blocks computed, useful_macs = 4 N x the ordered in-band pairs (j, k) with both in E2, self included, and
+ * the scratch bytes.  gv_ld_clump_last: the rounds the selection of the index markers took (0 with E1 empty; it may depend on the
+ * scheduling of the device, the result does not), |E1| and |E2|; gv_ld_clump_seconds: the block pass and the selection apart.
+ * Refused with a message that names the reason: everything gv_ld_scores_pos refuses (dosage codes with or without gv_set_ld_dosage,
+ * methylation data, raw rows only, statistics not computed, pos == NULL, a non-finite or decreasing position, a chromosome id that
+ * reappears, a reach above 8192, a non-finite or negative radius); p or index_of NULL; p1, p2 or r2 not finite; p1 > p2; p1 < 0; r2
+ * outside [0, 1].  M == 0 returns 0 and touches nothing. */
+int gv_ld_clump(gv_ctx* ctx, const double* pos /* M */, double radius, const int* chrom /* M or NULL */,
+                const double* p /* M */, double p1, double p2, double r2,
+                int64_t* index_of /* M */, int64_t* n_index /* 1, or NULL */);
+int gv_ld_clump_last(const gv_ctx* ctx, int* rounds, int64_t* n_e1, int64_t* n_e2);   /* of the last gv_ld_clump */
+int gv_ld_clump_seconds(const gv_ctx* ctx, double* block_pass, double* selection);    /* of the last gv_ld_clump */
 /* ---- LD of 8-bit dosage codes (additions only: GV_ABI_VERSION stays 4) ----------------------------------------
  * gv_set_ld_dosage(ctx, 1): gv_ld_scores, gv_ld_band and gv_ld_info accept a context whose resident data are 8-bit dosage codes and
  * whose mask is set.  Per context, default 0, it outlives the dataset; with 0 nothing changes by a bit or by a message.  Marker

@@ -20,6 +20,14 @@ random 0 / 1 annotation of C categories at the first --wind-kb (0 = no annotatio
 useful_macs, scratch_bytes and the pass count.
 
     python scripts/bench_ld.py --kind pos --wind-kb 512 2048 --ncat 1 16 64 97 --out profiles/ld_pos_400k_125k.json
+
+--kind clump: gv_ld_clump on the same positions (1 kb between neighbours, the first --wind-kb) with a deterministic
+synthetic p of which a share of 100 %, 5 % and 0.5 % of the markers is eligible (p <= p2 = 0.01; every eligible marker may be an index,
+p1 = p2), in a random order and -- at 100 % -- in the order of the marker index, the deep chain of dependencies.  Per leg: the seconds
+of the call, of its block pass and of its selection, the rounds, the blocks launched against the blocks in band; gv_ld_scores_pos with
+one category on the same window is timed in the same process and round.
+
+    python scripts/bench_ld.py --kind clump --wind-kb 512 --out profiles/ld_clump_400k_125k.json
 """
 import argparse
 import json
@@ -122,11 +130,65 @@ def positional(a):
         f.write("\n")
 
 
+def clump_summary(rows):
+    """the per-round seconds of the scores call and of the 100 % block pass, the speed-up of the smaller shares over the 100 % share
+    (medians of the call's seconds) and the selection's share of the call on the order by marker index"""
+    def med(v):
+        return sorted(v)[len(v) // 2]
+
+    def secs(leg, key="seconds"):
+        return [r[key] for r in rows if r.get("leg", r["call"]) == leg]
+
+    full = "share 1, random order"
+    out = dict(scores_pos_seconds=secs("gv_ld_scores_pos"), clump_full_seconds=secs(full), clump_full_block_seconds=secs(full, "block_seconds"))
+    for share in ("0.05", "0.005"):
+        out["speedup_share_%s" % share] = med(secs(full)) / med(secs("share %s, random order" % share))
+    deep = "share 1, p increasing with the marker index"
+    out["selection_share_of_call_index_order"] = med(secs(deep, "select_seconds")) / med(secs(deep))
+    out["rounds_index_order"] = max(r["rounds"] for r in rows if r.get("leg") == deep)
+    return out
+
+
+def clump(a):
+    import numpy as np
+    M, X = a.M, a.wind_kb[0]
+    pos = 1000.0 * np.arange(M)
+    rng = np.random.default_rng(5)
+    u = rng.random(M)
+    # share -> p: the markers of u below the share get p = 0.01 u / share in (0, 0.01], the others p = 0.5
+    legs = [("share %g, random order" % sh_, sh_, np.where(u < sh_, 0.01 * u / sh_, 0.5)) for sh_ in (1.0, 0.05, 0.005)]
+    legs.append(("share 1, p increasing with the marker index", 1.0, 0.01 * (np.arange(M) + 1.0) / M))
+    rows = []
+    with capi.Shard(a.N, M) as sh:
+        sh.synth_bed(77, 5000, ld_block=a.ld_block, ld_ppm=900000)
+        sh.compute_markers_statistics()
+        for rd in range(-1, a.rounds):          # (round -1 warms every shape up and is not recorded)
+            sh.ld_scores_pos(pos, 1000.0 * X)
+            st = sh.ld_info()
+            in_band = st["block_pairs"]
+            if rd >= 0:
+                rows.append(dict(round=rd, call="gv_ld_scores_pos", wind_kb=X, ncat=0, seconds=st["seconds"], block_pairs=in_band))
+                print(json.dumps(rows[-1]), flush=True)
+            for name, share, p in legs:
+                idx, n_index = sh.ld_clump(pos, 1000.0 * X, p, 0.01, 0.01, a.clump_r2)
+                st, last = sh.ld_info(), sh.ld_clump_last()
+                if rd >= 0:
+                    rows.append(dict(round=rd, call="gv_ld_clump", leg=name, share=share, wind_kb=X, r2=a.clump_r2, seconds=st["seconds"],
+                                     block_seconds=last["block_seconds"], select_seconds=last["select_seconds"], rounds=last["rounds"],
+                                     n_e1=last["n_e1"], n_e2=last["n_e2"], n_index=n_index, blocks_launched=st["block_pairs"],
+                                     blocks_in_band=in_band, useful_macs=st["useful_macs"], scratch_bytes=st["scratch_bytes"]))
+                    print(json.dumps(rows[-1]), flush=True)
+    with open(a.out, "w") as f:
+        json.dump(dict(kind="clump", N=a.N, M=M, ld_block=a.ld_block, layout="default", calls=rows, summary=clump_summary(rows)), f)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--kind", choices=["bed", "dosage8", "pos"], default="bed")
+    ap.add_argument("--kind", choices=["bed", "dosage8", "pos", "clump"], default="bed")
     ap.add_argument("--wind-kb", type=float, nargs="+", default=[512.0])
     ap.add_argument("--pos-cluster", action="store_true")
+    ap.add_argument("--clump-r2", type=float, default=0.5)
     ap.add_argument("--ncat", type=int, nargs="*", default=[])
     ap.add_argument("--N", type=int, default=400000)
     ap.add_argument("--M", type=int, default=125000)
@@ -140,6 +202,8 @@ def main():
         return dosage8(a)
     if a.kind == "pos":
         return positional(a)
+    if a.kind == "clump":
+        return clump(a)
     rounds = []
     with capi.Shard(a.N, a.M) as sh:
         sh.synth_bed(77, 5000, ld_block=a.ld_block, ld_ppm=900000)
