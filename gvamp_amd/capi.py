@@ -34,6 +34,7 @@ EXPORTS = [
     "gv_ld_clump", "gv_ld_clump_last", "gv_ld_clump_seconds",
     "gv_set_ld_dosage", "gv_get_ld_dosage",
     "gv_synth_dosage_ld",
+    "gv_score_dev", "gv_score", "gv_score_info",
 ]
 
 
@@ -53,6 +54,14 @@ class AssocOut(C.Structure):           # gv_assoc_out
 class DosageStats(C.Structure):        # gv_dosage_stats
     _fields_ = [("scale", C.c_double), ("reserved", C.c_uint64), ("bits", C.c_int), ("missing", C.c_int), ("na_kernels", C.c_int),
                 ("pad_", C.c_int)]
+
+
+class ScoreStats(C.Structure):         # gv_score_stats
+    _fields_ = [("path", C.c_int), ("cols_per_pass", C.c_int), ("ksegs", C.c_int), ("min_cols", C.c_int), ("columns", C.c_int64),
+                ("passes", C.c_int64), ("scratch_bytes", C.c_uint64), ("seconds", C.c_double)]
+
+
+SCORE_PATH_KERNEL, SCORE_PATH_FALLBACK = 1, 2
 
 
 class CgStats(C.Structure):
@@ -208,6 +217,9 @@ def load():
     L.gv_ld_clump.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), dp, C.c_double, C.c_double, C.c_double, C.POINTER(i64), C.POINTER(i64)]
     L.gv_ld_clump_last.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(i64), C.POINTER(i64)]
     L.gv_ld_clump_seconds.argtypes = [vp, dp, dp]
+    L.gv_score_dev.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(vp)]
+    L.gv_score.argtypes = [vp, i64, dp, dp]
+    L.gv_score_info.argtypes = [vp, C.POINTER(ScoreStats)]
     L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
     L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
@@ -634,6 +646,35 @@ class Shard:
         st = LdStats()
         self._ck(self.L.gv_ld_info(self.h, C.byref(st)))
         return {"seconds": st.seconds, "block_pairs": st.block_pairs, "useful_macs": st.useful_macs, "scratch_bytes": st.scratch_bytes}
+
+    def score_dev(self, xs, outs):
+        """gv_score_dev: outs[j] = data::Ax(xs[j]) for every column, many columns per pass over the genotypes (xs M-space, outs N-space
+        vectors; None in place of a list passes a NULL array)"""
+        n = len(xs) if xs is not None else len(outs)
+
+        def arr(vs):
+            if vs is None:
+                return None
+            return (C.c_void_p * max(len(vs), 1))(*[None if v is None else v.h for v in vs])
+        self._ck(self.L.gv_score_dev(self.h, n, arr(xs), arr(outs)))
+
+    def score(self, W):
+        """gv_score: W of shape (C, M) or (M,) on the host -> (C, 4 * mbytes), row j = data::Ax(W[j])"""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim == 1:
+            W = W[None, :]
+        assert W.ndim == 2 and W.shape[1] == self.M, (W.shape, self.M)
+        out = np.empty((W.shape[0], 4 * self.mbytes))
+        self._ck(self.L.gv_score(self.h, W.shape[0], _dp(W), _dp(out)))
+        return out
+
+    def score_info(self):
+        """gv_score_info of the last score_dev / score as a dict; path is "kernel", "fallback" or None"""
+        st = ScoreStats()
+        self._ck(self.L.gv_score_info(self.h, C.byref(st)))
+        return dict(path={SCORE_PATH_KERNEL: "kernel", SCORE_PATH_FALLBACK: "fallback"}.get(st.path), cols_per_pass=st.cols_per_pass,
+                    ksegs=st.ksegs, min_cols=st.min_cols, columns=st.columns, passes=st.passes, scratch_bytes=int(st.scratch_bytes),
+                    seconds=st.seconds)
 
     def ax2_dev(self, xa, xb, outa, outb):
         self._ck(self.L.gv_ax2_dev(self.h, xa.h, xb.h, outa.h, outb.h))

@@ -182,6 +182,7 @@ static void free_dataset(gv_ctx* c) {
     F(c->bed); F(c->mask2); F(c->mave); F(c->msig); F(c->t3); F(c->ax_partial); F(c->counts);
     dense_release(c);
     free_layouts(c);
+    score_release(c);
     F(c->cgx_state); F(c->cgx_go);
     if (c->cgx_rel_h) (void)hipHostFree(c->cgx_rel_h);
     c->cgx_rel = c->cgx_rel_h = nullptr;
@@ -312,6 +313,31 @@ int gv_create(int device, gv_ctx** out) {
         }
         c->ld_part_bytes = mb * 1048576.0;
     }
+    // GV_SCORE_COLS=<4|8|16> and GV_SCORE_KS=<k> (development, read per context): the columns per pass and the K-segments of
+    // gv_score_dev's kernel.  Neither changes a bit; a k that breaks the int32 bound on a shard is refused by the call.
+    // GV_SCORE_KERNEL=1 / 0: the kernel from one column on / never (the fallback serves every call).
+    if (const char* sc = getenv("GV_SCORE_COLS")) {
+        char* end = nullptr;
+        const long v = strtol(sc, &end, 10);
+        if (end == sc || *end != 0 || (v != 4 && v != 8 && v != 16)) {
+            g_create_err = "gv_create: GV_SCORE_COLS=" + std::string(sc) + ": the columns per pass of gv_score_dev are 4, 8 or 16";
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->score_cols = (int)v;
+    }
+    if (const char* sk = getenv("GV_SCORE_KS")) {
+        char* end = nullptr;
+        const long v = strtol(sk, &end, 10);
+        if (end == sk || *end != 0 || v < 1 || v > gvm::GV_MAX_KS) {
+            g_create_err = "gv_create: GV_SCORE_KS=" + std::string(sk) + ": the K-segments of gv_score_dev are a positive integer <= " +
+                           std::to_string(gvm::GV_MAX_KS);
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->score_ks = (int)v;
+    }
+    if (const char* kn = getenv("GV_SCORE_KERNEL")) c->score_min_cols = atoi(kn) != 0 ? 1 : 0x7fffffff;
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)

@@ -72,6 +72,9 @@ struct DenseData {
     size_t bytes(int64_t M) const { return elem_bytes() * (size_t)M * (size_t)pitch; }
 };
 
+// gv_score_dev: the fewest columns for which its own kernel is the path where it applies (measured: DESIGN.md section 21)
+constexpr int GV_SCORE_MIN_COLS_DEFAULT = 4;
+
 struct gv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -194,6 +197,14 @@ struct gv_ctx {
     int clump_rounds = 0;
     int64_t clump_n_e1 = 0, clump_n_e2 = 0;
     double clump_block_s = 0.0, clump_select_s = 0.0;
+    // gv_score_dev (gv_score.hip): scratch of the kernel path (grown on demand, freed with the dataset), the
+    // development overrides GV_SCORE_COLS / GV_SCORE_KS (0: the library's pick), the fewest columns that take the kernel
+    // (GV_SCORE_KERNEL=1 / 0: 1 / never) and what gv_score_info reports
+    void* score_buf = nullptr;
+    size_t score_cap = 0;
+    int score_cols = 0, score_ks = 0;
+    int score_min_cols = GV_SCORE_MIN_COLS_DEFAULT;
+    gv_score_stats score_last{};
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;
@@ -478,6 +489,9 @@ inline gvd::View dense_view(const gv_ctx* c) {
 void dense_release(gv_ctx* c, bool keep_alloc = false);
 // frees the genotype layouts of the MFMA family: the stripe slab, the two stripe sets, the tiles and the plan's digit / weight / sum buffers
 void free_layouts(gv_ctx* c);
+// gv_score.hip: Z = A W on device pointers (C > 0 columns, x[j] M doubles, out[j] npad doubles); the scratch of its kernel path
+int score_device(gv_ctx* c, int64_t C, const double* const* x, double* const* out);
+void score_release(gv_ctx* c);
 
 struct Timer {
     gv_ctx* c;

@@ -337,6 +337,22 @@ std::vector<double> data::Ax(double* __restrict__ phen) {
     return out;
 }
 
+std::vector<std::vector<double>> data::score(const std::vector<std::vector<double>>& cols) {
+    const size_t C = cols.size(), Mp = M > 0 ? (size_t)M : 0, n4 = 4 * (size_t)mbytes;
+    std::vector<double> W(C * Mp > 0 ? C * Mp : 1, 0.0), Z(C * n4 > 0 ? C * n4 : 1, 0.0);
+    for (size_t j = 0; j < C; j++) {
+        if (cols[j].size() != Mp) {
+            std::cout << "FATAL: data::score: column " << j << " has " << cols[j].size() << " entries, the shard " << Mp << " markers" << std::endl;
+            exit(EXIT_FAILURE);
+        }
+        std::copy(cols[j].begin(), cols[j].end(), W.begin() + j * Mp);
+    }
+    ck(ctx, gv_score(ctx, (int64_t)C, W.data(), Z.data()), "gv_score");
+    std::vector<std::vector<double>> out(C);
+    for (size_t j = 0; j < C; j++) out[j].assign(Z.begin() + j * n4, Z.begin() + (j + 1) * n4);
+    return out;
+}
+
 std::vector<double> data::ATx(double* __restrict__ phen) {
     std::vector<double> out(M > 0 ? M : 0, 0.0);
     ck(ctx, gv_atx(ctx, phen, out.data()), "gv_atx");

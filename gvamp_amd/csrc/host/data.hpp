@@ -74,6 +74,8 @@ public:
     void read_dosage_data();                // [ext] type_data == "dosage8" / "dosage16": 8- / 16-bit dosage codes
     std::vector<int> read_chromosome_info(std::string bim_file);   // data.cpp:346-380
     void compute_markers_statistics();      // data.cpp:392-546
+    // [ext] many weight vectors in one pass over the genotypes (gv_score): column j = Ax(cols[j]), bit for bit
+    std::vector<std::vector<double>> score(const std::vector<std::vector<double>>& cols);
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled
     std::vector<double> ATx(double* __restrict__ phen);   // data.cpp:810 : 4*mbytes doubles -> M
     // covariates of the probit model (data.cpp:286-331, :1050-1058): one row of C values per individual

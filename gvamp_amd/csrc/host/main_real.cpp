@@ -11,6 +11,7 @@
 
 #include "data.hpp"
 #include "options.hpp"
+#include "score_cols.hpp"
 #include "utilities.hpp"
 #include "vamp.hpp"
 
@@ -394,6 +395,100 @@ int main(int argc, char** argv) {
         std::cout << ", p1 " << opt.get_clump_p1() << ", p2 " << opt.get_clump_p2() << ", r2 " << opt.get_clump_r2() << ", " << Mt << " markers, "
                   << st.seconds << " seconds, " << n_index << " clumps, " << rounds << " rounds, " << st.block_pairs << " blocks launched"
                   << std::endl;
+    } else if (mode == "score") {                                                      // [ext] DESIGN.md section 21
+        // many weight vectors applied to a cohort in one go: <out>_scores.bin = C columns of N float64
+        const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
+        const long long C0 = (long long)opt.get_score_cols();
+        const std::string sfile = opt.get_score_file(), units = opt.get_score_units();
+        const std::vector<double>& thr = opt.get_score_p_thresholds();
+        const bool ct = !thr.empty() || opt.get_score_clump_index() != "" || opt.get_score_p_file() != "";
+        if (sfile == "") {
+            std::cout << "FATAL: --run-mode score needs --score-file: --score-cols x " << Mt_test << " raw float64 weights, column after column"
+                      << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (ct && (thr.empty() || opt.get_score_clump_index() == "" || opt.get_score_p_file() == "")) {
+            std::cout << "FATAL: --score-clump-index, --score-p-file and --score-p-thresholds go together: all three or none" << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (ct && C0 != 1) {
+            std::cout << "FATAL: --score-p-thresholds builds its columns from column 0 of the score file: it needs --score-cols 1, not "
+                      << C0 << std::endl;
+            return EXIT_FAILURE;
+        }
+        // a whole file of `count` float64 values, FATAL with both byte counts when it is short
+        auto read_f64 = [&](const std::string& file, const char* what, long long count, std::vector<double>& dst) {
+            std::ifstream fp(file, std::ios::binary | std::ios::ate);
+            if (!fp.is_open()) {
+                std::cout << "FATAL: cannot open the " << what << " file " << file << std::endl;
+                return false;
+            }
+            const long long bytes = (long long)fp.tellg();
+            if (bytes < 8LL * count) {
+                std::cout << "FATAL: the " << what << " file " << file << " holds " << bytes << " bytes, fewer than the " << 8LL * count
+                          << " of " << count << " float64 values" << std::endl;
+                return false;
+            }
+            dst.assign((size_t)count, 0.0);
+            fp.seekg(0);
+            fp.read(reinterpret_cast<char*>(dst.data()), 8LL * count);
+            return true;
+        };
+        std::vector<double> wall, pall, iall;
+        if (!read_f64(sfile, "score", C0 * Mt_test, wall)) return EXIT_FAILURE;
+        if (ct && (!read_f64(opt.get_score_p_file(), "p", Mt_test, pall) || !read_f64(opt.get_score_clump_index(), "clump index", Mt_test, iall)))
+            return EXIT_FAILURE;
+        std::vector<double> MS = divide_work(Mt_test);
+        const int M_test = (int)MS[0], S_test = (int)MS[1];
+        data dataset_test(std::vector<double>(N_test, 0.0), opt.get_bed_file_test(), N_test, M_test, Mt_test, S_test, rank,
+                          type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
+        // this shard's slice of every column
+        std::vector<std::vector<double>> cols;
+        if (ct) {
+            // (index_of is global in the file; a marker is an index marker iff it names itself, which a shard-local index keeps)
+            std::vector<int64_t> idx((size_t)M_test);
+            for (int j = 0; j < M_test; j++) {
+                const double g = iall[(size_t)S_test + j];
+                idx[(size_t)j] = g == (double)(S_test + j) ? (int64_t)j : (g < 0 ? -1 : (int64_t)M_test + 1);
+            }
+            cols = score_cols::threshold_columns(wall.data() + S_test, idx.data(), pall.data() + S_test, (size_t)M_test, thr);
+        } else
+            for (long long k = 0; k < C0; k++)
+                cols.emplace_back(wall.begin() + k * Mt_test + S_test, wall.begin() + k * Mt_test + S_test + M_test);
+        const size_t C = cols.size();
+        const double sqrtN = sqrt((double)N_test);
+        std::vector<double> konst(C, 0.0);
+        for (size_t k = 0; k < C; k++) {
+            if (units == "allele") {
+                konst[k] = score_cols::allele_constant(cols[k].data(), dataset_test.get_mave(), (size_t)M_test);
+                cols[k] = score_cols::allele_to_std(cols[k].data(), dataset_test.get_msig(), (size_t)M_test, sqrtN);
+            } else
+                for (double& v : cols[k]) v *= sqrtN;                                    // as predict scales an estimate
+        }
+        if (units == "allele" && gv_env_nranks() > 1 && gv_allreduce_host(dataset_test.get_ctx(), konst.data(), (int)C)) {
+            std::cout << "FATAL: gv_allreduce_host: " << gv_last_error(dataset_test.get_ctx()) << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::vector<std::vector<double>> z = dataset_test.score(cols);
+        gv_score_stats st;
+        gv_score_info(dataset_test.get_ctx(), &st);
+        const std::string pre = opt.get_out_dir() + opt.get_out_name();
+        if (rank == 0) {
+            std::ofstream fo(pre + "_scores.bin", std::ios::binary);
+            for (size_t k = 0; k < C; k++) {
+                if (units == "allele")
+                    for (int i = 0; i < N_test; i++) z[k][(size_t)i] += konst[k];
+                fo.write(reinterpret_cast<const char*>(z[k].data()), 8LL * N_test);
+            }
+            fo.close();
+            if (!fo.good()) {
+                std::cout << "FATAL: cannot write " << pre << "_scores.bin" << std::endl;
+                return EXIT_FAILURE;
+            }
+            std::cout << "scores: " << C << " columns (" << units << " units) x " << N_test << " individuals, "
+                      << (st.path == GV_SCORE_PATH_KERNEL ? "kernel" : "fallback") << " path, " << st.passes << " passes, " << st.seconds
+                      << " seconds -> " << pre << "_scores.bin" << std::endl;
+        }
     } else if (mode == "predict" || mode == "predict_single") {                        // :386-594
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);

@@ -198,6 +198,26 @@ void Options::read_command_line_options(int argc, char** argv) {
             fatal(std::string("FATAL  : option --clump-kb has to be a non-negative number! (") + a + " was passed)");
         clump_kb = v;
     };
+    str("--score-file", score_file);
+    str("--score-clump-index", score_clump_index);
+    str("--score-p-file", score_p_file);
+    uns("--score-cols", score_cols, POS, "a strictly positive integer");
+    H["--score-units"] = [&](const char* a) {
+        if (strcmp(a, "std") && strcmp(a, "allele"))
+            fatal(std::string("FATAL  : option --score-units has to be std or allele! (") + a + " was passed)");
+        score_units = a;
+    };
+    H["--score-p-thresholds"] = [&](const char* a) {
+        score_p_thresholds.clear();
+        for (auto& v : split_commas(a)) {
+            char* end = nullptr;
+            const double t = strtod(v.c_str(), &end);
+            if (end == v.c_str() || *end != 0 || !(t >= 0))
+                fatal(std::string("FATAL  : option --score-p-thresholds has to be a comma-separated list of non-negative numbers! (") + a +
+                      " was passed)");
+            score_p_thresholds.push_back(t);
+        }
+    };
     H["--ld-adjust"] = [&](const char* a) {
         if (strcmp(a, "0") && strcmp(a, "1"))
             fatal(std::string("FATAL  : option --ld-adjust has to be 0 or 1! (") + a + " was passed)");

@@ -63,7 +63,13 @@
        --run-mode clump (gv_ld_clump) with --clump-p-file FILE (Mt raw float64, the format of      \
        <out>_assoc_p.bin), --clump-p1 (default 1e-4: index markers), --clump-p2 (default 1e-2: members), --clump-r2      \
        (default 0.5) and exactly one window: --clump-kb X (default 250; needs --bim-file), --ld-wind-cm X or --ld-window B \
-       -- LD clumping of association results: <out>_clump_index.bin and <out>_clumps.txt */                             \
+       -- LD clumping of association results: <out>_clump_index.bin and <out>_clumps.txt;                               \
+       --run-mode score (gv_score) with --bed-file-test / --N-test / --Mt-test, --score-file FILE   \
+       (raw float64, C x Mt values, column after column) and --score-cols C (default 1): <out>_scores.bin, C columns of  \
+       N float64; --score-units std|allele (default std: a column is effects per standardised genotype, scaled by       \
+       sqrt(N) as predict scales them; allele: weights per copy of the .bim file's first allele, a missing genotype      \
+       counts as the marker's mean); --score-clump-index FILE --score-p-file FILE --score-p-thresholds t1,t2,...:        \
+       clumping and thresholding, column k = column 0 at the index markers with p <= t_k (needs --score-cols 1) */     \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
@@ -72,7 +78,9 @@
     X(int, ld_window, 200) X(int, ld_adjust, 0) X(int, ld_dosage, 0)                                                   \
     X(double, ld_wind_kb, -1) X(double, ld_wind_cm, -1) X(std::string, ld_annot, "")                                   \
     X(std::string, clump_p_file, "") X(double, clump_p1, 1e-4) X(double, clump_p2, 1e-2) X(double, clump_r2, 0.5)      \
-    X(double, clump_kb, -1)
+    X(double, clump_kb, -1)                                                                                          \
+    X(std::string, score_file, "") X(unsigned int, score_cols, 1) X(std::string, score_units, "std")                \
+    X(std::string, score_clump_index, "") X(std::string, score_p_file, "")
 
 class Options {
 public:
@@ -95,6 +103,7 @@ public:
     const std::vector<std::string>& get_true_signal_files() const { return true_signal_files; }
     int count_phen_files() const { return (int)phen_files.size(); }
     int count_phen_files_test() const { return (int)phen_files_test.size(); }
+    const std::vector<double>& get_score_p_thresholds() const { return score_p_thresholds; }      // [ext] --score-p-thresholds
     int count_ld_windows() const { return ld_windows_given; }      // [ext] how many of --ld-window / --ld-wind-kb / --ld-wind-cm were given
     void list_phen_files() const;
 
@@ -123,6 +132,7 @@ private:
     std::vector<int> test_iter_range = std::vector<int>(2, -1);
     std::vector<std::string> phen_files, phen_files_test, true_signal_files;
     int ld_windows_given = 0;
+    std::vector<double> score_p_thresholds;
 
     void fail_if_last(char** argv, const int i);
     void check_options();

@@ -781,6 +781,46 @@ int gv_get_ld_dosage(const gv_ctx* ctx, int* on);
  * Still refused, each by a message that names its reason: 16-bit codes ("16-bit codes"), methylation data, the N-space solvers and
  * gv_cg_warm::ata_v_b under kind 1, N > 2^29 - 1.  If kind 1 was accepted and the option is then switched off, the next solve,
  * gv_precond_apply or gv_precond_window_gram refuses with a message that names gv_set_ld_dosage. */
+/* ---- many weight vectors in one pass: Z = A W (additions only: GV_ABI_VERSION stays 4) ---------------------
+ * gv_score_dev: out[j] = data::Ax(x[j]) for j = 0 .. C-1.  Column j is bit-identical to gv_ax_dev(ctx, x[j], out[j]) called alone on
+ * the same context: in every kernel mode, on every resident layout, for every data kind gv_ax_dev serves, with or without a
+ * communicator, whatever C is, whatever position the column has and whatever the other columns hold (a column with a NaN or an
+ * infinity is NaN as gv_ax_dev makes it; its neighbours are untouched).
+ * Path.  In kernel mode 1 on the tile layout (gv_get_layout() == 2), 2-bit genotypes, one rank, and C >= gv_score_stats.min_cols, a
+ * kernel of its own multiplies up to cols_per_pass columns per pass over the genotypes (GV_SCORE_PATH_KERNEL).  Everywhere else --
+ * two stripe sets, kernel modes 0 and 2, methylation and dosage data, a communicator or gv_debug_force_multi, an empty shard, fewer
+ * columns -- the dispatcher behind gv_ax_dev / gv_ax2_dev runs, in pairs where a two-vector pass exists and singly otherwise
+ * (GV_SCORE_PATH_FALLBACK).  GV_SCORE_KERNEL=1 / 0 (development, read by gv_create per context) makes min_cols 1 / unreachable.
+ * Edge rules.  C == 0 succeeds and does nothing.  Refused with a message: C < 0; NULL arrays or handles; an x that is not M-space or
+ * an out that is not N-space; two outputs that are the same vector; an output that is also an input; marker statistics or mask missing
+ * (the message of gv_ax_dev).  Inputs may repeat.
+ * The call leaves the context as it found it: the tuned decompositions, the ticket counter, the digit and operand buffers of the other
+ * products and the CG work vectors are not touched by the kernel path; a gv_ax_dev, gv_ax2_dev or gv_lmmse_mult after it returns the
+ * bits it returned before.  It is enqueued on the context's stream like gv_ax_dev.
+ * Scratch (kernel path): digits, int32 partial sums and scalars of one pass, gv_score_stats.scratch_bytes in all.  It is OWNED BY THE
+ * CONTEXT: allocated or grown by the call that needs it, kept for the next call, freed with the dataset (gv_set_dims) and by
+ * gv_destroy.  A call that cannot get it fails with the byte count in the message.
+ * No K-segment of a pass spans more than 4 194 303 markers (the int32 digit sums); a shard that no split into 64 segments serves is
+ * refused.  GV_SCORE_COLS=<4|8|16> pins the columns per pass and GV_SCORE_KS=<k> the K-segments (development, read by gv_create per
+ * context; gv_create refuses other values, the call refuses a k that breaks the bound); neither changes a bit.
+ * gv_score: the same on host arrays: column j of W at W + j * M, column j of the result at out + j * 4 * mbytes; returns when out is
+ * filled.  gv_score_info: the last gv_score_dev / gv_score call of the context. */
+#define GV_SCORE_PATH_KERNEL 1
+#define GV_SCORE_PATH_FALLBACK 2
+#define GV_SCORE_COLS_DEFAULT 8
+typedef struct gv_score_stats {
+    int path;                    /* 0 no call yet, GV_SCORE_PATH_KERNEL, GV_SCORE_PATH_FALLBACK */
+    int cols_per_pass;           /* kernel: 4, 8 or 16 (the last pass may run narrower); fallback: 2 where a two-vector pass exists, else 1 */
+    int ksegs;                   /* kernel: K-segments of a pass; fallback: 0 */
+    int min_cols;                /* the fewest columns for which the kernel is the path where it applies */
+    int64_t columns;             /* C */
+    int64_t passes;              /* passes over the genotypes */
+    uint64_t scratch_bytes;      /* kernel: bytes of scratch the call needed; fallback: 0 */
+    double seconds;              /* host wall time of the call (gv_score_dev enqueues: its device work may still be running) */
+} gv_score_stats;
+int gv_score_dev(gv_ctx* ctx, int64_t C, const gv_vec* const* x /* C handles, GV_SPACE_M */, gv_vec* const* out /* C handles, GV_SPACE_N */);
+int gv_score(gv_ctx* ctx, int64_t C, const double* W /* column j at W + j*M */, double* out /* column j at out + j*4*mbytes */);
+int gv_score_info(const gv_ctx* ctx, gv_score_stats* out);
 
 #ifdef __cplusplus
 }
