@@ -330,6 +330,14 @@ class Shard:
         if rc:
             raise GvError(self.L.gv_last_error(self.h).decode())
 
+    def set_dims(self, N, M, Mt=None, S=0):
+        """gv_set_dims on a live context: the data set, the mask (everyone present again) and the statistics go; vectors allocated
+        before do not outlive the call (every entry point refuses them) -- free them and allocate new ones"""
+        Mt = M if Mt is None else Mt
+        self._ck(self.L.gv_set_dims(self.h, N, M, Mt, S))
+        self.N, self.M, self.Mt, self.S = N, M, Mt, S
+        self.mbytes = self.L.gv_mbytes(self.h)
+
     def close(self):
         if self.h:
             self.L.gv_destroy(self.h)

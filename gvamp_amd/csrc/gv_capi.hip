@@ -3,6 +3,7 @@
 // gv_ingest.hip / gv_stats.hip, ranks: gv_comm.hip).  No CPU fallback anywhere: every compute entry point launches HIP
 // kernels on the context's stream or fails.
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -58,6 +59,18 @@ int vec_new(gv_ctx* c, int space, gv_vec** out) {
     return 0;
 }
 
+int vec_need(gv_ctx* c, const char* who, const char* arg, const gv_vec* v, int space) {
+    if (!v) return fail(c, "%s: %s is NULL", who, arg);
+    if (v->ctx != c) return fail(c, "%s: %s belongs to another context (a gv_vec is used with the context that allocated it)", who, arg);
+    if (space < 0) space = v->space;
+    if (v->space != space) return fail(c, "%s: %s must be %s-space", who, arg, space == GV_SPACE_M ? "M" : "N");
+    if (!vec_ok(c, v, space))
+        return fail(c, "%s: %s was allocated for earlier dimensions (%lld doubles, the context now needs %lld): vectors do not outlive "
+                       "gv_set_dims -- free it and allocate it again", who, arg, (long long)v->cap,
+                    (long long)(space == GV_SPACE_M ? (c->M > 0 ? c->M : 1) : c->npad));
+    return 0;
+}
+
 // every gv_vec of a context goes through vec_new / vec_del, so gv_destroy can release what a caller never freed
 void vec_del(gv_ctx* c, gv_vec* v) {
     if (!v) return;
@@ -79,7 +92,11 @@ int ensure_w2(gv_ctx* c) {
     return 0;
 }
 int ensure_work(gv_ctx* c) {
-    if (c->w_n && c->cg_d) return 0;
+    if (c->w_n && c->cg_d) {
+        // free_dataset (gv_set_dims, gv_destroy) deletes every internal vector, so one that exists has the current dimensions
+        assert(vec_ok(c, c->w_n, GV_SPACE_N) && vec_ok(c, c->cg_r, GV_SPACE_M) && vec_ok(c, c->cg_d, GV_SPACE_M));
+        return 0;
+    }
     // all or nothing: a half-built set must never be published (the entry points test w_n / cg_d and then use all five)
     gv_vec* made[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     auto undo = [&]() {
@@ -201,7 +218,7 @@ static void free_dataset(gv_ctx* c) {
             vec_del(c, *v);
             *v = nullptr;
         }
-    c->have_stats = false;
+    c->have_stats = c->have_people = false;
 }
 
 }  // namespace gvi
@@ -467,18 +484,23 @@ void gv_vec_free(gv_ctx* c, gv_vec* v) {
 }
 int64_t gv_vec_len(const gv_vec* v) { return v->len; }
 int gv_vec_upload(gv_ctx* c, gv_vec* v, const double* src) {
+    NEED_VEC(c, "gv_vec_upload", v, -1);
     return to_device(c, v->d, src, sizeof(double) * (v->len > 0 ? v->len : 0));
 }
 int gv_vec_download(gv_ctx* c, const gv_vec* v, double* dst) {
+    NEED_VEC(c, "gv_vec_download", v, -1);
     return to_host(c, dst, v->d, sizeof(double) * (v->len > 0 ? v->len : 0));
 }
 int gv_vec_fill(gv_ctx* c, gv_vec* v, double value) {
+    NEED_VEC(c, "gv_vec_fill", v, -1);
     gvk::fill(c->stream, v->d, v->len, value);
     KCHK(c);
     return 0;
 }
 int gv_vec_copy(gv_ctx* c, gv_vec* dst, const gv_vec* src) {
     NEED(c, dst->space == src->space, "gv_vec_copy: space mismatch");
+    NEED_VEC(c, "gv_vec_copy", dst, -1);
+    NEED_VEC(c, "gv_vec_copy", src, -1);
     gvk::copy(c->stream, dst->d, src->d, src->cap);      // (a kernel: enqueued in ~3 us where hipMemcpyAsync takes the host 10-15)
     KCHK(c);
     return 0;
@@ -486,12 +508,18 @@ int gv_vec_copy(gv_ctx* c, gv_vec* dst, const gv_vec* src) {
 int gv_vec_axpby(gv_ctx* c, gv_vec* out, double a, const gv_vec* x, double b, const gv_vec* y) {
     NEED(c, out->space == x->space && (!y || y->space == x->space), "gv_vec_axpby: space mismatch");
     NEED(c, y || b == 0.0, "gv_vec_axpby: y is NULL but b != 0");
+    NEED_VEC(c, "gv_vec_axpby", out, -1);
+    NEED_VEC(c, "gv_vec_axpby", x, -1);
+    NEED_VEC_OPT(c, "gv_vec_axpby", y, -1);
     gvk::axpby(c->stream, out->d, a, x->d, b, y ? y->d : nullptr, x->len);
     KCHK(c);
     return 0;
 }
 int gv_vec_mul(gv_ctx* c, gv_vec* out, const gv_vec* x, const gv_vec* y) {
     NEED(c, out->space == x->space && y->space == x->space, "gv_vec_mul: space mismatch");
+    NEED_VEC(c, "gv_vec_mul", out, -1);
+    NEED_VEC(c, "gv_vec_mul", x, -1);
+    NEED_VEC(c, "gv_vec_mul", y, -1);
     gvk::mul(c->stream, out->d, x->d, y->d, x->len);
     KCHK(c);
     return 0;
@@ -501,6 +529,8 @@ int gv_vec_dots(gv_ctx* c, int n, const gv_vec* const* x, const gv_vec* const* y
     const double *xs[8], *ys[8];
     for (int k = 0; k < n; k++) {
         NEED(c, x[k]->space == x[0]->space && y[k]->space == x[0]->space, "gv_vec_dots: space mismatch");
+        NEED_VEC(c, "gv_vec_dots", x[k], -1);
+        NEED_VEC(c, "gv_vec_dots", y[k], -1);
         xs[k] = x[k]->d;
         ys[k] = y[k]->d;
     }
@@ -520,6 +550,10 @@ int gv_vec_dots_ex(gv_ctx* c, int n, const gv_dot_spec* spec, double* out) {
         NEED(c, q.xa && q.ya, "gv_vec_dots_ex: xa and ya are required");
         NEED(c, q.ya->space == q.xa->space && (!q.xb || q.xb->space == q.xa->space) && (!q.yb || q.yb->space == q.xa->space),
              "gv_vec_dots_ex: the vectors of one pair live in one space");
+        NEED_VEC(c, "gv_vec_dots_ex", q.xa, -1);
+        NEED_VEC(c, "gv_vec_dots_ex", q.ya, -1);
+        NEED_VEC_OPT(c, "gv_vec_dots_ex", q.xb, -1);
+        NEED_VEC_OPT(c, "gv_vec_dots_ex", q.yb, -1);
         xa[k] = q.xa->d; xb[k] = q.xb ? q.xb->d : nullptr;
         ya[k] = q.ya->d; yb[k] = q.yb ? q.yb->d : nullptr;
         len[k] = q.xa->len;
@@ -545,6 +579,7 @@ int gv_vec_dot(gv_ctx* c, const gv_vec* x, const gv_vec* y, int sync, double* ou
 
 int gv_set_phen(gv_ctx* c, gv_vec* y_out, const double* y_host) {
     NEED(c, y_out->space == GV_SPACE_N, "gv_set_phen: y_out must be N-space");
+    NEED_VEC(c, "gv_set_phen", y_out, GV_SPACE_N);
     if (ensure_work(c)) return 1;
     std::vector<double> tmp(c->npad, 0.0);
     memcpy(tmp.data(), y_host, sizeof(double) * c->N);
@@ -569,6 +604,9 @@ static int fill_prior(gv_ctx* c, gv_prior& pr, const double* probs, const double
 static int denoise_impl(gv_ctx* c, const gv_vec* r1, double gam1, const double* probs, const double* vars, int L,
                         gv_vec* x1_out, gv_vec* d_out, double* sums2, bool global) {
     NEED(c, r1->space == GV_SPACE_M && x1_out->space == GV_SPACE_M, "gv_denoise: M-space vectors required");
+    NEED_VEC(c, "gv_denoise", r1, GV_SPACE_M);
+    NEED_VEC(c, "gv_denoise", x1_out, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_denoise", d_out, GV_SPACE_M);
     gv_prior pr;
     if (fill_prior(c, pr, probs, vars, L)) return 1;
     const bool multi = global && is_multi(c);
@@ -589,6 +627,7 @@ int gv_denoise_global(gv_ctx* c, const gv_vec* r1, double gam1, const double* pr
 static int prior_estep_impl(gv_ctx* c, const gv_vec* r1, double gam1, double lambda, const double* omegas,
                             const double* vars, int L, double* sums, bool global) {
     NEED(c, r1->space == GV_SPACE_M, "gv_prior_estep: M-space vector required");
+    NEED_VEC(c, "gv_prior_estep", r1, GV_SPACE_M);
     NEED(c, L >= 2, "gv_prior_estep: L >= 2");
     gv_prior pr;
     if (fill_prior(c, pr, omegas, vars, L)) return 1;
@@ -613,6 +652,10 @@ int gv_probit_denoise_cov(gv_ctx* c, const gv_vec* p1, const gv_vec* y, const gv
     NEED(c, p1->space == GV_SPACE_N && y->space == GV_SPACE_N && z1_out->space == GV_SPACE_N &&
                 (!m_cov || m_cov->space == GV_SPACE_N),
          "gv_probit_denoise: N-space vectors required");
+    NEED_VEC(c, "gv_probit_denoise", p1, GV_SPACE_N);
+    NEED_VEC(c, "gv_probit_denoise", y, GV_SPACE_N);
+    NEED_VEC(c, "gv_probit_denoise", z1_out, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_probit_denoise", m_cov, GV_SPACE_N);
     arm_scalars(c);
     gvk::probit_denoise(c->stream, p1->d, y->d, m_cov ? m_cov->d : nullptr, c->N, c->npad, tau1, probit_var, z1_out->d,
                         c->red_partial, c->red_out);
@@ -629,6 +672,9 @@ int gv_probit_denoise(gv_ctx* c, const gv_vec* p1, const gv_vec* y, double tau1,
 int gv_huber_denoise(gv_ctx* c, const gv_vec* p1, const gv_vec* y, double tau1, double deltaH, gv_vec* z1_out, double* sums2) {
     NEED(c, p1 && y && z1_out && p1->space == GV_SPACE_N && y->space == GV_SPACE_N && z1_out->space == GV_SPACE_N,
          "gv_huber_denoise: N-space vectors required");
+    NEED_VEC(c, "gv_huber_denoise", p1, GV_SPACE_N);
+    NEED_VEC(c, "gv_huber_denoise", y, GV_SPACE_N);
+    NEED_VEC(c, "gv_huber_denoise", z1_out, GV_SPACE_N);
     arm_scalars(c);
     gvk::huber_denoise(c->stream, p1->d, y->d, c->N, c->npad, tau1, deltaH, z1_out->d, c->red_partial, c->red_out);
     KCHK(c);
@@ -643,6 +689,8 @@ static double huber_log_norm(double d) {
 
 int gv_huber_delta(gv_ctx* c, const gv_vec* p1, const gv_vec* y, double tau1, const double* grid, int G, double* obj_out) {
     NEED(c, p1 && y && p1->space == GV_SPACE_N && y->space == GV_SPACE_N, "gv_huber_delta: N-space vectors required");
+    NEED_VEC(c, "gv_huber_delta", p1, GV_SPACE_N);
+    NEED_VEC(c, "gv_huber_delta", y, GV_SPACE_N);
     NEED(c, grid && obj_out && G >= 1 && G <= gvk::HUBER_GMAX, "gv_huber_delta: 1 <= G <= 16 grid values required");
     gvk::HuberGrid hg{};
     for (int g = 0; g < G; g++) {

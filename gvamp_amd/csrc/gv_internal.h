@@ -167,6 +167,9 @@ struct gv_ctx {
     double* aat_slab = nullptr;    // work vectors of the N-space solvers (gv_solvers.hip: aat_scratch), kept between calls
     size_t aat_slab_cap = 0;
     gv_vec *mave_p = nullptr, *msig_p = nullptr, *numb_p = nullptr;   // people statistics (gv_people_stats), N-space
+    // the people statistics belong to the data set, mask and marker statistics they were summed over: set by gv_people_stats, cleared
+    // wherever have_stats is (gv_set_mask, gv_marker_stats, every ingest, free_dataset)
+    bool have_people = false;
     gv_vec *w_n = nullptr, *w_n2 = nullptr;                  // N-space scratch (lmmse_mult, two-vector form)
     gv_vec *cg2_r = nullptr, *cg2_z = nullptr, *cg2_p = nullptr, *cg2_d = nullptr;   // second CG system (gv_cg_solve2)
     gv_vec *cg_r = nullptr, *cg_z = nullptr, *cg_p = nullptr, *cg_d = nullptr;  // CG work vectors
@@ -422,6 +425,14 @@ namespace gvi {
 int fail(gv_ctx* c, const char* fmt, ...);
 int vec_new(gv_ctx* c, int space, gv_vec** out);
 void vec_del(gv_ctx* c, gv_vec* v);
+// a vector an entry point may read or write M / npad doubles through: of this context, of that space, and of the length and capacity
+// vec_new would give it NOW (a caller's vector that survived gv_set_dims keeps those of the earlier dimensions)
+inline bool vec_ok(const gv_ctx* c, const gv_vec* v, int space) {
+    return v && v->ctx == c && v->space == space && v->len == (space == GV_SPACE_M ? c->M : 4 * c->mbytes) &&
+           v->cap == (space == GV_SPACE_M ? (c->M > 0 ? c->M : 1) : c->npad);
+}
+// vec_ok as a refusal: the message names the entry point, the argument and what is wrong with it.  space < 0: the vector's own
+int vec_need(gv_ctx* c, const char* who, const char* arg, const gv_vec* v, int space = -1);
 int ensure_w2(gv_ctx* c);       // the second N-space scratch vector (behind w_n in one allocation)
 int ensure_work(gv_ctx* c);     // scratch vectors of the matvecs and the CG
 int read_scalars(gv_ctx* c, int K, double* out);                            // red_out[0..K) -> host (mailbox or copy)
@@ -526,6 +537,15 @@ struct Timer {
 #define NEED(c, cond, msg)                 \
     do {                                   \
         if (!(cond)) return fail(c, msg);  \
+    } while (0)
+// a gv_vec argument of an entry point (vec_ok); NEED_VEC_OPT: it may be NULL
+#define NEED_VEC(c, who, v, space)                                  \
+    do {                                                            \
+        if (gvi::vec_need(c, who, #v, v, space)) return 1;          \
+    } while (0)
+#define NEED_VEC_OPT(c, who, v, space)                              \
+    do {                                                            \
+        if ((v) && gvi::vec_need(c, who, #v, v, space)) return 1;   \
     } while (0)
 // an entry point the dense kinds refuse, when the resident dataset is compact dense data (the fp64 kind keeps its own message)
 #define REFUSE_DOSAGE(c, who, why)                                                                                      \

@@ -280,22 +280,34 @@ extern "C" {
 
 int gv_ax_dev(gv_ctx* c, const gv_vec* x, gv_vec* out) {
     NEED(c, x->space == GV_SPACE_M && out->space == GV_SPACE_N, "gv_ax_dev: x must be M-space, out N-space");
+    NEED_VEC(c, "gv_ax_dev", x, GV_SPACE_M);
+    NEED_VEC(c, "gv_ax_dev", out, GV_SPACE_N);
     return ax_device(c, x->d, out->d);
 }
 int gv_atx_dev(gv_ctx* c, const gv_vec* p, gv_vec* out) {
     NEED(c, p->space == GV_SPACE_N && out->space == GV_SPACE_M, "gv_atx_dev: p must be N-space, out M-space");
+    NEED_VEC(c, "gv_atx_dev", p, GV_SPACE_N);
+    NEED_VEC(c, "gv_atx_dev", out, GV_SPACE_M);
     return atx_device(c, p->d, out->d);
 }
 
 int gv_ax2_dev(gv_ctx* c, const gv_vec* xa, const gv_vec* xb, gv_vec* outa, gv_vec* outb) {
     NEED(c, xa->space == GV_SPACE_M && xb->space == GV_SPACE_M && outa->space == GV_SPACE_N && outb->space == GV_SPACE_N &&
                 outa != outb, "gv_ax2_dev: x M-space, out N-space, distinct outputs");
+    NEED_VEC(c, "gv_ax2_dev", xa, GV_SPACE_M);
+    NEED_VEC(c, "gv_ax2_dev", xb, GV_SPACE_M);
+    NEED_VEC(c, "gv_ax2_dev", outa, GV_SPACE_N);
+    NEED_VEC(c, "gv_ax2_dev", outb, GV_SPACE_N);
     if (ensure_work(c)) return 1;
     return ax2_device(c, xa->d, xb->d, outa->d, outb->d);
 }
 int gv_atx2_dev(gv_ctx* c, const gv_vec* pa, const gv_vec* pb, gv_vec* outa, gv_vec* outb) {
     NEED(c, pa->space == GV_SPACE_N && pb->space == GV_SPACE_N && outa->space == GV_SPACE_M && outb->space == GV_SPACE_M &&
                 outa != outb, "gv_atx2_dev: p N-space, out M-space, distinct outputs");
+    NEED_VEC(c, "gv_atx2_dev", pa, GV_SPACE_N);
+    NEED_VEC(c, "gv_atx2_dev", pb, GV_SPACE_N);
+    NEED_VEC(c, "gv_atx2_dev", outa, GV_SPACE_M);
+    NEED_VEC(c, "gv_atx2_dev", outb, GV_SPACE_M);
     if (ensure_work(c)) return 1;
     return atx2_device(c, pa->d, pb->d, outa->d, outb->d);
 }

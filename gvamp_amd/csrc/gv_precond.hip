@@ -255,6 +255,8 @@ int gv_precond_window_gram(gv_ctx* c, int grid, int64_t k, double* out) {
 
 int gv_precond_apply(gv_ctx* c, double tau, double gam2, const gv_vec* r, gv_vec* z) {
     NEED(c, r && z && r->space == GV_SPACE_M && z->space == GV_SPACE_M && r != z, "gv_precond_apply: M-space r and z, no aliasing");
+    NEED_VEC(c, "gv_precond_apply", r, GV_SPACE_M);
+    NEED_VEC(c, "gv_precond_apply", z, GV_SPACE_M);
     if (pc_prepare(c, tau, gam2)) return 1;
     pc_apply(c, r->d, z->d);
     KCHK(c);

@@ -423,6 +423,10 @@ int gv_score_dev(gv_ctx* c, int64_t C, const gv_vec* const* x, gv_vec* const* ou
         if (!x[j] || !out[j]) return fail(c, "gv_score_dev: the handle of column %lld is NULL", (long long)j);
         if (x[j]->space != GV_SPACE_M || out[j]->space != GV_SPACE_N)
             return fail(c, "gv_score_dev: column %lld: x must be M-space, out N-space", (long long)j);
+        if (!vec_ok(c, x[j], GV_SPACE_M) || !vec_ok(c, out[j], GV_SPACE_N)) {
+            const std::string who = "gv_score_dev: column " + std::to_string((long long)j);
+            return vec_need(c, who.c_str(), "x", x[j], GV_SPACE_M) || vec_need(c, who.c_str(), "out", out[j], GV_SPACE_N);
+        }
         if (!seen.insert(out[j]).second) return fail(c, "gv_score_dev: column %lld: two outputs are the same vector", (long long)j);
         xs[(size_t)j] = x[j]->d;
         os[(size_t)j] = out[j]->d;

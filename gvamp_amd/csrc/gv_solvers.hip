@@ -15,6 +15,8 @@ extern "C" {
 // ---- solver ---------------------------------------------------------------------------------------------
 int gv_lmmse_mult(gv_ctx* c, const gv_vec* v, double tau, double gam2, gv_vec* out) {
     NEED(c, v->space == GV_SPACE_M && out->space == GV_SPACE_M && v != out, "gv_lmmse_mult: M-space, no aliasing");
+    NEED_VEC(c, "gv_lmmse_mult", v, GV_SPACE_M);
+    NEED_VEC(c, "gv_lmmse_mult", out, GV_SPACE_M);
     return lmmse_device(c, v->d, tau, gam2, out->d);
 }
 
@@ -620,6 +622,10 @@ static int cg_run(gv_ctx* c, CgSys* sys, int nsys, double tau, double gam2, int 
     const int64_t M = c->M;
     const bool multi = is_multi(c);
     const double diag = tau * (double)(c->N - 1) / (double)c->N + gam2;   // :1137-1138
+    // the device-resident loop launches the streaming kernels itself, past the check of ax_pass / atx_pass: without this one a solve
+    // after gv_set_mask or an upload ran on the previous mave / msig (an empty shard has no statistics to wait for)
+    NEED(c, (c->have_stats && c->mask2) || M == 0, "CG solve: the mask and the marker statistics must be set first (gv_marker_stats after "
+                                                   "gv_set_mask or an upload)");
     // the LD preconditioner runs the host-driven loop (its z and <r,z> are not those of k_cgx_ab), factorised once per (tau, gam2)
     if (c->pc_kind == 1 && pc_prepare(c, tau, gam2)) return 1;
     const bool device_loop = cgx_usable(c) && c->pc_kind == 0;
@@ -707,6 +713,9 @@ static void cg_fill_stats(const CgSys& s, gv_cg_stats* st) {
 int gv_cg_solve(gv_ctx* c, const gv_vec* v, const gv_vec* mu_start, double tau, double gam2, int denoiser,
                 int max_iter, gv_vec* mu_out, gv_cg_stats* st, double* relres) {
     NEED(c, v->space == GV_SPACE_M && mu_out->space == GV_SPACE_M, "gv_cg_solve: M-space vectors required");
+    NEED_VEC(c, "gv_cg_solve", v, GV_SPACE_M);
+    NEED_VEC(c, "gv_cg_solve", mu_out, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve", mu_start, GV_SPACE_M);
     NEED(c, mu_out != v && mu_out != mu_start, "gv_cg_solve: mu_out must not alias v or mu_start");
     if (ensure_work(c)) return 1;
     const int64_t ax0 = c->cnt.n_ax, atx0 = c->cnt.n_atx;
@@ -736,6 +745,11 @@ int gv_cg_solve2w(gv_ctx* c, const gv_vec* v_a, const gv_vec* mu_start_a, const 
                   double* relres_b, const gv_cg_extras* ex, const gv_cg_warm* wm) {
     NEED(c, v_a->space == GV_SPACE_M && v_b->space == GV_SPACE_M && mu_a->space == GV_SPACE_M && mu_b->space == GV_SPACE_M,
          "gv_cg_solve2: M-space vectors required");
+    NEED_VEC(c, "gv_cg_solve2", v_a, GV_SPACE_M);
+    NEED_VEC(c, "gv_cg_solve2", v_b, GV_SPACE_M);
+    NEED_VEC(c, "gv_cg_solve2", mu_a, GV_SPACE_M);
+    NEED_VEC(c, "gv_cg_solve2", mu_b, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve2", mu_start_a, GV_SPACE_M);
     NEED(c, mu_a != v_a && mu_a != mu_start_a && mu_b != v_b && mu_a != mu_b, "gv_cg_solve2: outputs must not alias inputs");
     gv_cg_extras none{};
     if (!ex) ex = &none;
@@ -759,6 +773,14 @@ int gv_cg_solve2w(gv_ctx* c, const gv_vec* v_a, const gv_vec* mu_start_a, const 
                              wm->ata_v_b != v_a && tau != 0.0),
          "gv_cg_solve2w: ata_v_b is M-space, must not alias the systems' vectors, and needs tau != 0");
     NEED(c, !wm->have_ata_v_b || wm->ata_v_b, "gv_cg_solve2w: have_ata_v_b without ata_v_b");
+    NEED_VEC_OPT(c, "gv_cg_solve2x", ex->ride_x, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve2x", ex->ride_out, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve2x", ex->a_mu_a, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve2x", ex->ata_mu_b, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve2w", wm->ata_mu_start_a, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve2w", wm->a_mu_start_a, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve2w", wm->ata_mu_a, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve2w", wm->ata_v_b, GV_SPACE_M);
     NEED(c, c->pc_kind == 0 || !wm->ata_v_b,
          "gv_cg_solve2w: ata_v_b (A^T A v_b from the first step) needs the scalar preconditioner: pass NULL under the LD preconditioner");
     if (ensure_work(c)) return 1;
@@ -874,11 +896,15 @@ static int aat_init_scalars(gv_ctx* c, double* r, double* d, const double* diag,
 int gv_cg_solve_aat(gv_ctx* c, const gv_vec* v, const gv_vec* mu_start, double tau, double gam2, int max_iter,
                     gv_vec* mu_out, gv_cg_stats* st, double* relres) {
     NEED(c, v->space == GV_SPACE_N && mu_out->space == GV_SPACE_N, "gv_cg_solve_aat: N-space vectors required");
+    NEED_VEC(c, "gv_cg_solve_aat", v, GV_SPACE_N);
+    NEED_VEC(c, "gv_cg_solve_aat", mu_out, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat", mu_start, GV_SPACE_N);
     NEED(c, mu_out != v && mu_out != mu_start, "gv_cg_solve_aat: mu_out must not alias v or mu_start");
     REFUSE_DOSAGE(c, "gv_cg_solve_aat", "the N-space solver needs people statistics");
     NEED(c, !c->dense.resident, "gv_cg_solve_aat: the N-space solver needs people statistics, not available for methylation data");
     NEED(c, c->pc_kind == 0, "gv_cg_solve_aat: the N-space solver is refused while the LD preconditioner is set (gv_set_cg_precond kind 1)");
-    NEED(c, c->mave_p, "gv_cg_solve_aat: gv_people_stats must run first");
+    NEED(c, c->have_people && c->mave_p, "gv_cg_solve_aat: gv_people_stats must run first (and again after a new mask, new marker "
+                                        "statistics or an upload: the people statistics belong to them)");
     if (ensure_work(c)) return 1;
     hipStream_t s = c->stream;
     const int64_t n = c->npad;
@@ -1038,7 +1064,23 @@ int gv_cg_solve_aat2w(gv_ctx* c, gv_vec* v_a, const gv_vec* mu_start_a, const gv
     NEED(c, !ata_mu_b || (ata_mu_b->space == GV_SPACE_M && ata_mu_b != mu_b && ata_mu_b != v_b && ata_mu_b != at_mu_a),
          "gv_cg_solve_aat2: ata_mu_b");
     NEED(c, !(aat_mu_a || ata_mu_b) || tau != 0.0, "gv_cg_solve_aat2: the by-products need tau != 0");
-    NEED(c, c->mave_p, "gv_cg_solve_aat2: gv_people_stats must run first");
+    NEED_VEC(c, "gv_cg_solve_aat2", v_a, GV_SPACE_N);
+    NEED_VEC(c, "gv_cg_solve_aat2", mu_a, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2", mu_start_a, GV_SPACE_N);
+    NEED_VEC(c, "gv_cg_solve_aat2", v_b, GV_SPACE_M);
+    NEED_VEC(c, "gv_cg_solve_aat2", mu_b, GV_SPACE_M);
+    NEED_VEC(c, "gv_cg_solve_aat2", at_mu_a, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2", aat_mu_a, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2", ata_mu_b, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2w", wm->aat_mu_start_a, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2w", wm->at_mu_start_a, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2w", wm->ata_v_b, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2w", wm->pre_x, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2w", wm->pre_out, GV_SPACE_N);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2w", wm->ride_x, GV_SPACE_M);
+    NEED_VEC_OPT(c, "gv_cg_solve_aat2w", wm->ride_out, GV_SPACE_N);
+    NEED(c, c->have_people && c->mave_p, "gv_cg_solve_aat2: gv_people_stats must run first (and again after a new mask, new marker "
+                                        "statistics or an upload: the people statistics belong to them)");
     if (ensure_work(c)) return 1;
     hipStream_t s = c->stream;
     const int64_t n = c->npad, M = c->M;

@@ -21,13 +21,14 @@ int gv_set_mask(gv_ctx* c, const uint8_t* mask4, int64_t nonas) {
     HIPCHK(c, hipMemcpyAsync(c->mask2, m2.data(), sizeof(uint32_t) * P4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->nonas = nonas;
-    c->have_stats = false;
+    c->have_stats = c->have_people = false;
     pc_invalidate(c, false);
     return 0;
 }
 
 int gv_marker_stats(gv_ctx* c, double alpha_scale) {
     pc_invalidate(c, false);
+    c->have_people = false;       // (the people statistics are sums over the standardised genotypes: new mave / msig, new sums)
     if (c->dense.resident) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
         NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
         gvd::stats(c->stream, dense_view(c), c->mask2, (double)c->nonas, alpha_scale, c->mave);      // (codes: the same, in code units)
@@ -122,6 +123,7 @@ int gv_people_stats(gv_ctx* c, double* mave_people, double* msig_people, double*
     if (msig_people) HIPCHK(c, hipMemcpyAsync(msig_people, c->msig_p->d, n4, hipMemcpyDeviceToHost, c->stream));
     if (numb_people) HIPCHK(c, hipMemcpyAsync(numb_people, c->numb_p->d, n4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->have_people = true;
     return 0;
 }
 
@@ -155,6 +157,9 @@ static int pvals_impl(gv_ctx* c, bool assoc, const gv_vec* z1, const gv_vec* y, 
                                 "data.cpp:1187-1223, computes and stores nothing)");
     }
     if (!(z1->space == GV_SPACE_N && y->space == GV_SPACE_N && x1_hat->space == GV_SPACE_M)) return fail(c, "%s: bad vector spaces", who);
+    NEED_VEC(c, who, z1, GV_SPACE_N);
+    NEED_VEC(c, who, y, GV_SPACE_N);
+    NEED_VEC(c, who, x1_hat, GV_SPACE_M);
     if (!c->have_stats) return fail(c, "%s: marker statistics must be computed first", who);
     if (ensure_work(c) || ensure_w2(c)) return 1;
     const int64_t M = c->M;

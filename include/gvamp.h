@@ -200,6 +200,37 @@ int gv_set_mask(gv_ctx* ctx, const uint8_t* mask4, int64_t nonas);
 /* compute_markers_statistics (data.cpp:392-546, scalar-path semantics :451-484). */
 int gv_marker_stats(gv_ctx* ctx, double alpha_scale);
 int gv_get_marker_stats(gv_ctx* ctx, double* mave, double* msig); /* M doubles each (data.hpp:95-98) */
+/* ---- a context is reused: what an input change invalidates, and the call that restores it ------------------------------------------
+ * A context may see several masks, alpha_scales, data sets, layouts and dimensions in its life.  After the calls of the right-hand
+ * column it answers bit for bit as a context created for the new state (tests/test_gpu_context_reuse.py holds every row to that); an
+ * entry point asked BEFORE them refuses with a message naming the missing call -- it never answers from the previous state.
+ *
+ *   the caller changes                        | goes stale                                            | restored by
+ *   ------------------------------------------+-------------------------------------------------------+---------------------------------
+ *   gv_set_mask                               | marker statistics (mave, msig, genotype counts, the   | gv_marker_stats
+ *                                             | dosage mean codes and per-marker counts), people      | (+ gv_people_stats before an
+ *                                             | statistics, window Grams and inverses                 | N-space solve)
+ *   gv_marker_stats (a new alpha_scale, or    | people statistics, window Grams and inverses          | gv_people_stats before an N-space
+ *   the same one again)                       |                                                       | solve; Grams: rebuilt on demand
+ *   gv_upload_* / gv_synth_* (any kind; it    | the data set held before, marker and people           | gv_marker_stats (+ gv_people_stats)
+ *   replaces the data set held before)        | statistics, dosage counts, Grams and inverses         |
+ *   gv_set_layout                             | nothing until the next bed upload, which builds it    | gv_upload_bed, gv_marker_stats
+ *   gv_set_kernel_mode, gv_set_dosage_route   | nothing: read by every product; the marker statistics | -- (people statistics of kernel
+ *                                             | are the same exact counts in every kernel family      | mode 0 / 1: gv_people_stats again)
+ *   gv_set_ld_dosage, gv_set_cg_precond       | window Grams and inverses (rebuilt on demand)         | --
+ *   gv_set_dosage_missing                     | refused while codes uploaded with the other setting   | gv_set_dims or an upload of another
+ *                                             | are resident                                          | kind first, then the upload
+ *   gv_set_dims                               | everything above, the mask (everyone present again)   | gv_set_mask, upload, gv_marker_stats;
+ *                                             | and EVERY gv_vec of the context                       | gv_vec_free + gv_vec_alloc
+ *
+ * The N-space solvers gv_cg_solve_aat* refuse until gv_people_stats has run after the LAST gv_marker_stats.  The M-space solvers and
+ * every product refuse until gv_marker_stats has run after the last gv_set_mask or upload.
+ * What survives a data set (and gv_set_dims): the options "that outlive the data set" -- kernel mode, layout request, dosage route,
+ * gv_set_dosage_missing, gv_set_ld_dosage, the preconditioner kind and window, gv_set_expected_passes, the communicator, timing -- and
+ * the ticket counter of the streaming kernels.  The tuner's decomposition picks are made again per resident layout (and change no
+ * bit); the run-ahead hints of the device-resident CG go with the data set (they change no bit either).
+ * Vectors: a gv_vec belongs to the context that allocated it and to the dimensions it was allocated under.  Every entry point checks
+ * each gv_vec argument and refuses, naming the argument, one that belongs to another context or that survived gv_set_dims. */
 
 /* ---- matvecs with the reference's host signatures ---------------------------------------------------
  * data::Ax (data.cpp:848-1009): x[M] -> out[4*mbytes], summed over ranks (if a communicator is attached),

@@ -156,6 +156,7 @@ def test_joint_solvers_with_no_or_one_step(max_iter):
         sh.compute_people_statistics()
         sh.set_kernel_mode(1)
         sh.compute_markers_statistics()
+        sh.compute_people_statistics()          # new marker statistics: the people statistics are summed over them again
         dv, du, dx, dm0, dvn = sh.vecM(v), sh.vecM(u), sh.vecM(xr), sh.vecM(mu0), sh.vecN(vn)
         a1, b1, a2, b2 = sh.vecM(), sh.vecM(), sh.vecM(), sh.vecM()
         zr, za, wb = sh.vecN(), sh.vecN(), sh.vecM()

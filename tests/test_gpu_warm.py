@@ -91,6 +91,7 @@ def test_xxt_joint_solver_with_a_known_start_product():
         sh.compute_people_statistics()
         sh.set_kernel_mode(1)
         sh.compute_markers_statistics()
+        sh.compute_people_statistics()          # new marker statistics: the people statistics are summed over them again
         du = sh.vecM(u)
         n_e, n_w, at_e, at_w, m_e, m_w = sh.vecN(), sh.vecN(), sh.vecM(), sh.vecM(), sh.vecM(), sh.vecM()
         s_e, s_w, aat_w = sh.vecN(), sh.vecN(), sh.vecN()
@@ -254,6 +255,7 @@ def test_xxt_joint_solver_completes_its_right_hand_side_and_carries_a_rider(layo
         sh.compute_people_statistics()
         sh.set_kernel_mode(1)
         sh.compute_markers_statistics()
+        sh.compute_people_statistics()          # new marker statistics: the people statistics are summed over them again
         du, dr2, dx1, dy = sh.vecM(u), sh.vecM(r2), sh.vecM(x1), sh.vecN(yv)
         # outside: one two-vector Ax for z1 and A r2, then the joint solve
         z1_e, ar2_e, v_e = sh.vecN(), sh.vecN(), sh.vecN()
