@@ -35,6 +35,7 @@ EXPORTS = [
     "gv_set_ld_dosage", "gv_get_ld_dosage",
     "gv_synth_dosage_ld",
     "gv_score_dev", "gv_score", "gv_score_info",
+    "gv_atxm_dev", "gv_atxm", "gv_atxm_info", "gv_screen_dev",
 ]
 
 
@@ -62,6 +63,14 @@ class ScoreStats(C.Structure):         # gv_score_stats
 
 
 SCORE_PATH_KERNEL, SCORE_PATH_FALLBACK = 1, 2
+
+
+class AtxmStats(C.Structure):          # gv_atxm_stats
+    _fields_ = [("path", C.c_int), ("cols_per_pass", C.c_int), ("ksegs", C.c_int), ("min_cols", C.c_int), ("columns", C.c_int64),
+                ("passes", C.c_int64), ("scratch_bytes", C.c_uint64), ("seconds", C.c_double)]
+
+
+ATXM_PATH_KERNEL, ATXM_PATH_FALLBACK = 1, 2
 
 
 class CgStats(C.Structure):
@@ -220,6 +229,10 @@ def load():
     L.gv_score_dev.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(vp)]
     L.gv_score.argtypes = [vp, i64, dp, dp]
     L.gv_score_info.argtypes = [vp, C.POINTER(ScoreStats)]
+    L.gv_atxm_dev.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(vp)]
+    L.gv_atxm.argtypes = [vp, i64, dp, dp]
+    L.gv_atxm_info.argtypes = [vp, C.POINTER(AtxmStats)]
+    L.gv_screen_dev.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
     L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
@@ -322,6 +335,7 @@ class Shard:
         self.N, self.M, self.Mt, self.S = N, M, (M if Mt is None else Mt), S
         self._ck(self.L.gv_set_dims(h, N, M, self.Mt, S))
         self.mbytes = self.L.gv_mbytes(h)
+        self._present = None              # the mask as set_mask left it (None: everyone has a phenotype); read by screen()
         if anchor:
             self.set_layout(True, 1)
             self.set_kernel_mode(0)
@@ -337,6 +351,7 @@ class Shard:
         self._ck(self.L.gv_set_dims(self.h, N, M, Mt, S))
         self.N, self.M, self.Mt, self.S = N, M, Mt, S
         self.mbytes = self.L.gv_mbytes(self.h)
+        self._present = None
 
     def close(self):
         if self.h:
@@ -445,6 +460,7 @@ class Shard:
         m = np.ascontiguousarray(mask4, dtype=np.uint8)
         assert m.size == self.mbytes
         self._ck(self.L.gv_set_mask(self.h, _up(m), nonas))
+        self._present = (((m.reshape(-1)[:, None] >> np.arange(4, dtype=np.uint8)) & 1).reshape(-1)[:self.N]).astype(bool)
 
     def compute_markers_statistics(self, alpha_scale=1.0):
         self._ck(self.L.gv_marker_stats(self.h, alpha_scale))
@@ -683,6 +699,82 @@ class Shard:
         return dict(path={SCORE_PATH_KERNEL: "kernel", SCORE_PATH_FALLBACK: "fallback"}.get(st.path), cols_per_pass=st.cols_per_pass,
                     ksegs=st.ksegs, min_cols=st.min_cols, columns=st.columns, passes=st.passes, scratch_bytes=int(st.scratch_bytes),
                     seconds=st.seconds)
+
+    @staticmethod
+    def _handles(vs):
+        if vs is None:
+            return None
+        return (C.c_void_p * max(len(vs), 1))(*[None if v is None else v.h for v in vs])
+
+    def atxm_dev(self, ps, outs):
+        """gv_atxm_dev: outs[j] = data::ATx(ps[j]) for every column, many columns per pass over the genotypes (ps N-space, outs M-space
+        vectors; None in place of a list passes a NULL array)"""
+        n = len(ps) if ps is not None else len(outs)
+        self._ck(self.L.gv_atxm_dev(self.h, n, self._handles(ps), self._handles(outs)))
+
+    def atxm(self, Y):
+        """gv_atxm: Y of shape (C, 4 * mbytes) or (4 * mbytes,) on the host -> (C, M), row j = data::ATx(Y[j])"""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[None, :]
+        assert Y.ndim == 2 and Y.shape[1] == 4 * self.mbytes, (Y.shape, self.mbytes)
+        out = np.empty((Y.shape[0], self.M))
+        self._ck(self.L.gv_atxm(self.h, Y.shape[0], _dp(Y), _dp(out)))
+        return out
+
+    def atxm_info(self):
+        """gv_atxm_info of the last atxm_dev / atxm / screen as a dict; path is "kernel", "fallback" or None"""
+        st = AtxmStats()
+        self._ck(self.L.gv_atxm_info(self.h, C.byref(st)))
+        return dict(path={ATXM_PATH_KERNEL: "kernel", ATXM_PATH_FALLBACK: "fallback"}.get(st.path), cols_per_pass=st.cols_per_pass,
+                    ksegs=st.ksegs, min_cols=st.min_cols, columns=st.columns, passes=st.passes, scratch_bytes=int(st.scratch_bytes),
+                    seconds=st.seconds)
+
+    def screen_dev(self, us, rs, ts=None, ps=None):
+        """gv_screen_dev: prepared phenotype columns us (N-space) -> r, t, p per marker (M-space; ts and ps may be None)"""
+        n = len(us) if us is not None else len(rs)
+        self._ck(self.L.gv_screen_dev(self.h, n, self._handles(us), self._handles(rs), self._handles(ts), self._handles(ps)))
+
+    def screen_prepare(self, Y):
+        """the prepared columns u of gv_screen_dev from raw phenotype columns Y of shape (C, N), NaN for NA: zero at the individuals the
+        context's mask leaves out and at pad slots, centred over the phenotyped, scaled by sqrt((n - 1) / sum (y - mean)^2).  A NaN at
+        an individual the mask keeps is refused: the NA pattern of every column must lie inside the mask."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[None, :]
+        assert Y.ndim == 2 and Y.shape[1] == self.N, (Y.shape, self.N)
+        pres = np.ones(self.N, dtype=bool) if self._present is None else self._present
+        n = int(pres.sum())
+        if n < 3:
+            raise GvError("screen: fewer than 3 individuals with a phenotype")
+        U = np.zeros((Y.shape[0], 4 * self.mbytes))
+        for c, y in enumerate(Y):
+            if np.any(np.isnan(y[pres])):
+                raise GvError("screen: column %d is NA at an individual the context's mask keeps (set the merged mask first)" % c)
+            d = y[pres] - y[pres].sum() / n
+            ss = float((d * d).sum())
+            if not ss > 0:
+                raise GvError("screen: column %d has no variance over the phenotyped individuals" % c)
+            U[c, np.nonzero(pres)[0]] = d * np.sqrt((n - 1) / ss)
+        return U
+
+    def screen(self, Y, cols_per_call=64):
+        """the marginal association screen of raw phenotype columns Y (C, N): (r, t, p), each of shape (C, M)"""
+        U = self.screen_prepare(Y)
+        out = [np.empty((U.shape[0], self.M)) for _ in range(3)]
+        for j0 in range(0, U.shape[0], cols_per_call):
+            blk = U[j0:j0 + cols_per_call]
+            us = [self.vecN(u) for u in blk]
+            res = [[self.vecM() for _ in blk] for _ in range(3)]
+            try:
+                self.screen_dev(us, *res)
+                for k in range(3):
+                    for j, v in enumerate(res[k]):
+                        out[k][j0 + j] = v.download()
+            finally:
+                for v in us + res[0] + res[1] + res[2]:
+                    v.free()
+        return tuple(out)
 
     def ax2_dev(self, xa, xb, outa, outb):
         self._ck(self.L.gv_ax2_dev(self.h, xa.h, xb.h, outa.h, outb.h))

@@ -200,6 +200,7 @@ static void free_dataset(gv_ctx* c) {
     dense_release(c);
     free_layouts(c);
     score_release(c);
+    atxm_release(c);
     F(c->cgx_state); F(c->cgx_go);
     if (c->cgx_rel_h) (void)hipHostFree(c->cgx_rel_h);
     c->cgx_rel = c->cgx_rel_h = nullptr;
@@ -355,6 +356,30 @@ int gv_create(int device, gv_ctx** out) {
         c->score_ks = (int)v;
     }
     if (const char* kn = getenv("GV_SCORE_KERNEL")) c->score_min_cols = atoi(kn) != 0 ? 1 : 0x7fffffff;
+    // GV_ATXM_COLS=<4|8>, GV_ATXM_KS=<k>, GV_ATXM_KERNEL=1|0 (development, read per context): the same three for gv_atxm_dev's kernel.
+    // None changes a bit; k is clipped to the K-steps there are.
+    if (const char* sc = getenv("GV_ATXM_COLS")) {
+        char* end = nullptr;
+        const long v = strtol(sc, &end, 10);
+        if (end == sc || *end != 0 || (v != 4 && v != 8)) {
+            g_create_err = "gv_create: GV_ATXM_COLS=" + std::string(sc) + ": the columns per pass of gv_atxm_dev are 4 or 8";
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->atxm_cols = (int)v;
+    }
+    if (const char* sk = getenv("GV_ATXM_KS")) {
+        char* end = nullptr;
+        const long v = strtol(sk, &end, 10);
+        if (end == sk || *end != 0 || v < 1 || v > gvm::GV_MAX_KS) {
+            g_create_err = "gv_create: GV_ATXM_KS=" + std::string(sk) + ": the K-segments of gv_atxm_dev are a positive integer <= " +
+                           std::to_string(gvm::GV_MAX_KS);
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->atxm_ks = (int)v;
+    }
+    if (const char* kn = getenv("GV_ATXM_KERNEL")) c->atxm_min_cols = atoi(kn) != 0 ? 1 : 0x7fffffff;
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)

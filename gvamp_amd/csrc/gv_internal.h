@@ -74,6 +74,8 @@ struct DenseData {
 
 // gv_score_dev: the fewest columns for which its own kernel is the path where it applies (measured: DESIGN.md section 21)
 constexpr int GV_SCORE_MIN_COLS_DEFAULT = 4;
+// gv_atxm_dev: the same for its kernel (measured: DESIGN.md section 23)
+constexpr int GV_ATXM_MIN_COLS_DEFAULT = 4;
 
 struct gv_ctx {
     int device = 0;
@@ -208,6 +210,12 @@ struct gv_ctx {
     int score_cols = 0, score_ks = 0;
     int score_min_cols = GV_SCORE_MIN_COLS_DEFAULT;
     gv_score_stats score_last{};
+    // gv_atxm_dev (gv_atxm.hip): the same five for the ATx side (GV_ATXM_COLS / GV_ATXM_KS / GV_ATXM_KERNEL)
+    void* atxm_buf = nullptr;
+    size_t atxm_cap = 0;
+    int atxm_cols = 0, atxm_ks = 0;
+    int atxm_min_cols = GV_ATXM_MIN_COLS_DEFAULT;
+    gv_atxm_stats atxm_last{};
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;
@@ -503,6 +511,9 @@ void free_layouts(gv_ctx* c);
 // gv_score.hip: Z = A W on device pointers (C > 0 columns, x[j] M doubles, out[j] npad doubles); the scratch of its kernel path
 int score_device(gv_ctx* c, int64_t C, const double* const* x, double* const* out);
 void score_release(gv_ctx* c);
+// gv_atxm.hip: R = A^T Y on device pointers (C > 0 columns, p[j] npad doubles, out[j] M doubles); the scratch of its kernel path
+int atxm_device(gv_ctx* c, int64_t C, const double* const* p, double* const* out);
+void atxm_release(gv_ctx* c);
 
 struct Timer {
     gv_ctx* c;

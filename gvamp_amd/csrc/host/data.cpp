@@ -353,6 +353,82 @@ std::vector<std::vector<double>> data::score(const std::vector<std::vector<doubl
     return out;
 }
 
+std::vector<std::vector<double>> data::ATx_multi(const std::vector<std::vector<double>>& cols) {
+    const size_t C = cols.size(), Mp = M > 0 ? (size_t)M : 0, n4 = 4 * (size_t)mbytes;
+    std::vector<double> Y(C * n4 > 0 ? C * n4 : 1, 0.0), R(C * Mp > 0 ? C * Mp : 1, 0.0);
+    for (size_t j = 0; j < C; j++) {
+        if (cols[j].size() != n4) {
+            std::cout << "FATAL: data::ATx_multi: column " << j << " has " << cols[j].size() << " entries, not 4 * mbytes = " << n4 << std::endl;
+            exit(EXIT_FAILURE);
+        }
+        std::copy(cols[j].begin(), cols[j].end(), Y.begin() + j * n4);
+    }
+    ck(ctx, gv_atxm(ctx, (int64_t)C, Y.data(), R.data()), "gv_atxm");
+    std::vector<std::vector<double>> out(C);
+    for (size_t j = 0; j < C; j++) out[j].assign(R.begin() + j * Mp, R.begin() + (j + 1) * Mp);
+    return out;
+}
+
+void data::set_mask(const std::vector<unsigned char>& m4, int nonas_) {
+    if (m4.size() != mbytes) {
+        std::cout << "FATAL: data::set_mask: " << m4.size() << " mask bytes, not mbytes = " << mbytes << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    mask4 = m4;
+    nonas = nonas_;
+    nas = N - nonas_;
+    push_mask();
+    compute_markers_statistics();
+}
+
+std::vector<std::vector<std::vector<double>>> data::screen(const std::vector<std::vector<double>>& cols) {
+    const size_t C = cols.size(), Mp = M > 0 ? (size_t)M : 0, n4 = 4 * (size_t)mbytes;
+    std::vector<std::vector<std::vector<double>>> out(3, std::vector<std::vector<double>>(C, std::vector<double>(Mp, 0.0)));
+    if (C == 0) return out;
+    if (nonas < 3) {
+        std::cout << "FATAL: data::screen: fewer than 3 individuals with a phenotype" << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    std::vector<gv_vec*> u(C, nullptr), res(3 * C, nullptr);
+    std::vector<double> buf(n4);
+    for (size_t j = 0; j < C; j++) {
+        if (cols[j].size() < (size_t)N) {
+            std::cout << "FATAL: data::screen: column " << j << " has " << cols[j].size() << " entries, fewer than N = " << N << std::endl;
+            exit(EXIT_FAILURE);
+        }
+        // the prepared column: zero at NA and pad slots, centred over the phenotyped, scaled by sqrt((n - 1) / sum (y - mean)^2)
+        double sum = 0.0, ss = 0.0;
+        for (int n = 0; n < N; n++)
+            if ((mask4[n / 4] >> (n % 4)) & 1) {
+                if (std::isnan(cols[j][n])) {
+                    std::cout << "FATAL: data::screen: column " << j << " is NA at individual " << n << ", which the mask keeps" << std::endl;
+                    exit(EXIT_FAILURE);
+                }
+                sum += cols[j][n];
+            }
+        const double avg = sum / double(nonas);
+        for (int n = 0; n < N; n++)
+            if ((mask4[n / 4] >> (n % 4)) & 1) ss += (cols[j][n] - avg) * (cols[j][n] - avg);
+        if (!(ss > 0.0)) {
+            std::cout << "FATAL: data::screen: column " << j << " has no variance over the phenotyped individuals" << std::endl;
+            exit(EXIT_FAILURE);
+        }
+        const double sc = sqrt(double(nonas - 1) / ss);
+        std::fill(buf.begin(), buf.end(), 0.0);
+        for (int n = 0; n < N; n++)
+            if ((mask4[n / 4] >> (n % 4)) & 1) buf[n] = (cols[j][n] - avg) * sc;
+        ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &u[j]), "gv_vec_alloc");
+        ck(ctx, gv_vec_upload(ctx, u[j], buf.data()), "gv_vec_upload");
+        for (int k = 0; k < 3; k++) ck(ctx, gv_vec_alloc(ctx, GV_SPACE_M, &res[k * C + j]), "gv_vec_alloc");
+    }
+    ck(ctx, gv_screen_dev(ctx, (int64_t)C, u.data(), res.data(), res.data() + C, res.data() + 2 * C), "gv_screen_dev");
+    for (int k = 0; k < 3; k++)
+        for (size_t j = 0; j < C && Mp > 0; j++) ck(ctx, gv_vec_download(ctx, res[k * C + j], out[k][j].data()), "gv_vec_download");
+    for (gv_vec* v : u) gv_vec_free(ctx, v);
+    for (gv_vec* v : res) gv_vec_free(ctx, v);
+    return out;
+}
+
 std::vector<double> data::ATx(double* __restrict__ phen) {
     std::vector<double> out(M > 0 ? M : 0, 0.0);
     ck(ctx, gv_atx(ctx, phen, out.data()), "gv_atx");

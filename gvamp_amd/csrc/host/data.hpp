@@ -76,6 +76,14 @@ public:
     void compute_markers_statistics();      // data.cpp:392-546
     // [ext] many weight vectors in one pass over the genotypes (gv_score): column j = Ax(cols[j]), bit for bit
     std::vector<std::vector<double>> score(const std::vector<std::vector<double>>& cols);
+    // [ext] many phenotype vectors in one pass over the genotypes (gv_atxm): column j = ATx(cols[j]), bit for bit;
+    // cols[j] holds 4 * mbytes doubles
+    std::vector<std::vector<double>> ATx_multi(const std::vector<std::vector<double>>& cols);
+    // [ext] the marginal association screen (gv_screen_dev): cols[j] = N raw phenotype values, NaN for NA, every NA outside the mask.
+    // Returns {r, t, p}, each C columns of M values.
+    std::vector<std::vector<std::vector<double>>> screen(const std::vector<std::vector<double>>& cols);
+    // [ext] replace the mask (bit n & 3 of byte n >> 2 set: individual n has a phenotype) and recompute the marker statistics
+    void set_mask(const std::vector<unsigned char>& m4, int nonas_);
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled
     std::vector<double> ATx(double* __restrict__ phen);   // data.cpp:810 : 4*mbytes doubles -> M
     // covariates of the probit model (data.cpp:286-331, :1050-1058): one row of C values per individual

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <sstream>
 
 #include "data.hpp"
@@ -489,6 +490,83 @@ int main(int argc, char** argv) {
                       << (st.path == GV_SCORE_PATH_KERNEL ? "kernel" : "fallback") << " path, " << st.passes << " passes, " << st.seconds
                       << " seconds -> " << pre << "_scores.bin" << std::endl;
         }
+    } else if (mode == "screen") {                                                     // [ext] DESIGN.md section 23
+        // every phenotype file against every marker: <out>_screen_{r,t,p}.bin = C columns of Mt float64
+        if (type_data != "bed") {
+            std::cout << "FATAL: --run-mode screen works on 2-bit genotypes only, not on --geno-format " << type_data << std::endl;
+            return EXIT_FAILURE;
+        }
+        const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
+        std::vector<double> MS = divide_work(Mt);
+        const int M = (int)MS[0], S = (int)MS[1];
+        need_phen(opt.get_phen_files(), "--phen-files");
+        const std::vector<std::string>& files = opt.get_phen_files();
+        const size_t C = files.size();
+        if ((long long)C * Mt > 2147483647LL) {
+            std::cout << "FATAL: --run-mode screen: " << C << " columns x " << Mt << " markers exceed the 2^31 - 1 values of an output file" << std::endl;
+            return EXIT_FAILURE;
+        }
+        // the third token of every line, NA -> NaN; complete cases: an individual with NA in any file is masked
+        std::vector<std::vector<double>> Y(C);
+        const size_t mb = (size_t)(N + 3) / 4;
+        std::vector<unsigned char> m4(mb, 0);
+        std::vector<char> have((size_t)N, 1);
+        for (size_t c = 0; c < C; c++) {
+            std::ifstream in(files[c]);
+            if (!in.is_open()) {
+                std::cout << "FATAL: could not open phenotype file: " << files[c] << std::endl;
+                return EXIT_FAILURE;
+            }
+            std::string line;
+            while (getline(in, line)) {
+                std::istringstream ls(line);
+                std::string a, b, v;
+                if (!(ls >> a >> b >> v)) {
+                    std::cout << "FATAL: phenotype line with fewer than 3 columns in " << files[c] << std::endl;
+                    return EXIT_FAILURE;
+                }
+                Y[c].push_back(v == "NA" ? std::numeric_limits<double>::quiet_NaN() : atof(v.c_str()));
+            }
+            if ((int)Y[c].size() != N) {
+                std::cout << "FATAL: " << files[c] << " holds " << Y[c].size() << " lines, not --N = " << N << std::endl;
+                return EXIT_FAILURE;
+            }
+            for (int n = 0; n < N; n++)
+                if (std::isnan(Y[c][(size_t)n])) have[(size_t)n] = 0;
+        }
+        int nonas = 0;
+        for (int n = 0; n < N; n++)
+            if (have[(size_t)n]) {
+                m4[(size_t)n / 4] |= (unsigned char)(1u << (n % 4));
+                nonas++;
+            }
+        if (nonas < 3) {
+            std::cout << "FATAL: --run-mode screen: " << nonas << " complete cases leave the test no degree of freedom" << std::endl;
+            return EXIT_FAILURE;
+        }
+        data dataset(std::vector<double>(N, 0.0), opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss,
+                     droute);
+        dataset.set_mask(m4, nonas);
+        const std::string pre = opt.get_out_dir() + opt.get_out_name();
+        const char* tag[3] = {"_screen_r.bin", "_screen_t.bin", "_screen_p.bin"};
+        const size_t per = opt.get_screen_cols();
+        long long passes = 0;
+        double seconds = 0.0;
+        gv_atxm_stats st{};
+        for (size_t c0 = 0; c0 < C; c0 += per) {
+            const size_t c1 = c0 + per < C ? c0 + per : C;
+            const std::vector<std::vector<double>> blk(Y.begin() + c0, Y.begin() + c1);
+            const auto res = dataset.screen(blk);
+            gv_atxm_info(dataset.get_ctx(), &st);
+            passes += st.passes;
+            seconds += st.seconds;
+            for (int k = 0; k < 3; k++)
+                for (size_t c = c0; c < c1; c++) mpi_store_vec_to_file(pre + tag[k], res[(size_t)k][c - c0], (int)(c * (size_t)Mt) + S, M);
+        }
+        if (rank == 0)
+            std::cout << "screen: " << C << " phenotypes x " << Mt << " markers, " << nonas << " complete cases of " << N << ", "
+                      << (st.path == GV_ATXM_PATH_KERNEL ? "kernel" : "fallback") << " path, " << passes << " passes, " << seconds
+                      << " seconds -> " << pre << "_screen_{r,t,p}.bin" << std::endl;
     } else if (mode == "predict" || mode == "predict_single") {                        // :386-594
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);

@@ -202,6 +202,7 @@ void Options::read_command_line_options(int argc, char** argv) {
     str("--score-clump-index", score_clump_index);
     str("--score-p-file", score_p_file);
     uns("--score-cols", score_cols, POS, "a strictly positive integer");
+    uns("--screen-cols", screen_cols, POS, "a strictly positive integer");
     H["--score-units"] = [&](const char* a) {
         if (strcmp(a, "std") && strcmp(a, "allele"))
             fatal(std::string("FATAL  : option --score-units has to be std or allele! (") + a + " was passed)");

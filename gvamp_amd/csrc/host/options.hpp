@@ -69,7 +69,11 @@
        N float64; --score-units std|allele (default std: a column is effects per standardised genotype, scaled by       \
        sqrt(N) as predict scales them; allele: weights per copy of the .bim file's first allele, a missing genotype      \
        counts as the marker's mean); --score-clump-index FILE --score-p-file FILE --score-p-thresholds t1,t2,...:        \
-       clumping and thresholding, column k = column 0 at the index markers with p <= t_k (needs --score-cols 1) */     \
+       clumping and thresholding, column k = column 0 at the index markers with p <= t_k (needs --score-cols 1);        \
+       --run-mode screen (gv_screen_dev) with --phen-files f0,f1,...: the marginal association      \
+       screen of every phenotype file against every marker over the complete cases (an individual with NA in any file    \
+       is masked): <out>_screen_{r,t,p}.bin, one column of Mt float64 per file; --screen-cols K (default 64): columns    \
+       per call */                                                                                                      \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
@@ -80,7 +84,7 @@
     X(std::string, clump_p_file, "") X(double, clump_p1, 1e-4) X(double, clump_p2, 1e-2) X(double, clump_r2, 0.5)      \
     X(double, clump_kb, -1)                                                                                          \
     X(std::string, score_file, "") X(unsigned int, score_cols, 1) X(std::string, score_units, "std")                \
-    X(std::string, score_clump_index, "") X(std::string, score_p_file, "")
+    X(std::string, score_clump_index, "") X(std::string, score_p_file, "") X(unsigned int, screen_cols, 64)
 
 class Options {
 public:

@@ -853,6 +853,64 @@ int gv_score_dev(gv_ctx* ctx, int64_t C, const gv_vec* const* x /* C handles, GV
 int gv_score(gv_ctx* ctx, int64_t C, const double* W /* column j at W + j*M */, double* out /* column j at out + j*4*mbytes */);
 int gv_score_info(const gv_ctx* ctx, gv_score_stats* out);
 
+/* ---- many phenotype vectors in one pass: R = A^T Y, and a marginal screen on it (additions only: GV_ABI_VERSION stays 4; DESIGN.md
+ * section 23) ------------------------------------------------------------------------------------------------------------------------
+ * gv_atxm_dev: out[j] = data::ATx(p[j]) for j = 0 .. C-1.  Column j is bit-identical to gv_atx_dev(ctx, p[j], out[j]) called alone on
+ * the same context: in every kernel mode, on every resident layout, for every data kind gv_atx_dev serves, with or without a
+ * communicator, whatever C is, whatever position the column has and whatever the other columns hold (a column with a NaN or an
+ * infinity comes out as gv_atx_dev makes it; its neighbours do not move).  As in gv_atx_dev, p is used as given: the caller zeroes NA
+ * and pad slots.
+ * Path.  In kernel mode 1 on the tile layout (gv_get_layout() == 2), 2-bit genotypes, M > 0 and C >= gv_atxm_stats.min_cols, a kernel
+ * of its own multiplies up to cols_per_pass columns per pass over the genotypes (GV_ATXM_PATH_KERNEL).  ATx issues no collective, so a
+ * communicator or gv_debug_force_multi does not change the path.  Everywhere else -- two stripe sets, kernel modes 0 and 2, methylation
+ * and dosage data, an empty shard, fewer columns -- the dispatcher behind gv_atx_dev / gv_atx2_dev runs, in pairs where a two-vector
+ * pass exists and singly otherwise (GV_ATXM_PATH_FALLBACK).  min_cols is 4, measured.  GV_ATXM_KERNEL=1 / 0
+ * (development, read by gv_create per context) makes min_cols 1 / unreachable.
+ * Edge rules.  C == 0 succeeds and does nothing.  Refused with a message: C < 0; NULL arrays or handles; a p that is not N-space or an
+ * out that is not M-space; two outputs that are the same vector; an output that is also an input; marker statistics missing (the
+ * message of gv_atx_dev).  Inputs may repeat.
+ * The call leaves the context as it found it: the tuned decompositions, the ticket counter (work items are dealt by block index), the
+ * digit, scalar and partial-sum buffers of the other products, the reduction partials and the CG work vectors are not touched by the
+ * kernel path.  It is enqueued on the context's stream like gv_atx_dev, and counted in the ATx counters (C products, its passes).
+ * Scratch (kernel path): digits, int32 partial sums and scalars of one pass, gv_atxm_stats.scratch_bytes in all (the formula:
+ * gv_atxm_plan.h).  It is OWNED BY THE CONTEXT: allocated or grown by the call that needs it, kept for the next call, freed with the
+ * dataset (gv_set_dims) and by gv_destroy.  A call that cannot get it fails with the byte count in the message.
+ * GV_ATXM_COLS=<4|8> pins the columns per pass and GV_ATXM_KS=<k> the K-segments (development, read by gv_create per context;
+ * gv_create refuses other values; k is clipped to the K-steps there are); neither changes a bit.
+ * gv_atxm: the same on host arrays: column j of Y at Y + j * 4 * mbytes, column j of the result at out + j * M; the staged copy of a
+ * column is masked as gv_atx masks its own; returns when out is filled.  gv_atxm_info: the last gv_atxm_dev / gv_atxm / gv_screen_dev.
+ *
+ * gv_screen_dev: the marginal association screen of C prepared phenotype columns u[c] (N-space) against every marker.  u[c] is zero
+ * at NA and pad slots, centred over the n = nonas phenotyped individuals of the context's mask and scaled by
+ * sqrt((n - 1) / sum (y - mean)^2).  With z = gv_atxm_dev(u), per marker and column, in this order of fp64 roundings:
+ *     a  = fl(fl(sqrt(N)) / (n - 1))          (host, once)
+ *     r  = fl(z a)                            the Pearson correlation of the mean-imputed genotype column with the phenotype
+ *     om = fma(-r, r, 1)                      1 - r^2 in one rounding
+ *     t  = fl(r fl(sqrt(fl((n - 2) / om))))   p = gvp::t_two_sided(|t|, n - 2)
+ * om <= 0 gives t = +-inf (the sign of r) and p = 0.  A marker without variance among the phenotyped present genotypes (monomorphic
+ * or all missing: sumsqx == 0 in the expression of the association test) gives NaN in all three outputs.  (The other half of that
+ * test's rule, fewer than three present genotypes, does not apply: under mean imputation the degrees of freedom are n - 2 for every
+ * marker.)  r, t, p are M-space; t and p may be NULL arrays.  All outputs are distinct vectors, none is an input.
+ * Refused with a message: everything gv_atxm_dev refuses; n < 3; methylation and dosage data; marker statistics of alpha_scale != 1. */
+#define GV_ATXM_PATH_KERNEL 1
+#define GV_ATXM_PATH_FALLBACK 2
+#define GV_ATXM_COLS_DEFAULT 8
+typedef struct gv_atxm_stats {
+    int path;                    /* 0 no call yet, GV_ATXM_PATH_KERNEL, GV_ATXM_PATH_FALLBACK */
+    int cols_per_pass;           /* kernel: 4 or 8 (the last pass may run narrower); fallback: 2 where a two-vector pass exists, else 1 */
+    int ksegs;                   /* kernel: K-segments of a pass; fallback: 0 */
+    int min_cols;                /* the fewest columns for which the kernel is the path where it applies */
+    int64_t columns;             /* C */
+    int64_t passes;              /* passes over the genotypes */
+    uint64_t scratch_bytes;      /* kernel: bytes of scratch the call needed; fallback: 0 */
+    double seconds;              /* host wall time of the call (gv_atxm_dev enqueues: its device work may still be running) */
+} gv_atxm_stats;
+int gv_atxm_dev(gv_ctx* ctx, int64_t C, const gv_vec* const* p /* C handles, GV_SPACE_N */, gv_vec* const* out /* C handles, GV_SPACE_M */);
+int gv_atxm(gv_ctx* ctx, int64_t C, const double* Y /* column j at Y + j*4*mbytes */, double* out /* column j at out + j*M */);
+int gv_atxm_info(const gv_ctx* ctx, gv_atxm_stats* out);
+int gv_screen_dev(gv_ctx* ctx, int64_t C, const gv_vec* const* u /* C, GV_SPACE_N */, gv_vec* const* r, gv_vec* const* t,
+                  gv_vec* const* p /* C each, GV_SPACE_M; t and p may be NULL arrays */);
+
 #ifdef __cplusplus
 }
 #endif

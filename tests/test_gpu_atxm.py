@@ -1,0 +1,377 @@
+"""gv_atxm_dev / gv_atxm: R = A^T Y, many phenotype vectors in one pass over the resident genotypes.
+
+The promise is bit identity: column j equals gv_atx_dev of that column alone -- on the kernel path (tile layout, kernel mode 1) under
+the library's pick and under the development overrides GV_ATXM_COLS / GV_ATXM_KS, and on the fallback everywhere else.  Columns 0 and
+C - 1 of a batch are also held to the integer restatement of tests/bed_fixed_restatement.py, something outside the kernels.  Inputs: the
+two shapes of that module (ragged: N = 1003 x M = 517: a ragged last K-step, a ragged last marker group, a last quad of one group, NA
+phenotypes, a monomorphic and an all-missing marker; even: N = 2100 x M = 1100), two small ones (N = 5 x M = 3: one partial tile;
+N = 257 x M = 65: a second K-step of one individual and a second marker group of one marker) and the module's four kinds of vector,
+cycled (N = 5 has too few individuals for the quantiser probes of kind 3: a scaled kind 1 stands in there)."""
+import numpy as np
+import pytest
+
+import bed_fixed_restatement as bx
+from gvamp_amd import capi, synth
+
+pytestmark = pytest.mark.gpu
+COUNTS = (1, 2, 3, 5, 8, 9, 17)
+PINS = [dict()] + [dict(GV_ATXM_COLS=str(cp), GV_ATXM_KS=str(ks)) for cp in (4, 8) for ks in (1, 3)]
+SMALL = {"tile": dict(N=5, M=3, seed=51), "second-step": dict(N=257, M=65, seed=53)}
+ALL_SHAPES = list(bx.SHAPES) + list(SMALL)
+_CACHE = {}
+
+
+@pytest.fixture(autouse=True)
+def _env(monkeypatch):
+    monkeypatch.setenv("GV_TUNE_CACHE", "0")
+    for k in ("GV_ATXM_COLS", "GV_ATXM_KS", "GV_ATXM_KERNEL", "GV_SCORE_COLS", "GV_SCORE_KS", "GV_SCORE_KERNEL"):
+        monkeypatch.delenv(k, raising=False)
+
+
+def _case(name):
+    if name not in _CACHE:
+        if name in SMALL:
+            sp = SMALL[name]
+            N, M = sp["N"], sp["M"]
+            mb = (N + 3) // 4
+            bed = synth.synth_bed(N, M, seed=sp["seed"], miss_ppm=50000)
+            _CACHE[name] = dict(name=name, N=N, M=M, npad=4 * mb, bed=np.asarray(bed, dtype=np.uint8).reshape(-1),
+                                present=np.ones(N, dtype=bool), m4=None, nonas=N)
+        else:
+            _CACHE[name] = bx.case(name)
+    return _CACHE[name]
+
+
+def _shard(cs, layout=2, mode=1, env=None, kernel="1"):
+    """kernel: GV_ATXM_KERNEL of the context ("1": the kernel from one column on, None: the library's threshold)"""
+    with pytest.MonkeyPatch.context() as mp:
+        for k, v in (env or {}).items():
+            mp.setenv(k, v)
+        if kernel is not None:
+            mp.setenv("GV_ATXM_KERNEL", kernel)
+        sh = capi.Shard(cs["N"], cs["M"])
+    if layout == "raw":
+        sh.set_layout(True, 1)
+    else:
+        sh.set_layout(False, layout)
+    sh.set_kernel_mode(mode)
+    sh.upload_bed(cs["bed"])
+    if cs["m4"] is not None:
+        sh.set_mask(cs["m4"], cs["nonas"])
+    sh.compute_markers_statistics()
+    return sh
+
+
+def _columns(cs, C):
+    key = ("cols", cs["name"])
+    if key not in _CACHE:
+        kinds = [bx.vector_p(cs, k) if not (k == 3 and cs["N"] < 130) else bx.vector_p(cs, 1) * 2.0 ** -20 for k in (1, 2, 3, 4)]
+        _CACHE[key] = kinds
+    kinds = _CACHE[key]
+    return [kinds[j % 4] for j in range(C)]
+
+
+def _singles(sh, cols):
+    """gv_atx_dev of every column alone"""
+    out = []
+    pv, ov = sh.vecN(), sh.vecM()
+    for p in cols:
+        pv.upload(p)
+        sh.atx_dev(pv, ov)
+        out.append(ov.download())
+    pv.free()
+    ov.free()
+    return out
+
+
+def _atxm(sh, cols):
+    ps, os_ = [sh.vecN(p) for p in cols], [sh.vecM().fill(7.0) for _ in cols]
+    sh.atxm_dev(ps, os_)
+    out = [o.download() for o in os_]
+    for v in ps + os_:
+        v.free()
+    return out
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64))
+
+
+# ---- 1. bit identity to the one-vector product ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pin", PINS, ids=lambda p: "pick" if not p else "cols%s-ks%s" % (p["GV_ATXM_COLS"], p["GV_ATXM_KS"]))
+@pytest.mark.parametrize("name", ALL_SHAPES)
+def test_every_column_equals_the_one_vector_product(name, pin):
+    cs = _case(name)
+    nkb = -(-cs["N"] // 256)
+    with _shard(cs, env=pin) as sh:
+        assert sh.get_layout() == 2 and sh.get_kernel_mode() == 1
+        cols = _columns(cs, max(COUNTS))
+        want = _singles(sh, cols)
+        for C in COUNTS:
+            got = _atxm(sh, cols[:C])
+            info = sh.atxm_info()
+            cp = info["cols_per_pass"]
+            assert info["path"] == "kernel" and info["columns"] == C and info["passes"] == -(-C // cp), info
+            if pin:
+                assert cp <= int(pin["GV_ATXM_COLS"]) and info["ksegs"] == min(int(pin["GV_ATXM_KS"]), nkb), info
+                assert cp == int(pin["GV_ATXM_COLS"]) or C <= cp      # a narrow batch may take a narrower instantiation
+            for j in range(C):
+                bad = np.nonzero(got[j].view(np.uint64) != want[j].view(np.uint64))[0]
+                assert len(bad) == 0, (C, j, bad[:5], got[j][bad[:5]], want[j][bad[:5]])
+                assert got[j].shape == (cs["M"],) and not np.any(got[j] == 7.0)         # (the outputs were filled with 7)
+        assert any(np.any(w != 0) for w in want)
+
+
+def test_the_library_pick_switches_path_at_min_cols():
+    cs = _case("ragged")
+    with _shard(cs, kernel=None) as sh:
+        cols = _columns(cs, 17)
+        want = _singles(sh, cols)
+        for C in COUNTS:
+            got = _atxm(sh, cols[:C])
+            info = sh.atxm_info()
+            assert info["min_cols"] >= 1
+            assert info["path"] == ("kernel" if C >= info["min_cols"] else "fallback"), info
+            assert all(_same_bits(got[j], want[j]) for j in range(C)), (C, info)
+
+
+def test_host_entry_point_and_repeated_inputs():
+    cs = _case("ragged")
+    with _shard(cs) as sh:
+        cols = _columns(cs, 5)
+        want = _singles(sh, cols)
+        R = sh.atxm(np.array(cols))
+        assert R.shape == (5, cs["M"]) and sh.atxm_info()["path"] == "kernel" and sh.atxm_info()["seconds"] > 0
+        assert all(_same_bits(R[j], want[j]) for j in range(5))
+        assert _same_bits(sh.atxm(cols[0])[0], want[0])
+        pv, oa, ob = sh.vecN(cols[1]), sh.vecM(), sh.vecM()
+        sh.atxm_dev([pv, pv], [oa, ob])                                 # inputs may repeat
+        assert _same_bits(oa.download(), want[1]) and _same_bits(ob.download(), want[1])
+
+
+# ---- 2. held to something outside the kernels ----------------------------------------------------------------------------------------
+def test_first_and_last_column_are_held_to_the_integer_restatement():
+    cs = _case("ragged")
+    planes = bx.planes(cs["bed"], cs["N"], cs["M"], cs["present"])
+    C = 11                                                              # column 10 is kind 3: the quantiser's tie and flush probes
+    with _shard(cs) as sh:
+        mave, msig = sh.marker_stats()
+        assert mave[bx.MONO] == 2.0 and msig[bx.MONO] == 1.0
+        cols = _columns(cs, C)
+        got = _atxm(sh, cols)
+        info = sh.atxm_info()
+        assert info["path"] == "kernel" and info["passes"] == -(-C // info["cols_per_pass"]) >= 2, info
+        for j in (0, C - 1):
+            S = bx.atx1_sums(planes, cols[j], cs["N"], cs["present"])
+            assert bx.lo_exact(S["lo"]) and S["sm"][bx.MONO] == 0.0
+            run = bx.find_P(S, got[j], mave, msig, cs["N"], bx.MONO)
+            exact, bound = bx.exact_P(cols[j]), bx.p_bound(cols[j], cs["N"])
+            near = run.nearest(exact)
+            print("column %d: %d doubles reproduce every entry; nearest %+.2f ulp from the exact P" %
+                  (j, run.count, bx.ulps(near, exact) if near is not None else float("nan")))
+            assert run.count > 0, "column %d: no single P reproduces every entry" % j
+            assert abs(bx.Fraction(near) - exact) <= bound
+        assert np.all(got[3] == 0.0) and np.all(got[7] == 0.0)          # the zero columns are exactly zero
+
+
+# ---- 3. company and position do not matter -------------------------------------------------------------------------------------------
+def test_position_and_neighbours_do_not_matter():
+    cs = _case("even")
+    with _shard(cs) as sh:
+        cols = _columns(cs, 17)
+        want = _singles(sh, cols)
+        rng = np.random.default_rng(5)
+        for pos in (0, 7, 16):
+            batch = []
+            for _ in range(17):
+                v = np.zeros(cs["npad"])
+                v[:cs["N"]] = rng.standard_normal(cs["N"]) * 10.0 ** rng.integers(-6, 6)
+                batch.append(v)
+            batch[pos] = cols[1]
+            assert _same_bits(_atxm(sh, batch)[pos], want[1]), pos
+        a, b = _atxm(sh, [cols[0], cols[2], cols[1]]), _atxm(sh, [cols[1], cols[2], cols[0]])       # swapping columns swaps outputs
+        assert _same_bits(a[0], b[2]) and _same_bits(a[2], b[0]) and _same_bits(a[1], b[1]) and not _same_bits(a[0], a[2])
+        batch = list(cols[:6])
+        batch[2] = cols[0].copy()
+        batch[2][11] = np.nan
+        batch[4] = cols[1].copy()
+        batch[4][200] = np.inf
+        got = _atxm(sh, batch)
+        alone = _singles(sh, [batch[2], batch[4]])
+        for j, al in zip((2, 4), alone):
+            assert np.all(np.isnan(got[j])) and _same_bits(got[j], al)
+        for j in (0, 1, 3, 5):
+            assert _same_bits(got[j], want[j]), j
+
+
+# ---- 4. fallback paths ------------------------------------------------------------------------------------------------------------------
+def _full_mask(N):
+    m4 = np.zeros((N + 3) // 4, dtype=np.uint8)
+    for n in range(N):
+        m4[n >> 2] |= 1 << (n & 3)
+    return m4
+
+
+@pytest.mark.parametrize("what", ["two-stripe-sets", "mode2", "mode0", "dosage8", "meth", "forced-multi"])
+def test_other_paths_report_themselves_and_keep_the_bits(what):
+    """everything but forced-multi is the fallback; ATx issues no collective, so gv_debug_force_multi keeps the kernel (section 23)"""
+    cs = _case("ragged")
+    if what in ("dosage8", "meth"):
+        N, M = 515, 300
+        sh = capi.Shard(N, M)
+        if what == "meth":
+            sh.synth_meth(3)
+        else:
+            sh.synth_dosage(3, 8)
+        sh.set_mask(_full_mask(N), N)
+        sh.compute_markers_statistics()
+        rng = np.random.default_rng(9)
+        cols = []
+        for k in range(5):
+            v = np.zeros(4 * sh.mbytes)
+            v[:N] = rng.standard_normal(N) * 10.0 ** k
+            cols.append(v)
+    else:
+        sh = _shard(cs, layout={"two-stripe-sets": 1, "mode0": "raw"}.get(what, 2), mode={"mode2": 2, "mode0": 0}.get(what, 1))
+        if what == "forced-multi":
+            sh.force_multi(1)
+        cols = _columns(cs, 5)
+    with sh:
+        want = _singles(sh, cols)
+        for C in (1, 2, 5):
+            got = _atxm(sh, cols[:C])
+            info = sh.atxm_info()
+            if what == "forced-multi":
+                assert info["path"] == "kernel" and info["columns"] == C and info["ksegs"] >= 1, info
+            else:
+                assert info["path"] == "fallback" and info["columns"] == C and info["ksegs"] == 0, info
+                assert info["passes"] == (-(-C // 2) if what in ("two-stripe-sets", "dosage8", "meth") else C), info
+            assert all(_same_bits(got[j], want[j]) for j in range(C)), (what, C)
+        assert any(np.any(w != 0) for w in want)
+
+
+def test_gv_create_refuses_bad_overrides(monkeypatch):
+    for k, v, msg in (("GV_ATXM_COLS", "5", "4 or 8"), ("GV_ATXM_COLS", "16", "4 or 8"), ("GV_ATXM_KS", "0", "positive integer"),
+                      ("GV_ATXM_KS", "65", "positive integer"), ("GV_ATXM_KS", "x", "positive integer")):
+        monkeypatch.setenv(k, v)
+        with pytest.raises(capi.GvError, match=msg):
+            capi.Shard(16, 64)
+        monkeypatch.delenv(k)
+
+
+# ---- 5. the context is left as it was ------------------------------------------------------------------------------------------------
+def _free_device_memory():
+    """hipMemGetInfo of the runtime the library has already loaded"""
+    import ctypes
+    hip = ctypes.CDLL("libamdhip64.so")
+    free, total = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    assert hip.hipMemGetInfo(ctypes.byref(free), ctypes.byref(total)) == 0
+    return free.value
+
+
+def test_the_context_is_left_as_it_was():
+    cs = _case("even")
+    with _shard(cs) as sh:
+        cols = _columns(cs, 16)
+        rng = np.random.default_rng(6)
+        xs = [rng.standard_normal(cs["M"]) for _ in range(4)]
+        pa, pb, oa, ob = sh.vecN(cols[0]), sh.vecN(cols[1]), sh.vecM(), sh.vecM()
+        xa, xb, za, zb, ov = sh.vecM(xs[0]), sh.vecM(xs[1]), sh.vecN(), sh.vecN(), sh.vecM()
+        sx, sz = [sh.vecM(x) for x in xs], [sh.vecN() for _ in xs]
+
+        def probe():
+            sh.atx_dev(pa, oa)
+            out = [oa.download()]
+            sh.atx2_dev(pa, pb, oa, ob)
+            out += [oa.download(), ob.download()]
+            sh.ax_dev(xa, za)
+            out.append(za.download())
+            sh.lmmse_mult(xa, 1.3, 0.4, ov)
+            out.append(ov.download())
+            sh.score_dev(sx, sz)
+            out += [z.download() for z in sz]
+            return [sh.decomp()] + out                                  # (after the products: the first one makes the on-device pick)
+
+        before = probe()
+        ps, os_ = [sh.vecN(p) for p in cols], [sh.vecM() for _ in cols]
+        sh.atxm_dev(ps, os_)
+        assert sh.atxm_info()["path"] == "kernel"
+        first = os_[5].download()
+        free1 = _free_device_memory()
+        for _ in range(50):
+            sh.atxm_dev(ps, os_)
+        assert _same_bits(os_[5].download(), first)
+        assert _free_device_memory() == free1
+        after = probe()
+        assert before[0] == after[0]
+        assert all(_same_bits(b, a) for b, a in zip(before[1:], after[1:]))
+
+
+def test_the_scratch_goes_with_the_dataset():
+    """two rounds on one context, the second with gv_atxm_dev calls on the kernel path: after gv_set_dims has dropped the dataset the free
+    device memory is what it was after the first round"""
+    cs = _case("even")
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("GV_ATXM_KERNEL", "1")
+        sh = capi.Shard(cs["N"], cs["M"])
+    free = []
+    with sh:
+        for rnd in (0, 1):
+            sh.set_layout(False, 2)
+            sh.upload_bed(cs["bed"])
+            sh.compute_markers_statistics()
+            cols = _columns(cs, 9)
+            ps, os_ = [sh.vecN(p) for p in cols], [sh.vecM() for _ in cols]
+            sh.atx_dev(ps[0], os_[0])
+            if rnd:
+                sh.atxm_dev(ps, os_)
+                assert sh.atxm_info()["path"] == "kernel" and sh.atxm_info()["scratch_bytes"] > 0
+            os_[0].download()
+            for v in ps + os_:
+                v.free()
+            sh.set_dims(cs["N"], cs["M"])
+            free.append(_free_device_memory())
+    assert free[0] == free[1], free
+
+
+# ---- 6. refusals ------------------------------------------------------------------------------------------------------------------------
+def test_refusals_by_message_and_the_context_stays_usable():
+    cs = _case("ragged")
+    with _shard(cs) as sh:
+        cols = _columns(cs, 3)
+        want = _singles(sh, cols)
+        ps, os_ = [sh.vecN(p) for p in cols], [sh.vecM() for _ in cols]
+        vp = capi.C.c_void_p
+        sh.atxm_dev([], [])                                                        # C == 0 succeeds and does nothing
+        with pytest.raises(capi.GvError, match="negative"):
+            sh._ck(sh.L.gv_atxm_dev(sh.h, -1, (vp * 1)(), (vp * 1)()))
+        with pytest.raises(capi.GvError, match="arrays of column handles are NULL"):
+            sh._ck(sh.L.gv_atxm_dev(sh.h, 2, None, None))
+        with pytest.raises(capi.GvError, match="handle of column 1 is NULL"):
+            sh.atxm_dev([ps[0], None], os_[:2])
+        with pytest.raises(capi.GvError, match="column 0: p must be N-space, out M-space"):
+            sh.atxm_dev([os_[0]], [os_[1]])
+        with pytest.raises(capi.GvError, match="column 1: p must be N-space, out M-space"):
+            sh.atxm_dev(ps[:2], [os_[0], ps[2]])
+        with pytest.raises(capi.GvError, match="column 2: two outputs are the same vector"):
+            sh.atxm_dev(ps, [os_[0], os_[1], os_[0]])
+        with pytest.raises(capi.GvError, match="negative"):
+            sh._ck(sh.L.gv_atxm(sh.h, -2, None, None))
+        with pytest.raises(capi.GvError, match="Y or out is NULL"):
+            sh._ck(sh.L.gv_atxm(sh.h, 2, None, None))
+        got = _atxm(sh, cols)
+        assert all(_same_bits(got[j], want[j]) for j in range(3))
+    # marker statistics missing: refused as gv_atx_dev refuses it, on the kernel path and on the fallback
+    for kernel in ("1", "0"):
+        with pytest.MonkeyPatch.context() as mp:
+            mp.setenv("GV_ATXM_KERNEL", kernel)
+            sh = capi.Shard(cs["N"], cs["M"])
+        with sh:
+            sh.set_layout(False, 2)
+            sh.upload_bed(cs["bed"])
+            ps, os_ = [sh.vecN().fill(0.0) for _ in range(4)], [sh.vecM() for _ in range(4)]
+            with pytest.raises(capi.GvError) as single:
+                sh.atx_dev(ps[0], os_[0])
+            with pytest.raises(capi.GvError) as batch:
+                sh.atxm_dev(ps, os_)
+            assert str(batch.value) == str(single.value) and "statistics" in str(batch.value)
