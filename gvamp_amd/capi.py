@@ -36,6 +36,7 @@ EXPORTS = [
     "gv_synth_dosage_ld",
     "gv_score_dev", "gv_score", "gv_score_info",
     "gv_atxm_dev", "gv_atxm", "gv_atxm_info", "gv_screen_dev",
+    "gv_pca_dev", "gv_pca_loadings_dev", "gv_pca_info",
 ]
 
 
@@ -71,6 +72,15 @@ class AtxmStats(C.Structure):          # gv_atxm_stats
 
 
 ATXM_PATH_KERNEL, ATXM_PATH_FALLBACK = 1, 2
+
+
+class PcaStats(C.Structure):           # gv_pca_stats
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("block", C.c_int), ("pad_", C.c_int), ("cols_atxm", C.c_int64),
+                ("cols_score", C.c_int64), ("scratch_bytes", C.c_uint64), ("seconds_products", C.c_double),
+                ("seconds_panel", C.c_double), ("seconds", C.c_double)]
+
+
+PCA_MAX_BLOCK = 32
 
 
 class CgStats(C.Structure):
@@ -233,6 +243,9 @@ def load():
     L.gv_atxm.argtypes = [vp, i64, dp, dp]
     L.gv_atxm_info.argtypes = [vp, C.POINTER(AtxmStats)]
     L.gv_screen_dev.argtypes = [vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.gv_pca_dev.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_double, C.c_int, C.POINTER(vp), dp, dp]
+    L.gv_pca_loadings_dev.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(vp)]
+    L.gv_pca_info.argtypes = [vp, C.POINTER(PcaStats)]
     L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
     L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
@@ -775,6 +788,56 @@ class Shard:
                 for v in us + res[0] + res[1] + res[2]:
                     v.free()
         return tuple(out)
+
+    def pca_dev(self, q0, us, tol, max_iter, k=None, L=None):
+        """gv_pca_dev: the len(us) largest eigenpairs of the relationship matrix from the starting block q0 (N-space vectors, not
+        modified) into us (N-space vectors).  Returns (eval, resid); k / L override the counts the lists imply (None in place of a
+        list passes a NULL array)"""
+        k = len(us) if k is None else k
+        L = len(q0) if L is None else L
+        ev, rs = np.full(max(k, 1), np.nan), np.full(max(k, 1), np.nan)
+        self._ck(self.L.gv_pca_dev(self.h, int(k), int(L), self._handles(q0), float(tol), int(max_iter), self._handles(us), _dp(ev), _dp(rs)))
+        return ev[:k], rs[:k]
+
+    def pca_loadings_dev(self, us, ev, vs):
+        """gv_pca_loadings_dev: vs[i] = c_i * ATx(us[i]), the right singular vectors of this rank's markers (M-space vectors)"""
+        ev = np.ascontiguousarray(ev, dtype=np.float64)
+        assert ev.size == len(us) == len(vs)
+        self._ck(self.L.gv_pca_loadings_dev(self.h, len(us), self._handles(us), _dp(ev), self._handles(vs)))
+
+    def pca_info(self):
+        """gv_pca_info of the last pca_dev / pca as a dict"""
+        st = PcaStats()
+        self._ck(self.L.gv_pca_info(self.h, C.byref(st)))
+        return dict(iterations=st.iterations, converged=st.converged, block=st.block, cols_atxm=st.cols_atxm, cols_score=st.cols_score,
+                    scratch_bytes=int(st.scratch_bytes), seconds_products=st.seconds_products, seconds_panel=st.seconds_panel,
+                    seconds=st.seconds)
+
+    def pca(self, k, block=None, tol=1e-8, max_iter=100, seed=0, loadings=False, strict=True):
+        """the k leading principal components of the resident genotypes: dict eval (k,), evec (k, N), resid (k,), info and, with
+        loadings, loadings (k, M).  The starting block is `block` columns (default min(32, k + max(8, k))) of standard normals from
+        numpy.random.default_rng(seed); an unconverged result raises GvError unless strict is false."""
+        L = min(PCA_MAX_BLOCK, k + max(8, k)) if block is None else int(block)
+        if k < 1 or L < k or L > PCA_MAX_BLOCK:
+            raise GvError("pca: need 1 <= k <= block <= %d (k = %d, block = %d)" % (PCA_MAX_BLOCK, k, L))
+        Q0 = np.zeros((L, 4 * self.mbytes))
+        Q0[:, :self.N] = np.random.default_rng(seed).standard_normal((L, self.N))
+        q0, us, vs = [self.vecN(q) for q in Q0], [self.vecN() for _ in range(k)], []
+        try:
+            ev, rs = self.pca_dev(q0, us, tol, max_iter)
+            info = self.pca_info()
+            if strict and not info["converged"]:
+                raise GvError("pca: not converged after %d iterations (largest r / theta = %.3g, tol = %.3g)"
+                              % (info["iterations"], float(np.max(rs / ev)), tol))
+            out = dict(eval=ev, resid=rs, info=info, evec=np.stack([u.download()[:self.N] for u in us]))
+            if loadings:
+                vs = [self.vecM() for _ in range(k)]
+                self.pca_loadings_dev(us, ev, vs)
+                out["loadings"] = np.stack([v.download() for v in vs])
+            return out
+        finally:
+            for v in q0 + us + vs:
+                v.free()
 
     def ax2_dev(self, xa, xb, outa, outb):
         self._ck(self.L.gv_ax2_dev(self.h, xa.h, xb.h, outa.h, outb.h))

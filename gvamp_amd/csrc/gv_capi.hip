@@ -201,6 +201,7 @@ static void free_dataset(gv_ctx* c) {
     free_layouts(c);
     score_release(c);
     atxm_release(c);
+    pca_release(c);
     F(c->cgx_state); F(c->cgx_go);
     if (c->cgx_rel_h) (void)hipHostFree(c->cgx_rel_h);
     c->cgx_rel = c->cgx_rel_h = nullptr;

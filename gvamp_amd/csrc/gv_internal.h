@@ -216,6 +216,11 @@ struct gv_ctx {
     int atxm_cols = 0, atxm_ks = 0;
     int atxm_min_cols = GV_ATXM_MIN_COLS_DEFAULT;
     gv_atxm_stats atxm_last{};
+    // gv_pca_dev (gv_pca.hip): the work panels and small buffers (grown on demand, freed with the dataset) and what
+    // gv_pca_info reports
+    void* pca_buf = nullptr;
+    size_t pca_cap = 0;
+    gv_pca_stats pca_last{};
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;
@@ -514,6 +519,8 @@ void score_release(gv_ctx* c);
 // gv_atxm.hip: R = A^T Y on device pointers (C > 0 columns, p[j] npad doubles, out[j] M doubles); the scratch of its kernel path
 int atxm_device(gv_ctx* c, int64_t C, const double* const* p, double* const* out);
 void atxm_release(gv_ctx* c);
+// gv_pca.hip: the scratch of gv_pca_dev
+void pca_release(gv_ctx* c);
 
 struct Timer {
     gv_ctx* c;

@@ -369,6 +369,61 @@ std::vector<std::vector<double>> data::ATx_multi(const std::vector<std::vector<d
     return out;
 }
 
+double data::pca_start(unsigned long long seed, unsigned long long index) {
+    auto mix = [](unsigned long long z) {
+        z += 0x9E3779B97F4A7C15ULL;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+        return z ^ (z >> 31);
+    };
+    const unsigned long long base = mix(seed);
+    const double u1 = ((double)(mix(base + 2 * index) >> 11) + 0.5) * 0x1p-53, u2 = ((double)(mix(base + 2 * index + 1) >> 11) + 0.5) * 0x1p-53;
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+data::pca_result data::pca(int k, int L, double tol, int max_iter, unsigned long long seed, bool loadings) {
+    pca_result out;
+    const size_t n4 = 4 * (size_t)mbytes, Mp = M > 0 ? (size_t)M : 0;
+    std::vector<gv_vec*> q0, u, v;
+    auto drop = [&]() {
+        for (auto* vs : {&q0, &u, &v})
+            for (gv_vec* x : *vs) gv_vec_free(ctx, x);
+    };
+    auto vec = [&](int space, std::vector<gv_vec*>& to) {
+        gv_vec* x = nullptr;
+        ck(ctx, gv_vec_alloc(ctx, space, &x), "gv_vec_alloc");
+        to.push_back(x);
+        return x;
+    };
+    std::vector<double> buf(n4, 0.0);
+    for (int j = 0; j < L; j++) {
+        for (int n = 0; n < N; n++) buf[(size_t)n] = pca_start(seed, (unsigned long long)j * (unsigned long long)N + (unsigned long long)n);
+        ck(ctx, gv_vec_upload(ctx, vec(GV_SPACE_N, q0), buf.data()), "gv_vec_upload");
+    }
+    for (int i = 0; i < k; i++) vec(GV_SPACE_N, u);
+    out.eval.assign((size_t)(k > 0 ? k : 1), 0.0);
+    out.resid.assign((size_t)(k > 0 ? k : 1), 0.0);
+    if (gv_pca_dev(ctx, k, L, q0.data(), tol, max_iter, u.data(), out.eval.data(), out.resid.data())) {
+        std::cout << "FATAL: gv_pca_dev: " << gv_last_error(ctx) << std::endl;
+        drop();
+        exit(EXIT_FAILURE);
+    }
+    gv_pca_info(ctx, &out.info);
+    out.evec.assign((size_t)k, std::vector<double>(n4, 0.0));
+    for (int i = 0; i < k; i++) ck(ctx, gv_vec_download(ctx, u[(size_t)i], out.evec[(size_t)i].data()), "gv_vec_download");
+    if (loadings) {
+        for (int i = 0; i < k; i++) vec(GV_SPACE_M, v);
+        ck(ctx, gv_pca_loadings_dev(ctx, k, u.data(), out.eval.data(), v.data()), "gv_pca_loadings_dev");
+        out.loadings.assign((size_t)k, std::vector<double>(Mp > 0 ? Mp : 1, 0.0));
+        for (int i = 0; i < k; i++) {
+            ck(ctx, gv_vec_download(ctx, v[(size_t)i], out.loadings[(size_t)i].data()), "gv_vec_download");
+            out.loadings[(size_t)i].resize(Mp);
+        }
+    }
+    drop();
+    return out;
+}
+
 void data::set_mask(const std::vector<unsigned char>& m4, int nonas_) {
     if (m4.size() != mbytes) {
         std::cout << "FATAL: data::set_mask: " << m4.size() << " mask bytes, not mbytes = " << mbytes << std::endl;

@@ -82,6 +82,16 @@ public:
     // [ext] the marginal association screen (gv_screen_dev): cols[j] = N raw phenotype values, NaN for NA, every NA outside the mask.
     // Returns {r, t, p}, each C columns of M values.
     std::vector<std::vector<std::vector<double>>> screen(const std::vector<std::vector<double>>& cols);
+    // [ext] principal components of the resident genotypes (gv_pca_dev): the k leading eigenpairs of the
+    // relationship matrix from a starting block of L columns of pca_start(seed, ...); loadings: this shard's M values per component
+    struct pca_result {
+        std::vector<double> eval, resid;
+        std::vector<std::vector<double>> evec, loadings;      // k x 4 * mbytes, k x M (empty without loadings)
+        gv_pca_stats info;
+    };
+    pca_result pca(int k, int L, double tol, int max_iter, unsigned long long seed, bool loadings);
+    // entry n of column j of the starting block: Box-Muller on two splitmix64 outputs of the counter 2 (j N + n) (+ 1) from `seed`
+    static double pca_start(unsigned long long seed, unsigned long long index);
     // [ext] replace the mask (bit n & 3 of byte n >> 2 set: individual n has a phenotype) and recompute the marker statistics
     void set_mask(const std::vector<unsigned char>& m4, int nonas_);
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled

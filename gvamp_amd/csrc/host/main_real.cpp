@@ -1,6 +1,7 @@
 // main_real.cpp -- real-data driver mirroring the reference's main_real.cpp:13-599, all run modes:
 //   infere (:34-128), test (:129-213), both (:214-283), pvals-calc (:284-368), restart (:369-385),
-//   predict (:386-437), predict_single (:438-594); [ext] ldscore (gv_ld_scores), clump (gv_ld_clump, section 20).
+//   predict (:386-437), predict_single (:438-594); [ext] ldscore (gv_ld_scores), clump (gv_ld_clump, section 20),
+//   score (section 21), screen (section 23), pca (gv_pca_dev, section 24).
 // Every mode is "load data, maybe run vamp::infere, one or more data::Ax, a reduction, a file": the matvecs are HIP
 // kernels behind libgvamp, the rest is host code.  One process per GPU (RANK / WORLD_SIZE from the launcher).
 #include <algorithm>
@@ -567,6 +568,62 @@ int main(int argc, char** argv) {
             std::cout << "screen: " << C << " phenotypes x " << Mt << " markers, " << nonas << " complete cases of " << N << ", "
                       << (st.path == GV_ATXM_PATH_KERNEL ? "kernel" : "fallback") << " path, " << passes << " passes, " << seconds
                       << " seconds -> " << pre << "_screen_{r,t,p}.bin" << std::endl;
+    } else if (mode == "pca") {                                                        // [ext] DESIGN.md section 24
+        // the K leading principal components of the standardised genotypes among the individuals with a phenotype
+        const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
+        const int K = (int)opt.get_pca_k();
+        if (K < 1) {
+            std::cout << "FATAL: --run-mode pca needs --pca-k K, the number of principal components (1.." << GV_PCA_MAX_BLOCK << ")" << std::endl;
+            return EXIT_FAILURE;
+        }
+        const int L = opt.get_pca_block() ? (int)opt.get_pca_block() : std::min(GV_PCA_MAX_BLOCK, K + std::max(8, K));
+        if (L < K || L > GV_PCA_MAX_BLOCK) {
+            std::cout << "FATAL: --run-mode pca: the block has to hold --pca-k = " << K << " vectors and at most " << GV_PCA_MAX_BLOCK
+                      << " (--pca-block " << L << ")" << std::endl;
+            return EXIT_FAILURE;
+        }
+        if ((long long)K * Mt > 2147483647LL) {
+            std::cout << "FATAL: --run-mode pca: " << K << " columns x " << Mt << " markers exceed the 2^31 - 1 values of an output file" << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::vector<double> MS = divide_work(Mt);
+        const int M = (int)MS[0], S = (int)MS[1];
+        need_phen(opt.get_phen_files(), "--phen-files");
+        data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss, droute);
+        const data::pca_result res = dataset.pca(K, L, opt.get_pca_tol(), (int)opt.get_pca_max_iter(), opt.get_pca_seed(), true);
+        const std::string pre = opt.get_out_dir() + opt.get_out_name();
+        double worst = 0.0;
+        for (int i = 0; i < K; i++) worst = std::max(worst, res.resid[(size_t)i] / res.eval[(size_t)i]);
+        if (!res.info.converged) {
+            // eigenvectors that missed the tolerance are not covariates anybody asked for: nothing is written unless the caller says so
+            const bool allow = opt.get_pca_allow_unconverged() == 1;
+            std::cout << (allow ? "WARNING" : "FATAL") << ": --run-mode pca: NOT converged after " << res.info.iterations
+                      << " iterations (largest r / theta = " << worst << ", --pca-tol " << opt.get_pca_tol() << ")"
+                      << (allow ? ": the files hold the last Ritz pairs (--pca-allow-unconverged 1)"
+                                : ": nothing written; raise --pca-max-iter or --pca-block, or pass --pca-allow-unconverged 1")
+                      << std::endl;
+            if (!allow) return EXIT_FAILURE;
+        }
+        // column i of the loadings starts at value i * Mt of the file: within an int by the K * Mt check above
+        for (int i = 0; i < K; i++) mpi_store_vec_to_file(pre + "_pca_loadings.bin", res.loadings[(size_t)i], (int)((size_t)i * (size_t)Mt) + S, M);
+        if (rank == 0) {                                       // N-space is the same on every rank
+            FILE* fv = fopen((pre + "_pca_eigenval.txt").c_str(), "w");
+            FILE* fu = fopen((pre + "_pca_eigenvec.txt").c_str(), "w");
+            bool ok = fv && fu;
+            for (int i = 0; i < K && ok; i++) ok = fprintf(fv, "%.17g\n", res.eval[(size_t)i]) > 0;
+            for (int n = 0; n < N && ok; n++)
+                for (int i = 0; i < K && ok; i++) ok = fprintf(fu, i + 1 < K ? "%.17g " : "%.17g\n", res.evec[(size_t)i][(size_t)n]) > 0;
+            if (fv) ok = fclose(fv) == 0 && ok;
+            if (fu) ok = fclose(fu) == 0 && ok;
+            if (!ok) {
+                std::cout << "FATAL: cannot write " << pre << "_pca_eigenval.txt / _pca_eigenvec.txt" << std::endl;
+                return EXIT_FAILURE;
+            }
+            std::cout << "pca: " << K << " components of " << N << " individuals x " << Mt << " markers, block " << L << ", "
+                      << res.info.iterations << " iterations, " << (res.info.converged ? "converged" : "NOT converged") << " (largest r / theta = "
+                      << worst << ", tol " << opt.get_pca_tol() << "), products " << res.info.seconds_products << " s, panel kernels "
+                      << res.info.seconds_panel << " s -> " << pre << "_pca_{eigenval.txt,eigenvec.txt,loadings.bin}" << std::endl;
+        }
     } else if (mode == "predict" || mode == "predict_single") {                        // :386-594
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);

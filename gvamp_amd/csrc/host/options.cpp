@@ -203,6 +203,12 @@ void Options::read_command_line_options(int argc, char** argv) {
     str("--score-p-file", score_p_file);
     uns("--score-cols", score_cols, POS, "a strictly positive integer");
     uns("--screen-cols", screen_cols, POS, "a strictly positive integer");
+    uns("--pca-k", pca_k, POS, "a strictly positive integer");
+    uns("--pca-block", pca_block, POS, "a strictly positive integer");
+    uns("--pca-max-iter", pca_max_iter, POS, "a strictly positive integer");
+    uns("--pca-seed", pca_seed, NONNEG, "a non-negative integer");
+    uns("--pca-allow-unconverged", pca_allow_unconverged, NONNEG, "a non-negative integer");
+    num("--pca-tol", pca_tol);
     H["--score-units"] = [&](const char* a) {
         if (strcmp(a, "std") && strcmp(a, "allele"))
             fatal(std::string("FATAL  : option --score-units has to be std or allele! (") + a + " was passed)");

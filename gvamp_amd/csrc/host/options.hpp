@@ -73,7 +73,14 @@
        --run-mode screen (gv_screen_dev) with --phen-files f0,f1,...: the marginal association      \
        screen of every phenotype file against every marker over the complete cases (an individual with NA in any file    \
        is masked): <out>_screen_{r,t,p}.bin, one column of Mt float64 per file; --screen-cols K (default 64): columns    \
-       per call */                                                                                                      \
+       per call;                                                                                                        \
+       --run-mode pca (gv_pca_dev) with --pca-k K: the K leading principal components of the       \
+       standardised genotypes among the individuals with a phenotype, by block subspace iteration on a block of          \
+       --pca-block L vectors (default min(32, K + max(8, K))) to --pca-tol t (default 1e-8) within --pca-max-iter n       \
+       (default 100) iterations from the starting block of --pca-seed s (default 0); a run that misses the tolerance      \
+       writes nothing and exits non-zero unless --pca-allow-unconverged 1 (default 0): <out>_pca_eigenval.txt,            \
+       <out>_pca_eigenvec.txt (N lines of K numbers: a --cov-file for --C K) and <out>_pca_loadings.bin (K columns of    \
+       Mt float64: a --score-file for --score-cols K) */                                                                 \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
@@ -84,7 +91,9 @@
     X(std::string, clump_p_file, "") X(double, clump_p1, 1e-4) X(double, clump_p2, 1e-2) X(double, clump_r2, 0.5)      \
     X(double, clump_kb, -1)                                                                                          \
     X(std::string, score_file, "") X(unsigned int, score_cols, 1) X(std::string, score_units, "std")                \
-    X(std::string, score_clump_index, "") X(std::string, score_p_file, "") X(unsigned int, screen_cols, 64)
+    X(std::string, score_clump_index, "") X(std::string, score_p_file, "") X(unsigned int, screen_cols, 64)   \
+    X(unsigned int, pca_k, 0) X(unsigned int, pca_block, 0) X(double, pca_tol, 1e-8) X(unsigned int, pca_max_iter, 100)          \
+    X(unsigned int, pca_seed, 0) X(unsigned int, pca_allow_unconverged, 0)
 
 class Options {
 public:

@@ -911,6 +911,57 @@ int gv_atxm_info(const gv_ctx* ctx, gv_atxm_stats* out);
 int gv_screen_dev(gv_ctx* ctx, int64_t C, const gv_vec* const* u /* C, GV_SPACE_N */, gv_vec* const* r, gv_vec* const* t,
                   gv_vec* const* p /* C each, GV_SPACE_M; t and p may be NULL arrays */);
 
+/* ---- principal components of the resident genotypes by block subspace iteration (additions only: GV_ABI_VERSION stays 4; DESIGN.md
+ * section 24) ------------------------------------------------------------------------------------------------------------------------
+ * A is the matrix gv_ax_dev / gv_atx_dev apply (mean-imputed, centred, scaled by msig, divided by sqrt(N), rows of NA and pad
+ * individuals zero) and G = (N / Mt) A A^T the genetic relationship matrix over the markers of all ranks.  gv_pca_dev returns the k
+ * largest eigenpairs (eval[i], u[i]) of G, eval descending; u[i] is N-space, of unit 2-norm, zero at NA and pad slots, and its entry of
+ * largest magnitude is positive (the lowest index on ties).
+ * Algorithm, on a block of L vectors, k <= L <= GV_PCA_MAX_BLOCK, the caller giving the starting block q0 (not modified):
+ *     Q <- orth(mask q0)
+ *     each iteration:  B = gv_atxm_dev(Q);  Y = fl((N / Mt) gv_score_dev(B));  T = sym(Q^T Y) = V Theta V^T, Theta descending;
+ *                      U = Q V;  R = Y V - U Theta;  r_i = ||R_i||_2
+ *     stop when r_i <= tol * theta_i for every i < k; otherwise Q <- orth(Y), up to max_iter iterations.
+ * orth is CholeskyQR applied twice (S = Y^T Y, S = R^T R, Y <- Y R^-1).  A pivot d of the factorisation that is not above
+ * 32 * 2^-52 times its own diagonal entry of S counts as not positive: the block is rank deficient to working precision.
+ * Everything between two products runs in kernels of gv_pca.hip, in fp64, in an order of operations that is a function of (npad, L)
+ * alone: no atomics, fixed grids, a fixed rotation order in the eigensolver.  The products are bit-identical per column whatever their
+ * path and pins (GV_SCORE_COLS / GV_SCORE_KS / GV_SCORE_KERNEL, GV_ATXM_COLS / GV_ATXM_KS / GV_ATXM_KERNEL, a communicator), so u, eval
+ * and resid are bit-reproducible across them.  Per iteration the host reads back theta[0..k), r[0..k) and the Cholesky flag through the
+ * scalar mailbox, once; that read-back is the convergence decision.  Everything but B is N-space, identical on every rank behind Ax's
+ * own all-reduce: a sharded job needs no collective of its own.
+ * Running out of max_iter is not an error: the call returns 0 with gv_pca_stats.converged = 0 and the last Ritz pairs and residuals.
+ * resid[i] is the residual of (eval[i], u[i]) as the iteration formed it from the Y it already had: ||G u_i - eval_i u_i|| up to the
+ * products' own error.
+ * Refused with a message, no output written: k < 1; L < k; L > GV_PCA_MAX_BLOCK; L > min(nonas, Mt); tol not a positive finite number;
+ * max_iter < 1; NULL arrays or handles; vectors that are not N-space, of another context or of earlier dimensions; two outputs that
+ * are the same vector; an output that is also an input; mask or marker statistics missing (the message of gv_ax_dev); a Cholesky
+ * pivot that is not positive by the rule above (a rank-deficient starting block, or rank(G) < L; the message names the threshold).
+ * Served wherever gv_score_dev / gv_atxm_dev are: every data kind, layout and kernel mode, with or without a communicator.
+ * Scratch: four N-space panels and one M-space panel of L columns and a few small buffers, gv_pca_stats.scratch_bytes in all, OWNED BY
+ * THE CONTEXT: grown by the call that needs it, kept for the next, freed with the dataset (gv_set_dims) and by gv_destroy.  The call
+ * leaves the context as it found it, by the rule of gv_score_dev / gv_atxm_dev; it writes the reduction scalars as gv_vec_dots does.
+ * gv_pca_loadings_dev: v[i] = fl(c_i * gv_atx_dev(u[i])), c_i = fl(fl(sqrt(fl(N / Mt))) / fl(sqrt(eval[i]))): the right singular
+ * vectors in M-space (this rank's markers), one rounding after the product; k <= GV_PCA_MAX_BLOCK, eval[i] positive and finite.
+ * gv_pca_info: the last successful gv_pca_dev of the context. */
+#define GV_PCA_MAX_BLOCK 32
+typedef struct gv_pca_stats {
+    int iterations;              /* iterations run (each one pass of L columns through both batch products) */
+    int converged;               /* 1: r_i <= tol * theta_i for every i < k; 0: max_iter ran out */
+    int block;                   /* L */
+    int pad_;
+    int64_t cols_atxm;           /* columns through gv_atxm_dev's product in all */
+    int64_t cols_score;          /* columns through gv_score_dev's product in all */
+    uint64_t scratch_bytes;      /* bytes of the work panels and small buffers */
+    double seconds_products;     /* device time in the two batch products (events on the context's stream) */
+    double seconds_panel;        /* device time in the panel kernels: orthonormalisation, Rayleigh-Ritz, rotation, residuals */
+    double seconds;              /* host wall time of the call */
+} gv_pca_stats;
+int gv_pca_dev(gv_ctx* ctx, int k, int L, const gv_vec* const* q0 /* L, GV_SPACE_N, not modified */, double tol, int max_iter,
+               gv_vec* const* u /* k, GV_SPACE_N */, double* eval /* k */, double* resid /* k */);
+int gv_pca_loadings_dev(gv_ctx* ctx, int k, const gv_vec* const* u, const double* eval, gv_vec* const* v /* k, GV_SPACE_M */);
+int gv_pca_info(const gv_ctx* ctx, gv_pca_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
