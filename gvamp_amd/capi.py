@@ -37,6 +37,7 @@ EXPORTS = [
     "gv_score_dev", "gv_score", "gv_score_info",
     "gv_atxm_dev", "gv_atxm", "gv_atxm_info", "gv_screen_dev",
     "gv_pca_dev", "gv_pca_loadings_dev", "gv_pca_info",
+    "gv_king_block", "gv_king_pairs", "gv_king_info",
 ]
 
 
@@ -81,6 +82,11 @@ class PcaStats(C.Structure):           # gv_pca_stats
 
 
 PCA_MAX_BLOCK = 32
+
+
+class KingStats(C.Structure):          # gv_king_stats
+    _fields_ = [("seconds", C.c_double), ("block_pairs", C.c_int64), ("used_markers", C.c_int64), ("pairs", C.c_int64),
+                ("useful_macs", C.c_double), ("scratch_bytes", C.c_double)]
 
 
 class CgStats(C.Structure):
@@ -231,6 +237,10 @@ def load():
     L.gv_ld_scores.argtypes = [vp, i64, C.POINTER(C.c_int), C.c_int, dp, dp]
     L.gv_ld_band.argtypes = [vp, i64, C.POINTER(C.c_int), i64, i64, dp]
     L.gv_ld_info.argtypes = [vp, C.POINTER(LdStats)]
+    i32p = C.POINTER(C.c_int32)
+    L.gv_king_block.argtypes = [vp, up, i64, i64, i64, i64, dp, i32p]
+    L.gv_king_pairs.argtypes = [vp, up, C.c_double, i64, i32p, i32p, dp, i32p, C.POINTER(i64)]
+    L.gv_king_info.argtypes = [vp, C.POINTER(KingStats)]
     L.gv_ld_scores_pos.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, dp]
     L.gv_ld_last_passes.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_ld_clump.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), dp, C.c_double, C.c_double, C.c_double, C.POINTER(i64), C.POINTER(i64)]
@@ -804,6 +814,57 @@ class Shard:
         ev = np.ascontiguousarray(ev, dtype=np.float64)
         assert ev.size == len(us) == len(vs)
         self._ck(self.L.gv_pca_loadings_dev(self.h, len(us), self._handles(us), _dp(ev), self._handles(vs)))
+
+    # ---- pairwise kinship (gv_king_*) ------------------------------------------------
+    def _use(self, use):
+        if use is None:
+            return None, None
+        u = np.ascontiguousarray(use, dtype=np.uint8)
+        assert u.size == self.M, (u.size, self.M)
+        return u, _up(u)
+
+    def king_block(self, i0, ni, j0, nj, use=None):
+        """gv_king_block: (kin[ni, nj] float64, counts[ni, nj, 5] int32 = nsnp, hethet, ibs0, het_i, het_j) of the individuals
+        [i0, i0 + ni) x [j0, j0 + nj); use: M bytes, non-zero = the marker counts (None: every marker)"""
+        ni_, nj_ = int(ni), int(nj)
+        kin = np.zeros((max(ni_, 0), max(nj_, 0)))
+        cnt = np.zeros((max(ni_, 0), max(nj_, 0), 5), dtype=np.int32)
+        u, upt = self._use(use)
+        self._ck(self.L.gv_king_block(self.h, upt, int(i0), ni_, int(j0), nj_, _dp(kin) if kin.size else None,
+                                      cnt.ctypes.data_as(C.POINTER(C.c_int32)) if cnt.size else None))
+        return kin, cnt
+
+    def king_pairs_raw(self, cutoff, cap, use=None):
+        """gv_king_pairs with the caller's cap: (n_found, i, j, kin, counts); the arrays hold the pairs only when n_found <= cap"""
+        cap_ = int(cap)
+        n = max(cap_, 1)
+        pi, pj = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        kin, cnt = np.zeros(n), np.zeros((n, 5), dtype=np.int32)
+        found = C.c_int64(-1)
+        u, upt = self._use(use)
+        i32p = C.POINTER(C.c_int32)
+        self._ck(self.L.gv_king_pairs(self.h, upt, float(cutoff), cap_, pi.ctypes.data_as(i32p), pj.ctypes.data_as(i32p), _dp(kin),
+                                      cnt.ctypes.data_as(i32p), C.byref(found)))
+        return found.value, pi, pj, kin, cnt
+
+    def king_pairs(self, cutoff, use=None, cap=None):
+        """every pair i < j with kin >= cutoff in ascending (i, j): (i, j, kin, counts[., 5]).  cap: the first call's slots (default
+        65536); one more call with the number found when they did not suffice"""
+        cap_ = 65536 if cap is None else int(cap)
+        found, pi, pj, kin, cnt = self.king_pairs_raw(cutoff, cap_, use)
+        if found > cap_:
+            cap_ = found
+            found, pi, pj, kin, cnt = self.king_pairs_raw(cutoff, cap_, use)
+            if found > cap_:
+                raise GvError("king_pairs: %d pairs found with room for %d on the second call" % (found, cap_))
+        return pi[:found].copy(), pj[:found].copy(), kin[:found].copy(), cnt[:found].copy()
+
+    def king_info(self):
+        """gv_king_info of the last king_block / king_pairs call as a dict"""
+        st = KingStats()
+        self._ck(self.L.gv_king_info(self.h, C.byref(st)))
+        return dict(seconds=st.seconds, block_pairs=st.block_pairs, used_markers=st.used_markers, pairs=st.pairs,
+                    useful_macs=st.useful_macs, scratch_bytes=st.scratch_bytes)
 
     def pca_info(self):
         """gv_pca_info of the last pca_dev / pca as a dict"""

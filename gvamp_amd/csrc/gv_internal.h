@@ -221,6 +221,7 @@ struct gv_ctx {
     void* pca_buf = nullptr;
     size_t pca_cap = 0;
     gv_pca_stats pca_last{};
+    gv_king_stats king_last{};      // gv_king_info: the last gv_king_block / gv_king_pairs call (gv_king.hip)
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;

@@ -424,6 +424,42 @@ data::pca_result data::pca(int k, int L, double tol, int max_iter, unsigned long
     return out;
 }
 
+data::king_result data::king_pairs(double cutoff, const std::vector<unsigned char>& use) {
+    if (!use.empty() && use.size() != (size_t)(M > 0 ? M : 0)) die("FATAL: data::king_pairs: the marker selection must hold M bytes");
+    king_result out;
+    int64_t cap = 65536, found = 0;
+    for (int round = 0; round < 2; round++) {
+        out.i.assign((size_t)cap, 0);
+        out.j.assign((size_t)cap, 0);
+        out.kin.assign((size_t)cap, 0.0);
+        out.counts.assign(5 * (size_t)cap, 0);
+        ck(ctx, gv_king_pairs(ctx, use.empty() ? nullptr : use.data(), cutoff, cap, out.i.data(), out.j.data(), out.kin.data(), out.counts.data(),
+                              &found), "gv_king_pairs");
+        if (found <= cap) break;
+        if (round == 1) die("FATAL: data::king_pairs: more pairs on the second call than the first one counted");
+        cap = found;
+    }
+    out.i.resize((size_t)found);
+    out.j.resize((size_t)found);
+    out.kin.resize((size_t)found);
+    out.counts.resize(5 * (size_t)found);
+    gv_king_info(ctx, &out.info);
+    return out;
+}
+
+data::king_result data::king_block(int64_t i0, int64_t ni, int64_t j0, int64_t nj, const std::vector<unsigned char>& use) {
+    if (!use.empty() && use.size() != (size_t)(M > 0 ? M : 0)) die("FATAL: data::king_block: the marker selection must hold M bytes");
+    king_result out;
+    const size_t ne = ni > 0 && nj > 0 ? (size_t)ni * (size_t)nj : 0;
+    out.kin.assign(ne ? ne : 1, 0.0);
+    out.counts.assign(5 * (ne ? ne : 1), 0);
+    ck(ctx, gv_king_block(ctx, use.empty() ? nullptr : use.data(), i0, ni, j0, nj, out.kin.data(), out.counts.data()), "gv_king_block");
+    out.kin.resize(ne);
+    out.counts.resize(5 * ne);
+    gv_king_info(ctx, &out.info);
+    return out;
+}
+
 void data::set_mask(const std::vector<unsigned char>& m4, int nonas_) {
     if (m4.size() != mbytes) {
         std::cout << "FATAL: data::set_mask: " << m4.size() << " mask bytes, not mbytes = " << mbytes << std::endl;

@@ -92,6 +92,17 @@ public:
     pca_result pca(int k, int L, double tol, int max_iter, unsigned long long seed, bool loadings);
     // entry n of column j of the starting block: Box-Muller on two splitmix64 outputs of the counter 2 (j N + n) (+ 1) from `seed`
     static double pca_start(unsigned long long seed, unsigned long long index);
+    // [ext] pairwise kinship of the resident genotypes (gv_king_pairs / gv_king_block).  use: M bytes, non-zero = the
+    // marker counts (empty: every marker).  king_pairs: every pair i < j with kin >= cutoff in ascending (i, j), re-called once with the
+    // number found when the first call's slots did not suffice; king_block: the rectangle [i0, i0 + ni) x [j0, j0 + nj), row-major
+    struct king_result {
+        std::vector<int32_t> i, j;          // king_pairs only
+        std::vector<double> kin;
+        std::vector<int32_t> counts;        // 5 per entry: nsnp, hethet, ibs0, het_i, het_j
+        gv_king_stats info;
+    };
+    king_result king_pairs(double cutoff, const std::vector<unsigned char>& use = std::vector<unsigned char>());
+    king_result king_block(int64_t i0, int64_t ni, int64_t j0, int64_t nj, const std::vector<unsigned char>& use = std::vector<unsigned char>());
     // [ext] replace the mask (bit n & 3 of byte n >> 2 set: individual n has a phenotype) and recompute the marker statistics
     void set_mask(const std::vector<unsigned char>& m4, int nonas_);
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled

@@ -1,7 +1,7 @@
 // main_real.cpp -- real-data driver mirroring the reference's main_real.cpp:13-599, all run modes:
 //   infere (:34-128), test (:129-213), both (:214-283), pvals-calc (:284-368), restart (:369-385),
 //   predict (:386-437), predict_single (:438-594); [ext] ldscore (gv_ld_scores), clump (gv_ld_clump, section 20),
-//   score (section 21), screen (section 23), pca (gv_pca_dev, section 24).
+//   score (section 21), screen (section 23), pca (gv_pca_dev, section 24), king (gv_king_pairs, section 25).
 // Every mode is "load data, maybe run vamp::infere, one or more data::Ax, a reduction, a file": the matvecs are HIP
 // kernels behind libgvamp, the rest is host code.  One process per GPU (RANK / WORLD_SIZE from the launcher).
 #include <algorithm>
@@ -624,6 +624,45 @@ int main(int argc, char** argv) {
                       << worst << ", tol " << opt.get_pca_tol() << "), products " << res.info.seconds_products << " s, panel kernels "
                       << res.info.seconds_panel << " s -> " << pre << "_pca_{eigenval.txt,eigenvec.txt,loadings.bin}" << std::endl;
         }
+    } else if (mode == "king") {                                                       // [ext] DESIGN.md section 25
+        // the pairs of individuals at or above a kinship cutoff, from the genotypes alone: no phenotype file
+        if (type_data != "bed") {
+            std::cout << "FATAL: --run-mode king works on 2-bit genotypes only, not on --geno-format " << type_data << std::endl;
+            return EXIT_FAILURE;
+        }
+        if (gv_env_nranks() > 1) {
+            std::cout << "FATAL: --run-mode king runs on one rank: the counts of a pair are sums over the markers of all ranks, and the "
+                         "integer all-reduce that would add them is not built" << std::endl;
+            return EXIT_FAILURE;
+        }
+        const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
+        std::vector<unsigned char> use;
+        if (opt.get_king_marker_file() != "") {
+            std::ifstream in(opt.get_king_marker_file(), std::ios::binary);
+            use.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+            if (!in.is_open() || use.size() != (size_t)Mt) {
+                std::cout << "FATAL: --king-marker-file " << opt.get_king_marker_file() << " must hold Mt = " << Mt << " bytes of 0 / 1 ("
+                          << (in.is_open() ? std::to_string(use.size()) + " bytes read" : std::string("cannot open it")) << ")" << std::endl;
+                return EXIT_FAILURE;
+            }
+        }
+        setenv("GVAMP_RESIDENT_LAYOUT", "2", 0);      // the kernel reads the tile layout (a --resident-layout given on the command line stands)
+        data dataset(std::vector<double>(N, 0.0), opt.get_bed_file(), N, Mt, Mt, 0, rank, type_data, alpha_scale, bimfp, dev, km);
+        const data::king_result res = dataset.king_pairs(opt.get_king_cutoff(), use);
+        const std::string path = opt.get_out_dir() + opt.get_out_name() + "_king.kin0.txt";
+        FILE* f = fopen(path.c_str(), "w");
+        bool ok = f != nullptr;
+        for (size_t t = 0; t < res.i.size() && ok; t++) {
+            const int32_t* q = &res.counts[5 * t];
+            ok = fprintf(f, "%d %d %d %d %d %d %d %.17g\n", res.i[t], res.j[t], q[0], q[1], q[2], q[3], q[4], res.kin[t]) > 0;
+        }
+        if (f) ok = fclose(f) == 0 && ok;
+        if (!ok) {
+            std::cout << "FATAL: cannot write " << path << std::endl;
+            return EXIT_FAILURE;
+        }
+        std::cout << "king: " << N << " individuals x " << res.info.used_markers << " of " << Mt << " markers, cutoff " << opt.get_king_cutoff()
+                  << ": " << res.i.size() << " pairs, " << res.info.seconds << " seconds -> " << path << std::endl;
     } else if (mode == "predict" || mode == "predict_single") {                        // :386-594
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
         std::vector<double> MS = divide_work(Mt_test);

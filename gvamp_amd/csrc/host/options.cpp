@@ -209,6 +209,8 @@ void Options::read_command_line_options(int argc, char** argv) {
     uns("--pca-seed", pca_seed, NONNEG, "a non-negative integer");
     uns("--pca-allow-unconverged", pca_allow_unconverged, NONNEG, "a non-negative integer");
     num("--pca-tol", pca_tol);
+    num("--king-cutoff", king_cutoff);
+    str("--king-marker-file", king_marker_file);
     H["--score-units"] = [&](const char* a) {
         if (strcmp(a, "std") && strcmp(a, "allele"))
             fatal(std::string("FATAL  : option --score-units has to be std or allele! (") + a + " was passed)");

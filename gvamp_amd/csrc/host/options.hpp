@@ -80,7 +80,11 @@
        (default 100) iterations from the starting block of --pca-seed s (default 0); a run that misses the tolerance      \
        writes nothing and exits non-zero unless --pca-allow-unconverged 1 (default 0): <out>_pca_eigenval.txt,            \
        <out>_pca_eigenvec.txt (N lines of K numbers: a --cov-file for --C K) and <out>_pca_loadings.bin (K columns of    \
-       Mt float64: a --score-file for --score-cols K) */                                                                 \
+       Mt float64: a --score-file for --score-cols K);                                                                   \
+       --run-mode king (gv_king_pairs) with --king-cutoff x (default 0.0884, second degree):        \
+       every pair of individuals whose KING-robust kinship is at least x, from the bed file alone (no phenotype file),    \
+       over the markers of --king-marker-file F (Mt bytes of 0 / 1; default: every marker): <out>_king.kin0.txt, one     \
+       line "i j nsnp hethet ibs0 het_i het_j kinship" per pair in ascending (i, j) */                                   \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
@@ -93,7 +97,8 @@
     X(std::string, score_file, "") X(unsigned int, score_cols, 1) X(std::string, score_units, "std")                \
     X(std::string, score_clump_index, "") X(std::string, score_p_file, "") X(unsigned int, screen_cols, 64)   \
     X(unsigned int, pca_k, 0) X(unsigned int, pca_block, 0) X(double, pca_tol, 1e-8) X(unsigned int, pca_max_iter, 100)          \
-    X(unsigned int, pca_seed, 0) X(unsigned int, pca_allow_unconverged, 0)
+    X(unsigned int, pca_seed, 0) X(unsigned int, pca_allow_unconverged, 0)                                           \
+    X(double, king_cutoff, 0.0884) X(std::string, king_marker_file, "")
 
 class Options {
 public:

@@ -962,6 +962,50 @@ int gv_pca_dev(gv_ctx* ctx, int k, int L, const gv_vec* const* q0 /* L, GV_SPACE
 int gv_pca_loadings_dev(gv_ctx* ctx, int k, const gv_vec* const* u, const double* eval, gv_vec* const* v /* k, GV_SPACE_M */);
 int gv_pca_info(const gv_ctx* ctx, gv_pca_stats* out);
 
+/* ---- pairwise kinship (KING-robust) of the resident genotypes (additions only: GV_ABI_VERSION stays 4) -----------
+ * Data: bed data resident in the TILE LAYOUT (gv_get_layout() == 2; kernel mode 1 or 2, the layout is the same), one rank.  The
+ * phenotype mask and the marker statistics are NOT consulted and need not exist: relatedness is a property of the genotypes, and a call
+ * before gv_set_mask works.
+ * For individual n and marker m, a in {0, 1, 2} is the allele count the re-encoding stores (r' = a; r' = 3: missing).  The planes:
+ *   P = present,   H = [a = 1] P,   D = (a - 1) P   (-1, 0 or 1)
+ * `use` (M bytes, one per marker of the shard, non-zero = used; NULL = every marker) multiplies all three.  Pad markers and pad
+ * individuals contribute nothing.  The five integer counts of a pair (i, j), summed over the used markers:
+ *   nsnp = sum P_i P_j    hethet = sum H_i H_j    het_i = sum H_i P_j    het_j = sum P_i H_j    dd = sum D_i D_j
+ * and from them
+ *   homhom = nsnp - het_i - het_j + hethet
+ *   ibs0   = (homhom - dd) / 2          (exact: the markers where both are present and opposite homozygotes)
+ *   d2     = 4 ibs0 + (het_i - hethet) + (het_j - hethet)          (= sum over both present of (a_i - a_j)^2)
+ * Kinship is the between-family KING-robust estimator (Manichaikul et al. 2010):
+ *   mn  = min(het_i, het_j)                       (int64)
+ *   kin = 0.5 - (double)d2 / (double)(4 mn)       one correctly rounded division, one subtraction
+ *   kin = NaN if mn == 0                          (a NaN never passes a cutoff)
+ * The expression is symmetric in exact integers, so kin[i][j] and kin[j][i] are the same bits.  One marker adds at most 1 in magnitude
+ * to any sum: no int32 sum is segmented for M <= 2^31 - 1, and a larger shard is refused.
+ * gv_king_block: the dense rectangle of individuals [i0, i0 + ni) x [j0, j0 + nj), row-major.  counts: 5 int32 per entry in the order
+ *   nsnp, hethet, ibs0, het_i, het_j, het_i being the row individual's and het_j the column individual's.  Either output may be NULL.
+ *   The diagonal gets the same formula (0.5 wherever the individual has a heterozygote).
+ * gv_king_pairs: every pair i < j < N with kin >= cutoff (-inf: every pair whose kin is a number).  *n_found is always set to the number
+ *   of such pairs; the arrays are written only when *n_found <= cap, and then in ascending (i, j) order, het_i being individual i's.
+ *   With *n_found > cap nothing is promised about the arrays, the return code is still 0, and the caller calls again with a larger cap.
+ *   Delivered order and content are a function of the data alone: two calls give the same bytes.  N^2 outputs never exist.
+ * Scratch is taken for the call and freed after it.
+ * Refused with a message, no output written: dosage or methylation data; raw rows only; two stripe sets resident (upload under the tile
+ * layout, gv_set_layout(ctx, .., 2)); a job of more than one rank (the counts are sums over ALL ranks' markers; the integer all-reduce
+ * is not built); NULL n_found, NULL arrays with cap > 0; a rectangle outside [0, N); cap < 0; a cutoff that is NaN or +inf. */
+typedef struct gv_king_stats {
+    double seconds;              /* wall time of the last gv_king_block / gv_king_pairs call */
+    int64_t block_pairs;         /* pairs of 64-individual groups it computed */
+    int64_t used_markers;        /* markers of the shard that counted (use != 0) */
+    int64_t pairs;               /* pairs delivered: ni * nj of a rectangle, the N (N - 1) / 2 pairs gv_king_pairs decided */
+    double useful_macs;          /* 5 products x used_markers x pairs */
+    double scratch_bytes;        /* device scratch it allocated and released */
+} gv_king_stats;
+int gv_king_block(gv_ctx* ctx, const uint8_t* use /* M or NULL */, int64_t i0, int64_t ni, int64_t j0, int64_t nj,
+                  double* kin /* ni * nj or NULL */, int32_t* counts /* ni * nj * 5 or NULL */);
+int gv_king_pairs(gv_ctx* ctx, const uint8_t* use /* M or NULL */, double cutoff, int64_t cap, int32_t* pi, int32_t* pj, double* kin,
+                  int32_t* counts /* cap (x 5) each */, int64_t* n_found);
+int gv_king_info(gv_ctx* ctx, gv_king_stats* info);
+
 #ifdef __cplusplus
 }
 #endif
