@@ -5,15 +5,13 @@
 // sets, kernel modes 0 and 2, methylation and dosage data, an empty shard, fewer columns than min_cols -- the existing dispatcher
 // (gvi::atx_pass) runs, in pairs and singly: identical by construction.  (ATx issues no collective, so a communicator or
 // gv_debug_force_multi does not disqualify the kernel.)  The kernel is identical because every sum is an exact integer and the
-// floating-point steps around it are restated here with the roundings and the orders of gv_mfma.hip:
+// floating-point steps around it are the functions gv_mfma.hip runs (gv_mfma.h: prep_block_partials, prep_scalars, digits_of,
+// combine).  What this file writes itself, in the form of k_prep_atx (without its CG hook) and k_fin_atx (without addx):
 //   scale, P      max |p| (raised to +inf by a NaN or an infinity) and P = sum p over all npad slots: a grid-stride loop of
-//                 prep_blocks(npad) blocks of 256 threads, each thread's terms in index order (s += val), wave butterfly, the four wave
-//                 sums in order (k_prep_atx without its CG hook), then over the blocks: thread t adds blocks t, t + 256, ..., a binary
-//                 tree over 256 threads (prep_scalars).  Both depend on npad alone.
-//   digits        q = rint(val * 2^(54-e)), seven balanced base-256 digits, digit column 7 zero                        (k_quant)
+//                 prep_blocks(npad) blocks of 256 threads, each thread's terms in index order (s += val).  Both depend on npad alone.
 //   planes        X = sum r' digit, Y = sum miss digit per marker, kept apart: the epilogue scales them differently
-//   epilogue      (hi, lo) limbs of each plane (combine); sa = fl(fl(fl(xh - 3 yh) 2^32 + fl(xl - 3 yl)) scale),
-//                 sm = fl(fl(fl(yh) 2^32 + fl(yl)) scale), out = fl(fl(msig fma(-mave, fl(P - sm), sa)) / sqrt(N))   (k_fin_atx, no addx)
+//   epilogue      (hi, lo) limbs of each plane; sa = fl(fl(fl(xh - 3 yh) 2^32 + fl(xl - 3 yl)) scale),
+//                 sm = fl(fl(fl(yh) 2^32 + fl(yl)) scale), out = fl(fl(msig fma(-mave, fl(P - sm), sa)) / sqrt(N))
 // A column with a NaN or an infinity quantises with multiplier 0 and is scaled by NaN: that column is NaN, no other is touched
 // (every column has its own digit columns and accumulators).
 //
@@ -39,30 +37,15 @@
 #include "gv_atxm_plan.h"
 #include "gv_pval_dev.h"
 
-static_assert(gvx::MAX_KS == gvm::GV_MAX_KS, "gv_atxm_plan.h restates GV_MAX_KS");
-static_assert(gvx::PREP_BLOCKS_MAX == RED_BLOCKS, "gv_atxm_plan.h restates the stride of the preparation's block partials");
-
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int PREP_STRIDE = 2 * RED_BLOCKS;   // doubles of block partials per column (as gv_mfma.hip)
-constexpr int PREP_BLOCKS = 256;              // most blocks of the preparation launch (as gv_mfma.hip)
+// the fixed-point operand pipeline, the tile-layout operand helpers and the launch arithmetic: the one copy in gv_mfma.h
+using gvm::v4i; using gvm::u32x4; using gvm::PREP_STRIDE; using gvm::prep_blocks; using gvm::nblk; using gvm::prep_block_partials;
+using gvm::prep_scalars; using gvm::digits_of; using gvm::combine; using gvm::plane_x; using gvm::plane_y; using gvm::wg_barrier_lds;
+using gvm::ABufT; using gvm::transpose_piece;
 
 struct Cols { const double* p[gvx::CP_MAX]; double* out[gvx::CP_MAX]; };
 struct SegB { uint32_t b[gvx::MAX_KS + 1]; };
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 // ---- preparation: block partials [2b] = max |p|, [2b + 1] = sum p of column blockIdx.y (k_prep_atx without its hook)
 __global__ __launch_bounds__(256) void k_atxm_prep(Cols a, int64_t n, double* __restrict__ partial) {
@@ -75,48 +58,7 @@ __global__ __launch_bounds__(256) void k_atxm_prep(Cols a, int64_t n, double* __
         mx = isfinite(val) ? fmax(mx, fabs(val)) : __longlong_as_double(0x7ff0000000000000LL);   // fmax would drop a NaN
         s += val;
     }
-    mx = wave_max(mx);
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) { shm[threadIdx.x >> 6] = mx; shs[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* pv = partial + (int64_t)v * PREP_STRIDE;
-        pv[2 * blockIdx.x] = fmax(fmax(shm[0], shm[1]), fmax(shm[2], shm[3]));
-        pv[2 * blockIdx.x + 1] = shs[0] + shs[1] + shs[2] + shs[3];
-    }
-}
-
-// the four scalars of a column from its block partials: amax, P, 2^(54-e), 2^(e-54) (prep_scalars of gv_mfma.hip, same order)
-__device__ __forceinline__ void atxm_scalars(const double* __restrict__ partial, int nblocks, double* shm, double* shs, double (&out)[4]) {
-    double mx = 0.0, s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        mx = fmax(mx, partial[2 * b]);
-        s += partial[2 * b + 1];
-    }
-    shm[threadIdx.x] = mx;
-    shs[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) {
-            shm[threadIdx.x] = fmax(shm[threadIdx.x], shm[threadIdx.x + off]);
-            shs[threadIdx.x] += shs[threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-    const double amax = shm[0];
-    out[0] = amax;
-    out[1] = shs[0];
-    if (amax > 0.0 && amax <= 1.7976931348623157e308) {
-        int e = ilogb(amax) + 1;
-        out[2] = ldexp(1.0, 54 - e);
-        out[3] = ldexp(1.0, e - 54);
-    } else if (amax == 0.0) {
-        out[2] = 0.0;
-        out[3] = 0.0;
-    } else {      // a NaN or an infinity in the column: digits with multiplier 0, the epilogue multiplies by NaN
-        out[2] = 0.0;
-        out[3] = __longlong_as_double(0x7ff8000000000000LL);
-    }
+    prep_block_partials(partial + (int64_t)v * PREP_STRIDE, mx, s, shm, shs);
 }
 
 // ---- digits of the pass: K-step kb holds CP / 2 pairs x 256 elements of 16 bytes; dword index
@@ -129,7 +71,7 @@ __global__ __launch_bounds__(256) void k_atxm_quant(Cols a, int64_t n, int64_t n
     double mult = 0.0;
     if (col < ncols) {
         double sc[4];
-        atxm_scalars(partial + (int64_t)col * PREP_STRIDE, nblocks, shm, shs, sc);
+        prep_scalars(partial + (int64_t)col * PREP_STRIDE, nblocks, shm, shs, sc);
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             double* o = scal + 4 * col;
             o[0] = sc[0]; o[1] = sc[1]; o[2] = sc[2]; o[3] = sc[3];
@@ -147,13 +89,7 @@ __global__ __launch_bounds__(256) void k_atxm_quant(Cols a, int64_t n, int64_t n
         for (int t = 0; t < 4; t++) {
             const int64_t k = kb * 256 + 64 * g + 16 * d + 4 * t + s;
             const double val = (k < n) ? v[k] : 0.0;
-            long long q = (long long)rint(val * mult);
-#pragma unroll
-            for (int c7 = 0; c7 < 7; c7++) {
-                long long dg = (long long)(signed char)(q & 0xFF);   // balanced digit in [-128, 127]
-                q = (q - dg) >> 8;
-                d8[c7] |= (uint32_t)(dg & 0xFF) << (8 * t);
-            }
+            digits_of((long long)rint(val * mult), t, d8);
         }
     }
     uint32_t* o = dig + kb * ((int64_t)cp * 512) + (col >> 1) * 1024 + d * 256 + g * 64 + (col & 1) * 32 + s;
@@ -161,15 +97,9 @@ __global__ __launch_bounds__(256) void k_atxm_quant(Cols a, int64_t n, int64_t n
     for (int c8 = 0; c8 < 8; c8++) o[c8 * 4] = d8[c8];
 }
 
-__device__ __forceinline__ void wg_barrier_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-struct ABufT { u32x4 t[4]; };
-
-// the four 16-byte non-temporal loads of a super-block, ATx side (load_t<0> of gv_mfma.hip)
+// the four 16-byte non-temporal loads of a super-block, ATx side: the pieces of gvm::load_t<0>.  It stays a function of this file for
+// the form of its address alone -- pointer steps, where load_t adds the offsets up as one int first -- which the compiler turns into
+// other address arithmetic in the pass kernel; k_atxm's instruction stream is held to the one it was measured with
 __device__ __forceinline__ void load_sb(ABufT& a, const u32x4* __restrict__ sb, int lane) {
     const int r = lane & 15, g = lane >> 4;
 #pragma unroll
@@ -188,19 +118,14 @@ __device__ __forceinline__ void compute_step(const ABufT& a, const u32x4* sb, in
             const u32x4 bq = sb[p * 256 + g * 64 + i * 16 + c];
             B[p] = (v4i){(int)bq.x, (int)bq.y, (int)bq.z, (int)bq.w};
         }
-        const uint32_t L0 = a.t[i].x, L1 = a.t[i].y, L2 = a.t[i].z, L3 = a.t[i].w;
-        const uint32_t a0 = __builtin_amdgcn_perm(L1, L0, 0x05010400u), a1 = __builtin_amdgcn_perm(L1, L0, 0x07030602u);
-        const uint32_t b0 = __builtin_amdgcn_perm(L3, L2, 0x05010400u), b1 = __builtin_amdgcn_perm(L3, L2, 0x07030602u);
-        const uint32_t T[4] = {__builtin_amdgcn_perm(b0, a0, 0x05040100u), __builtin_amdgcn_perm(b0, a0, 0x07060302u),
-                               __builtin_amdgcn_perm(b1, a1, 0x05040100u), __builtin_amdgcn_perm(b1, a1, 0x07060302u)};
+        uint32_t T[4];
+        transpose_piece(a.t[i], T);
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             const uint32_t w = T[t];
             const uint32_t e0 = w & 0x03030303u, e1 = (w >> 2) & 0x03030303u, e2 = (w >> 4) & 0x03030303u, e3 = (w >> 6) & 0x03030303u;
-            const v4i X = {(int)e0, (int)e1, (int)e2, (int)e3};                                // r' plane: the code itself
-            const v4i Y = {(int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e0), (int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e1),
-                           (int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e2),
-                           (int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e3)};          // miss plane: 1 where the code is 3
+            const v4i X = {(int)plane_x<0>(e0), (int)plane_x<0>(e1), (int)plane_x<0>(e2), (int)plane_x<0>(e3)};      // r' plane
+            const v4i Y = {(int)plane_y<0>(e0), (int)plane_y<0>(e1), (int)plane_y<0>(e2), (int)plane_y<0>(e3)};      // miss plane
 #pragma unroll
             for (int p = 0; p < NP; p++) {
                 accX[p][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(X, B[p], accX[p][t], 0, 0, 0);
@@ -297,12 +222,6 @@ __global__ __launch_bounds__(256, 2) void k_atxm(const u32x4* __restrict__ tiles
     }
 }
 
-// exact digit recombination: sum_c s_c 256^c as (hi, lo) with value = hi * 2^32 + lo (combine of gv_mfma.hip)
-__device__ __forceinline__ void combine7(const long long (&s)[7], long long& hi, long long& lo) {
-    lo = s[0] + (s[1] << 8) + (s[2] << 16) + (s[3] << 24);
-    hi = s[4] + (s[5] << 8) + (s[6] << 16);
-}
-
 // ---- epilogue of column blockIdx.y: out[m] = msig (sum a p - mave sum b p) / sqrt(N) (k_fin_atx without addx)
 __global__ __launch_bounds__(256) void k_atxm_fin(const int32_t* __restrict__ partial, int ks, int ncols, int64_t rows_p, int64_t M,
                                                   const double* __restrict__ scal_base, const double* __restrict__ mave,
@@ -322,8 +241,8 @@ __global__ __launch_bounds__(256) void k_atxm_fin(const int32_t* __restrict__ pa
         sy[4] += y1.x; sy[5] += y1.y; sy[6] += y1.z;
     }
     long long xh, xl, yh, yl;
-    combine7(sx, xh, xl);
-    combine7(sy, yh, yl);
+    combine(sx, xh, xl);
+    combine(sy, yh, yl);
     const double scale = scal[3], P = scal[1];
     // P - sm is written the way the compiler contracts it in k_fin_atx, fma(-scale, Y, P): the product by the power of two is exact, so
     // this is fl(P - sm) bit for bit, and with a NaN scale (a column with a NaN or an infinity) the NaN that comes out has the sign and
@@ -364,12 +283,6 @@ __global__ __launch_bounds__(256) void k_screen_fin(ScreenCols a, int64_t M, con
     if (a.p[v]) a.p[v][m] = p;
 }
 
-int prep_blocks(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > PREP_BLOCKS ? PREP_BLOCKS : b));
-}
-inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
 template <int CP>
 void launch_pass(hipStream_t s, const gv_ctx* c, const gvx::Plan& p, const SegB& sb, const u32x4* dig, int32_t* part, int ncols) {
     hipLaunchKernelGGL(k_atxm<CP>, dim3((unsigned)p.items), dim3(256), 0, s, (const u32x4*)c->plan.tiles, dig, p.nrg, p.nkb, p.nq, sb, part,
@@ -379,12 +292,6 @@ void launch_pass(hipStream_t s, const gv_ctx* c, const gvx::Plan& p, const SegB&
 }  // namespace
 
 namespace gvi {
-
-void atxm_release(gv_ctx* c) {
-    if (c->atxm_buf) (void)hipFree(c->atxm_buf);
-    c->atxm_buf = nullptr;
-    c->atxm_cap = 0;
-}
 
 // the kernel applies: kernel mode 1 on the tile layout, 2-bit genotypes, a shard with markers (ATx issues no collective: any rank count)
 static bool atxm_kernel_applies(const gv_ctx* c) {
@@ -403,17 +310,10 @@ static int atxm_kernel(gv_ctx* c, int64_t C, const double* const* p, double* con
     if (pl.nrg != c->plan.nrg_m || pl.nkb != c->plan.nkb_m)
         return fail(c, "gv_atxm_dev: the resident tile layout has %lld x %lld super-blocks, the plan %lld x %lld", (long long)c->plan.nrg_m,
                     (long long)c->plan.nkb_m, (long long)pl.nrg, (long long)pl.nkb);
-    if (pl.scratch_bytes > c->atxm_cap) {
-        atxm_release(c);
-        if (hipMalloc(&c->atxm_buf, pl.scratch_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            c->atxm_buf = nullptr;
-            return fail(c, "gv_atxm_dev: cannot allocate %zu bytes of scratch (digits %zu, partial sums %zu)", pl.scratch_bytes, pl.dig_bytes,
-                        pl.part_bytes);
-        }
-        c->atxm_cap = pl.scratch_bytes;
-    }
-    char* buf = static_cast<char*>(c->atxm_buf);
+    if (!c->atxm_scratch.reserve(pl.scratch_bytes))
+        return fail(c, "gv_atxm_dev: cannot allocate %zu bytes of scratch (digits %zu, partial sums %zu)", pl.scratch_bytes, pl.dig_bytes,
+                    pl.part_bytes);
+    char* buf = static_cast<char*>(c->atxm_scratch.buf);
     u32x4* dig = reinterpret_cast<u32x4*>(buf);
     int32_t* part = reinterpret_cast<int32_t*>(buf + pl.dig_bytes);
     double* scal = reinterpret_cast<double*>(buf + pl.dig_bytes + pl.part_bytes);
@@ -471,29 +371,6 @@ int atxm_device(gv_ctx* c, int64_t C, const double* const* p, double* const* out
     return 0;
 }
 
-// the checks every entry point of this file makes on its arrays of handles; who names the entry point
-static int atxm_args(gv_ctx* c, const char* who, int64_t C, const gv_vec* const* p, gv_vec* const* out, const char* pname,
-                     std::vector<const double*>& ps, std::vector<double*>& os) {
-    ps.resize((size_t)C);
-    os.resize((size_t)C);
-    std::unordered_set<const gv_vec*> seen;
-    for (int64_t j = 0; j < C; j++) {
-        if (!p[j] || !out[j]) return fail(c, "%s: the handle of column %lld is NULL", who, (long long)j);
-        if (p[j]->space != GV_SPACE_N || out[j]->space != GV_SPACE_M)
-            return fail(c, "%s: column %lld: %s must be N-space, out M-space", who, (long long)j, pname);
-        if (!vec_ok(c, p[j], GV_SPACE_N) || !vec_ok(c, out[j], GV_SPACE_M)) {
-            const std::string w = std::string(who) + ": column " + std::to_string((long long)j);
-            return vec_need(c, w.c_str(), pname, p[j], GV_SPACE_N) || vec_need(c, w.c_str(), "out", out[j], GV_SPACE_M);
-        }
-        if (!seen.insert(out[j]).second) return fail(c, "%s: column %lld: two outputs are the same vector", who, (long long)j);
-        ps[(size_t)j] = p[j]->d;
-        os[(size_t)j] = out[j]->d;
-    }
-    for (int64_t j = 0; j < C; j++)
-        if (seen.count(p[j])) return fail(c, "%s: column %lld: an output is also an input", who, (long long)j);
-    return 0;
-}
-
 }  // namespace gvi
 
 using namespace gvi;
@@ -506,7 +383,7 @@ int gv_atxm_dev(gv_ctx* c, int64_t C, const gv_vec* const* p, gv_vec* const* out
     NEED(c, p && out, "gv_atxm_dev: the arrays of column handles are NULL");
     std::vector<const double*> ps;
     std::vector<double*> os;
-    if (atxm_args(c, "gv_atxm_dev", C, p, out, "p", ps, os)) return 1;
+    if (batch_args(c, "gv_atxm_dev", C, p, out, "p", GV_SPACE_N, ps, os)) return 1;
     return atxm_device(c, C, ps.data(), os.data());
 }
 
@@ -515,28 +392,8 @@ int gv_atxm(gv_ctx* c, int64_t C, const double* Y, double* out) {
     if (C == 0) return 0;
     NEED(c, Y && out, "gv_atxm: Y or out is NULL");
     NEED(c, c->mask2, "gv_atxm: the phenotype mask must be set first");
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<gv_vec*> pv, ov;
-    auto drop = [&]() {
-        for (gv_vec* v : pv) vec_del(c, v);
-        for (gv_vec* v : ov) vec_del(c, v);
-    };
-    for (int64_t j = 0; j < C; j++) {
-        gv_vec *a = nullptr, *b = nullptr;
-        if (vec_new(c, GV_SPACE_N, &a)) { drop(); return 1; }
-        pv.push_back(a);
-        if (vec_new(c, GV_SPACE_M, &b)) { drop(); return 1; }
-        ov.push_back(b);
-        if (to_device(c, a->d, Y + j * 4 * c->mbytes, sizeof(double) * 4 * c->mbytes, false)) { drop(); return 1; }
-        // the staged copy is masked as gv_atx masks its own (a no-op for a filtered column; methylation data: used as given)
-        if (!c->dense.resident) gvk::mask_copy(c->stream, a->d, a->d, c->mask2, c->npad);
-    }
-    int rc = gv_atxm_dev(c, C, pv.data(), ov.data());
-    for (int64_t j = 0; j < C && !rc && c->M > 0; j++) rc = to_host(c, out + j * c->M, ov[(size_t)j]->d, sizeof(double) * c->M);
-    if (!rc) rc = hipStreamSynchronize(c->stream) == hipSuccess ? 0 : fail(c, "gv_atxm: hipStreamSynchronize failed");
-    drop();
-    if (!rc) c->atxm_last.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    // the staged copies are masked as gv_atx masks its own (a no-op for a filtered column; methylation data: used as given)
+    return batch_host(c, "gv_atxm", C, Y, GV_SPACE_N, !c->dense.resident, out, gv_atxm_dev, &c->atxm_last.seconds);
 }
 
 int gv_atxm_info(const gv_ctx* c, gv_atxm_stats* out) {
@@ -556,7 +413,7 @@ int gv_screen_dev(gv_ctx* c, int64_t C, const gv_vec* const* u, gv_vec* const* r
     NEED(c, c->nonas >= 3, "gv_screen_dev: fewer than 3 individuals with a phenotype leave the test no degree of freedom");
     std::vector<const double*> us;
     std::vector<double*> rs;
-    if (atxm_args(c, "gv_screen_dev", C, u, r, "u", us, rs)) return 1;
+    if (batch_args(c, "gv_screen_dev", C, u, r, "u", GV_SPACE_N, us, rs)) return 1;
     // t and p: M-space vectors of this context, distinct from each other, from r and from the inputs
     std::unordered_set<const gv_vec*> seen;
     for (int64_t j = 0; j < C; j++) { seen.insert(u[j]); seen.insert(r[j]); }

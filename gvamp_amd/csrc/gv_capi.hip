@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 
 #include "gv_internal.h"
@@ -69,6 +70,62 @@ int vec_need(gv_ctx* c, const char* who, const char* arg, const gv_vec* v, int s
                        "gv_set_dims -- free it and allocate it again", who, arg, (long long)v->cap,
                     (long long)(space == GV_SPACE_M ? (c->M > 0 ? c->M : 1) : c->npad));
     return 0;
+}
+
+int batch_args(gv_ctx* c, const char* who, int64_t C, const gv_vec* const* in, gv_vec* const* out, const char* in_name, int in_space,
+               std::vector<const double*>& is, std::vector<double*>& os) {
+    const int out_space = in_space == GV_SPACE_M ? GV_SPACE_N : GV_SPACE_M;
+    is.resize((size_t)C);
+    os.resize((size_t)C);
+    std::unordered_set<const gv_vec*> seen;
+    for (int64_t j = 0; j < C; j++) {
+        if (!in[j] || !out[j]) return fail(c, "%s: the handle of column %lld is NULL", who, (long long)j);
+        if (in[j]->space != in_space || out[j]->space != out_space)
+            return fail(c, "%s: column %lld: %s must be %s-space, out %s-space", who, (long long)j, in_name, in_space == GV_SPACE_M ? "M" : "N",
+                        out_space == GV_SPACE_M ? "M" : "N");
+        if (!vec_ok(c, in[j], in_space) || !vec_ok(c, out[j], out_space)) {
+            const std::string w = std::string(who) + ": column " + std::to_string((long long)j);
+            return vec_need(c, w.c_str(), in_name, in[j], in_space) || vec_need(c, w.c_str(), "out", out[j], out_space);
+        }
+        if (!seen.insert(out[j]).second) return fail(c, "%s: column %lld: two outputs are the same vector", who, (long long)j);
+        is[(size_t)j] = in[j]->d;
+        os[(size_t)j] = out[j]->d;
+    }
+    for (int64_t j = 0; j < C; j++)
+        if (seen.count(in[j])) return fail(c, "%s: column %lld: an output is also an input", who, (long long)j);
+    return 0;
+}
+
+int batch_host(gv_ctx* c, const char* who, int64_t C, const double* in, int in_space, bool mask_in, double* out,
+               int (*dev)(gv_ctx*, int64_t, const gv_vec* const*, gv_vec* const*), double* seconds) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int out_space = in_space == GV_SPACE_M ? GV_SPACE_N : GV_SPACE_M;
+    // Per space, whichever side it is on: a host column of M-space holds M doubles, one of N-space 4 * mbytes; an M-space column is
+    // not moved when the shard has no marker (M == 0: the device vector still has one double, the host column none), an N-space
+    // column always is
+    auto len = [&](int space) { return space == GV_SPACE_M ? c->M : 4 * c->mbytes; };
+    auto copied = [&](int space) { return space == GV_SPACE_N || c->M > 0; };
+    std::vector<gv_vec*> iv, ov;
+    auto drop = [&]() {
+        for (gv_vec* v : iv) vec_del(c, v);
+        for (gv_vec* v : ov) vec_del(c, v);
+    };
+    for (int64_t j = 0; j < C; j++) {
+        gv_vec *a = nullptr, *b = nullptr;
+        if (vec_new(c, in_space, &a)) { drop(); return 1; }
+        iv.push_back(a);
+        if (vec_new(c, out_space, &b)) { drop(); return 1; }
+        ov.push_back(b);
+        if (copied(in_space) && to_device(c, a->d, in + j * len(in_space), sizeof(double) * len(in_space), false)) { drop(); return 1; }
+        if (mask_in) gvk::mask_copy(c->stream, a->d, a->d, c->mask2, c->npad);
+    }
+    int rc = dev(c, C, iv.data(), ov.data());
+    for (int64_t j = 0; j < C && !rc && copied(out_space); j++)
+        rc = to_host(c, out + j * len(out_space), ov[(size_t)j]->d, sizeof(double) * len(out_space));
+    if (!rc) rc = hipStreamSynchronize(c->stream) == hipSuccess ? 0 : fail(c, "%s: hipStreamSynchronize failed", who);
+    drop();
+    if (!rc) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
 }
 
 // every gv_vec of a context goes through vec_new / vec_del, so gv_destroy can release what a caller never freed
@@ -199,9 +256,9 @@ static void free_dataset(gv_ctx* c) {
     F(c->bed); F(c->mask2); F(c->mave); F(c->msig); F(c->t3); F(c->ax_partial); F(c->counts);
     dense_release(c);
     free_layouts(c);
-    score_release(c);
-    atxm_release(c);
-    pca_release(c);
+    c->score_scratch.release();
+    c->atxm_scratch.release();
+    c->pca_scratch.release();
     F(c->cgx_state); F(c->cgx_go);
     if (c->cgx_rel_h) (void)hipHostFree(c->cgx_rel_h);
     c->cgx_rel = c->cgx_rel_h = nullptr;
@@ -236,6 +293,37 @@ int gv_abi_version(void) { return GV_ABI_VERSION; }
 // call is on any hot path.
 static std::mutex g_lifecycle_mu;
 static void gv_destroy_locked(gv_ctx* c);      // the caller holds g_lifecycle_mu and has drained the streams
+
+// The three development knobs of a batch product's kernel, <prefix>_COLS / _KS / _KERNEL: the columns per pass (one of `widths`,
+// which widths_text lists for the message), the K-segments, and whether the kernel runs from one column on (1) or never (0).
+// who: the entry point the messages name.  false: g_create_err says which value is refused.
+static bool batch_knobs(const char* prefix, const char* who, std::initializer_list<int> widths, const char* widths_text, int& cols,
+                        int& ks, int& min_cols) {
+    const std::string pre(prefix);
+    if (const char* sc = getenv((pre + "_COLS").c_str())) {
+        char* end = nullptr;
+        const long v = strtol(sc, &end, 10);
+        bool ok = false;
+        for (int w : widths) ok = ok || v == w;
+        if (end == sc || *end != 0 || !ok) {
+            g_create_err = "gv_create: " + pre + "_COLS=" + std::string(sc) + ": the columns per pass of " + who + " are " + widths_text;
+            return false;
+        }
+        cols = (int)v;
+    }
+    if (const char* sk = getenv((pre + "_KS").c_str())) {
+        char* end = nullptr;
+        const long v = strtol(sk, &end, 10);
+        if (end == sk || *end != 0 || v < 1 || v > gvm::GV_MAX_KS) {
+            g_create_err = "gv_create: " + pre + "_KS=" + std::string(sk) + ": the K-segments of " + who + " are a positive integer <= " +
+                           std::to_string(gvm::GV_MAX_KS);
+            return false;
+        }
+        ks = (int)v;
+    }
+    if (const char* kn = getenv((pre + "_KERNEL").c_str())) min_cols = atoi(kn) != 0 ? 1 : 0x7fffffff;
+    return true;
+}
 
 int gv_create(int device, gv_ctx** out) {
     if (!out) return fail(nullptr, "gv_create: out is NULL");
@@ -332,55 +420,14 @@ int gv_create(int device, gv_ctx** out) {
         }
         c->ld_part_bytes = mb * 1048576.0;
     }
-    // GV_SCORE_COLS=<4|8|16> and GV_SCORE_KS=<k> (development, read per context): the columns per pass and the K-segments of
-    // gv_score_dev's kernel.  Neither changes a bit; a k that breaks the int32 bound on a shard is refused by the call.
-    // GV_SCORE_KERNEL=1 / 0: the kernel from one column on / never (the fallback serves every call).
-    if (const char* sc = getenv("GV_SCORE_COLS")) {
-        char* end = nullptr;
-        const long v = strtol(sc, &end, 10);
-        if (end == sc || *end != 0 || (v != 4 && v != 8 && v != 16)) {
-            g_create_err = "gv_create: GV_SCORE_COLS=" + std::string(sc) + ": the columns per pass of gv_score_dev are 4, 8 or 16";
-            gv_destroy_locked(c);
-            return 1;
-        }
-        c->score_cols = (int)v;
+    // GV_SCORE_COLS=<4|8|16>, GV_SCORE_KS=<k>, GV_SCORE_KERNEL=1|0 and GV_ATXM_COLS=<4|8>, GV_ATXM_KS=<k>, GV_ATXM_KERNEL=1|0 (development,
+    // read per context).  None changes a bit.  A GV_SCORE_KS that breaks the int32 bound on a shard is refused by the call; a
+    // GV_ATXM_KS is clipped to the K-steps there are.
+    if (!batch_knobs("GV_SCORE", "gv_score_dev", {4, 8, 16}, "4, 8 or 16", c->score_cols, c->score_ks, c->score_min_cols) ||
+        !batch_knobs("GV_ATXM", "gv_atxm_dev", {4, 8}, "4 or 8", c->atxm_cols, c->atxm_ks, c->atxm_min_cols)) {
+        gv_destroy_locked(c);
+        return 1;
     }
-    if (const char* sk = getenv("GV_SCORE_KS")) {
-        char* end = nullptr;
-        const long v = strtol(sk, &end, 10);
-        if (end == sk || *end != 0 || v < 1 || v > gvm::GV_MAX_KS) {
-            g_create_err = "gv_create: GV_SCORE_KS=" + std::string(sk) + ": the K-segments of gv_score_dev are a positive integer <= " +
-                           std::to_string(gvm::GV_MAX_KS);
-            gv_destroy_locked(c);
-            return 1;
-        }
-        c->score_ks = (int)v;
-    }
-    if (const char* kn = getenv("GV_SCORE_KERNEL")) c->score_min_cols = atoi(kn) != 0 ? 1 : 0x7fffffff;
-    // GV_ATXM_COLS=<4|8>, GV_ATXM_KS=<k>, GV_ATXM_KERNEL=1|0 (development, read per context): the same three for gv_atxm_dev's kernel.
-    // None changes a bit; k is clipped to the K-steps there are.
-    if (const char* sc = getenv("GV_ATXM_COLS")) {
-        char* end = nullptr;
-        const long v = strtol(sc, &end, 10);
-        if (end == sc || *end != 0 || (v != 4 && v != 8)) {
-            g_create_err = "gv_create: GV_ATXM_COLS=" + std::string(sc) + ": the columns per pass of gv_atxm_dev are 4 or 8";
-            gv_destroy_locked(c);
-            return 1;
-        }
-        c->atxm_cols = (int)v;
-    }
-    if (const char* sk = getenv("GV_ATXM_KS")) {
-        char* end = nullptr;
-        const long v = strtol(sk, &end, 10);
-        if (end == sk || *end != 0 || v < 1 || v > gvm::GV_MAX_KS) {
-            g_create_err = "gv_create: GV_ATXM_KS=" + std::string(sk) + ": the K-segments of gv_atxm_dev are a positive integer <= " +
-                           std::to_string(gvm::GV_MAX_KS);
-            gv_destroy_locked(c);
-            return 1;
-        }
-        c->atxm_ks = (int)v;
-    }
-    if (const char* kn = getenv("GV_ATXM_KERNEL")) c->atxm_min_cols = atoi(kn) != 0 ? 1 : 0x7fffffff;
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;
     // GVAMP_FORCE_MULTI=<transport>[:<delay_us>] -- gv_debug_force_multi for every context of the process (drivers, bench.py)

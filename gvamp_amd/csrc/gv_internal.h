@@ -72,6 +72,29 @@ struct DenseData {
     size_t bytes(int64_t M) const { return elem_bytes() * (size_t)M * (size_t)pitch; }
 };
 
+// Grow-only device scratch of a batch product (gv_score_dev, gv_atxm_dev, gv_pca_dev): kept between calls, freed with the dataset
+struct DevScratch {
+    void* buf = nullptr;
+    size_t cap = 0;
+    void release() {
+        if (buf) (void)hipFree(buf);
+        buf = nullptr;
+        cap = 0;
+    }
+    // at least `bytes` (the contents do not survive growing); false: the allocation failed and nothing is held
+    bool reserve(size_t bytes) {
+        if (bytes <= cap) return true;
+        release();
+        if (hipMalloc(&buf, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            buf = nullptr;
+            return false;
+        }
+        cap = bytes;
+        return true;
+    }
+};
+
 // gv_score_dev: the fewest columns for which its own kernel is the path where it applies (measured: DESIGN.md section 21)
 constexpr int GV_SCORE_MIN_COLS_DEFAULT = 4;
 // gv_atxm_dev: the same for its kernel (measured: DESIGN.md section 23)
@@ -205,21 +228,18 @@ struct gv_ctx {
     // gv_score_dev (gv_score.hip): scratch of the kernel path (grown on demand, freed with the dataset), the
     // development overrides GV_SCORE_COLS / GV_SCORE_KS (0: the library's pick), the fewest columns that take the kernel
     // (GV_SCORE_KERNEL=1 / 0: 1 / never) and what gv_score_info reports
-    void* score_buf = nullptr;
-    size_t score_cap = 0;
+    DevScratch score_scratch;
     int score_cols = 0, score_ks = 0;
     int score_min_cols = GV_SCORE_MIN_COLS_DEFAULT;
     gv_score_stats score_last{};
     // gv_atxm_dev (gv_atxm.hip): the same five for the ATx side (GV_ATXM_COLS / GV_ATXM_KS / GV_ATXM_KERNEL)
-    void* atxm_buf = nullptr;
-    size_t atxm_cap = 0;
+    DevScratch atxm_scratch;
     int atxm_cols = 0, atxm_ks = 0;
     int atxm_min_cols = GV_ATXM_MIN_COLS_DEFAULT;
     gv_atxm_stats atxm_last{};
     // gv_pca_dev (gv_pca.hip): the work panels and small buffers (grown on demand, freed with the dataset) and what
     // gv_pca_info reports
-    void* pca_buf = nullptr;
-    size_t pca_cap = 0;
+    DevScratch pca_scratch;
     gv_pca_stats pca_last{};
     gv_king_stats king_last{};      // gv_king_info: the last gv_king_block / gv_king_pairs call (gv_king.hip)
 
@@ -251,7 +271,7 @@ struct gv_ctx {
     size_t ev_used = 0;
 };
 
-constexpr int RED_BLOCKS = 1024;
+// (RED_BLOCKS: gv_mfma.h, beside the stride of the prep launches' block partials)
 constexpr int RED_MAXK = 80;   // >= 1 + 2*(LMAX-1) with LMAX = 32
 constexpr int GV_LMAX = 32;
 
@@ -514,14 +534,19 @@ inline gvd::View dense_view(const gv_ctx* c) {
 void dense_release(gv_ctx* c, bool keep_alloc = false);
 // frees the genotype layouts of the MFMA family: the stripe slab, the two stripe sets, the tiles and the plan's digit / weight / sum buffers
 void free_layouts(gv_ctx* c);
-// gv_score.hip: Z = A W on device pointers (C > 0 columns, x[j] M doubles, out[j] npad doubles); the scratch of its kernel path
+// The batch products (gv_score.hip, gv_atxm.hip).  batch_args: the checks their entry points make on C > 0 columns of handles -- `in`
+// (named in_name in the messages) of in_space, `out` of the other space, of this context and its dimensions, the outputs distinct from
+// each other and from the inputs -- and the device pointers behind them.  batch_host: the host-pointer form -- the C columns of `in`
+// (one vector of in_space after the other) staged into fresh vectors (mask_in: masked as gv_atx masks its own), dev() on them, the C
+// result columns copied to `out`, the stream synchronised, and the wall time of it all in *seconds
+int batch_args(gv_ctx* c, const char* who, int64_t C, const gv_vec* const* in, gv_vec* const* out, const char* in_name, int in_space,
+               std::vector<const double*>& is, std::vector<double*>& os);
+int batch_host(gv_ctx* c, const char* who, int64_t C, const double* in, int in_space, bool mask_in, double* out,
+               int (*dev)(gv_ctx*, int64_t, const gv_vec* const*, gv_vec* const*), double* seconds);
+// gv_score.hip: Z = A W on device pointers (C > 0 columns, x[j] M doubles, out[j] npad doubles)
 int score_device(gv_ctx* c, int64_t C, const double* const* x, double* const* out);
-void score_release(gv_ctx* c);
-// gv_atxm.hip: R = A^T Y on device pointers (C > 0 columns, p[j] npad doubles, out[j] M doubles); the scratch of its kernel path
+// gv_atxm.hip: R = A^T Y on device pointers (C > 0 columns, p[j] npad doubles, out[j] M doubles)
 int atxm_device(gv_ctx* c, int64_t C, const double* const* p, double* const* out);
-void atxm_release(gv_ctx* c);
-// gv_pca.hip: the scratch of gv_pca_dev
-void pca_release(gv_ctx* c);
 
 struct Timer {
     gv_ctx* c;

@@ -1,7 +1,11 @@
-// gv_mfma.h -- host-side plan and launchers of the fixed-point i8 MFMA family (gv_mfma.hip).
+// gv_mfma.h -- host-side plan and launchers of the fixed-point i8 MFMA family (gv_mfma.hip), and -- for HIP translation units, at
+// the end -- the ONE copy of the device helpers of its fixed-point operand pipeline, shared with the batch products (gv_score.hip,
+// gv_atxm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+
+constexpr int RED_BLOCKS = 1024;   // most block partials of a reduction (gvk::dots, the prep launches)
 
 namespace gvm {
 
@@ -326,5 +330,146 @@ void ax_wide(hipStream_t s, const Plan& pl, const double* x, const double* mave,
              int64_t npad, double post, double* red_partial, double* out);
 void atx_wide(hipStream_t s, const Plan& pl, const double* p, int64_t npad, const double* mave, const double* msig, double inv_sqrt_n,
               double* red_partial, double* out, const double* addx = nullptr, double tau = 1.0, double gam2 = 0.0);
+
+}  // namespace gvm
+
+// ---- the fixed-point operand pipeline: one copy for gv_mfma.hip, gv_score.hip and gv_atxm.hip ------------------------------------------
+// The batch kernels promise that column j is bit-identical to gv_ax_dev / gv_atx_dev of that column alone; the floating-point steps
+// around the exact integer sums -- block partials, the four scalars, the digit split, the limbs -- are these functions in all three
+// files, so their roundings and orders agree by construction.  They live here because this file is part of the kernel-source hash
+// (build.kernel_src_hash): the streaming kernels compile them in, and a tuning pick or a profile belongs to that hash.
+namespace gvm {
+
+constexpr int PREP_STRIDE = 2 * RED_BLOCKS;   // doubles of block partials per vector
+// Blocks of a prep launch (every block of the quantisation launch behind it adds their partials up: prep_scalars)
+constexpr int PREP_BLOCKS = 256;
+inline int prep_blocks(int64_t n) {
+    int64_t b = (n + 255) / 256;
+    return (int)(b < 1 ? 1 : (b > PREP_BLOCKS ? PREP_BLOCKS : b));
+}
+inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
+
+#if defined(__HIPCC__)
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    return v;
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// scal[0] = amax, scal[1] = sum (ordered), scal[2] = 2^(54-e) (quantisation multiplier, 0 if amax is 0 / not finite),
+// scal[3] = 2^(e-54).  The prep kernels leave block partials; every block of the quantisation launch behind them adds them up
+// for itself in a fixed order (prep_scalars: thread t adds blocks t, t + 256, ..., then a binary tree over the 256 threads) and block 0
+// stores the four scalars for the epilogue of the pass.  (Until round 3
+// the LAST block of the prep launch did it behind a ticket counter: 256 serialised atomics per vector, 12 of the 17-21 us a
+// two-vector k_prep_ax took at M = 200k -- profiles/r3_cfg5_gaps.txt.)
+__device__ __forceinline__ void prep_scalars(const double* __restrict__ partial, int nblocks, double* shm, double* shs,
+                                              double (&out)[4]) {
+    double mx = 0.0, s = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 256) {
+        mx = fmax(mx, partial[2 * b]);
+        s += partial[2 * b + 1];
+    }
+    shm[threadIdx.x] = mx;
+    shs[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (threadIdx.x < off) {
+            shm[threadIdx.x] = fmax(shm[threadIdx.x], shm[threadIdx.x + off]);
+            shs[threadIdx.x] += shs[threadIdx.x + off];
+        }
+        __syncthreads();
+    }
+    const double amax = shm[0];
+    out[0] = amax;
+    out[1] = shs[0];
+    if (amax > 0.0 && amax <= 1.7976931348623157e308) {
+        int e = ilogb(amax) + 1;
+        out[2] = ldexp(1.0, 54 - e);
+        out[3] = ldexp(1.0, e - 54);
+    } else if (amax == 0.0) {
+        out[2] = 0.0;
+        out[3] = 0.0;
+    } else {
+        // a NaN or an infinity among the entries (the prep kernels raise amax to +inf for either): fixed point has no
+        // encoding for it.  Defined behaviour = what fp64 sums over the whole vector give in the reference: every
+        // output entry of this product is NaN (digits are quantised with multiplier 0, the epilogue multiplies by NaN).
+        out[2] = 0.0;
+        out[3] = __longlong_as_double(0x7ff8000000000000LL);
+    }
+}
+// block partials of a prep launch of 256 threads: [2b] = max, [2b + 1] = sum (fixed order within the block: wave butterflies, then the
+// four wave results in order)
+__device__ __forceinline__ void prep_block_partials(double* partial_v, double mx, double s, double* shm, double* shs) {
+    mx = wave_max(mx);
+    s = wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) { shm[threadIdx.x >> 6] = mx; shs[threadIdx.x >> 6] = s; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial_v[2 * blockIdx.x] = fmax(fmax(shm[0], shm[1]), fmax(shm[2], shm[3]));
+        partial_v[2 * blockIdx.x + 1] = shs[0] + shs[1] + shs[2] + shs[3];
+    }
+}
+// the seven balanced base-256 digits of q into byte t of dig[0..7) (digit column 7 stays zero)
+__device__ __forceinline__ void digits_of(long long q, int t, uint32_t (&dig)[8]) {
+#pragma unroll
+    for (int c = 0; c < 7; c++) {
+        long long dg = (long long)(signed char)(q & 0xFF);   // balanced digit in [-128, 127]
+        q = (q - dg) >> 8;
+        dig[c] |= (uint32_t)(dg & 0xFF) << (8 * t);
+    }
+}
+// exact digit recombination: sum_c s_c 256^c as (hi, lo) with value = hi * 2^32 + lo
+__device__ __forceinline__ void combine(const long long (&s)[7], long long& hi, long long& lo) {
+    lo = s[0] + (s[1] << 8) + (s[2] << 16) + (s[3] << 24);
+    hi = s[4] + (s[5] << 8) + (s[6] << 16);
+}
+
+// The two operand planes of four expanded 2-bit codes e (one per byte).  PK 0: r' (the code itself) / missing (1 where the code is 3);
+// 1: a^2 (byte LUT r' -> {0,1,4,0}) / missing; 2: a' = a if present else 0 (r' -> {0,1,2,0}) / present (r' -> {1,1,1,0})
+template <int PK> __device__ __forceinline__ uint32_t plane_x(uint32_t e) {
+    return PK == 0 ? e : __builtin_amdgcn_perm(PK == 1 ? 0x00040100u : 0x00020100u, PK == 1 ? 0x00040100u : 0x00020100u, e);
+}
+template <int PK> __device__ __forceinline__ uint32_t plane_y(uint32_t e) {
+    return __builtin_amdgcn_perm(PK == 2 ? 0x00010101u : 0x01000000u, PK == 2 ? 0x00010101u : 0x01000000u, e);
+}
+
+// one workgroup barrier that orders LDS only: the vector-memory prefetches in flight (vmcnt) stay in flight across it
+__device__ __forceinline__ void wg_barrier_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// a super-block of the tile layout in registers (gv_mfma.hip, "ONE resident layout for both products"): four 16-byte pieces per lane
+struct ABufT { u32x4 t[4]; };
+
+template <int DIR>   // 0: ATx side (rows = markers), 1: Ax side (rows = individuals)
+__device__ __forceinline__ void load_t(ABufT& a, const u32x4* __restrict__ sb, int lane) {
+    const int r = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int off = (DIR == 0) ? i * 64 + r * 4 + g : (r >> 2) * 64 + (4 * i + g) * 4 + (r & 3);
+        a.t[i] = __builtin_nontemporal_load(sb + off);
+    }
+}
+// ATx side: the 4 x 4 byte transpose of the four dwords of a piece, T[t] byte d = byte t of dword d
+__device__ __forceinline__ void transpose_piece(const u32x4& p, uint32_t (&T)[4]) {
+    const uint32_t L0 = p.x, L1 = p.y, L2 = p.z, L3 = p.w;
+    const uint32_t a0 = __builtin_amdgcn_perm(L1, L0, 0x05010400u), a1 = __builtin_amdgcn_perm(L1, L0, 0x07030602u);
+    const uint32_t b0 = __builtin_amdgcn_perm(L3, L2, 0x05010400u), b1 = __builtin_amdgcn_perm(L3, L2, 0x07030602u);
+    T[0] = __builtin_amdgcn_perm(b0, a0, 0x05040100u);
+    T[1] = __builtin_amdgcn_perm(b0, a0, 0x07060302u);
+    T[2] = __builtin_amdgcn_perm(b1, a1, 0x05040100u);
+    T[3] = __builtin_amdgcn_perm(b1, a1, 0x07060302u);
+}
+#endif  // __HIPCC__
 
 }  // namespace gvm

@@ -33,7 +33,10 @@
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
+// the shared copy of the operand pipeline's helpers (gv_mfma.h)
+using gvm::v4i; using gvm::u32x4; using gvm::wave_max; using gvm::wave_sum_d; using gvm::prep_scalars; using gvm::prep_block_partials;
+using gvm::digits_of; using gvm::combine; using gvm::plane_x; using gvm::plane_y; using gvm::wg_barrier_lds; using gvm::ABufT;
+using gvm::load_t; using gvm::transpose_piece; using gvm::PREP_STRIDE; using gvm::nblk;
 
 __device__ __forceinline__ uint32_t recode(uint32_t w) {   // PLINK code -> r'
     return ((~w) & 0xAAAAAAAAu) | (((w >> 1) ^ w) & 0x55555555u);
@@ -185,70 +188,7 @@ __global__ __launch_bounds__(256) void k_stats_stripes(const uint4* __restrict__
 }
 
 // ---- vector preparation -------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// scal[0] = amax, scal[1] = sum (ordered), scal[2] = 2^(54-e) (quantisation multiplier, 0 if amax is 0 / not finite),
-// scal[3] = 2^(e-54).  The prep kernels leave block partials; every block of the quantisation launch behind them adds them up
-// for itself in a fixed order (prep_scalars) and block 0 stores the four scalars for the epilogue of the pass.  (Until round 3
-// the LAST block of the prep launch did it behind a ticket counter: 256 serialised atomics per vector, 12 of the 17-21 us a
-// two-vector k_prep_ax took at M = 200k -- profiles/r3_cfg5_gaps.txt.)
-__device__ __forceinline__ void prep_scalars(const double* __restrict__ partial, int nblocks, double* shm, double* shs,
-                                              double (&out)[4]) {
-    double mx = 0.0, s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        mx = fmax(mx, partial[2 * b]);
-        s += partial[2 * b + 1];
-    }
-    shm[threadIdx.x] = mx;
-    shs[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) {
-            shm[threadIdx.x] = fmax(shm[threadIdx.x], shm[threadIdx.x + off]);
-            shs[threadIdx.x] += shs[threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-    const double amax = shm[0];
-    out[0] = amax;
-    out[1] = shs[0];
-    if (amax > 0.0 && amax <= 1.7976931348623157e308) {
-        int e = ilogb(amax) + 1;
-        out[2] = ldexp(1.0, 54 - e);
-        out[3] = ldexp(1.0, e - 54);
-    } else if (amax == 0.0) {
-        out[2] = 0.0;
-        out[3] = 0.0;
-    } else {
-        // a NaN or an infinity among the entries (the prep kernels raise amax to +inf for either): fixed point has no
-        // encoding for it.  Defined behaviour = what fp64 sums over the whole vector give in the reference: every
-        // output entry of this product is NaN (digits are quantised with multiplier 0, the epilogue multiplies by NaN).
-        out[2] = 0.0;
-        out[3] = __longlong_as_double(0x7ff8000000000000LL);
-    }
-}
-// block partials of a prep launch: [2b] = max, [2b + 1] = sum (fixed order within the block)
-__device__ __forceinline__ void prep_block_partials(double* partial_v, double mx, double s, double* shm, double* shs) {
-    mx = wave_max(mx);
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) { shm[threadIdx.x >> 6] = mx; shs[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial_v[2 * blockIdx.x] = fmax(fmax(shm[0], shm[1]), fmax(shm[2], shm[3]));
-        partial_v[2 * blockIdx.x + 1] = shs[0] + shs[1] + shs[2] + shs[3];
-    }
-}
-
-constexpr int PREP_STRIDE = 2 * RED_BLOCKS;   // doubles of block partials per vector
+// (wave_max, wave_sum_d, prep_scalars, prep_block_partials and PREP_STRIDE: gv_mfma.h)
 
 // Ax operands: c = msig*x, e = (mave-3)*c  (out = sum r' c + sum miss e - K0, K0 = sum mave*c).  blockIdx.y = vector.
 // block partials: [0] = max(|c|,|e|), [1] = sum mave*c
@@ -414,14 +354,6 @@ __device__ __forceinline__ double quant_scale(const QuantArgs& a) {
 // col0 + 8 .. col0 + 15.  v = q 2^(e-54) + q2 2^(e-108) to within 2^(e-109): ~108 bits below the vector's largest entry instead of
 // 54, in the two slots of ONE two-vector pass.  (A vector whose largest entry is below 2^-915 has no second level: its residual
 // multiplier would overflow.)
-__device__ __forceinline__ void digits_of(long long q, int t, uint32_t (&dig)[8]) {
-#pragma unroll
-    for (int c = 0; c < 7; c++) {
-        long long dg = (long long)(signed char)(q & 0xFF);   // balanced digit in [-128, 127]
-        q = (q - dg) >> 8;
-        dig[c] |= (uint32_t)(dg & 0xFF) << (8 * t);
-    }
-}
 __device__ __forceinline__ double wide_mult2(double mult) { return (mult > 0.0 && mult < 0x1p969) ? mult * 0x1p54 : 0.0; }
 template <bool WIDE>
 __global__ __launch_bounds__(256) void k_quant(QuantArgs a, int64_t n, int64_t nkb, int ncol) {
@@ -472,8 +404,6 @@ __global__ __launch_bounds__(256) void k_quant(QuantArgs a, int64_t n, int64_t n
 // ds_read_b128 per dword-slot -- a wave fetching its own copy from L2 (the first version of this kernel) put 1.5-3x the
 // HBM stream on the vector-memory path and cost 6 % (MODE 1) to 25 % (MODE 3).  One workgroup barrier per K-block: a
 // bare s_barrier behind an LDS-only fence, so the stripe prefetches (vmcnt) stay in flight across it.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct ABuf { u32x4 t[4]; };
 
 __device__ __forceinline__ void load_a(ABuf& a, const u32x4* __restrict__ ap) {
@@ -491,12 +421,6 @@ template <int MODE> struct MD {
     static constexpr bool two_atx = MODE == 2 || MODE == 5;
     static constexpr int planes = MODE == 4 ? 1 : (MODE >= 5 ? 2 : 0);   // 0: r' / missing, 1: a^2 / missing, 2: a' / present
 };
-template <int PK> __device__ __forceinline__ uint32_t plane_x(uint32_t e) {
-    return PK == 0 ? e : __builtin_amdgcn_perm(PK == 1 ? 0x00040100u : 0x00020100u, PK == 1 ? 0x00040100u : 0x00020100u, e);
-}
-template <int PK> __device__ __forceinline__ uint32_t plane_y(uint32_t e) {
-    return __builtin_amdgcn_perm(PK == 2 ? 0x00010101u : 0x01000000u, PK == 2 ? 0x00010101u : 0x01000000u, e);
-}
 
 template <int MODE>
 struct BFrag { u32x4 d[4]; u32x4 e[MD<MODE>::two_ax ? 4 : 1]; };
@@ -534,12 +458,6 @@ __device__ __forceinline__ void compute_step(const ABuf& a, const BFrag<MODE>& b
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-}
-
-__device__ __forceinline__ void wg_barrier_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // Work decomposition.  The work is the grid of (quad = 4 row groups, K-block) cells, linearised quad-major:
@@ -818,17 +736,7 @@ namespace {
 // load i; the r' plane multiplies dig0 = [c_a | c_b], the missing plane dig1 = [e_a | e_b], both into ONE accumulator per
 // tile (64 accumulator registers); digits in the order of k_quant_t.  A one-vector Ax is the two-vector pass with nv = 1.
 // All sums are the same integers as in the two-layout kernels: results are bit-identical.
-struct ABufT { u32x4 t[4]; };
-
-template <int DIR>   // 0: ATx side (rows = markers), 1: Ax side (rows = individuals)
-__device__ __forceinline__ void load_t(ABufT& a, const u32x4* __restrict__ sb, int lane) {
-    const int r = lane & 15, g = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int off = (DIR == 0) ? i * 64 + r * 4 + g : (r >> 2) * 64 + (4 * i + g) * 4 + (r & 3);
-        a.t[i] = __builtin_nontemporal_load(sb + off);
-    }
-}
+// (ABufT, load_t<DIR> and the byte transpose: gv_mfma.h)
 
 // ATx side, one K-block (256 individuals): per load i a byte transpose, then 4 tiles x (r' plane, missing plane)
 template <int MODE>   // 0: one vector (8 digit columns, lanes c >= 8 alias), 2: two vectors, 5: head | residual of one vector (MD)
@@ -839,11 +747,8 @@ __device__ __forceinline__ void compute_atx_t(const ABufT& a, const u32x4* sb, i
     for (int i = 0; i < 4; i++) {
         const u32x4 bq = (MODE == 0) ? sb[g * 32 + i * 8 + (c & 7)] : sb[g * 64 + i * 16 + c];
         const v4i B = {(int)bq.x, (int)bq.y, (int)bq.z, (int)bq.w};
-        const uint32_t L0 = a.t[i].x, L1 = a.t[i].y, L2 = a.t[i].z, L3 = a.t[i].w;
-        const uint32_t a0 = __builtin_amdgcn_perm(L1, L0, 0x05010400u), a1 = __builtin_amdgcn_perm(L1, L0, 0x07030602u);
-        const uint32_t b0 = __builtin_amdgcn_perm(L3, L2, 0x05010400u), b1 = __builtin_amdgcn_perm(L3, L2, 0x07030602u);
-        const uint32_t T[4] = {__builtin_amdgcn_perm(b0, a0, 0x05040100u), __builtin_amdgcn_perm(b0, a0, 0x07060302u),
-                               __builtin_amdgcn_perm(b1, a1, 0x05040100u), __builtin_amdgcn_perm(b1, a1, 0x07060302u)};
+        uint32_t T[4];
+        transpose_piece(a.t[i], T);
 #pragma unroll
         for (int t = 0; t < 4; t++) {
             const uint32_t w = T[t];
@@ -1202,8 +1107,6 @@ __global__ __launch_bounds__(256) void k_quant_t(QuantArgs a, int64_t n, int64_t
     }
 }
 
-__device__ __forceinline__ void combine(const long long (&s)[7], long long& hi, long long& lo);
-
 // Digit sums of P consecutive planes (p0 ...) of one row over its np pieces.  Four pieces are fetched before any is added: the
 // loads of a piece do not depend on the previous one, but a loop of unknown length waits for each piece in turn -- 25 round trips
 // for a row of the hybrid decomposition's remainder.  (DEEP = false: the plain loop -- k_fin_atx_dot, whose many one-piece rows lost
@@ -1282,12 +1185,6 @@ __global__ __launch_bounds__(128) void k_fin_pvals(const int32_t* __restrict__ p
         return;
     }
     a.pvals[m] = gvp::marker_pval(a.cnt[3 * m], a.cnt[3 * m + 1], a.cnt[3 * m + 2], a.mave[m], a.msig[m], s4, cself);
-}
-
-// exact digit recombination: sum_c s_c 256^c as (hi, lo) with value = hi * 2^32 + lo
-__device__ __forceinline__ void combine(const long long (&s)[7], long long& hi, long long& lo) {
-    lo = s[0] + (s[1] << 8) + (s[2] << 16) + (s[3] << 24);
-    hi = s[4] + (s[5] << 8) + (s[6] << 16);
 }
 
 // data::ATx epilogue (data.cpp:779, :825-832): out[m] = msig (sum a p - mave sum b p) / sqrt(N),
@@ -1455,8 +1352,6 @@ __global__ __launch_bounds__(256) void k_fin_atx_wide(const int32_t* __restrict_
     out[m] = addx ? fma(tau, r, gam2 * addx[m]) : r;
 }
 
-inline int nblk(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
-
 // launch of the streaming kernel of one matvec (HIP events around it when the roofline timing is on)
 // grid and ticket arguments of one streaming launch over `items` work items: dealt when the plan carries a ticket counter and the launch
 // goes to the counter's stream (the counter's base advances by the grid, whether or not the device then skips the pass)
@@ -1551,13 +1446,6 @@ void stats_from_stripes(hipStream_t s, const void* stripes_m, const uint32_t* ma
                                        nkb, P4, nonas, alpha_scale, mave, msig, counts)
     if (unr == 2) GV_STATS(2); else if (unr == 3) GV_STATS(3); else GV_STATS(4);
 #undef GV_STATS
-}
-
-// Blocks of a prep launch (every block of the quantisation launch behind it adds their partials up: prep_scalars)
-constexpr int PREP_BLOCKS = 256;
-static int prep_blocks(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > PREP_BLOCKS ? PREP_BLOCKS : b));
 }
 
 // vector preparation of one (nv = 1) or two (nv = 2) N-vectors: scal[4v..] and the digit columns 8v.. of dig0

@@ -379,16 +379,9 @@ inline int64_t m_stride(const gv_ctx* c) { return ((c->M > 0 ? c->M : 1) + 31) /
 int reserve(gv_ctx* c, const char* who, int L, Work& w) {
     const int64_t mcap = m_stride(c);
     const size_t need = carve(nullptr, L, c->npad, mcap).bytes;
-    if (need > c->pca_cap) {
-        pca_release(c);
-        if (hipMalloc(&c->pca_buf, need) != hipSuccess) {
-            (void)hipGetLastError();
-            c->pca_buf = nullptr;
-            return fail(c, "%s: cannot allocate %zu bytes of scratch (four N-space panels and one M-space panel of %d columns)", who, need, L);
-        }
-        c->pca_cap = need;
-    }
-    w = carve(static_cast<char*>(c->pca_buf), L, c->npad, mcap);
+    if (!c->pca_scratch.reserve(need))
+        return fail(c, "%s: cannot allocate %zu bytes of scratch (four N-space panels and one M-space panel of %d columns)", who, need, L);
+    w = carve(static_cast<char*>(c->pca_scratch.buf), L, c->npad, mcap);
     return 0;
 }
 
@@ -443,12 +436,6 @@ const char* const CHOL_MSG =
 }  // namespace
 
 namespace gvi {
-
-void pca_release(gv_ctx* c) {
-    if (c->pca_buf) (void)hipFree(c->pca_buf);
-    c->pca_buf = nullptr;
-    c->pca_cap = 0;
-}
 
 // a k-array of handles of one space, all of this context and distinct; `seen` carries the vectors already named by the call
 static int pca_handles(gv_ctx* c, const char* who, const char* arg, int n, const gv_vec* const* v, int space, bool outputs,

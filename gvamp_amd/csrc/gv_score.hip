@@ -4,14 +4,13 @@
 // Column j of the result is bit-identical to gv_ax_dev of that column alone.  Where the kernel below does not apply -- two stripe
 // sets, kernel modes 0 and 2, methylation and dosage data, a communicator or gv_debug_force_multi, an empty shard -- the existing
 // dispatcher (gvi::ax_pass) runs, in pairs and singly: identical by construction.  The kernel is identical because every sum is an
-// exact integer and the floating-point steps around it are restated here with the roundings and the orders of gv_mfma.hip:
-//   operands      c = fl(msig x), e = fl(fl(mave - 3) c); a column's scale from max(|c|, |e|)                       (k_prep_ax)
+// exact integer and the floating-point steps around it are the functions gv_mfma.hip runs (gv_mfma.h: prep_block_partials,
+// prep_scalars, digits_of, combine).  What this file writes itself, in the form of k_prep_ax and k_fin_ax:
+//   operands      c = fl(msig x), e = fl(fl(mave - 3) c); a column's scale from max(|c|, |e|)
 //   K0            sum of fl(mave c): a grid-stride loop of prep_blocks(M) blocks of 256 threads, each thread's terms in index order
-//                 (s += mave * c, contracted to one fma by the compiler as in k_prep_ax), wave butterfly, the four wave sums in
-//                 order, then over the blocks: thread t adds blocks t, t + 256, ..., a binary tree over 256 threads (prep_scalars)
-//   digits        q = rint(v * 2^(54-e)), seven balanced base-256 digits, digit column 7 zero                       (k_quant_t)
-//   T             fl(fl(hi) * 2^32 + fl(lo)) of the exact (hi, lo) limbs, times the power of two 2^(e-54)            (k_fin_ax)
-//   out           fl(fl(T - K0) * post) at an individual with a phenotype, an exact 0 elsewhere                     (k_fin_ax)
+//                 (s += mave * c, contracted to one fma by the compiler as in k_prep_ax)
+//   T             fl(fl(hi) * 2^32 + fl(lo)) of the exact (hi, lo) limbs, times the power of two 2^(e-54)
+//   out           fl(fl(T - K0) * post) at an individual with a phenotype, an exact 0 elsewhere
 // A column with a NaN or an infinity quantises with multiplier 0 and is scaled by NaN: that column is NaN, no other is touched
 // (every column has its own digit columns and accumulators).
 //
@@ -34,31 +33,19 @@
 #include "gv_internal.h"
 #include "gv_score_plan.h"
 
-static_assert(gvs::MAX_KS == gvm::GV_MAX_KS, "gv_score_plan.h restates GV_MAX_KS");
+// the plan headers are host-only (no HIP include): what they restate of gv_mfma.h is pinned here
+static_assert(gvb::MAX_KS == gvm::GV_MAX_KS, "gv_batch_plan.h restates GV_MAX_KS");
 static_assert(gvs::ENTRY_MAX == gvm::GV_AX_ENTRY_MAX, "gv_score_plan.h restates the int32 bound of the Ax side");
-static_assert(gvs::PREP_BLOCKS_MAX == RED_BLOCKS, "gv_score_plan.h restates the stride of the preparation's block partials");
+static_assert(gvb::PREP_BLOCKS_MAX == RED_BLOCKS, "gv_batch_plan.h restates the stride of the preparation's block partials");
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int PREP_STRIDE = 2 * RED_BLOCKS;   // doubles of block partials per column (as gv_mfma.hip)
-constexpr int PREP_BLOCKS = 256;              // most blocks of the preparation launch (as gv_mfma.hip)
+// the fixed-point operand pipeline, the tile-layout operand helpers and the launch arithmetic: the one copy in gv_mfma.h
+using gvm::v4i; using gvm::u32x4; using gvm::PREP_STRIDE; using gvm::prep_blocks; using gvm::nblk; using gvm::prep_block_partials;
+using gvm::prep_scalars; using gvm::digits_of; using gvm::combine; using gvm::plane_x; using gvm::plane_y; using gvm::wg_barrier_lds;
 
 struct Cols { const double* x[gvs::CP_MAX]; double* out[gvs::CP_MAX]; };
 struct SegB { uint32_t b[gvs::MAX_KS + 1]; };
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 // ---- preparation: block partials [2b] = max(|c|, |e|), [2b + 1] = sum mave * c of column blockIdx.y (k_prep_ax without its hooks)
 __global__ __launch_bounds__(256) void k_score_prep(Cols a, const double* __restrict__ mave, const double* __restrict__ msig, int64_t M,
@@ -74,48 +61,7 @@ __global__ __launch_bounds__(256) void k_score_prep(Cols a, const double* __rest
         mx = (isfinite(c) && isfinite(e)) ? fmax(mx, fmax(fabs(c), fabs(e))) : __longlong_as_double(0x7ff0000000000000LL);
         s += mu * c;
     }
-    mx = wave_max(mx);
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) { shm[threadIdx.x >> 6] = mx; shs[threadIdx.x >> 6] = s; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double* pv = partial + (int64_t)v * PREP_STRIDE;
-        pv[2 * blockIdx.x] = fmax(fmax(shm[0], shm[1]), fmax(shm[2], shm[3]));
-        pv[2 * blockIdx.x + 1] = shs[0] + shs[1] + shs[2] + shs[3];
-    }
-}
-
-// the four scalars of a column from its block partials: amax, K0, 2^(54-e), 2^(e-54) (prep_scalars of gv_mfma.hip, same order)
-__device__ __forceinline__ void score_scalars(const double* __restrict__ partial, int nblocks, double* shm, double* shs, double (&out)[4]) {
-    double mx = 0.0, s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        mx = fmax(mx, partial[2 * b]);
-        s += partial[2 * b + 1];
-    }
-    shm[threadIdx.x] = mx;
-    shs[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (threadIdx.x < off) {
-            shm[threadIdx.x] = fmax(shm[threadIdx.x], shm[threadIdx.x + off]);
-            shs[threadIdx.x] += shs[threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-    const double amax = shm[0];
-    out[0] = amax;
-    out[1] = shs[0];
-    if (amax > 0.0 && amax <= 1.7976931348623157e308) {
-        int e = ilogb(amax) + 1;
-        out[2] = ldexp(1.0, 54 - e);
-        out[3] = ldexp(1.0, e - 54);
-    } else if (amax == 0.0) {
-        out[2] = 0.0;
-        out[3] = 0.0;
-    } else {      // a NaN or an infinity in the column: digits with multiplier 0, the epilogue multiplies by NaN
-        out[2] = 0.0;
-        out[3] = __longlong_as_double(0x7ff8000000000000LL);
-    }
+    prep_block_partials(partial + (int64_t)v * PREP_STRIDE, mx, s, shm, shs);
 }
 
 // ---- digits of the pass: K-step kstep holds CP / 2 pairs x (c block | e block) x 64 lanes x 16 bytes; dword index
@@ -129,7 +75,7 @@ __global__ __launch_bounds__(256) void k_score_quant(Cols a, const double* __res
     double mult = 0.0;
     if (col < ncols) {
         double sc[4];
-        score_scalars(partial + (int64_t)col * PREP_STRIDE, nblocks, shm, shs, sc);
+        prep_scalars(partial + (int64_t)col * PREP_STRIDE, nblocks, shm, shs, sc);
         if (blockIdx.x == 0 && threadIdx.x == 0 && plane == 0) {
             double* o = scal + 4 * col;
             o[0] = sc[0]; o[1] = sc[1]; o[2] = sc[2]; o[3] = sc[3];
@@ -151,24 +97,12 @@ __global__ __launch_bounds__(256) void k_score_quant(Cols a, const double* __res
                 const double c = msig[k] * x[k];
                 val = plane ? (mave[k] - 3.0) * c : c;
             }
-            long long q = (long long)rint(val * mult);
-#pragma unroll
-            for (int c7 = 0; c7 < 7; c7++) {
-                long long dg = (long long)(signed char)(q & 0xFF);   // balanced digit in [-128, 127]
-                q = (q - dg) >> 8;
-                d8[c7] |= (uint32_t)(dg & 0xFF) << (8 * t);
-            }
+            digits_of((long long)rint(val * mult), t, d8);
         }
     }
     uint32_t* o = dig + kstep * ((int64_t)cp * 256) + (((col >> 1) * 2 + plane) * 64 + gam * 16 + (col & 1) * 8) * 4 + i;
 #pragma unroll
     for (int c8 = 0; c8 < 8; c8++) o[c8 * 4] = d8[c8];
-}
-
-__device__ __forceinline__ void wg_barrier_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
 // ---- the pass.  grid = ks * nrg, item = segment * nrg + row group (segment-major).  partial: [(segment * ncols + column) * rows_p +
@@ -224,10 +158,8 @@ __global__ __launch_bounds__(256, CP == 16 ? 2 : 3) void k_score(const uint32_t*
         for (int s = 0; s < 4; s++) {
             const uint32_t e0 = (a0 >> (2 * s)) & 0x03030303u, e1 = (a1 >> (2 * s)) & 0x03030303u, e2 = (a2 >> (2 * s)) & 0x03030303u,
                            e3 = (a3 >> (2 * s)) & 0x03030303u;
-            X[s] = (v4i){(int)e0, (int)e1, (int)e2, (int)e3};                                  // r' plane: the code itself
-            Y[s] = (v4i){(int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e0), (int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e1),
-                         (int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e2),
-                         (int)__builtin_amdgcn_perm(0x01000000u, 0x01000000u, e3)};            // miss plane: 1 where the code is 3
+            X[s] = (v4i){(int)plane_x<0>(e0), (int)plane_x<0>(e1), (int)plane_x<0>(e2), (int)plane_x<0>(e3)};      // r' plane
+            Y[s] = (v4i){(int)plane_y<0>(e0), (int)plane_y<0>(e1), (int)plane_y<0>(e2), (int)plane_y<0>(e3)};      // miss plane
         }
 #pragma unroll
         for (int p = 0; p < NP; p++) {
@@ -280,19 +212,13 @@ __global__ __launch_bounds__(256) void k_score_fin(const int32_t* __restrict__ p
             s[0] += x0.x; s[1] += x0.y; s[2] += x0.z; s[3] += x0.w;
             s[4] += x1.x; s[5] += x1.y; s[6] += x1.z;
         }
-        const long long xl = s[0] + (s[1] << 8) + (s[2] << 16) + (s[3] << 24);
-        const long long xh = s[4] + (s[5] << 8) + (s[6] << 16);
+        long long xh, xl;
+        combine(s, xh, xl);
         const double T = ((double)xh * 4294967296.0 + (double)xl) * scal[3];
         val = (T - scal[1]) * post;
     }
     out[n] = val;
 }
-
-int prep_blocks(int64_t n) {
-    int64_t b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > PREP_BLOCKS ? PREP_BLOCKS : b));
-}
-inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 template <int CP>
 void launch_pass(hipStream_t s, const gv_ctx* c, const gvs::Plan& p, const SegB& sb, const u32x4* dig, int32_t* part, int ncols) {
@@ -302,12 +228,6 @@ void launch_pass(hipStream_t s, const gv_ctx* c, const gvs::Plan& p, const SegB&
 }  // namespace
 
 namespace gvi {
-
-void score_release(gv_ctx* c) {
-    if (c->score_buf) (void)hipFree(c->score_buf);
-    c->score_buf = nullptr;
-    c->score_cap = 0;
-}
 
 // the kernel applies: kernel mode 1 on the tile layout, 2-bit genotypes, one rank, a shard with markers
 static bool score_kernel_applies(const gv_ctx* c) {
@@ -336,17 +256,10 @@ static int score_kernel(gv_ctx* c, int64_t C, const double* const* x, double* co
     if (p.nrg != c->plan.nrg_n || p.nkb != c->plan.nkb_n)
         return fail(c, "gv_score_dev: the resident tile layout has %lld x %lld super-blocks, the plan %lld x %lld", (long long)c->plan.nrg_n,
                     (long long)c->plan.nkb_n, (long long)p.nrg, (long long)p.nkb);
-    if (p.scratch_bytes > c->score_cap) {
-        score_release(c);
-        if (hipMalloc(&c->score_buf, p.scratch_bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            c->score_buf = nullptr;
-            return fail(c, "gv_score_dev: cannot allocate %zu bytes of scratch (digits %zu, partial sums %zu)", p.scratch_bytes, p.dig_bytes,
-                        p.part_bytes);
-        }
-        c->score_cap = p.scratch_bytes;
-    }
-    char* buf = static_cast<char*>(c->score_buf);
+    if (!c->score_scratch.reserve(p.scratch_bytes))
+        return fail(c, "gv_score_dev: cannot allocate %zu bytes of scratch (digits %zu, partial sums %zu)", p.scratch_bytes, p.dig_bytes,
+                    p.part_bytes);
+    char* buf = static_cast<char*>(c->score_scratch.buf);
     u32x4* dig = reinterpret_cast<u32x4*>(buf);
     int32_t* part = reinterpret_cast<int32_t*>(buf + p.dig_bytes);
     double* scal = reinterpret_cast<double*>(buf + p.dig_bytes + p.part_bytes);
@@ -416,23 +329,9 @@ int gv_score_dev(gv_ctx* c, int64_t C, const gv_vec* const* x, gv_vec* const* ou
     NEED(c, C >= 0, "gv_score_dev: the number of columns is negative");
     if (C == 0) return 0;
     NEED(c, x && out, "gv_score_dev: the arrays of column handles are NULL");
-    std::vector<const double*> xs((size_t)C);
-    std::vector<double*> os((size_t)C);
-    std::unordered_set<const gv_vec*> seen;
-    for (int64_t j = 0; j < C; j++) {
-        if (!x[j] || !out[j]) return fail(c, "gv_score_dev: the handle of column %lld is NULL", (long long)j);
-        if (x[j]->space != GV_SPACE_M || out[j]->space != GV_SPACE_N)
-            return fail(c, "gv_score_dev: column %lld: x must be M-space, out N-space", (long long)j);
-        if (!vec_ok(c, x[j], GV_SPACE_M) || !vec_ok(c, out[j], GV_SPACE_N)) {
-            const std::string who = "gv_score_dev: column " + std::to_string((long long)j);
-            return vec_need(c, who.c_str(), "x", x[j], GV_SPACE_M) || vec_need(c, who.c_str(), "out", out[j], GV_SPACE_N);
-        }
-        if (!seen.insert(out[j]).second) return fail(c, "gv_score_dev: column %lld: two outputs are the same vector", (long long)j);
-        xs[(size_t)j] = x[j]->d;
-        os[(size_t)j] = out[j]->d;
-    }
-    for (int64_t j = 0; j < C; j++)
-        if (seen.count(x[j])) return fail(c, "gv_score_dev: column %lld: an output is also an input", (long long)j);
+    std::vector<const double*> xs;
+    std::vector<double*> os;
+    if (batch_args(c, "gv_score_dev", C, x, out, "x", GV_SPACE_M, xs, os)) return 1;
     return score_device(c, C, xs.data(), os.data());
 }
 
@@ -440,26 +339,7 @@ int gv_score(gv_ctx* c, int64_t C, const double* W, double* out) {
     NEED(c, C >= 0, "gv_score: the number of columns is negative");
     if (C == 0) return 0;
     NEED(c, W && out, "gv_score: W or out is NULL");
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<gv_vec*> xv, ov;
-    auto drop = [&]() {
-        for (gv_vec* v : xv) vec_del(c, v);
-        for (gv_vec* v : ov) vec_del(c, v);
-    };
-    for (int64_t j = 0; j < C; j++) {
-        gv_vec *a = nullptr, *b = nullptr;
-        if (vec_new(c, GV_SPACE_M, &a)) { drop(); return 1; }
-        xv.push_back(a);
-        if (vec_new(c, GV_SPACE_N, &b)) { drop(); return 1; }
-        ov.push_back(b);
-        if (c->M > 0 && to_device(c, a->d, W + j * c->M, sizeof(double) * c->M, false)) { drop(); return 1; }
-    }
-    int rc = gv_score_dev(c, C, xv.data(), ov.data());
-    for (int64_t j = 0; j < C && !rc; j++) rc = to_host(c, out + j * 4 * c->mbytes, ov[(size_t)j]->d, sizeof(double) * 4 * c->mbytes);
-    if (!rc) rc = hipStreamSynchronize(c->stream) == hipSuccess ? 0 : fail(c, "gv_score: hipStreamSynchronize failed");
-    drop();
-    if (!rc) c->score_last.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
+    return batch_host(c, "gv_score", C, W, GV_SPACE_M, false, out, gv_score_dev, &c->score_last.seconds);
 }
 
 int gv_score_info(const gv_ctx* c, gv_score_stats* out) {
