@@ -38,6 +38,7 @@ EXPORTS = [
     "gv_atxm_dev", "gv_atxm", "gv_atxm_info", "gv_screen_dev",
     "gv_pca_dev", "gv_pca_loadings_dev", "gv_pca_info",
     "gv_king_block", "gv_king_pairs", "gv_king_info",
+    "gv_screen_cov_set", "gv_screen_cov_dev", "gv_screen_cov_info",
 ]
 
 
@@ -87,6 +88,13 @@ PCA_MAX_BLOCK = 32
 class KingStats(C.Structure):          # gv_king_stats
     _fields_ = [("seconds", C.c_double), ("block_pairs", C.c_int64), ("used_markers", C.c_int64), ("pairs", C.c_int64),
                 ("useful_macs", C.c_double), ("scratch_bytes", C.c_double)]
+
+
+class ScreenCovStats(C.Structure):     # gv_screen_cov_stats
+    _fields_ = [("K", C.c_int), ("pad_", C.c_int), ("nu", C.c_int64), ("cached_bytes", C.c_uint64),
+                ("set_seconds_products", C.c_double), ("set_seconds_panel", C.c_double), ("set_seconds", C.c_double),
+                ("columns", C.c_int64), ("call_seconds_products", C.c_double), ("call_seconds_panel", C.c_double),
+                ("call_seconds", C.c_double)]
 
 
 class CgStats(C.Structure):
@@ -256,6 +264,9 @@ def load():
     L.gv_pca_dev.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp), C.c_double, C.c_int, C.POINTER(vp), dp, dp]
     L.gv_pca_loadings_dev.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(vp)]
     L.gv_pca_info.argtypes = [vp, C.POINTER(PcaStats)]
+    L.gv_screen_cov_set.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.gv_screen_cov_dev.argtypes = [vp, i64, C.POINTER(vp), C.c_double] + [C.POINTER(vp)] * 5
+    L.gv_screen_cov_info.argtypes = [vp, C.POINTER(ScreenCovStats)]
     L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
     L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
@@ -798,6 +809,73 @@ class Shard:
                 for v in us + res[0] + res[1] + res[2]:
                     v.free()
         return tuple(out)
+
+    # ---- the covariate-adjusted screen (gv_screen_cov_*) -----------------------------------
+    def screen_cov_set(self, Cov, K=None):
+        """gv_screen_cov_set: Cov is a list of N-space vectors (used as they are) or raw covariate columns of shape (K, N) / (N,) on the
+        host (uploaded, the call made, freed); None or an empty list is K = 0, the intercept alone.  K overrides the count the list
+        implies (None in place of a list passes a NULL array)"""
+        if Cov is None or (isinstance(Cov, (list, tuple)) and all(v is None or isinstance(v, Vec) for v in Cov)):
+            k = (0 if Cov is None else len(Cov)) if K is None else K
+            self._ck(self.L.gv_screen_cov_set(self.h, int(k), self._handles(Cov)))
+            return
+        A = np.ascontiguousarray(Cov, dtype=np.float64)
+        if A.ndim == 1:
+            A = A[None, :]
+        assert A.ndim == 2 and A.shape[1] == self.N, (A.shape, self.N)
+        vs = [self.vecN(self._padN(a)) for a in A]
+        try:
+            self._ck(self.L.gv_screen_cov_set(self.h, len(vs) if K is None else int(K), self._handles(vs)))
+        finally:
+            for v in vs:
+                v.free()
+
+    def _padN(self, a):
+        out = np.zeros(4 * self.mbytes)
+        out[:self.N] = a
+        return out
+
+    def screen_cov_dev(self, ys, rs, ts=None, ps=None, betas=None, ses=None, vif=50.0):
+        """gv_screen_cov_dev: raw phenotype columns ys (N-space vectors) -> r, t, p, beta, se per marker (M-space vectors; all but rs may
+        be None)"""
+        n = len(ys) if ys is not None else len(rs)
+        self._ck(self.L.gv_screen_cov_dev(self.h, n, self._handles(ys), float(vif), self._handles(rs), self._handles(ts), self._handles(ps),
+                                          self._handles(betas), self._handles(ses)))
+
+    def screen_cov(self, Y, Cov, vif=50.0, cols_per_call=64):
+        """the covariate-adjusted screen of raw phenotype columns Y (C, N) given raw covariate columns Cov (K, N), or None for the
+        intercept alone: dict r, t, p, beta, se, each of shape (C, M).  Values at the individuals the context's mask leaves out are
+        ignored (NaN there is fine); Cov=False keeps the covariates of the last screen_cov_set"""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[None, :]
+        assert Y.ndim == 2 and Y.shape[1] == self.N, (Y.shape, self.N)
+        if Cov is not False:
+            self.screen_cov_set(Cov)
+        names = ("r", "t", "p", "beta", "se")
+        out = {k: np.empty((Y.shape[0], self.M)) for k in names}
+        for j0 in range(0, Y.shape[0], cols_per_call):
+            blk = Y[j0:j0 + cols_per_call]
+            ys = [self.vecN(self._padN(y)) for y in blk]
+            res = [[self.vecM() for _ in blk] for _ in names]
+            try:
+                self.screen_cov_dev(ys, *res, vif=vif)
+                for k, name in enumerate(names):
+                    for j, v in enumerate(res[k]):
+                        out[name][j0 + j] = v.download()
+            finally:
+                for v in ys + [v for vs in res for v in vs]:
+                    v.free()
+        return out
+
+    def screen_cov_info(self):
+        """gv_screen_cov_info as a dict; K is None when no covariate state is cached"""
+        st = ScreenCovStats()
+        self._ck(self.L.gv_screen_cov_info(self.h, C.byref(st)))
+        return dict(K=None if st.K < 0 else st.K, nu=st.nu, cached_bytes=int(st.cached_bytes), set_seconds_products=st.set_seconds_products,
+                    set_seconds_panel=st.set_seconds_panel, set_seconds=st.set_seconds, columns=st.columns,
+                    call_seconds_products=st.call_seconds_products, call_seconds_panel=st.call_seconds_panel,
+                    call_seconds=st.call_seconds)
 
     def pca_dev(self, q0, us, tol, max_iter, k=None, L=None):
         """gv_pca_dev: the len(us) largest eigenpairs of the relationship matrix from the starting block q0 (N-space vectors, not

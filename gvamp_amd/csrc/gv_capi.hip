@@ -259,6 +259,7 @@ static void free_dataset(gv_ctx* c) {
     c->score_scratch.release();
     c->atxm_scratch.release();
     c->pca_scratch.release();
+    c->cov_cache.release();
     F(c->cgx_state); F(c->cgx_go);
     if (c->cgx_rel_h) (void)hipHostFree(c->cgx_rel_h);
     c->cgx_rel = c->cgx_rel_h = nullptr;
@@ -278,6 +279,7 @@ static void free_dataset(gv_ctx* c) {
             *v = nullptr;
         }
     c->have_stats = c->have_people = false;
+    cov_drop(c);
 }
 
 }  // namespace gvi

@@ -70,6 +70,7 @@ static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed,
     const int64_t M = c->M, P = c->pitch;
     gvm::Plan& pl = c->plan;
     c->have_raw = c->have_stripes = c->have_stats = c->have_people = false;
+    cov_drop(c);
     pc_invalidate(c, false);      // (window Grams belong to the data set they were built from)
     dense_release(c);      // uploading any kind replaces the dataset held before
     if (c->want_raw && !c->bed) HIPCHK(c, hipMalloc(&c->bed, (size_t)(M > 0 ? M : 1) * P));
@@ -320,6 +321,7 @@ static int dense_begin(gv_ctx* c, int bits, double scale, DenseClock* clk) {
     free_layouts(c);
     if (c->bed) { (void)hipFree(c->bed); c->bed = nullptr; }
     c->have_raw = c->have_stripes = c->have_stats = c->have_people = false;
+    cov_drop(c);
     pc_invalidate(c, false);        // (window Grams belong to the data set they were built from)
     c->ingest_bytes = 0;
     DenseData& d = c->dense;

@@ -242,6 +242,14 @@ struct gv_ctx {
     DevScratch pca_scratch;
     gv_pca_stats pca_last{};
     gv_king_stats king_last{};      // gv_king_info: the last gv_king_block / gv_king_pairs call (gv_king.hip)
+    // gv_screen_cov_set / gv_screen_cov_dev (gv_screen_cov.hip): the cached state of the covariate side -- the
+    // orthonormal basis Q (cov_K columns of npad doubles) and behind it v (M doubles), in an allocation of its own (the work panels of
+    // both calls are pca_scratch's).  It belongs to the data set, mask and marker statistics it was computed from: have_cov is cleared
+    // wherever have_stats is cleared or set anew (cov_drop: gv_set_mask, gv_marker_stats, every ingest, free_dataset, which also frees it)
+    DevScratch cov_cache;
+    bool have_cov = false;
+    int cov_K = 0;
+    gv_screen_cov_stats cov_last{};
 
     // communicator ---------------------------------------------------------------------------------
     ncclComm_t comm = nullptr;
@@ -547,6 +555,21 @@ int batch_host(gv_ctx* c, const char* who, int64_t C, const double* in, int in_s
 int score_device(gv_ctx* c, int64_t C, const double* const* x, double* const* out);
 // gv_atxm.hip: R = A^T Y on device pointers (C > 0 columns, p[j] npad doubles, out[j] M doubles)
 int atxm_device(gv_ctx* c, int64_t C, const double* const* p, double* const* out);
+// gv_pca.hip: its panel kernels for the other files that work on panels of L <= GV_PCA_MAX_BLOCK separate fp64 columns of npad doubles
+// (gv_screen_cov.hip).  The small buffers are the caller's (panel_bufs_bytes of device memory, 256-byte aligned); every array of column
+// pointers holds L valid columns.  panel_gram: b.S = X^T Y, LM x LM row-major with LM = L <= 16 ? 16 : 32, through k_pca_gram and
+// k_pca_gram_fin; an entry's summation order is a function of npad alone.  panel_orth: X <- orth(X) in place, CholeskyQR applied twice
+// (k_pca_gram, k_pca_small in Cholesky mode, k_pca_apply); *b.flag, zeroed by the caller, is set to 1 by a pivot that is not positive
+struct PanelBufs { double *part, *S, *W, *theta; int* flag; };
+size_t panel_bufs_bytes();
+PanelBufs panel_bufs_carve(char* base);
+void panel_gram(gv_ctx* c, const PanelBufs& b, double* const* X, double* const* Y, int L);
+void panel_orth(gv_ctx* c, const PanelBufs& b, double* const* X, int L);
+// the cached state of gv_screen_cov_set is no longer that of the context's mask and marker statistics
+inline void cov_drop(gv_ctx* c) {
+    c->have_cov = false;
+    c->cov_K = 0;
+}
 
 struct Timer {
     gv_ctx* c;

@@ -437,6 +437,42 @@ const char* const CHOL_MSG =
 
 namespace gvi {
 
+// ---- the panel helpers for the other files that work on panels (gv_internal.h; gv_screen_cov.hip): the launches above, unchanged ----
+size_t panel_bufs_bytes() {
+    return up256(sizeof(double) * GRAM_BLOCKS * LMAX * LMAX) + 2 * up256(sizeof(double) * LMAX * LMAX) + up256(sizeof(double) * LMAX) +
+           up256(sizeof(int));
+}
+
+PanelBufs panel_bufs_carve(char* base) {
+    PanelBufs b{};
+    size_t off = 0;
+    auto take = [&](size_t nbytes) { char* p = base + off; off += up256(nbytes); return p; };
+    b.part = (double*)take(sizeof(double) * GRAM_BLOCKS * LMAX * LMAX);
+    b.S = (double*)take(sizeof(double) * LMAX * LMAX);
+    b.W = (double*)take(sizeof(double) * LMAX * LMAX);
+    b.theta = (double*)take(sizeof(double) * LMAX);
+    b.flag = (int*)take(sizeof(int));
+    return b;
+}
+
+static Work work_of(const PanelBufs& b) {
+    Work w{};
+    w.part = b.part; w.S = b.S; w.W = b.W; w.theta = b.theta; w.flag = b.flag;
+    return w;
+}
+
+static Panel panel_from(double* const* p, int L) {
+    Panel P{};
+    for (int j = 0; j < L; j++) P.p[j] = p[j];
+    return P;
+}
+
+void panel_gram(gv_ctx* c, const PanelBufs& b, double* const* X, double* const* Y, int L) {
+    gram(c, work_of(b), panel_from(X, L), panel_from(Y, L), L);
+}
+
+void panel_orth(gv_ctx* c, const PanelBufs& b, double* const* X, int L) { orth(c, work_of(b), panel_from(X, L), L); }
+
 // a k-array of handles of one space, all of this context and distinct; `seen` carries the vectors already named by the call
 static int pca_handles(gv_ctx* c, const char* who, const char* arg, int n, const gv_vec* const* v, int space, bool outputs,
                        std::unordered_set<const gv_vec*>& seen) {

@@ -22,6 +22,7 @@ int gv_set_mask(gv_ctx* c, const uint8_t* mask4, int64_t nonas) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->nonas = nonas;
     c->have_stats = c->have_people = false;
+    cov_drop(c);
     pc_invalidate(c, false);
     return 0;
 }
@@ -29,6 +30,7 @@ int gv_set_mask(gv_ctx* c, const uint8_t* mask4, int64_t nonas) {
 int gv_marker_stats(gv_ctx* c, double alpha_scale) {
     pc_invalidate(c, false);
     c->have_people = false;       // (the people statistics are sums over the standardised genotypes: new mave / msig, new sums)
+    cov_drop(c);                  // (and so are the covariate side's products)
     if (c->dense.resident) {      // the meth branch of compute_markers_statistics (data.cpp:487-540)
         NEED(c, c->mask2, "gv_marker_stats: mask must be set first");
         gvd::stats(c->stream, dense_view(c), c->mask2, (double)c->nonas, alpha_scale, c->mave);      // (codes: the same, in code units)

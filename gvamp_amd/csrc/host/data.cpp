@@ -520,6 +520,50 @@ std::vector<std::vector<std::vector<double>>> data::screen(const std::vector<std
     return out;
 }
 
+void data::screen_cov_set() {
+    const size_t K = covs.empty() ? 0 : covs[0].size(), n4 = 4 * (size_t)mbytes;
+    if (K > 0 && covs.size() < (size_t)N) {
+        std::cout << "FATAL: data::screen_cov_set: " << covs.size() << " covariate rows, fewer than N = " << N << std::endl;
+        exit(EXIT_FAILURE);
+    }
+    std::vector<gv_vec*> cv(K, nullptr);
+    std::vector<double> buf(n4);
+    for (size_t k = 0; k < K; k++) {
+        std::fill(buf.begin(), buf.end(), 0.0);
+        for (int n = 0; n < N; n++) buf[n] = covs[n][k];
+        ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &cv[k]), "gv_vec_alloc");
+        ck(ctx, gv_vec_upload(ctx, cv[k], buf.data()), "gv_vec_upload");
+    }
+    ck(ctx, gv_screen_cov_set(ctx, (int)K, cv.data()), "gv_screen_cov_set");
+    for (gv_vec* v : cv) gv_vec_free(ctx, v);
+}
+
+std::vector<std::vector<std::vector<double>>> data::screen_cov(const std::vector<std::vector<double>>& cols, double vif_max) {
+    const size_t C = cols.size(), Mp = M > 0 ? (size_t)M : 0, n4 = 4 * (size_t)mbytes;
+    std::vector<std::vector<std::vector<double>>> out(5, std::vector<std::vector<double>>(C, std::vector<double>(Mp, 0.0)));
+    if (C == 0) return out;
+    std::vector<gv_vec*> y(C, nullptr), res(5 * C, nullptr);
+    std::vector<double> buf(n4);
+    for (size_t j = 0; j < C; j++) {
+        if (cols[j].size() < (size_t)N) {
+            std::cout << "FATAL: data::screen_cov: column " << j << " has " << cols[j].size() << " entries, fewer than N = " << N << std::endl;
+            exit(EXIT_FAILURE);
+        }
+        std::fill(buf.begin(), buf.end(), 0.0);
+        std::copy(cols[j].begin(), cols[j].begin() + N, buf.begin());
+        ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &y[j]), "gv_vec_alloc");
+        ck(ctx, gv_vec_upload(ctx, y[j], buf.data()), "gv_vec_upload");
+        for (int k = 0; k < 5; k++) ck(ctx, gv_vec_alloc(ctx, GV_SPACE_M, &res[k * C + j]), "gv_vec_alloc");
+    }
+    ck(ctx, gv_screen_cov_dev(ctx, (int64_t)C, y.data(), vif_max, res.data(), res.data() + C, res.data() + 2 * C, res.data() + 3 * C,
+                              res.data() + 4 * C), "gv_screen_cov_dev");
+    for (int k = 0; k < 5; k++)
+        for (size_t j = 0; j < C && Mp > 0; j++) ck(ctx, gv_vec_download(ctx, res[k * C + j], out[k][j].data()), "gv_vec_download");
+    for (gv_vec* v : y) gv_vec_free(ctx, v);
+    for (gv_vec* v : res) gv_vec_free(ctx, v);
+    return out;
+}
+
 std::vector<double> data::ATx(double* __restrict__ phen) {
     std::vector<double> out(M > 0 ? M : 0, 0.0);
     ck(ctx, gv_atx(ctx, phen, out.data()), "gv_atx");

@@ -82,6 +82,12 @@ public:
     // [ext] the marginal association screen (gv_screen_dev): cols[j] = N raw phenotype values, NaN for NA, every NA outside the mask.
     // Returns {r, t, p}, each C columns of M values.
     std::vector<std::vector<std::vector<double>>> screen(const std::vector<std::vector<double>>& cols);
+    // [ext] the covariate-adjusted screen (gv_screen_cov_set / gv_screen_cov_dev).  screen_cov_set: the K columns
+    // of the covariates read_covariates / set_covs left (N rows of K values; none: the intercept alone) become the context's cached
+    // basis.  screen_cov: cols[j] = N raw phenotype values, used as they are (values outside the mask are ignored).  Returns
+    // {r, t, p, beta, se}, each C columns of M values.
+    void screen_cov_set();
+    std::vector<std::vector<std::vector<double>>> screen_cov(const std::vector<std::vector<double>>& cols, double vif_max);
     // [ext] principal components of the resident genotypes (gv_pca_dev): the k leading eigenpairs of the
     // relationship matrix from a starting block of L columns of pca_start(seed, ...); loadings: this shard's M values per component
     struct pca_result {

@@ -547,14 +547,63 @@ int main(int argc, char** argv) {
         }
         data dataset(std::vector<double>(N, 0.0), opt.get_bed_file(), N, M, Mt, S, rank, type_data, alpha_scale, bimfp, dev, km, dscale, dmiss,
                      droute);
+        // [ext] --cov-file F --C K: the screen adjusted for K covariates and an intercept; complete cases over
+        // the phenotype files and the covariates
+        const bool with_cov = opt.get_cov_file() != "";
+        const int K = with_cov ? (int)opt.get_C() : 0;
+        if (with_cov) {
+            if (K < 1 || K > GV_PCA_MAX_BLOCK) {
+                std::cout << "FATAL: --run-mode screen --cov-file needs --C K, the number of covariates per line (1.." << GV_PCA_MAX_BLOCK << ")"
+                          << std::endl;
+                return EXIT_FAILURE;
+            }
+            dataset.read_covariates(opt.get_cov_file(), K);
+            const std::vector<std::vector<double>> Z = dataset.get_covs();
+            for (int n = 0; n < N; n++) {
+                bool fin = true;
+                for (int k = 0; k < K; k++) fin = fin && std::isfinite(Z[(size_t)n][(size_t)k]);
+                if (!fin && have[(size_t)n]) {
+                    have[(size_t)n] = 0;
+                    m4[(size_t)n / 4] &= (unsigned char)~(1u << (n % 4));
+                    nonas--;
+                }
+            }
+            if (nonas - 2 - K < 1) {
+                std::cout << "FATAL: --run-mode screen: " << nonas << " complete cases and " << K << " covariates leave the test no degree of freedom"
+                          << std::endl;
+                return EXIT_FAILURE;
+            }
+        }
         dataset.set_mask(m4, nonas);
         const std::string pre = opt.get_out_dir() + opt.get_out_name();
+        if (with_cov) {
+            const char* tag5[5] = {"_screen_r.bin", "_screen_t.bin", "_screen_p.bin", "_screen_beta.bin", "_screen_se.bin"};
+            const size_t per5 = opt.get_screen_cols();
+            dataset.screen_cov_set();
+            gv_screen_cov_stats cs{};
+            gv_screen_cov_info(dataset.get_ctx(), &cs);
+            double prod = 0.0, panel = 0.0;
+            for (size_t c0 = 0; c0 < C; c0 += per5) {
+                const size_t c1 = c0 + per5 < C ? c0 + per5 : C;
+                const std::vector<std::vector<double>> blk(Y.begin() + c0, Y.begin() + c1);
+                const auto res = dataset.screen_cov(blk, opt.get_screen_vif());
+                gv_screen_cov_info(dataset.get_ctx(), &cs);
+                prod += cs.call_seconds_products;
+                panel += cs.call_seconds_panel;
+                for (int k = 0; k < 5; k++)
+                    for (size_t c = c0; c < c1; c++) mpi_store_vec_to_file(pre + tag5[k], res[(size_t)k][c - c0], (int)(c * (size_t)Mt) + S, M);
+            }
+            if (rank == 0)
+                std::cout << "screen: " << C << " phenotypes x " << Mt << " markers adjusted for " << K << " covariates, " << nonas
+                          << " complete cases of " << N << ", nu = " << cs.nu << ", set " << cs.set_seconds << " seconds, products " << prod
+                          << " s, panel and finishing kernels " << panel << " s -> " << pre << "_screen_{r,t,p,beta,se}.bin" << std::endl;
+        }
         const char* tag[3] = {"_screen_r.bin", "_screen_t.bin", "_screen_p.bin"};
         const size_t per = opt.get_screen_cols();
         long long passes = 0;
         double seconds = 0.0;
         gv_atxm_stats st{};
-        for (size_t c0 = 0; c0 < C; c0 += per) {
+        for (size_t c0 = 0; c0 < C && !with_cov; c0 += per) {
             const size_t c1 = c0 + per < C ? c0 + per : C;
             const std::vector<std::vector<double>> blk(Y.begin() + c0, Y.begin() + c1);
             const auto res = dataset.screen(blk);
@@ -564,7 +613,7 @@ int main(int argc, char** argv) {
             for (int k = 0; k < 3; k++)
                 for (size_t c = c0; c < c1; c++) mpi_store_vec_to_file(pre + tag[k], res[(size_t)k][c - c0], (int)(c * (size_t)Mt) + S, M);
         }
-        if (rank == 0)
+        if (rank == 0 && !with_cov)
             std::cout << "screen: " << C << " phenotypes x " << Mt << " markers, " << nonas << " complete cases of " << N << ", "
                       << (st.path == GV_ATXM_PATH_KERNEL ? "kernel" : "fallback") << " path, " << passes << " passes, " << seconds
                       << " seconds -> " << pre << "_screen_{r,t,p}.bin" << std::endl;

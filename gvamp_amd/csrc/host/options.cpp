@@ -203,6 +203,7 @@ void Options::read_command_line_options(int argc, char** argv) {
     str("--score-p-file", score_p_file);
     uns("--score-cols", score_cols, POS, "a strictly positive integer");
     uns("--screen-cols", screen_cols, POS, "a strictly positive integer");
+    num("--screen-vif", screen_vif);
     uns("--pca-k", pca_k, POS, "a strictly positive integer");
     uns("--pca-block", pca_block, POS, "a strictly positive integer");
     uns("--pca-max-iter", pca_max_iter, POS, "a strictly positive integer");

@@ -73,7 +73,11 @@
        --run-mode screen (gv_screen_dev) with --phen-files f0,f1,...: the marginal association      \
        screen of every phenotype file against every marker over the complete cases (an individual with NA in any file    \
        is masked): <out>_screen_{r,t,p}.bin, one column of Mt float64 per file; --screen-cols K (default 64): columns    \
-       per call;                                                                                                        \
+       per call; with --cov-file F --C K (gv_screen_cov_set / gv_screen_cov_dev; F holds N lines    \
+       of K numbers, the format of <out>_pca_eigenvec.txt) the screen is adjusted for the K covariates and an            \
+       intercept: an individual with a non-finite covariate is masked together with the NA phenotypes, a marker whose     \
+       variance-inflation factor given the covariates is above --screen-vif (default 50) gets NaN, and                    \
+       <out>_screen_{beta,se}.bin (per copy of the counted allele) are written beside the three files;                    \
        --run-mode pca (gv_pca_dev) with --pca-k K: the K leading principal components of the       \
        standardised genotypes among the individuals with a phenotype, by block subspace iteration on a block of          \
        --pca-block L vectors (default min(32, K + max(8, K))) to --pca-tol t (default 1e-8) within --pca-max-iter n       \
@@ -96,6 +100,7 @@
     X(double, clump_kb, -1)                                                                                          \
     X(std::string, score_file, "") X(unsigned int, score_cols, 1) X(std::string, score_units, "std")                \
     X(std::string, score_clump_index, "") X(std::string, score_p_file, "") X(unsigned int, screen_cols, 64)   \
+    X(double, screen_vif, 50.0)                                                                                      \
     X(unsigned int, pca_k, 0) X(unsigned int, pca_block, 0) X(double, pca_tol, 1e-8) X(unsigned int, pca_max_iter, 100)          \
     X(unsigned int, pca_seed, 0) X(unsigned int, pca_allow_unconverged, 0)                                           \
     X(double, king_cutoff, 0.0884) X(std::string, king_marker_file, "")

@@ -225,6 +225,12 @@ int gv_get_marker_stats(gv_ctx* ctx, double* mave, double* msig); /* M doubles e
  *
  * The N-space solvers gv_cg_solve_aat* refuse until gv_people_stats has run after the LAST gv_marker_stats.  The M-space solvers and
  * every product refuse until gv_marker_stats has run after the last gv_set_mask or upload.
+ *
+ *   gv_set_mask, gv_marker_stats, gv_upload_* | the covariate side of the adjusted screen (the basis  | gv_marker_stats, then
+ *   / gv_synth_*, gv_set_dims                 | Q and the per-marker v of gv_screen_cov_set)          | gv_screen_cov_set
+ *
+ * gv_screen_cov_dev refuses, naming gv_screen_cov_set, until that call has run after the LAST gv_marker_stats
+ * (tests/test_gpu_screen_cov_reuse.py holds this row as the other file holds the rows above).
  * What survives a data set (and gv_set_dims): the options "that outlive the data set" -- kernel mode, layout request, dosage route,
  * gv_set_dosage_missing, gv_set_ld_dosage, the preconditioner kind and window, gv_set_expected_passes, the communicator, timing -- and
  * the ticket counter of the streaming kernels.  The tuner's decomposition picks are made again per resident layout (and change no
@@ -1005,6 +1011,71 @@ int gv_king_block(gv_ctx* ctx, const uint8_t* use /* M or NULL */, int64_t i0, i
 int gv_king_pairs(gv_ctx* ctx, const uint8_t* use /* M or NULL */, double cutoff, int64_t cap, int32_t* pi, int32_t* pj, double* kin,
                   int32_t* counts /* cap (x 5) each */, int64_t* n_found);
 int gv_king_info(gv_ctx* ctx, gv_king_stats* info);
+
+/* ---- covariate-adjusted association screen: partial regression on the batch product (additions only: GV_ABI_VERSION stays 4; DESIGN.md
+ * section 26) ------------------------------------------------------------------------------------------------------------------------
+ * The regression of a phenotype y on [1, covariates, g_j] for every marker j, by the Frisch-Waugh-Lovell theorem: with Q an
+ * orthonormal basis of the centred covariates and u the unit-norm residual of y, everything a marker needs is A^T u and A^T Q.
+ * Data, mask and marker statistics are those of gv_screen_dev: 2-bit genotypes, alpha_scale == 1, n = nonas, a missing genotype counts
+ * as the marker's mean.  xh_j = sqrt(N / (n - 1)) A_j is the unit-norm centred mean-imputed column of marker j (msig_j^2 sxx_j = n - 1).
+ *
+ * gv_screen_cov_set(ctx, K, cov): cov[k] are K raw covariate columns (N-space, not modified; values at NA and pad slots are ignored),
+ * 0 <= K <= GV_PCA_MAX_BLOCK.  On the device, column k is zeroed outside the mask; centred, q <- q - fl(sum q / n) at the phenotyped; and
+ * divided by fl(sqrt(sum q^2)); every sum in a fixed order that is a function of npad alone.  The panel is then orthonormalised by
+ * CholeskyQR applied twice with the kernels and under the pivot rule of gv_pca_dev (32 * 2^-52 of the diagonal entry).  A column whose
+ * sum of squares is not a positive finite number (constant over the phenotyped, or not finite there) and a pivot that is not positive
+ * refuse the call: the covariates are collinear with each other or with the intercept, which is implicit (Q is orthogonal to the mask
+ * vector because its columns are centred).  Then, with Z = gv_atxm_dev(Q) (M x K, scratch only) and c = fl(N / (n - 1)):
+ *     s_j = sum_k z_jk^2     ascending k, s = fma(z, z, s) from 0
+ *     v_j = fma(-c, s_j, 1)  the share of marker j's variance that the covariates leave; 1 / v_j is its variance-inflation factor
+ * The context keeps Q (K columns of npad doubles), v (M doubles) and K in an allocation of its own, gv_screen_cov_stats.cached_bytes,
+ * until gv_set_mask, gv_marker_stats, an upload or gv_set_dims drops them (the table above).  K == 0 is valid: an intercept only,
+ * v == 1.  A refused call leaves the state cached before it as it was.  The call returns when its device work has finished.
+ *
+ * gv_screen_cov_dev(ctx, C, y, vif_max, r, t, p, beta, se): y[c] are C raw phenotype columns (N-space, not modified; values outside
+ * the mask are ignored; a NaN inside the mask makes that column's outputs NaN and no other's).  C is processed in blocks of at most 32
+ * columns.  On the device, per column: zeroed outside the mask and centred as a covariate is; projected twice,
+ *     g_k = sum_n q_k[n] y[n] (the order of k_pca_gram)        y[n] <- fma(-q_k[n], g_k, y[n]) for k ascending
+ * S = sum y^2 (fixed order), u = fl(y / fl(sqrt(S))).  With w = gv_atxm_dev(u), nu = n - 2 - K, per marker and column, in this order of
+ * fp64 roundings:
+ *     a    = fl(sqrt(fl(N / (n - 1))))                       (host, once)
+ *     rho  = fl(fl(w a) / fl(sqrt(v_j)))                     the partial correlation              -> r
+ *     om   = fma(-rho, rho, 1)
+ *     t    = fl(rho fl(sqrt(fl(nu / om))))                   p = gvp::t_two_sided(|t|, nu)
+ *     d    = fl(fl((n - 1) / fl(msig_j msig_j)) v_j)         sxx_j v_j
+ *     beta = fl(rho fl(sqrt(fl(S / d))))                     per unit of the genotype value 0 / 1 / 2
+ *     se   = fl(sqrt(fl(fl(S om) / fl(nu d))))
+ * om <= 0 gives t = +-inf (the sign of rho), p = 0, se = 0.  NaN in all five outputs: a marker with sumsqx == 0 (the rule of
+ * gv_screen_dev); a marker with v_j vif_max < 1 (the --vif rule of plink2 --glm; it bounds the cancellation in v_j); a column whose S is
+ * not positive (the covariates explain the phenotype; accepted, not refused).  vif_max is finite and >= 1.
+ * r is required; t, p, beta and se may be NULL arrays.  All outputs are distinct M-space vectors.
+ * Column independence: the outputs of a column are bit-identical whatever C is, wherever the column stands and whatever the other
+ * columns hold: the batch product guarantees it, a Gram entry's summation order is a function of npad alone, and every other step is
+ * per column.
+ * Refused with a message, nothing written: everything gv_screen_dev refuses; K < 0 or K > GV_PCA_MAX_BLOCK; nu < 1; NULL arrays or
+ * handles, vectors of the wrong space, of another context or of earlier dimensions; two outputs that are the same vector; vif_max that is
+ * NaN, infinite or < 1; collinear covariates; gv_screen_cov_dev before gv_screen_cov_set, or after its state was dropped (the message
+ * names gv_screen_cov_set).
+ * Work panels: gv_pca_dev's scratch, owned by the context, grown on demand.  The calls leave the context as they found it, by the rule
+ * of gv_atxm_dev / gv_pca_dev.  Both return when their device work has finished (the seconds below are device events). */
+typedef struct gv_screen_cov_stats {
+    int K;                       /* covariates of the cached state; -1: none cached */
+    int pad_;
+    int64_t nu;                  /* n - 2 - K of the cached state (0 when none) */
+    uint64_t cached_bytes;       /* bytes of Q and v the context holds */
+    double set_seconds_products; /* last successful gv_screen_cov_set: device time in the batch product */
+    double set_seconds_panel;    /* ... in the panel kernels: masking, centring, scaling, CholeskyQR, v */
+    double set_seconds;          /* ... host wall time of the call */
+    int64_t columns;             /* last gv_screen_cov_dev: C */
+    double call_seconds_products; /* ... device time in the batch product */
+    double call_seconds_panel;   /* ... in the panel and finishing kernels */
+    double call_seconds;         /* ... host wall time of the call */
+} gv_screen_cov_stats;
+int gv_screen_cov_set(gv_ctx* ctx, int K, const gv_vec* const* cov /* K, GV_SPACE_N, not modified */);
+int gv_screen_cov_dev(gv_ctx* ctx, int64_t C, const gv_vec* const* y /* C, GV_SPACE_N, not modified */, double vif_max,
+                      gv_vec* const* r, gv_vec* const* t, gv_vec* const* p, gv_vec* const* beta,
+                      gv_vec* const* se /* C each, GV_SPACE_M; all but r may be NULL arrays */);
+int gv_screen_cov_info(const gv_ctx* ctx, gv_screen_cov_stats* out);
 
 #ifdef __cplusplus
 }
