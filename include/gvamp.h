@@ -841,7 +841,13 @@ int gv_get_ld_dosage(const gv_ctx* ctx, int* on);
  * refused.  GV_SCORE_COLS=<4|8|16> pins the columns per pass and GV_SCORE_KS=<k> the K-segments (development, read by gv_create per
  * context; gv_create refuses other values, the call refuses a k that breaks the bound); neither changes a bit.
  * gv_score: the same on host arrays: column j of W at W + j * M, column j of the result at out + j * 4 * mbytes; returns when out is
- * filled.  gv_score_info: the last gv_score_dev / gv_score call of the context. */
+ * filled.  gv_score_info: the last gv_score_dev / gv_score call of the context.
+ * A context joined to others (gv_comm_init*, a marker-sharded job): x[j] holds this rank's M entries of column j, out[j] is the sum
+ * over the ranks, the same bits on every rank.  Every column is one collective (two for a pair): EVERY rank of the job makes the call,
+ * with the same C, at the same place in its sequence of collective calls, under the same mask and kernel mode -- a rank without
+ * markers (M == 0) included, which adds zeros.  A rank that stays away leaves its peers waiting.  The sum over the ranks is another
+ * rounding than the sum of one context over all markers: a sharded result equals a one-rank result to the accuracy of gv_ax_dev, not
+ * by bits (tests/test_gpu_sharded_products.py). */
 #define GV_SCORE_PATH_KERNEL 1
 #define GV_SCORE_PATH_FALLBACK 2
 #define GV_SCORE_COLS_DEFAULT 8
@@ -897,7 +903,12 @@ int gv_score_info(const gv_ctx* ctx, gv_score_stats* out);
  * or all missing: sumsqx == 0 in the expression of the association test) gives NaN in all three outputs.  (The other half of that
  * test's rule, fewer than three present genotypes, does not apply: under mean imputation the degrees of freedom are n - 2 for every
  * marker.)  r, t, p are M-space; t and p may be NULL arrays.  All outputs are distinct vectors, none is an input.
- * Refused with a message: everything gv_atxm_dev refuses; n < 3; methylation and dosage data; marker statistics of alpha_scale != 1. */
+ * Refused with a message: everything gv_atxm_dev refuses; n < 3; methylation and dosage data; marker statistics of alpha_scale != 1.
+ * A context joined to others (a marker-sharded job): gv_atxm_dev and gv_screen_dev issue no collective and every output is a quantity
+ * of one marker, so a rank may call them alone and the outputs of the ranks, put side by side in marker order, are the output of one
+ * context on all markers bit for bit -- PROVIDED every rank has set the same mask (gv_set_mask with the same bytes and nonas: the
+ * statistics of a marker and n depend on it) and passes the same columns.  On a rank without markers the calls succeed and write
+ * nothing. */
 #define GV_ATXM_PATH_KERNEL 1
 #define GV_ATXM_PATH_FALLBACK 2
 #define GV_ATXM_COLS_DEFAULT 8
@@ -949,7 +960,15 @@ int gv_screen_dev(gv_ctx* ctx, int64_t C, const gv_vec* const* u /* C, GV_SPACE_
  * leaves the context as it found it, by the rule of gv_score_dev / gv_atxm_dev; it writes the reduction scalars as gv_vec_dots does.
  * gv_pca_loadings_dev: v[i] = fl(c_i * gv_atx_dev(u[i])), c_i = fl(fl(sqrt(fl(N / Mt))) / fl(sqrt(eval[i]))): the right singular
  * vectors in M-space (this rank's markers), one rounding after the product; k <= GV_PCA_MAX_BLOCK, eval[i] positive and finite.
- * gv_pca_info: the last successful gv_pca_dev of the context. */
+ * gv_pca_info: the last successful gv_pca_dev of the context.
+ * A context joined to others (a marker-sharded job): the relationship matrix is that of all Mt markers.  gv_pca_dev is a sequence of
+ * collectives (L columns of gv_score_dev's fallback per iteration) and nothing else crosses the ranks: EVERY rank makes the call -- a
+ * rank with fewer markers than L, or with none, included: the block is bounded by min(nonas, Mt) -- with the same k, L, tol and
+ * max_iter, the same bits in q0 and the same mask.  Then the N-space state is the same bits on every rank, every rank takes the same
+ * decisions (the Cholesky flag, convergence) from the same scalars and leaves the loop in the same iteration; u, eval, resid and
+ * gv_pca_info's iterations / converged are identical on every rank.  A rank whose q0, mask or arguments differ decides differently
+ * and leaves its peers waiting in a collective: the caller's to guarantee, nothing checks it.  gv_pca_loadings_dev issues no
+ * collective; v holds this rank's M markers of the Mt-vector. */
 #define GV_PCA_MAX_BLOCK 32
 typedef struct gv_pca_stats {
     int iterations;              /* iterations run (each one pass of L columns through both batch products) */
@@ -1057,7 +1076,12 @@ int gv_king_info(gv_ctx* ctx, gv_king_stats* info);
  * NaN, infinite or < 1; collinear covariates; gv_screen_cov_dev before gv_screen_cov_set, or after its state was dropped (the message
  * names gv_screen_cov_set).
  * Work panels: gv_pca_dev's scratch, owned by the context, grown on demand.  The calls leave the context as they found it, by the rule
- * of gv_atxm_dev / gv_pca_dev.  Both return when their device work has finished (the seconds below are device events). */
+ * of gv_atxm_dev / gv_pca_dev.  Both return when their device work has finished (the seconds below are device events).
+ * A context joined to others (a marker-sharded job): neither call issues a collective.  The basis Q and the residual columns are
+ * N-space and computed by every rank for itself, in an order that depends on npad alone, so they are the same bits on every rank that
+ * was given the same covariates, columns and mask; v_j and the five outputs are quantities of one marker.  The outputs of the ranks,
+ * side by side in marker order, are the outputs of one context on all markers bit for bit.  Both calls succeed on a rank without
+ * markers. */
 typedef struct gv_screen_cov_stats {
     int K;                       /* covariates of the cached state; -1: none cached */
     int pad_;
