@@ -1,6 +1,7 @@
 // data.cpp -- see data.hpp.
 #include "data.hpp"
 
+#include <algorithm>
 #include <cassert>
 #include <chrono>
 #include <cmath>
@@ -27,6 +28,30 @@ namespace {
 void ck(gv_ctx* ctx, int rc, const char* what) {
     if (rc) die(std::string("FATAL: ") + what + ": " + gv_last_error(ctx));
 }
+// n device vectors of one space, freed with the object.  put(): a host column, cut or zero-padded to the vector's length (4 * mbytes
+// in N-space, M in M-space); get(): the vector's values
+struct dev_cols {
+    gv_ctx* ctx;
+    std::vector<gv_vec*> h;
+    dev_cols(gv_ctx* ctx, int space, size_t n) : ctx(ctx), h(n, nullptr) {
+        for (gv_vec*& v : h) ck(ctx, gv_vec_alloc(ctx, space, &v), "gv_vec_alloc");
+    }
+    ~dev_cols() {
+        for (gv_vec* v : h) gv_vec_free(ctx, v);
+    }
+    dev_cols(const dev_cols&) = delete;
+    dev_cols& operator=(const dev_cols&) = delete;
+    void put(size_t i, std::vector<double> col) {
+        col.resize((size_t)std::max<int64_t>(gv_vec_len(h[i]), 1), 0.0);
+        ck(ctx, gv_vec_upload(ctx, h[i], col.data()), "gv_vec_upload");
+    }
+    std::vector<double> get(size_t i) const {
+        std::vector<double> col((size_t)std::max<int64_t>(gv_vec_len(h[i]), 1), 0.0);
+        ck(ctx, gv_vec_download(ctx, h[i], col.data()), "gv_vec_download");
+        col.resize((size_t)std::max<int64_t>(gv_vec_len(h[i]), 0));
+        return col;
+    }
+};
 // whitespace split that keeps the reference's quirk: a leading blank yields an empty token 0 (std::regex
 // "\\s+" with sregex_token_iterator(-1), data.cpp:143-144)
 std::vector<std::string> split_ws(const std::string& line) {
@@ -383,44 +408,22 @@ double data::pca_start(unsigned long long seed, unsigned long long index) {
 
 data::pca_result data::pca(int k, int L, double tol, int max_iter, unsigned long long seed, bool loadings) {
     pca_result out;
-    const size_t n4 = 4 * (size_t)mbytes, Mp = M > 0 ? (size_t)M : 0;
-    std::vector<gv_vec*> q0, u, v;
-    auto drop = [&]() {
-        for (auto* vs : {&q0, &u, &v})
-            for (gv_vec* x : *vs) gv_vec_free(ctx, x);
-    };
-    auto vec = [&](int space, std::vector<gv_vec*>& to) {
-        gv_vec* x = nullptr;
-        ck(ctx, gv_vec_alloc(ctx, space, &x), "gv_vec_alloc");
-        to.push_back(x);
-        return x;
-    };
-    std::vector<double> buf(n4, 0.0);
+    dev_cols q0(ctx, GV_SPACE_N, (size_t)(L > 0 ? L : 0)), u(ctx, GV_SPACE_N, (size_t)(k > 0 ? k : 0));
+    std::vector<double> buf((size_t)N, 0.0);
     for (int j = 0; j < L; j++) {
         for (int n = 0; n < N; n++) buf[(size_t)n] = pca_start(seed, (unsigned long long)j * (unsigned long long)N + (unsigned long long)n);
-        ck(ctx, gv_vec_upload(ctx, vec(GV_SPACE_N, q0), buf.data()), "gv_vec_upload");
+        q0.put((size_t)j, buf);
     }
-    for (int i = 0; i < k; i++) vec(GV_SPACE_N, u);
     out.eval.assign((size_t)(k > 0 ? k : 1), 0.0);
     out.resid.assign((size_t)(k > 0 ? k : 1), 0.0);
-    if (gv_pca_dev(ctx, k, L, q0.data(), tol, max_iter, u.data(), out.eval.data(), out.resid.data())) {
-        std::cout << "FATAL: gv_pca_dev: " << gv_last_error(ctx) << std::endl;
-        drop();
-        exit(EXIT_FAILURE);
-    }
+    ck(ctx, gv_pca_dev(ctx, k, L, q0.h.data(), tol, max_iter, u.h.data(), out.eval.data(), out.resid.data()), "gv_pca_dev");
     gv_pca_info(ctx, &out.info);
-    out.evec.assign((size_t)k, std::vector<double>(n4, 0.0));
-    for (int i = 0; i < k; i++) ck(ctx, gv_vec_download(ctx, u[(size_t)i], out.evec[(size_t)i].data()), "gv_vec_download");
+    for (int i = 0; i < k; i++) out.evec.push_back(u.get((size_t)i));
     if (loadings) {
-        for (int i = 0; i < k; i++) vec(GV_SPACE_M, v);
-        ck(ctx, gv_pca_loadings_dev(ctx, k, u.data(), out.eval.data(), v.data()), "gv_pca_loadings_dev");
-        out.loadings.assign((size_t)k, std::vector<double>(Mp > 0 ? Mp : 1, 0.0));
-        for (int i = 0; i < k; i++) {
-            ck(ctx, gv_vec_download(ctx, v[(size_t)i], out.loadings[(size_t)i].data()), "gv_vec_download");
-            out.loadings[(size_t)i].resize(Mp);
-        }
+        dev_cols v(ctx, GV_SPACE_M, u.h.size());
+        ck(ctx, gv_pca_loadings_dev(ctx, k, u.h.data(), out.eval.data(), v.h.data()), "gv_pca_loadings_dev");
+        for (int i = 0; i < k; i++) out.loadings.push_back(v.get((size_t)i));
     }
-    drop();
     return out;
 }
 
@@ -480,7 +483,7 @@ std::vector<std::vector<std::vector<double>>> data::screen(const std::vector<std
         std::cout << "FATAL: data::screen: fewer than 3 individuals with a phenotype" << std::endl;
         exit(EXIT_FAILURE);
     }
-    std::vector<gv_vec*> u(C, nullptr), res(3 * C, nullptr);
+    dev_cols u(ctx, GV_SPACE_N, C), res(ctx, GV_SPACE_M, 3 * C);
     std::vector<double> buf(n4);
     for (size_t j = 0; j < C; j++) {
         if (cols[j].size() < (size_t)N) {
@@ -508,59 +511,46 @@ std::vector<std::vector<std::vector<double>>> data::screen(const std::vector<std
         std::fill(buf.begin(), buf.end(), 0.0);
         for (int n = 0; n < N; n++)
             if ((mask4[n / 4] >> (n % 4)) & 1) buf[n] = (cols[j][n] - avg) * sc;
-        ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &u[j]), "gv_vec_alloc");
-        ck(ctx, gv_vec_upload(ctx, u[j], buf.data()), "gv_vec_upload");
-        for (int k = 0; k < 3; k++) ck(ctx, gv_vec_alloc(ctx, GV_SPACE_M, &res[k * C + j]), "gv_vec_alloc");
+        u.put(j, buf);
     }
-    ck(ctx, gv_screen_dev(ctx, (int64_t)C, u.data(), res.data(), res.data() + C, res.data() + 2 * C), "gv_screen_dev");
+    gv_vec** r = res.h.data();
+    ck(ctx, gv_screen_dev(ctx, (int64_t)C, u.h.data(), r, r + C, r + 2 * C), "gv_screen_dev");
     for (int k = 0; k < 3; k++)
-        for (size_t j = 0; j < C && Mp > 0; j++) ck(ctx, gv_vec_download(ctx, res[k * C + j], out[k][j].data()), "gv_vec_download");
-    for (gv_vec* v : u) gv_vec_free(ctx, v);
-    for (gv_vec* v : res) gv_vec_free(ctx, v);
+        for (size_t j = 0; j < C && Mp > 0; j++) out[k][j] = res.get(k * C + j);
     return out;
 }
 
 void data::screen_cov_set() {
-    const size_t K = covs.empty() ? 0 : covs[0].size(), n4 = 4 * (size_t)mbytes;
+    const size_t K = covs.empty() ? 0 : covs[0].size();
     if (K > 0 && covs.size() < (size_t)N) {
         std::cout << "FATAL: data::screen_cov_set: " << covs.size() << " covariate rows, fewer than N = " << N << std::endl;
         exit(EXIT_FAILURE);
     }
-    std::vector<gv_vec*> cv(K, nullptr);
-    std::vector<double> buf(n4);
+    dev_cols cv(ctx, GV_SPACE_N, K);
+    std::vector<double> buf((size_t)N);
     for (size_t k = 0; k < K; k++) {
-        std::fill(buf.begin(), buf.end(), 0.0);
         for (int n = 0; n < N; n++) buf[n] = covs[n][k];
-        ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &cv[k]), "gv_vec_alloc");
-        ck(ctx, gv_vec_upload(ctx, cv[k], buf.data()), "gv_vec_upload");
+        cv.put(k, buf);
     }
-    ck(ctx, gv_screen_cov_set(ctx, (int)K, cv.data()), "gv_screen_cov_set");
-    for (gv_vec* v : cv) gv_vec_free(ctx, v);
+    ck(ctx, gv_screen_cov_set(ctx, (int)K, cv.h.data()), "gv_screen_cov_set");
 }
 
 std::vector<std::vector<std::vector<double>>> data::screen_cov(const std::vector<std::vector<double>>& cols, double vif_max) {
-    const size_t C = cols.size(), Mp = M > 0 ? (size_t)M : 0, n4 = 4 * (size_t)mbytes;
+    const size_t C = cols.size(), Mp = M > 0 ? (size_t)M : 0;
     std::vector<std::vector<std::vector<double>>> out(5, std::vector<std::vector<double>>(C, std::vector<double>(Mp, 0.0)));
     if (C == 0) return out;
-    std::vector<gv_vec*> y(C, nullptr), res(5 * C, nullptr);
-    std::vector<double> buf(n4);
+    dev_cols y(ctx, GV_SPACE_N, C), res(ctx, GV_SPACE_M, 5 * C);
     for (size_t j = 0; j < C; j++) {
         if (cols[j].size() < (size_t)N) {
             std::cout << "FATAL: data::screen_cov: column " << j << " has " << cols[j].size() << " entries, fewer than N = " << N << std::endl;
             exit(EXIT_FAILURE);
         }
-        std::fill(buf.begin(), buf.end(), 0.0);
-        std::copy(cols[j].begin(), cols[j].begin() + N, buf.begin());
-        ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &y[j]), "gv_vec_alloc");
-        ck(ctx, gv_vec_upload(ctx, y[j], buf.data()), "gv_vec_upload");
-        for (int k = 0; k < 5; k++) ck(ctx, gv_vec_alloc(ctx, GV_SPACE_M, &res[k * C + j]), "gv_vec_alloc");
+        y.put(j, std::vector<double>(cols[j].begin(), cols[j].begin() + N));
     }
-    ck(ctx, gv_screen_cov_dev(ctx, (int64_t)C, y.data(), vif_max, res.data(), res.data() + C, res.data() + 2 * C, res.data() + 3 * C,
-                              res.data() + 4 * C), "gv_screen_cov_dev");
+    gv_vec** r = res.h.data();
+    ck(ctx, gv_screen_cov_dev(ctx, (int64_t)C, y.h.data(), vif_max, r, r + C, r + 2 * C, r + 3 * C, r + 4 * C), "gv_screen_cov_dev");
     for (int k = 0; k < 5; k++)
-        for (size_t j = 0; j < C && Mp > 0; j++) ck(ctx, gv_vec_download(ctx, res[k * C + j], out[k][j].data()), "gv_vec_download");
-    for (gv_vec* v : y) gv_vec_free(ctx, v);
-    for (gv_vec* v : res) gv_vec_free(ctx, v);
+        for (size_t j = 0; j < C && Mp > 0; j++) out[k][j] = res.get(k * C + j);
     return out;
 }
 
@@ -735,37 +725,24 @@ std::vector<int64_t> data::ld_clump_dev(const std::vector<double>& pos, double r
     return index_of;
 }
 
-static std::vector<std::vector<double>> pvals_host(data* d, gv_ctx* ctx, int M, size_t mbytes,
-                                                   std::vector<std::vector<double>>& z1, std::vector<double>& y,
+static std::vector<std::vector<double>> pvals_host(data* d, gv_ctx* ctx, std::vector<std::vector<double>>& z1, std::vector<double>& y,
                                                    std::vector<std::vector<double>>& x1_hat, bool loco,
                                                    const std::vector<std::string>& prefixes = std::vector<std::string>()) {
     std::vector<std::vector<double>> out;
-    gv_vec *dz = nullptr, *dy = nullptr, *dx = nullptr;
-    ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &dz), "gv_vec_alloc");
-    ck(ctx, gv_vec_alloc(ctx, GV_SPACE_N, &dy), "gv_vec_alloc");
-    ck(ctx, gv_vec_alloc(ctx, GV_SPACE_M, &dx), "gv_vec_alloc");
-    std::vector<double> yp(y);
-    yp.resize(4 * mbytes, 0.0);
-    ck(ctx, gv_vec_upload(ctx, dy, yp.data()), "gv_vec_upload");
+    dev_cols zy(ctx, GV_SPACE_N, 2), dx(ctx, GV_SPACE_M, 1);      // z1 of the estimator at hand and y; its x1_hat
+    zy.put(1, y);
     for (size_t ie = 0; ie < z1.size(); ie++) {
-        std::vector<double> zp(z1[ie]);
-        zp.resize(4 * mbytes, 0.0);
-        ck(ctx, gv_vec_upload(ctx, dz, zp.data()), "gv_vec_upload");
-        std::vector<double> xp(x1_hat[ie]);
-        xp.resize(M > 0 ? M : 1, 0.0);
-        ck(ctx, gv_vec_upload(ctx, dx, xp.data()), "gv_vec_upload");
-        out.push_back(d->pvals_calc_dev(dz, dy, dx, loco, (loco && ie < prefixes.size()) ? prefixes[ie] : std::string()));
+        zy.put(0, z1[ie]);
+        dx.put(0, x1_hat[ie]);
+        out.push_back(d->pvals_calc_dev(zy.h[0], zy.h[1], dx.h[0], loco, (loco && ie < prefixes.size()) ? prefixes[ie] : std::string()));
     }
-    gv_vec_free(ctx, dz);
-    gv_vec_free(ctx, dy);
-    gv_vec_free(ctx, dx);
     return out;
 }
 
 std::vector<std::vector<double>> data::pvals_calc(std::vector<std::vector<double>> z1, std::vector<double> y,
                                                   std::vector<std::vector<double>> x1_hat,
                                                   std::vector<std::string> filepath) {
-    std::vector<std::vector<double>> pv = pvals_host(this, ctx, M, mbytes, z1, y, x1_hat, false);
+    std::vector<std::vector<double>> pv = pvals_host(this, ctx, z1, y, x1_hat, false);
     for (size_t ie = 0; ie < pv.size() && ie < filepath.size(); ie++) mpi_store_vec_to_file(filepath[ie], pv[ie], S, M);
     return pv;
 }
@@ -773,7 +750,7 @@ std::vector<std::vector<double>> data::pvals_calc(std::vector<std::vector<double
 std::vector<std::vector<double>> data::pvals_calc_LOCO(std::vector<std::vector<double>> z1, std::vector<double> y,
                                                        std::vector<std::vector<double>> x1_hat,
                                                        std::vector<std::string> filepath) {
-    std::vector<std::vector<double>> pv = pvals_host(this, ctx, M, mbytes, z1, y, x1_hat, true, filepath);
+    std::vector<std::vector<double>> pv = pvals_host(this, ctx, z1, y, x1_hat, true, filepath);
     for (size_t ie = 0; ie < pv.size() && ie < filepath.size(); ie++)
         mpi_store_vec_to_file(filepath[ie] + "_pvals_LOCO.bin", pv[ie], S, M);          // data.cpp:1347-1350
     return pv;

@@ -8,19 +8,12 @@
 #include <iostream>
 
 #include "data.hpp"
+#include "driver_common.hpp"
 #include "options.hpp"
 #include "utilities.hpp"
 #include "vamp.hpp"
 
 namespace {
-
-std::vector<double> load_estimate(const std::string& file, int M, int S) {
-    const size_t dot = file.find(".");
-    const std::string ext = dot == std::string::npos ? "" : file.substr(dot + 1);
-    std::vector<double> x = (ext == "bin") ? mpi_read_vec_from_file(file, M, S) : read_vec_from_file(file, M, S);
-    x.resize(M, 0.0);
-    return x;
-}
 
 // :112-160 / :170-219 / :262-312 -- z = A (x_est sqrt(N_test)) [+ Z cov_effect]; predicted label = [Phi(z) >= 0.5];
 // prints "P = .., N = .., TPR = .., FPR = .., " on rank 0.  Individuals with an NA phenotype (read_phen stores DBL_MAX)
@@ -46,13 +39,6 @@ void classify(data& ds_test, std::vector<double> x_est, int N_test, const std::v
         std::cout << "P = " << P << ", " << "N = " << Ne << ", TPR = " << (double)TP / P << ", FPR = " << (double)FP / Ne << ", ";
 }
 
-void need(const std::vector<std::string>& files, const char* flag) {
-    if (files.empty()) {
-        std::cout << "FATAL  : no phen file(s) provided! Please use the " << flag << " option." << std::endl;
-        exit(EXIT_FAILURE);
-    }
-}
-
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -69,18 +55,16 @@ int main(int argc, char** argv) {
 
     if (mode == "infere") {
         const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
-        std::vector<double> MS = divide_work(Mt);
-        const int M = (int)MS[0], S = (int)MS[1];
-        need(opt.get_phen_files(), "--phen-files");
+        const auto [M, S] = shard_of(Mt);
+        need_phen(opt.get_phen_files(), "--phen-files");
         data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, "bed", 1.0, "", dev, km);
         dataset.read_covariates(opt.get_cov_file(), C);
         vamp emvamp(M, 1e-8, 1, std::vector<double>(M, 0.0), rank, opt);
         emvamp.infere(&dataset);
     } else if (mode == "test") {
         const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
-        std::vector<double> MS = divide_work(Mt_test);
-        const int M_test = (int)MS[0], S_test = (int)MS[1];
-        need(opt.get_phen_files_test(), "--phen-files-test");
+        const auto [M_test, S_test] = shard_of(Mt_test);
+        need_phen(opt.get_phen_files_test(), "--phen-files-test");
         data dataset_test(opt.get_phen_files_test()[0], opt.get_bed_file_test(), N_test, M_test, Mt_test, S_test, rank, "bed",
                           1.0, "", dev, km);
         const std::vector<double> y_test = dataset_test.get_phen();
@@ -98,18 +82,16 @@ int main(int argc, char** argv) {
         if (rank == 0) std::cout << "iter range = [" << range[0] << ", " << range[1] << "]" << std::endl;
         if (range[0] != -1) {
             for (int it = range[0]; it <= range[1]; it++) {
-                const std::string f = est.substr(0, pos_it) + "it_" + std::to_string(it) + "." + ext;
-                classify(dataset_test, load_estimate(f, M_test, S_test), N_test, y_test, with_cov ? &zx : nullptr, rank);
+                classify(dataset_test, load_estimate(iteration_file(est, pos_it, ext, it), M_test, S_test), N_test, y_test, with_cov ? &zx : nullptr, rank);
             }
         } else
             classify(dataset_test, load_estimate(est, M_test, S_test), N_test, y_test, with_cov ? &zx : nullptr, rank);
         if (rank == 0) std::cout << std::endl;
     } else if (mode == "both") {
         const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
-        std::vector<double> MS = divide_work(Mt);
-        const int M = (int)MS[0], S = (int)MS[1];
-        need(opt.get_phen_files(), "--phen-files");
-        need(opt.get_phen_files_test(), "--phen-files-test");
+        const auto [M, S] = shard_of(Mt);
+        need_phen(opt.get_phen_files(), "--phen-files");
+        need_phen(opt.get_phen_files_test(), "--phen-files-test");
         std::vector<double> x_est, zx;
         {
             data dataset(opt.get_phen_files()[0], opt.get_bed_file(), N, M, Mt, S, rank, "bed", 1.0, "", dev, km);

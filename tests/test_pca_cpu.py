@@ -82,4 +82,4 @@ def test_declarations():
     for flag in ("--pca-k", "--pca-block", "--pca-tol", "--pca-max-iter", "--pca-seed", "--pca-allow-unconverged"):
         assert flag in opts, flag
     main = open(os.path.join(ROOT, "gvamp_amd", "csrc", "host", "main_real.cpp")).read()
-    assert 'mode == "pca"' in main and "_pca_eigenvec.txt" in main and "_pca_loadings.bin" in main
+    assert '{"pca", run_pca}' in main and "int run_pca(const Job& job)" in main and "_pca_eigenvec.txt" in main and "_pca_loadings.bin" in main
