@@ -1,12 +1,14 @@
 // gv_comm.hip -- the communicators of the C ABI (RCCL, the in-process rank group of the tests, the caller's host callback), the
-// forced one-rank loop-back of gv_debug_force_multi, and the all-reduces of device vectors and host scalars built on them.
-#include <condition_variable>
+// forced one-rank loop-back of gv_debug_force_multi, and the all-reduces of device vectors and host scalars built on them.  The
+// in-process rank group (LocalGroup) and the host half of its all-reduce live in gv_local_group.h, which needs no HIP and is run
+// under the address and thread sanitizers by tests/test_host_threads_cpu.py.
 #include <cstring>
 #include <map>
 #include <memory>
 #include <mutex>
 
 #include "gv_internal.h"
+#include "gv_local_group.h"
 
 namespace gvi {
 
@@ -27,28 +29,7 @@ int allreduce_scalars(gv_ctx* c, double* buf, int K) {
     return read_scalars(c, K, buf);
 }
 
-// ---- in-process communicator: nranks contexts of ONE process (threads) behave like nranks MPI ranks.  Sums in rank
-// order on the host (deterministic).  For tests of the sharded algorithm on a single GPU; production uses RCCL.
-namespace {
-struct LocalGroup {
-    int n = 0;
-    std::mutex mu;
-    std::condition_variable cv;
-    int arrived = 0;
-    long gen = 0;
-    std::vector<const double*> slots;
-    void barrier() {
-        std::unique_lock<std::mutex> lk(mu);
-        const long g = gen;
-        if (++arrived == n) {
-            arrived = 0;
-            gen++;
-            cv.notify_all();
-        } else
-            cv.wait(lk, [&] { return gen != g; });
-    }
-};
-}  // namespace
+// ---- in-process communicator (gv_local_group.h): the groups of gv_comm_init_local by their number
 static std::mutex g_groups_mu;
 static std::map<int, std::shared_ptr<LocalGroup>> g_groups;
 
@@ -101,15 +82,7 @@ int comm_allreduce_on(gv_ctx* c, double* dev, size_t n, hipStream_t stream) {
     c->local_buf.resize(n);
     HIPCHK(c, hipMemcpyAsync(c->local_buf.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
-    g->slots[c->rank] = c->local_buf.data();
-    g->barrier();
-    std::vector<double> sum(n, 0.0);
-    for (int r = 0; r < g->n; r++) {
-        const double* s = g->slots[r];
-        for (size_t i = 0; i < n; i++) sum[i] += s[i];
-    }
-    g->barrier();
-    c->local_buf.swap(sum);
+    local_group_allreduce(*g, c->rank, c->local_buf);
     HIPCHK(c, hipMemcpyAsync(dev, c->local_buf.data(), sizeof(double) * n, hipMemcpyHostToDevice, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
     return 0;

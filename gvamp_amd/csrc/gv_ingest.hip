@@ -1,6 +1,8 @@
 // gv_ingest.hip -- getting a dataset resident: PLINK .bed rows (host buffer, file, synthetic) re-encoded chunk by chunk into the
 // layouts of the streaming kernels, and the rows of the dense kinds -- fp64 values of methylation data, 8- / 16-bit codes of compact
-// dense data -- through one begin / copy / finish path (dense_begin, dense_finish).
+// dense data -- through one begin / copy / finish path (dense_begin, dense_finish).  The concurrent pread streams that fill a
+// staging slab (read_slab) live in gv_read_slab.h, which needs no HIP and is run under the address and thread sanitizers by
+// tests/test_host_threads_cpu.py.
 #include <cctype>
 #include <cerrno>
 #include <chrono>
@@ -15,6 +17,7 @@
 #include <unistd.h>
 
 #include "gv_internal.h"
+#include "gv_read_slab.h"
 
 using namespace gvi;
 
@@ -22,46 +25,6 @@ extern "C" {
 
 // Ingest: fills the resident layouts chunk by chunk (markers [m0, m0+mc), m0 % 256 == 0) so that the raw rows never
 // have to be resident as a whole when only the stripes are wanted (N=400k x M=1M: 100 GB raw + 2 x 100 GB stripes).
-// nbytes of the file at `off` into the pinned staging buffer, by GV_IO_THREADS (default 8) concurrent pread streams: one
-// thread copying out of the page cache moves ~9 GB/s, a fraction of what the PCIe link takes
-// returns 0 ok, -1 end of file before nbytes were read, else the errno of the failing pread (EINTR is retried)
-static int read_slab(int fd, int64_t off, uint8_t* dst, size_t nbytes) {
-    // 8 concurrent pread streams (measured at config-2 size out of the page cache: 4 -> 27, 8 -> 33-34, 12 -> 32-37 GB/s including
-    // the allocation of the layout), never more than the CPUs this process may use
-    int nt = 8;
-    {
-        cpu_set_t cs;
-        if (sched_getaffinity(0, sizeof(cs), &cs) == 0 && CPU_COUNT(&cs) < nt) nt = CPU_COUNT(&cs) < 1 ? 1 : CPU_COUNT(&cs);
-    }
-    if (const char* e = getenv("GV_IO_THREADS")) nt = atoi(e) < 1 ? 1 : (atoi(e) > 32 ? 32 : atoi(e));
-    if (nbytes < ((size_t)8 << 20)) nt = 1;
-    std::vector<int> st(nt, 0);
-    auto work = [&](int t) {
-        const size_t lo = nbytes * (size_t)t / (size_t)nt, hi = nbytes * (size_t)(t + 1) / (size_t)nt;
-        size_t done = lo;
-        while (done < hi) {
-            const ssize_t r = pread(fd, dst + done, hi - done, (off_t)(off + (int64_t)done));
-            if (r < 0 && errno == EINTR) continue;
-            if (r < 0) { st[t] = errno ? errno : EIO; return; }
-            if (r == 0) { st[t] = -1; return; }
-            done += (size_t)r;
-        }
-    };
-    std::vector<std::thread> th;
-    th.reserve((size_t)nt);
-    int started = 1;                            // ranges [1, started) have a thread; the rest are read by this one
-    try {
-        for (; started < nt; started++) th.emplace_back(work, started);
-    } catch (...) {
-    }
-    work(0);
-    for (int t = started; t < nt; t++) work(t);
-    for (std::thread& x : th) x.join();
-    for (int v : st) if (v > 0) return v;      // a real I/O error wins over a short file
-    for (int v : st) if (v) return v;
-    return 0;
-}
-
 static int ingest(gv_ctx* c, const uint8_t* host_bed, bool synth, uint64_t seed, uint32_t miss_thr, FILE* file = nullptr,
                   uint32_t ld_block = 0, uint32_t ld_thr = 0, int64_t file_off = 0) {
     NEED(c, c->N > 0, "ingest: gv_set_dims must be called first");
