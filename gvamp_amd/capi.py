@@ -38,6 +38,7 @@ EXPORTS = [
     "gv_atxm_dev", "gv_atxm", "gv_atxm_info", "gv_screen_dev",
     "gv_pca_dev", "gv_pca_loadings_dev", "gv_pca_info",
     "gv_king_block", "gv_king_pairs", "gv_king_info",
+    "gv_grm_weights", "gv_grm_block", "gv_grm_pairs", "gv_grm_info",
     "gv_screen_cov_set", "gv_screen_cov_dev", "gv_screen_cov_info",
 ]
 
@@ -88,6 +89,11 @@ PCA_MAX_BLOCK = 32
 class KingStats(C.Structure):          # gv_king_stats
     _fields_ = [("seconds", C.c_double), ("block_pairs", C.c_int64), ("used_markers", C.c_int64), ("pairs", C.c_int64),
                 ("useful_macs", C.c_double), ("scratch_bytes", C.c_double)]
+
+
+class GrmStats(C.Structure):           # gv_grm_stats
+    _fields_ = [("seconds", C.c_double), ("block_pairs", C.c_int64), ("counting_markers", C.c_int64), ("dropped_markers", C.c_int64),
+                ("pairs", C.c_int64), ("useful_macs", C.c_double), ("scratch_bytes", C.c_double)]
 
 
 class ScreenCovStats(C.Structure):     # gv_screen_cov_stats
@@ -249,6 +255,10 @@ def load():
     L.gv_king_block.argtypes = [vp, up, i64, i64, i64, i64, dp, i32p]
     L.gv_king_pairs.argtypes = [vp, up, C.c_double, i64, i32p, i32p, dp, i32p, C.POINTER(i64)]
     L.gv_king_info.argtypes = [vp, C.POINTER(KingStats)]
+    L.gv_grm_weights.argtypes = [vp, up, dp, dp, C.POINTER(i64)]
+    L.gv_grm_block.argtypes = [vp, up, i64, i64, i64, i64, dp, i32p]
+    L.gv_grm_pairs.argtypes = [vp, up, C.c_double, i64, i32p, i32p, dp, i32p, dp, i32p, C.POINTER(i64)]
+    L.gv_grm_info.argtypes = [vp, C.POINTER(GrmStats)]
     L.gv_ld_scores_pos.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, dp]
     L.gv_ld_last_passes.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_ld_clump.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), dp, C.c_double, C.c_double, C.c_double, C.POINTER(i64), C.POINTER(i64)]
@@ -943,6 +953,61 @@ class Shard:
         self._ck(self.L.gv_king_info(self.h, C.byref(st)))
         return dict(seconds=st.seconds, block_pairs=st.block_pairs, used_markers=st.used_markers, pairs=st.pairs,
                     useful_macs=st.useful_macs, scratch_bytes=st.scratch_bytes)
+
+    # ---- standardised genetic relationship matrix (gv_grm_*) -------------------------
+    def grm_weights(self, use=None):
+        """gv_grm_weights: (mu[M], rs[M], n_used) of the pre-pass; a marker that does not count has mu = rs = 0"""
+        mu, rs = np.zeros(max(self.M, 1)), np.zeros(max(self.M, 1))
+        n = C.c_int64(-1)
+        u, upt = self._use(use)
+        self._ck(self.L.gv_grm_weights(self.h, upt, _dp(mu), _dp(rs), C.byref(n)))
+        return mu[:self.M], rs[:self.M], n.value
+
+    def grm_block(self, i0, ni, j0, nj, use=None):
+        """gv_grm_block: (a[ni, nj] float64, m_common[ni, nj] int32) of the individuals [i0, i0 + ni) x [j0, j0 + nj); use: M bytes,
+        non-zero = the marker is selected (None: every marker)"""
+        ni_, nj_ = int(ni), int(nj)
+        a = np.zeros((max(ni_, 0), max(nj_, 0)))
+        mc = np.zeros((max(ni_, 0), max(nj_, 0)), dtype=np.int32)
+        u, upt = self._use(use)
+        self._ck(self.L.gv_grm_block(self.h, upt, int(i0), ni_, int(j0), nj_, _dp(a) if a.size else None,
+                                     mc.ctypes.data_as(C.POINTER(C.c_int32)) if mc.size else None))
+        return a, mc
+
+    def grm_pairs_raw(self, cutoff, cap, use=None, diag=True):
+        """gv_grm_pairs with the caller's cap: (n_found, i, j, a, m_common, diag, diag_m); the pair arrays hold the pairs only when
+        n_found <= cap; diag and diag_m are None without diag"""
+        cap_ = int(cap)
+        n = max(cap_, 1)
+        pi, pj = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        a, mc = np.zeros(n), np.zeros(n, dtype=np.int32)
+        d, dm = (np.zeros(self.N), np.zeros(self.N, dtype=np.int32)) if diag else (None, None)
+        found = C.c_int64(-1)
+        u, upt = self._use(use)
+        i32p = C.POINTER(C.c_int32)
+        self._ck(self.L.gv_grm_pairs(self.h, upt, float(cutoff), cap_, pi.ctypes.data_as(i32p), pj.ctypes.data_as(i32p), _dp(a),
+                                     mc.ctypes.data_as(i32p), _dp(d) if diag else None, dm.ctypes.data_as(i32p) if diag else None,
+                                     C.byref(found)))
+        return found.value, pi, pj, a, mc, d, dm
+
+    def grm_pairs(self, cutoff, use=None, cap=None, diag=True):
+        """every pair i < j with A_ij >= cutoff in ascending (i, j): (i, j, a, m_common, diag, diag_m).  cap: the first call's slots
+        (default 65536); one more call with the number found when they did not suffice"""
+        cap_ = 65536 if cap is None else int(cap)
+        found, pi, pj, a, mc, d, dm = self.grm_pairs_raw(cutoff, cap_, use, diag)
+        if found > cap_:
+            cap_ = found
+            found, pi, pj, a, mc, d, dm = self.grm_pairs_raw(cutoff, cap_, use, diag)
+            if found > cap_:
+                raise GvError("grm_pairs: %d pairs found with room for %d on the second call" % (found, cap_))
+        return pi[:found].copy(), pj[:found].copy(), a[:found].copy(), mc[:found].copy(), d, dm
+
+    def grm_info(self):
+        """gv_grm_info of the last grm_weights / grm_block / grm_pairs call as a dict"""
+        st = GrmStats()
+        self._ck(self.L.gv_grm_info(self.h, C.byref(st)))
+        return dict(seconds=st.seconds, block_pairs=st.block_pairs, counting_markers=st.counting_markers,
+                    dropped_markers=st.dropped_markers, pairs=st.pairs, useful_macs=st.useful_macs, scratch_bytes=st.scratch_bytes)
 
     def pca_info(self):
         """gv_pca_info of the last pca_dev / pca as a dict"""

@@ -242,6 +242,7 @@ struct gv_ctx {
     DevScratch pca_scratch;
     gv_pca_stats pca_last{};
     gv_king_stats king_last{};      // gv_king_info: the last gv_king_block / gv_king_pairs call (gv_king.hip)
+    gv_grm_stats grm_last{};        // gv_grm_info: the last gv_grm_weights / gv_grm_block / gv_grm_pairs call (gv_grm.hip, section 28)
     // gv_screen_cov_set / gv_screen_cov_dev (gv_screen_cov.hip): the cached state of the covariate side -- the
     // orthonormal basis Q (cov_K columns of npad doubles) and behind it v (M doubles), in an allocation of its own (the work panels of
     // both calls are pca_scratch's).  It belongs to the data set, mask and marker statistics it was computed from: have_cov is cleared

@@ -463,6 +463,46 @@ data::king_result data::king_block(int64_t i0, int64_t ni, int64_t j0, int64_t n
     return out;
 }
 
+data::grm_result data::grm_pairs(double cutoff, const std::vector<unsigned char>& use) {
+    if (!use.empty() && use.size() != (size_t)(M > 0 ? M : 0)) die("FATAL: data::grm_pairs: the marker selection must hold M bytes");
+    grm_result out;
+    out.diag.assign((size_t)(N > 0 ? N : 1), 0.0);
+    out.diag_m.assign((size_t)(N > 0 ? N : 1), 0);
+    int64_t cap = 65536, found = 0;
+    for (int round = 0; round < 2; round++) {
+        out.i.assign((size_t)cap, 0);
+        out.j.assign((size_t)cap, 0);
+        out.a.assign((size_t)cap, 0.0);
+        out.m_common.assign((size_t)cap, 0);
+        ck(ctx, gv_grm_pairs(ctx, use.empty() ? nullptr : use.data(), cutoff, cap, out.i.data(), out.j.data(), out.a.data(), out.m_common.data(),
+                             out.diag.data(), out.diag_m.data(), &found), "gv_grm_pairs");
+        if (found <= cap) break;
+        if (round == 1) die("FATAL: data::grm_pairs: more pairs on the second call than the first one counted");
+        cap = found;
+    }
+    out.i.resize((size_t)found);
+    out.j.resize((size_t)found);
+    out.a.resize((size_t)found);
+    out.m_common.resize((size_t)found);
+    out.diag.resize((size_t)(N > 0 ? N : 0));
+    out.diag_m.resize((size_t)(N > 0 ? N : 0));
+    gv_grm_info(ctx, &out.info);
+    return out;
+}
+
+data::grm_result data::grm_block(int64_t i0, int64_t ni, int64_t j0, int64_t nj, const std::vector<unsigned char>& use) {
+    if (!use.empty() && use.size() != (size_t)(M > 0 ? M : 0)) die("FATAL: data::grm_block: the marker selection must hold M bytes");
+    grm_result out;
+    const size_t ne = ni > 0 && nj > 0 ? (size_t)ni * (size_t)nj : 0;
+    out.a.assign(ne ? ne : 1, 0.0);
+    out.m_common.assign(ne ? ne : 1, 0);
+    ck(ctx, gv_grm_block(ctx, use.empty() ? nullptr : use.data(), i0, ni, j0, nj, out.a.data(), out.m_common.data()), "gv_grm_block");
+    out.a.resize(ne);
+    out.m_common.resize(ne);
+    gv_grm_info(ctx, &out.info);
+    return out;
+}
+
 void data::set_mask(const std::vector<unsigned char>& m4, int nonas_) {
     if (m4.size() != mbytes) {
         std::cout << "FATAL: data::set_mask: " << m4.size() << " mask bytes, not mbytes = " << mbytes << std::endl;

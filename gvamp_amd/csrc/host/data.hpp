@@ -109,6 +109,19 @@ public:
     };
     king_result king_pairs(double cutoff, const std::vector<unsigned char>& use = std::vector<unsigned char>());
     king_result king_block(int64_t i0, int64_t ni, int64_t j0, int64_t nj, const std::vector<unsigned char>& use = std::vector<unsigned char>());
+    // [ext] the standardised genetic relationship matrix of the resident genotypes (gv_grm_pairs / gv_grm_block).
+    // use as above.  grm_pairs: every pair i < j with A_ij >= cutoff in ascending (i, j) and the N diagonal entries, re-called once with
+    // the number found when the first call's slots did not suffice; grm_block: the rectangle [i0, i0 + ni) x [j0, j0 + nj), row-major
+    struct grm_result {
+        std::vector<int32_t> i, j;          // grm_pairs only
+        std::vector<double> a;
+        std::vector<int32_t> m_common;
+        std::vector<double> diag;           // grm_pairs only: A_ii
+        std::vector<int32_t> diag_m;        // grm_pairs only: M_ii
+        gv_grm_stats info;
+    };
+    grm_result grm_pairs(double cutoff, const std::vector<unsigned char>& use = std::vector<unsigned char>());
+    grm_result grm_block(int64_t i0, int64_t ni, int64_t j0, int64_t nj, const std::vector<unsigned char>& use = std::vector<unsigned char>());
     // [ext] replace the mask (bit n & 3 of byte n >> 2 set: individual n has a phenotype) and recompute the marker statistics
     void set_mask(const std::vector<unsigned char>& m4, int nonas_);
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled

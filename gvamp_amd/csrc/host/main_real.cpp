@@ -2,7 +2,7 @@
 // the run mode up in MODES; every mode is one function run_<mode>(const Job&) that returns the process's exit status:
 //   infere / restart (:34-128, :369-385), test (:129-213), both (:214-283), pvals-calc (:284-368), predict / predict_single (:386-594);
 //   [ext] ldscore (gv_ld_scores), clump (gv_ld_clump, section 20), score (section 21), screen (section 23 and,
-//   with --cov-file, 26), pca (gv_pca_dev, section 24), king (gv_king_pairs, section 25).
+//   with --cov-file, 26), pca (gv_pca_dev, section 24), king (gv_king_pairs, section 25), grm (gv_grm_pairs / gv_grm_block, section 28).
 // A new mode is one such function and one entry of MODES.  What the modes share sits above them: Job (the options every mode reads
 // and the two ways to build a `data` from them), require_bed / require_one_rank, read_f64_file and Window (an LD window by kb, cM or
 // marker count); driver_common.hpp holds what main_real_probit.cpp needs too.  Every mode is "load data, maybe run vamp::infere, one
@@ -672,6 +672,81 @@ int run_king(const Job& job) {                                                  
     return 0;
 }
 
+// <out>.grm.sp: GCTA's sparse text -- the N diagonal entries by row, then the pairs at or above the cutoff in ascending (i, j)
+int grm_sparse(const Job& job, data& dataset, const std::vector<unsigned char>& use, int N, int Mt) {
+    const data::grm_result res = dataset.grm_pairs(job.opt.get_grm_cutoff(), use);
+    const std::string path = job.out() + ".grm.sp";
+    FILE* f = fopen(path.c_str(), "w");
+    bool ok = f != nullptr;
+    for (int n = 0; n < N && ok; n++) ok = fprintf(f, "%d %d %.17g\n", n, n, res.diag[(size_t)n]) > 0;
+    for (size_t t = 0; t < res.i.size() && ok; t++) ok = fprintf(f, "%d %d %.17g\n", res.i[t], res.j[t], res.a[t]) > 0;
+    if (f) ok = fclose(f) == 0 && ok;
+    if (!ok) return refuse(std::cout << "FATAL: cannot write " << path);
+    std::cout << "grm: " << N << " individuals x " << res.info.counting_markers << " counting of " << Mt << " markers ("
+              << res.info.dropped_markers << " dropped as monomorphic or never present), cutoff " << job.opt.get_grm_cutoff() << ": "
+              << res.i.size() << " pairs, " << res.info.seconds << " seconds -> " << path << std::endl;
+    return 0;
+}
+
+// <out>.grm.bin / <out>.grm.N.bin: GCTA's dense format -- the lower triangle with the diagonal, row by row, as float32; streamed in row
+// panels [r0, r0 + P) x [0, r0 + P), so that N^2 doubles never sit on the host
+int grm_dense(const Job& job, data& dataset, const std::vector<unsigned char>& use, int N, int Mt) {
+    const std::string pa = job.out() + ".grm.bin", pn = job.out() + ".grm.N.bin";
+    FILE *fa = nullptr, *fn = nullptr;              // (opened after the first panel: a refused call leaves no file behind)
+    bool ok = true;
+    const int64_t P = std::max<int64_t>(64, std::min<int64_t>(N, ((int64_t)1 << 25) / N / 64 * 64));      // at most 2^25 entries a panel
+    double seconds = 0.0;
+    gv_grm_stats info{};
+    std::vector<float> row;
+    for (int64_t r0 = 0; r0 < N && ok; r0 += P) {
+        const int64_t nr = std::min<int64_t>(P, N - r0), nc = r0 + nr;
+        const data::grm_result res = dataset.grm_block(r0, nr, 0, nc, use);
+        info = res.info;
+        seconds += res.info.seconds;
+        if (r0 == 0) {
+            fa = fopen(pa.c_str(), "wb");
+            fn = fopen(pn.c_str(), "wb");
+            ok = fa && fn;
+        }
+        for (int64_t r = 0; r < nr && ok; r++) {
+            const size_t len = (size_t)(r0 + r + 1);
+            row.resize(len);
+            for (size_t k = 0; k < len; k++) row[k] = (float)res.a[(size_t)r * (size_t)nc + k];
+            ok = fwrite(row.data(), sizeof(float), len, fa) == len;
+            for (size_t k = 0; k < len; k++) row[k] = (float)res.m_common[(size_t)r * (size_t)nc + k];
+            ok = ok && fwrite(row.data(), sizeof(float), len, fn) == len;
+        }
+    }
+    if (fa) ok = fclose(fa) == 0 && ok;
+    if (fn) ok = fclose(fn) == 0 && ok;
+    if (!ok) return refuse(std::cout << "FATAL: cannot write " << pa << " / " << pn);
+    std::cout << "grm: " << N << " individuals x " << info.counting_markers << " counting of " << Mt << " markers (" << info.dropped_markers
+              << " dropped as monomorphic or never present), dense: " << (int64_t)N * (N + 1) / 2 << " pairs, " << seconds << " seconds -> "
+              << pa << ", " << pn << std::endl;
+    return 0;
+}
+
+int run_grm(const Job& job) {                                                          // [ext] DESIGN.md section 28
+    // the standardised genetic relationship matrix, from the genotypes alone: no phenotype file
+    const Options& opt = job.opt;
+    if (!require_bed(job)) return EXIT_FAILURE;
+    if (!require_one_rank(job, "S and the common-marker count of a pair are sums over the markers of all ranks, and the all-reduce that "
+                               "would add them is not built"))
+        return EXIT_FAILURE;
+    const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
+    std::vector<unsigned char> use;
+    if (opt.get_grm_marker_file() != "") {
+        std::ifstream in(opt.get_grm_marker_file(), std::ios::binary);
+        use.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+        if (!in.is_open() || use.size() != (size_t)Mt)
+            return refuse(std::cout << "FATAL: --grm-marker-file " << opt.get_grm_marker_file() << " must hold Mt = " << Mt << " bytes of 0 / 1 ("
+                                    << (in.is_open() ? std::to_string(use.size()) + " bytes read" : std::string("cannot open it")) << ")");
+    }
+    setenv("GVAMP_RESIDENT_LAYOUT", "2", 0);      // the kernel reads the tile layout (a --resident-layout given on the command line stands)
+    data dataset = job.load(std::vector<double>(N, 0.0), opt.get_bed_file(), N, Mt, Mt, 0);      // (bed data: the dosage arguments are unused)
+    return opt.get_grm_has_cutoff() ? grm_sparse(job, dataset, use, N, Mt) : grm_dense(job, dataset, use, N, Mt);
+}
+
 int run_predict(const Job& job) {                                                      // predict and predict_single (:386-594)
     const Options& opt = job.opt;
     const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
@@ -719,7 +794,7 @@ const struct {
     int (*run)(const Job&);
 } MODES[] = {{"infere", run_infere}, {"restart", run_infere}, {"test", run_test}, {"both", run_both}, {"pvals-calc", run_pvals_calc},
              {"predict", run_predict}, {"predict_single", run_predict}, {"ldscore", run_ldscore}, {"clump", run_clump},
-             {"score", run_score}, {"screen", run_screen}, {"pca", run_pca}, {"king", run_king}};
+             {"score", run_score}, {"screen", run_screen}, {"pca", run_pca}, {"king", run_king}, {"grm", run_grm}};
 
 }  // namespace
 

@@ -212,6 +212,14 @@ void Options::read_command_line_options(int argc, char** argv) {
     num("--pca-tol", pca_tol);
     num("--king-cutoff", king_cutoff);
     str("--king-marker-file", king_marker_file);
+    H["--grm-cutoff"] = [&](const char* a) {              // (given at all: the sparse file; NaN and +inf are the library's to refuse)
+        char* end = nullptr;
+        const double v = strtod(a, &end);
+        if (end == a || *end != 0) fatal(std::string("FATAL  : option --grm-cutoff has to be a number! (") + a + " was passed)");
+        grm_cutoff = v;
+        grm_has_cutoff = 1;
+    };
+    str("--grm-marker-file", grm_marker_file);
     H["--score-units"] = [&](const char* a) {
         if (strcmp(a, "std") && strcmp(a, "allele"))
             fatal(std::string("FATAL  : option --score-units has to be std or allele! (") + a + " was passed)");

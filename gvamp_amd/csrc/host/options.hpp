@@ -88,7 +88,13 @@
        --run-mode king (gv_king_pairs) with --king-cutoff x (default 0.0884, second degree):        \
        every pair of individuals whose KING-robust kinship is at least x, from the bed file alone (no phenotype file),    \
        over the markers of --king-marker-file F (Mt bytes of 0 / 1; default: every marker): <out>_king.kin0.txt, one     \
-       line "i j nsnp hethet ibs0 het_i het_j kinship" per pair in ascending (i, j) */                                   \
+       line "i j nsnp hethet ibs0 het_i het_j kinship" per pair in ascending (i, j);                                     \
+       --run-mode grm (gv_grm_pairs / gv_grm_block): the standardised genetic relationship matrix  \
+       A = Z Z^T / M_ij of GCTA from the bed file alone, over the markers of --grm-marker-file F (Mt bytes of 0 / 1;     \
+       default: every marker).  With --grm-cutoff x: <out>.grm.sp, GCTA's sparse text, "i j value" with 0-based          \
+       indices, the N diagonal entries first and then every pair with A_ij >= x in ascending (i, j).  Without it:        \
+       <out>.grm.bin (the lower triangle with the diagonal, row by row, float32) and <out>.grm.N.bin (the common-marker  \
+       counts in the same order, float32), GCTA's dense format */                                                        \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \
@@ -103,7 +109,8 @@
     X(double, screen_vif, 50.0)                                                                                      \
     X(unsigned int, pca_k, 0) X(unsigned int, pca_block, 0) X(double, pca_tol, 1e-8) X(unsigned int, pca_max_iter, 100)          \
     X(unsigned int, pca_seed, 0) X(unsigned int, pca_allow_unconverged, 0)                                           \
-    X(double, king_cutoff, 0.0884) X(std::string, king_marker_file, "")
+    X(double, king_cutoff, 0.0884) X(std::string, king_marker_file, "")                                              \
+    X(double, grm_cutoff, 0.0) X(int, grm_has_cutoff, 0) X(std::string, grm_marker_file, "")
 
 class Options {
 public:

@@ -1031,6 +1031,51 @@ int gv_king_pairs(gv_ctx* ctx, const uint8_t* use /* M or NULL */, double cutoff
                   int32_t* counts /* cap (x 5) each */, int64_t* n_found);
 int gv_king_info(gv_ctx* ctx, gv_king_stats* info);
 
+/* ---- standardised genetic relationship matrix (GRM) of the resident genotypes (additions only: GV_ABI_VERSION stays 4; DESIGN.md
+ * section 28) ------------------------------------------------------------------------------------------------------------------------
+ * Data: bed data resident in the TILE LAYOUT (gv_get_layout() == 2; kernel mode 1 or 2), one rank, as gv_king_*.  The phenotype mask and
+ * the marker statistics are NOT consulted and need not exist; frequencies are taken over all N individuals of the shard.
+ * For individual i and marker m, a in {0, 1, 2} is the allele count the re-encoding stores (r' = a; r' = 3: missing); `use` is one byte
+ * per marker of the shard (non-zero = selected; NULL = every marker).  Per marker, in exact integers:
+ *   n_m = number of individuals present        s_m = sum of a over them
+ * Marker m COUNTS iff use[m] && n_m > 0 && 0 < s_m < 2 n_m (selected, somebody present, not monomorphic).  Its weights, in exactly these
+ * fp64 operations, each correctly rounded:
+ *   mu = (double)s / (double)n        h = mu * (1.0 - 0.5 * mu)        rs = 1.0 / sqrt(h)
+ * A marker that does not count has mu = rs = 0.  The entries:
+ *   z_im = ((double)a - mu) * rs      where individual i is present at a counting marker m, else 0
+ * The common-marker count M_ij is the number of counting markers at which both i and j are present: an exact integer, int32.
+ *   S_ij = sum_m z_im z_jm            in fp64, over the markers of the shard in ascending order of K-step (4 markers), one accumulator;
+ *                                     the order is a function of (M, use) alone
+ *   A_ij = S_ij / (double)M_ij        one correctly rounded division; A_ij = NaN when M_ij = 0 (a NaN never passes a cutoff)
+ * This is GCTA's estimator (Yang et al. 2011): the denominator is per pair, not a global M.  A[i][j] and A[j][i] are the same bits, the
+ * diagonal gets the same formula, two calls give the same bytes, and the bits of an entry do not depend on the rectangle or the list it
+ * was asked through.  Pad markers and pad individuals contribute nothing.  M <= 2^31 - 1, as gv_king_*.
+ * gv_grm_weights: the pre-pass alone: mu and rs of every marker of the shard (either may be NULL) and *n_used, the markers that count.
+ * gv_grm_block: the dense rectangle of individuals [i0, i0 + ni) x [j0, j0 + nj), row-major.  Either output may be NULL.
+ * gv_grm_pairs: every pair i < j < N with A_ij >= cutoff (-inf: every pair whose value is a number), by the protocol of gv_king_pairs:
+ *   *n_found is always set; pi, pj, a and m_common are written only when *n_found <= cap, and then in ascending (i, j) order; with
+ *   *n_found > cap the return code is still 0 and the caller calls again with a larger cap.  diag (A_ii) and diag_m (M_ii), N values each,
+ *   are written by every successful call that passes them: a sparse GRM needs its diagonal, and N x N never exists.
+ * Scratch is taken for the call and freed after it.
+ * Refused with a message, no output written: dosage or methylation data; raw rows only; two stripe sets resident (upload under the tile
+ * layout, gv_set_layout(ctx, .., 2)); a job of more than one rank (S and M_ij are sums over ALL ranks' markers; the all-reduce is not
+ * built); NULL n_found, NULL arrays with cap > 0; a rectangle outside [0, N); cap < 0; a cutoff that is NaN or +inf. */
+typedef struct gv_grm_stats {
+    double seconds;              /* wall time of the last gv_grm_weights / gv_grm_block / gv_grm_pairs call */
+    int64_t block_pairs;         /* pairs of 64-individual groups it computed */
+    int64_t counting_markers;    /* markers of the shard that counted */
+    int64_t dropped_markers;     /* selected markers that did not: monomorphic or never present */
+    int64_t pairs;               /* pairs delivered: ni * nj of a rectangle, the N (N - 1) / 2 pairs gv_grm_pairs decided, 0 of the weights */
+    double useful_macs;          /* counting_markers x pairs */
+    double scratch_bytes;        /* device scratch it allocated and released */
+} gv_grm_stats;
+int gv_grm_weights(gv_ctx* ctx, const uint8_t* use /* M or NULL */, double* mu /* M or NULL */, double* rs /* M or NULL */, int64_t* n_used);
+int gv_grm_block(gv_ctx* ctx, const uint8_t* use /* M or NULL */, int64_t i0, int64_t ni, int64_t j0, int64_t nj,
+                 double* a /* ni * nj or NULL */, int32_t* m_common /* ni * nj or NULL */);
+int gv_grm_pairs(gv_ctx* ctx, const uint8_t* use /* M or NULL */, double cutoff, int64_t cap, int32_t* pi, int32_t* pj, double* a,
+                 int32_t* m_common /* cap each */, double* diag /* N or NULL */, int32_t* diag_m /* N or NULL */, int64_t* n_found);
+int gv_grm_info(gv_ctx* ctx, gv_grm_stats* info);
+
 /* ---- covariate-adjusted association screen: partial regression on the batch product (additions only: GV_ABI_VERSION stays 4; DESIGN.md
  * section 26) ------------------------------------------------------------------------------------------------------------------------
  * The regression of a phenotype y on [1, covariates, g_j] for every marker j, by the Frisch-Waugh-Lovell theorem: with Q an
