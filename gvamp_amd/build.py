@@ -8,7 +8,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgvamp.so")
 SOURCES = ["gv_kernels.hip", "gv_mfma.hip", "gv_capi.hip", "gv_comm.hip", "gv_xfer.hip", "gv_tune.hip", "gv_matvec.hip",
-           "gv_ingest.hip", "gv_stats.hip", "gv_solvers.hip", "gv_dense.hip", "gv_dense_mfma.hip", "gv_precond.hip", "gv_ld.hip",
+           "gv_ingest.hip", "gv_stats.hip", "gv_solvers.hip", "gv_dense.hip", "gv_dense_mfma.hip", "gv_dense_atxm.hip", "gv_precond.hip", "gv_ld.hip",
            "gv_score.hip", "gv_atxm.hip", "gv_pca.hip", "gv_king.hip", "gv_screen_cov.hip", "gv_grm.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I/opt/rocm/include"]

@@ -40,6 +40,7 @@ EXPORTS = [
     "gv_king_block", "gv_king_pairs", "gv_king_info",
     "gv_grm_weights", "gv_grm_block", "gv_grm_pairs", "gv_grm_info",
     "gv_screen_cov_set", "gv_screen_cov_dev", "gv_screen_cov_info",
+    "gv_set_screen_dosage", "gv_get_screen_dosage",
 ]
 
 
@@ -279,6 +280,8 @@ def load():
     L.gv_screen_cov_info.argtypes = [vp, C.POINTER(ScreenCovStats)]
     L.gv_set_ld_dosage.argtypes = [vp, C.c_int]
     L.gv_get_ld_dosage.argtypes = [vp, C.POINTER(C.c_int)]
+    L.gv_set_screen_dosage.argtypes = [vp, C.c_int]
+    L.gv_get_screen_dosage.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_people_stats.argtypes = [vp, dp, dp, dp]
     L.gv_cg_solve_aat.argtypes = [vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, C.POINTER(CgStats), dp]
     L.gv_cg_solve_aat2.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp, C.POINTER(CgStats),
@@ -778,6 +781,16 @@ class Shard:
         """gv_screen_dev: prepared phenotype columns us (N-space) -> r, t, p per marker (M-space; ts and ps may be None)"""
         n = len(us) if us is not None else len(rs)
         self._ck(self.L.gv_screen_dev(self.h, n, self._handles(us), self._handles(rs), self._handles(ts), self._handles(ps)))
+
+    def set_screen_dosage(self, on):
+        """gv_set_screen_dosage: 1 = screen / screen_dev / screen_cov_set / screen_cov_dev / screen_cov accept resident dosage codes
+        (8 or 16 bits, with or without missing entries, either route).  Default 0; it outlives the dataset"""
+        self._ck(self.L.gv_set_screen_dosage(self.h, int(on)))
+
+    def get_screen_dosage(self):
+        on = C.c_int(0)
+        self._ck(self.L.gv_get_screen_dosage(self.h, C.byref(on)))
+        return on.value
 
     def screen_prepare(self, Y):
         """the prepared columns u of gv_screen_dev from raw phenotype columns Y of shape (C, N), NaN for NA: zero at the individuals the

@@ -3,7 +3,8 @@
 //
 // Column j of the result is bit-identical to gv_atx_dev of that column alone.  Where the kernel below does not apply -- two stripe
 // sets, kernel modes 0 and 2, methylation and dosage data, an empty shard, fewer columns than min_cols -- the existing dispatcher
-// (gvi::atx_pass) runs, in pairs and singly: identical by construction.  (ATx issues no collective, so a communicator or
+// (gvi::atx_pass) runs, in pairs and singly: identical by construction.  8-bit dosage codes on the fixed-point route have a kernel of
+// their own (gv_dense_atxm.hip; atxm_dense_kernel below), with the same contract.  (ATx issues no collective, so a communicator or
 // gv_debug_force_multi does not disqualify the kernel.)  The kernel is identical because every sum is an exact integer and the
 // floating-point steps around it are the functions gv_mfma.hip runs (gv_mfma.h: prep_block_partials, prep_scalars, digits_of,
 // combine).  What this file writes itself, in the form of k_prep_atx (without its CG hook) and k_fin_atx (without addx):
@@ -35,6 +36,7 @@
 
 #include "gv_internal.h"
 #include "gv_atxm_plan.h"
+#include "gv_dense_atxm_plan.h"
 #include "gv_pval_dev.h"
 
 namespace {
@@ -254,14 +256,21 @@ __global__ __launch_bounds__(256) void k_atxm_fin(const int32_t* __restrict__ pa
 
 // ---- the screen's element-wise epilogue of column blockIdx.y (gvamp.h: the rounding sequence of r and t)
 struct ScreenCols { double* r[gvx::CP_MAX]; double* t[gvx::CP_MAX]; double* p[gvx::CP_MAX]; };
+// qss != NULL (dosage codes, gv_set_screen_dosage): the marker's q = sum ((b - mu') na)^2 of the statistics pass, exact zero for a
+// constant or all-missing marker, takes the place of the genotype counts
 __global__ __launch_bounds__(256) void k_screen_fin(ScreenCols a, int64_t M, const uint32_t* __restrict__ cnt, const double* __restrict__ mave,
-                                                    const double* __restrict__ msig, double rfac, double nu) {
+                                                    const double* __restrict__ msig, const double* __restrict__ qss, double rfac, double nu) {
     const int v = blockIdx.y;
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
-    // no variance among the phenotyped present genotypes: sumsqx of gvp::marker_stats, in its expression
-    const double n2 = cnt[3 * m], n1 = cnt[3 * m + 1], n0 = cnt[3 * m + 2], mu = mave[m], sg = msig[m];
-    const double sumsqx = sg * sg * (n2 * (2.0 - mu) * (2.0 - mu) + n1 * (1.0 - mu) * (1.0 - mu) + n0 * mu * mu);
+    double sumsqx;
+    if (qss) {
+        sumsqx = qss[m];
+    } else {
+        // no variance among the phenotyped present genotypes: sumsqx of gvp::marker_stats, in its expression
+        const double n2 = cnt[3 * m], n1 = cnt[3 * m + 1], n0 = cnt[3 * m + 2], mu = mave[m], sg = msig[m];
+        sumsqx = sg * sg * (n2 * (2.0 - mu) * (2.0 - mu) + n1 * (1.0 - mu) * (1.0 - mu) + n0 * mu * mu);
+    }
     double r, t, p;
     if (sumsqx == 0.0) {
         r = t = p = NAN;
@@ -347,13 +356,53 @@ static int atxm_kernel(gv_ctx* c, int64_t C, const double* const* p, double* con
     return 0;
 }
 
+// 8-bit dosage codes while the fixed-point route is in force (the plain kernels: no reserved code in the shard), a shard with markers
+static bool atxm_dense_kernel_applies(const gv_ctx* c) { return dosage_mfma_route(c) && c->M > 0; }
+
+static int atxm_dense_kernel(gv_ctx* c, int64_t C, const double* const* p, double* const* out, gv_atxm_stats& st) {
+    const int cp0 = c->atxm_cols ? c->atxm_cols : GV_ATXM_DENSE_COLS_DEFAULT;
+    const gvdx::Plan pl = gvdx::make_plan(c->N, c->M, C, cp0, c->dosage_seg, c->dense.cus);
+    if (pl.err) return fail(c, "gv_atxm_dev: no plan for N = %lld, M = %lld, C = %lld", (long long)c->N, (long long)c->M, (long long)C);
+    const gvdm::Shape sh = gvdm::atx_shape(c->N, c->M, c->dense.cus, c->dosage_seg);
+    if (sh.segs != pl.cut.segs || sh.seg_steps != pl.cut.seg_steps || sh.steps != pl.cut.steps || sh.blocks != pl.blocks)
+        return fail(c, "gv_atxm_dev: the plan cuts %d segments of %lld steps, the one-vector product %d of %lld", pl.cut.segs,
+                    (long long)pl.cut.seg_steps, sh.segs, (long long)sh.seg_steps);
+    if (!c->atxm_scratch.reserve(pl.scratch_bytes))
+        return fail(c, "gv_atxm_dev: cannot allocate %zu bytes of scratch (digits %zu, partial sums %zu)", pl.scratch_bytes, pl.dig_bytes,
+                    pl.part_bytes);
+    char* buf = static_cast<char*>(c->atxm_scratch.buf);
+    int32_t* part = reinterpret_cast<int32_t*>(buf + pl.dig_bytes);
+    char* small = buf + pl.dig_bytes + pl.part_bytes;
+    const gvd::View v = dense_view(c);
+    const double scale = 1.0 / sqrt((double)c->N);
+    for (int64_t ps = 0; ps < pl.passes; ps++) {
+        const int ncols = (int)gvdx::pass_cols(ps, C, pl.cp);
+        const int cp = ps == pl.passes - 1 ? pl.cp_last : pl.cp;
+        HIPCHK(c, gvdm::atxm_pass(c->stream, v, sh, cp, c->atxm_dense_tiles, ncols, p + ps * pl.cp, out + ps * pl.cp, scale, buf, pl.pair_dig_bytes, part, small,
+                                  pl.pair_small_bytes));
+        KCHK(c);
+    }
+    c->cnt.n_atx += C;
+    c->cnt.n_atx_pass += pl.passes;
+    st.path = GV_ATXM_PATH_KERNEL;
+    st.cols_per_pass = pl.cp;
+    st.passes = pl.passes;
+    st.ksegs = sh.segs;
+    st.scratch_bytes = pl.scratch_bytes;
+    return 0;
+}
+
 int atxm_device(gv_ctx* c, int64_t C, const double* const* p, double* const* out) {
     const auto t0 = std::chrono::steady_clock::now();
     gv_atxm_stats st{};
     st.columns = C;
-    st.min_cols = c->atxm_min_cols;
+    const bool dense_kernel = atxm_dense_kernel_applies(c) && C >= c->atxm_dense_min_cols;
+    st.min_cols = atxm_dense_kernel_applies(c) ? c->atxm_dense_min_cols : c->atxm_min_cols;
     const bool kernel = atxm_kernel_applies(c) && C >= c->atxm_min_cols;
-    if (kernel) {
+    if (dense_kernel) {
+        NEED(c, c->have_stats, "ATx: bed and marker statistics must be set first");
+        if (atxm_dense_kernel(c, C, p, out, st)) return 1;
+    } else if (kernel) {
         NEED(c, c->have_stats, "ATx: bed and marker statistics must be set first");
         if (atxm_kernel(c, C, p, out, st)) return 1;
     } else {
@@ -399,7 +448,19 @@ int gv_atxm(gv_ctx* c, int64_t C, const double* Y, double* out) {
 int gv_atxm_info(const gv_ctx* c, gv_atxm_stats* out) {
     if (!c || !out) return 1;
     *out = c->atxm_last;
-    out->min_cols = c->atxm_min_cols;
+    out->min_cols = atxm_dense_kernel_applies(c) ? c->atxm_dense_min_cols : c->atxm_min_cols;
+    return 0;
+}
+
+int gv_set_screen_dosage(gv_ctx* c, int on) {
+    NEED(c, on == 0 || on == 1, "gv_set_screen_dosage: on must be 0 or 1");
+    c->screen_dosage = on;
+    return 0;
+}
+
+int gv_get_screen_dosage(const gv_ctx* c, int* on) {
+    if (!c) return 1;
+    if (on) *on = c->screen_dosage;
     return 0;
 }
 
@@ -407,8 +468,10 @@ int gv_screen_dev(gv_ctx* c, int64_t C, const gv_vec* const* u, gv_vec* const* r
     NEED(c, C >= 0, "gv_screen_dev: the number of columns is negative");
     if (C == 0) return 0;
     NEED(c, u && r, "gv_screen_dev: the arrays of column handles are NULL");
-    NEED(c, !c->dense.resident, "gv_screen_dev: no screen is defined for methylation or dosage data (2-bit genotypes only)");
-    NEED(c, c->have_stats && c->mask2 && c->counts, "ATx: bed and marker statistics must be set first");
+    const bool dosage = screen_dosage(c);      // gv_set_screen_dosage is on and dosage codes are resident
+    NEED(c, dosage || !c->dense.resident, "gv_screen_dev: no screen is defined for methylation or dosage data (2-bit genotypes only)");
+    NEED(c, c->have_stats && c->mask2 && (dosage ? c->dense.qss != nullptr : c->counts != nullptr),
+         "ATx: bed and marker statistics must be set first");
     NEED(c, c->alpha_scale == 1.0, "gv_screen_dev: the marker statistics must be those of alpha_scale = 1 (r is a correlation)");
     NEED(c, c->nonas >= 3, "gv_screen_dev: fewer than 3 individuals with a phenotype leave the test no degree of freedom");
     std::vector<const double*> us;
@@ -438,7 +501,8 @@ int gv_screen_dev(gv_ctx* c, int64_t C, const gv_vec* const* u, gv_vec* const* r
             sc.t[j] = t ? t[j0 + j]->d : nullptr;
             sc.p[j] = p ? p[j0 + j]->d : nullptr;
         }
-        hipLaunchKernelGGL(k_screen_fin, dim3(nblk(c->M, 256), nc), dim3(256), 0, c->stream, sc, c->M, c->counts, c->mave, c->msig, rfac, nu);
+        hipLaunchKernelGGL(k_screen_fin, dim3(nblk(c->M, 256), nc), dim3(256), 0, c->stream, sc, c->M, c->counts, c->mave, c->msig,
+                           dosage ? c->dense.qss : nullptr, rfac, nu);
     }
     KCHK(c);
     return 0;

@@ -229,7 +229,7 @@ void dense_release(gv_ctx* c, bool keep_alloc) {
     d.resident = d.na = false;
     d.reserved = 0;
     if (keep_alloc) return;
-    for (void** q : {&d.rows, (void**)&d.mu, (void**)&d.cnt, (void**)&d.rcount, (void**)&d.rpart, (void**)&d.part})
+    for (void** q : {&d.rows, (void**)&d.mu, (void**)&d.cnt, (void**)&d.qss, (void**)&d.rcount, (void**)&d.rpart, (void**)&d.part})
         if (*q) { (void)hipFree(*q); *q = nullptr; }
     gvdm::release(d.fx);
     d.bits = 0;
@@ -429,6 +429,17 @@ int gv_create(int device, gv_ctx** out) {
         !batch_knobs("GV_ATXM", "gv_atxm_dev", {4, 8}, "4 or 8", c->atxm_cols, c->atxm_ks, c->atxm_min_cols)) {
         gv_destroy_locked(c);
         return 1;
+    }
+    if (getenv("GV_ATXM_KERNEL")) c->atxm_dense_min_cols = c->atxm_min_cols;      // (1 / never, as on the bed path)
+    // GV_ATXM_TILES=4|8 (development, read per context): the tiles of 16 marker rows a wave of the batch ATx kernel of 8-bit dosage codes
+    // owns.  It changes no bit.
+    if (const char* tl = getenv("GV_ATXM_TILES")) {
+        if (strcmp(tl, "4") != 0 && strcmp(tl, "8") != 0) {
+            g_create_err = "gv_create: GV_ATXM_TILES=" + std::string(tl) + ": the tiles per wave of the dosage batch kernel are 4 or 8";
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->atxm_dense_tiles = atoi(tl);
     }
     if (const char* ov = getenv("GV_OVERLAP")) c->overlap_tiles = atoi(ov) > 64 ? 64 : (atoi(ov) < 0 ? 0 : atoi(ov));
     *out = c;

@@ -350,7 +350,7 @@ template <typename T, bool NA>
 __global__ __launch_bounds__(256) void k_dosage_stats(const T* __restrict__ A, int64_t M, int64_t N, int64_t pitch,
                                                       const uint32_t* __restrict__ mask2, double nonas, double alpha_scale,
                                                       double wscale, double* __restrict__ dmu, double* __restrict__ mave,
-                                                      double* __restrict__ msig, double* __restrict__ dcnt) {
+                                                      double* __restrict__ msig, double* __restrict__ dcnt, double* __restrict__ dq) {
     typedef typename Code<T>::Quad Quad;
     const int lane = threadIdx.x & (WAVE - 1);
     const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -393,6 +393,7 @@ __global__ __launch_bounds__(256) void k_dosage_stats(const T* __restrict__ A, i
     if (lane == 0) {
         dmu[m] = mu;
         if (NA) dcnt[m] = (double)cnt;
+        dq[m] = q;
         mave[m] = wscale * mu;
         double sg = 1.0;      // a constant column: q == 0 exactly in code units, whatever the scale
         if (q != 0.0) {
@@ -808,7 +809,7 @@ void stats(hipStream_t s, const View& v, const uint32_t* mask2, double nonas, do
     with_codes(v.bits, v.na, [&](auto kind) {
         typedef typename decltype(kind)::type T;
         hipLaunchKernelGGL((k_dosage_stats<T, decltype(kind)::na>), dim3(nblk(M, 4)), dim3(256), 0, s, (const T*)v.rows, M, N, pitch, mask2,
-                           nonas, alpha_scale, v.wscale, v.centre, mave, v.msig, v.cnt);
+                           nonas, alpha_scale, v.wscale, v.centre, mave, v.msig, v.cnt, v.qss);
     });
 }
 

@@ -30,8 +30,12 @@
 // The int32 invariant: see gvdm::SEG_MAX (gv_internal.h) and seg_steps() below, the one place that cuts K-segments.  Every sum is an
 // integer: the results depend on no segment length, no order and no grid (bit-reproducible); there are no atomics.
 #include "gv_internal.h"
+#include "gv_dense_atxm_plan.h"
+#include "gv_dense_fx.h"
 
 namespace {
+
+using gvdm::limb_total; using gvdm::limbs_to_double; using gvdm::gather; using gvdm::atx_value;
 
 constexpr int WAVE = 64;
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -137,41 +141,6 @@ __global__ __launch_bounds__(256) void k_dm_quant(Operand o, int64_t n, int64_t 
             (shl[threadIdx.x][0] + shl[threadIdx.x][1]) + (shl[threadIdx.x][2] + shl[threadIdx.x][3]);
 }
 
-// the pass's one integer sum_k q_k = hi 2^32 + lo from the block limb sums (every block of an epilogue for itself; integers: any order)
-__device__ inline void limb_total(const long long* __restrict__ limb, int nb, long long& hi, long long& lo) {
-    __shared__ long long sh[2][256];
-    long long h = 0, l = 0;
-    for (int b = threadIdx.x; b < nb; b += 256) { h += limb[2 * b]; l += limb[2 * b + 1]; }
-    sh[0][threadIdx.x] = h;
-    sh[1][threadIdx.x] = l;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) { sh[0][threadIdx.x] += sh[0][threadIdx.x + off]; sh[1][threadIdx.x] += sh[1][threadIdx.x + off]; }
-        __syncthreads();
-    }
-    hi = sh[0][0];
-    lo = sh[1][0];
-}
-// hi 2^32 + lo with 0 <= lo < 2^32 after the carry: (double)hi 2^32 and (double)lo are exact (|hi| < 2^53), their sum rounds once
-__device__ inline double limbs_to_double(long long hi, long long lo) {
-    hi += lo >> 32;
-    lo &= 0xFFFFFFFFLL;
-    return fma((double)hi, 4294967296.0, (double)lo);
-}
-// the seven digit planes of one row and slot over the K-segments: value = hi 2^32 + lo (exact, as combine() of gv_mfma.hip)
-__device__ inline void gather(const int32_t* __restrict__ part, int segs, int64_t rows_p, int64_t row, int slot, long long& hi,
-                              long long& lo) {
-    long long s[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < segs; k++) {
-        const int4* q = reinterpret_cast<const int4*>(part + ((int64_t)k * rows_p + row) * 16 + 8 * slot);
-        const int4 x0 = q[0], x1 = q[1];
-        s[0] += x0.x; s[1] += x0.y; s[2] += x0.z; s[3] += x0.w;
-        s[4] += x1.x; s[5] += x1.y; s[6] += x1.z;
-    }
-    lo = s[0] + (s[1] << 8) + (s[2] << 16) + (s[3] << 24);
-    hi = s[4] + (s[5] << 8) + (s[6] << 16);
-}
-
 // ---- ATx streaming kernel.  partial[(seg rows_p + row) 16 + column] (int32), rows_p = 128 row blocks.
 constexpr int ATX_T = 8;      // tiles of 16 rows per wave
 __global__ __launch_bounds__(256) void k_dm_atx(const uint8_t* __restrict__ A, int64_t M, int64_t pitch, int64_t steps, int64_t seg_steps,
@@ -237,9 +206,8 @@ __global__ __launch_bounds__(256) void k_dm_fin_atx(const int32_t* __restrict__ 
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
     long long sh, sl;
-    gather(part, segs, rows_p, m, v, sh, sl);
-    const double core = fma(-(dmu[m] - 128.0), limbs_to_double(qh, ql), limbs_to_double(sh, sl));
-    const double res = (msig[m] * wscale) * (core * scal[v]) * scale;
+    gather(part, segs, rows_p, m, 16, 8 * v, sh, sl);
+    const double res = atx_value(dmu[m], msig[m], wscale, scale, scal[v], qh, ql, sh, sl);
     a.out[v][m] = a.addx[v] ? fma(tau, res, gam2 * a.addx[v][m]) : res;
 }
 
@@ -324,7 +292,7 @@ __global__ __launch_bounds__(256) void k_dm_fin_ax(const int32_t* __restrict__ p
     double val = 0.0;
     if (n < N) {
         long long th, tl;
-        gather(part, segs, rows_p, n, v, th, tl);
+        gather(part, segs, rows_p, n, 16, 8 * v, th, tl);
         val = limbs_to_double(th - 128 * eh, tl - 128 * el) * scal[v] * post;
     }
     (v == 0 ? outa : outb)[n] = val;
@@ -338,22 +306,12 @@ inline int64_t round128(int64_t k) { return (k + 127) / 128 * 128; }
 // K-steps of the kernel, at least one.  `want` segments are asked for to fill the device; the bound may only raise their number.
 static_assert(gvdm::SEG_MAX * 128 * 128 <= 2147483647LL, "an int32 column sum over SEG_MAX K-entries must fit");
 gvdm::Shape cut(int64_t K, int kstep, int64_t blocks, int64_t cap, int cus) {
+    const gvdx::Cut ct = gvdx::cut_segments(K, kstep, blocks, cap, cus, gvdm::SEG_MAX);      // (gv_dense_atxm_plan.h: the arithmetic)
     gvdm::Shape sh;
     sh.blocks = blocks;
-    sh.steps = (K + kstep - 1) / kstep;
-    if (cap > gvdm::SEG_MAX) cap = gvdm::SEG_MAX;
-    int64_t cap_steps = cap / kstep;
-    if (cap_steps < 1) cap_steps = 1;
-    // about 16 waves per CU in all, a segment at least 8 steps long
-    int64_t want = ((int64_t)16 * (cus > 0 ? cus : 256) + blocks - 1) / (blocks > 0 ? blocks : 1);
-    if (want > sh.steps / 8) want = sh.steps / 8;
-    if (want < 1) want = 1;
-    int64_t len = (sh.steps + want - 1) / want;
-    if (len > cap_steps) len = cap_steps;
-    if (len < 1) len = 1;
-    sh.seg_steps = len;
-    sh.segs = (int)((sh.steps + len - 1) / len);
-    if (sh.segs < 1) sh.segs = 1;
+    sh.steps = ct.steps;
+    sh.seg_steps = ct.seg_steps;
+    sh.segs = ct.segs;
     return sh;
 }
 
@@ -372,6 +330,14 @@ int quant_blocks(int64_t n) {
 }  // namespace
 
 namespace gvdm {
+
+static_assert(gvdx::SEG_MAX == SEG_MAX && gvdx::ATX_KSTEP == ATX_KSTEP && gvdx::QUANT_BLOCKS == BLOCKS, "the plan header's constants");
+
+void quantise_atx(hipStream_t s, const double* pa, const double* pb, int64_t n, const Scratch& w) {
+    const Operand o = {{pa, pb}, nullptr, nullptr, 1.0, 0};
+    quantise(s, o, pb ? 2 : 1, n, w);
+}
+int quant_blocks_of(int64_t n) { return quant_blocks(n); }
 
 Shape atx_shape(int64_t N, int64_t M, int cus, int64_t cap) { return cut(N, ATX_KSTEP, (M + 127) / 128, cap, cus); }
 Shape ax_shape(int64_t N, int64_t M, int cus, int64_t cap) { return cut(M, AX_KSTEP, (gvd::row_pitch(N) + 127) / 128, cap, cus); }

@@ -301,6 +301,7 @@ static int dense_begin(gv_ctx* c, int bits, double scale, DenseClock* clk) {
         hipError_t e = hipMalloc(&d.rows, d.bytes((int64_t)rows));
         if (e == hipSuccess && bits) e = hipMalloc(&d.mu, sizeof(double) * rows);
         if (e == hipSuccess && bits) e = hipMalloc(&d.cnt, sizeof(double) * rows);
+        if (e == hipSuccess && bits) e = hipMalloc(&d.qss, sizeof(double) * rows);
         if (e != hipSuccess) {
             dense_release(c);
             return fail(c, "dense upload: no room for %lld x %lld %s in HBM: %s", (long long)c->M, (long long)d.pitch,

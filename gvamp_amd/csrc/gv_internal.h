@@ -59,6 +59,9 @@ struct DenseData {
     double scale = 1.0;             // codes only: the factor between codes and values
     double* mu = nullptr;           // codes only: M mean codes mu' (mave = scale * mu'): the products work in code units
     double* cnt = nullptr;          // codes only: M per-marker counts sum b na of the last gv_marker_stats (missing-aware kernels only)
+    // codes only: M per-marker q = sum_present ((b - mu') na)^2 of the last gv_marker_stats, in code units -- the variance input of the
+    // screens on dosage data (gv_set_screen_dosage: q == 0 is the marker without variance, sxx = scale^2 q)
+    double* qss = nullptr;
     // missing entries: na = the codes were uploaded with gv_set_dosage_missing on; reserved = the reserved codes counted at that ingest
     // (device word rcount, block partials rpart)
     bool na = false;
@@ -99,6 +102,8 @@ struct DevScratch {
 constexpr int GV_SCORE_MIN_COLS_DEFAULT = 4;
 // gv_atxm_dev: the same for its kernel (measured: DESIGN.md section 23)
 constexpr int GV_ATXM_MIN_COLS_DEFAULT = 4;
+// ... and for its kernel on 8-bit dosage codes under the fixed-point route
+constexpr int GV_ATXM_DENSE_MIN_COLS_DEFAULT = 3;
 
 struct gv_ctx {
     int device = 0;
@@ -237,6 +242,13 @@ struct gv_ctx {
     int atxm_cols = 0, atxm_ks = 0;
     int atxm_min_cols = GV_ATXM_MIN_COLS_DEFAULT;
     gv_atxm_stats atxm_last{};
+    // ... on 8-bit dosage codes under the fixed-point route (gv_dense_atxm.hip): a threshold of its own, which
+    // GV_ATXM_KERNEL=1 / 0 sets as it sets atxm_min_cols; GV_ATXM_COLS picks the columns per pass of either kernel
+    int atxm_dense_min_cols = GV_ATXM_DENSE_MIN_COLS_DEFAULT;
+    int atxm_dense_tiles = 0;       // GV_ATXM_TILES=4|8 (development, per context): tiles of 16 rows per wave; 0 = the library's pick
+    // gv_set_screen_dosage: gv_screen_dev / gv_screen_cov_set / gv_screen_cov_dev accept resident dosage codes; it
+    // outlives the dataset.  Read by every call: nothing is derived from it
+    int screen_dosage = 0;
     // gv_pca_dev (gv_pca.hip): the work panels and small buffers (grown on demand, freed with the dataset) and what
     // gv_pca_info reports
     DevScratch pca_scratch;
@@ -407,6 +419,7 @@ struct View {
     double* msig;
     double wscale;                  // the factor between codes and values; 1 for fp64
     double* cnt;                    // codes: M per-marker counts sum b na, written by stats and read by assoc when na is set
+    double* qss;                    // codes: M per-marker q = sum ((b - mu') na)^2, written by stats (DenseData::qss)
 };
 // the device-generated matrix of the rows [S, S + M); miss_thr: codes with na set only (gv_synth_dosage_na)
 void synth(hipStream_t s, const View& v, int64_t S, uint64_t seed, uint64_t miss_thr = 0);
@@ -446,6 +459,16 @@ void atx(hipStream_t s, int nv, const gvd::View& v, const Scratch& w, const Shap
          double* outa, double* outb, const double* addxa, const double* addxb, double tau, double gam2, hipEvent_t ev0, hipEvent_t ev1);
 void ax(hipStream_t s, int nv, const gvd::View& v, const Scratch& w, const Shape& sh, const double* xa, const double* xb, int64_t npad,
         double post, double* outa, double* outb, hipEvent_t ev0, hipEvent_t ev1);
+// the quantisation of an ATx pass of one (pb == NULL) or two vectors of n entries into w.dig, with w.pmax / w.limb / w.scal
+void quantise_atx(hipStream_t s, const double* pa, const double* pb, int64_t n, const Scratch& w);
+int quant_blocks_of(int64_t n);       // the blocks whose limb sums that quantisation leaves
+// gv_dense_atxm.hip: one pass of the batch product over ncols <= cp columns (cp = 4 or 8: the instantiation), out[j] = gvdm::atx of
+// p[j] alone bit for bit.  sh = atx_shape(..); the buffers are the caller's (gv_dense_atxm_plan.h: cp / 2 pairs of pair_dig_bytes of
+// digits and of pair_small_bytes of maxima, limb sums and scalars; sh.segs * sh.blocks * 128 * cp * 8 int32 partials); tiles: 4 or 8
+// tiles of 16 rows per wave, 0 = atxm_tiles(cp)
+hipError_t atxm_pass(hipStream_t s, const gvd::View& v, const Shape& sh, int cp, int tiles, int ncols, const double* const* p, double* const* out,
+                     double scale, char* dig, size_t pair_dig_bytes, int32_t* part, char* small, size_t pair_small_bytes);
+int atxm_tiles(int cp);               // the library's pick of the tiles per wave for that instantiation
 }  // namespace gvdm
 
 // ---- LD-block preconditioner (gv_precond.hip; the window Grams are an epilogue of the LD block kernel, gv_ld.hip) --------------
@@ -523,6 +546,8 @@ void pc_invalidate(gv_ctx* c, bool free_mem);
 int planes_check(gv_ctx* c, const char* who, const char* why);
 // gv_set_ld_dosage is on and compact dosage data are resident: the section-17 / 18 kernels answer (8-bit codes) or refuse (16-bit codes)
 inline bool ld_dosage(const gv_ctx* c) { return c->ld_dosage && c->dense.resident && c->dense.bits != 0; }
+// gv_set_screen_dosage is on and compact dosage data are resident: the screens accept the context (methylation data stay refused)
+inline bool screen_dosage(const gv_ctx* c) { return c->screen_dosage && c->dense.resident && c->dense.bits != 0; }
 // ... and what the Gram build needs of them: 8-bit codes, the mask, marker statistics, N within the 128-bit epilogue
 int gram_dosage_check(gv_ctx* c, const char* who);
 // compact dense data: the missing-aware kernels run when the codes were uploaded with gv_set_dosage_missing on AND the ingest counted a
@@ -536,7 +561,7 @@ inline bool dosage_mfma_route(const gv_ctx* c) {
 // the resident dense matrix as the gvd:: launchers take it
 inline gvd::View dense_view(const gv_ctx* c) {
     const DenseData& d = c->dense;
-    return {d.rows, d.bits, dosage_na_kernels(c), c->M, c->N, d.pitch, d.bits ? d.mu : c->mave, c->msig, d.bits ? d.scale : 1.0, d.cnt};
+    return {d.rows, d.bits, dosage_na_kernels(c), c->M, c->N, d.pitch, d.bits ? d.mu : c->mave, c->msig, d.bits ? d.scale : 1.0, d.cnt, d.qss};
 }
 // Frees the dense matrix with everything that belongs to it and resets its state: whatever kind comes next starts without a missing
 // code and with no reserved code counted.  keep_alloc: the allocations stay for an upload of the same width (shape is the context's).

@@ -131,14 +131,24 @@ __global__ __launch_bounds__(256) void k_cov_v(Panel Z, int K, double c, int64_t
 }
 
 __global__ __launch_bounds__(256) void k_screen_cov_fin(FinCols a, int64_t M, const uint32_t* __restrict__ cnt, const double* __restrict__ mave,
-                                                         const double* __restrict__ msig, const double* __restrict__ v,
-                                                         const double* __restrict__ ss, double afac, double nu, double nm1, double vif_max) {
+                                                         const double* __restrict__ msig, const double* __restrict__ qss, double wscale2,
+                                                         const double* __restrict__ v, const double* __restrict__ ss, double afac, double nu,
+                                                         double nm1, double vif_max) {
     const int c = blockIdx.y;
     const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (m >= M) return;
-    // no variance among the phenotyped present genotypes: sumsqx of gvp::marker_stats, in its expression (k_screen_fin's rule)
-    const double n2 = cnt[3 * m], n1 = cnt[3 * m + 1], n0 = cnt[3 * m + 2], mu = mave[m], sg = msig[m];
-    const double sumsqx = sg * sg * (n2 * (2.0 - mu) * (2.0 - mu) + n1 * (1.0 - mu) * (1.0 - mu) + n0 * mu * mu);
+    // the variance input.  Bed data: sumsqx of gvp::marker_stats, in its expression (k_screen_fin's rule), sxx = (n - 1) / msig^2.
+    // Dosage codes (qss != NULL, gv_set_screen_dosage): q of the statistics pass, sxx = scale^2 q
+    const double sg = msig[m];
+    double sumsqx, sxx;
+    if (qss) {
+        sumsqx = qss[m];
+        sxx = wscale2 * sumsqx;
+    } else {
+        const double n2 = cnt[3 * m], n1 = cnt[3 * m + 1], n0 = cnt[3 * m + 2], mu = mave[m];
+        sumsqx = sg * sg * (n2 * (2.0 - mu) * (2.0 - mu) + n1 * (1.0 - mu) * (1.0 - mu) + n0 * mu * mu);
+        sxx = nm1 / (sg * sg);
+    }
     const double vj = v[m], S = ss[c];
     double r, t, p, beta, se;
     r = t = p = beta = se = NAN;
@@ -146,7 +156,7 @@ __global__ __launch_bounds__(256) void k_screen_cov_fin(FinCols a, int64_t M, co
         const double rho = (a.r[c][m] * afac) / sqrt(vj);
         if (!isnan(rho)) {
             const double om = fma(-rho, rho, 1.0);
-            const double d = (nm1 / (sg * sg)) * vj;
+            const double d = sxx * vj;
             r = rho;
             beta = rho * sqrt(S / d);
             if (om <= 0.0) {
@@ -233,9 +243,11 @@ double elapsed_s(hipEvent_t a, hipEvent_t b) {
 
 // what both entry points need of the context: the state gv_screen_dev asks for, under the caller's name
 int need_screen_state(gv_ctx* c, const char* who) {
-    if (c->dense.resident) return fail(c, "%s: no screen is defined for methylation or dosage data (2-bit genotypes only)", who);
+    const bool dosage = screen_dosage(c);      // gv_set_screen_dosage is on and dosage codes are resident
+    if (c->dense.resident && !dosage) return fail(c, "%s: no screen is defined for methylation or dosage data (2-bit genotypes only)", who);
     NEED(c, c->N > 0, "gv_set_dims must be called first");
-    NEED(c, c->have_stats && c->mask2 && c->counts, "ATx: bed and marker statistics must be set first");
+    NEED(c, c->have_stats && c->mask2 && (dosage ? c->dense.qss != nullptr : c->counts != nullptr),
+         "ATx: bed and marker statistics must be set first");
     if (c->alpha_scale != 1.0) return fail(c, "%s: the marker statistics must be those of alpha_scale = 1 (r is a correlation)", who);
     if (c->nonas < 3) return fail(c, "%s: fewer than 3 individuals with a phenotype leave the test no degree of freedom", who);
     return 0;
@@ -404,8 +416,8 @@ int gv_screen_cov_dev(gv_ctx* c, int64_t C, const gv_vec* const* y, double vif_m
         if (atxm_device(c, nc, Y.p, fc.r)) return 1;
         HIPCHK(c, hipEventRecord(ev.e[2], s));
         if (M > 0)
-            hipLaunchKernelGGL(k_screen_cov_fin, dim3(nblk(M, 256), nc), dim3(256), 0, s, fc, M, c->counts, c->mave, c->msig, cv, w.ss, afac, nu,
-                               nm1, vif_max);
+            hipLaunchKernelGGL(k_screen_cov_fin, dim3(nblk(M, 256), nc), dim3(256), 0, s, fc, M, c->counts, c->mave, c->msig,
+                               screen_dosage(c) ? c->dense.qss : nullptr, c->dense.scale * c->dense.scale, cv, w.ss, afac, nu, nm1, vif_max);
         KCHK(c);
         HIPCHK(c, hipEventRecord(ev.e[3], s));
         HIPCHK(c, hipEventSynchronize(ev.e[3]));         // (the four events are the next block's)

@@ -571,7 +571,9 @@ bool read_covariate_cases(const Screen& s, int K) {
 int run_screen(const Job& job) {                                                       // [ext] DESIGN.md section 23
     // every phenotype file against every marker: <out>_screen_{r,t,p}.bin = C columns of Mt float64
     const Options& opt = job.opt;
-    if (!require_bed(job)) return EXIT_FAILURE;
+    // [ext] --screen-dosage 1: dosage codes pass; without it the refusal stands
+    const bool dosage = opt.get_screen_dosage() == 1 && (job.type_data == "dosage8" || job.type_data == "dosage16");
+    if (!dosage && !require_bed(job)) return EXIT_FAILURE;
     const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
     const Shard sh = shard_of(Mt);
     need_phen(opt.get_phen_files(), "--phen-files");
@@ -582,6 +584,8 @@ int run_screen(const Job& job) {                                                
     if (!read_phenotypes(opt.get_phen_files(), N, ph)) return EXIT_FAILURE;
     if (ph.nonas < 3) return refuse(std::cout << "FATAL: --run-mode screen: " << ph.nonas << " complete cases leave the test no degree of freedom");
     data dataset = job.load(std::vector<double>(N, 0.0), opt.get_bed_file(), N, sh.M, Mt, sh.S);
+    if (dosage && gv_set_screen_dosage(dataset.get_ctx(), 1))
+        return refuse(std::cout << "FATAL: gv_set_screen_dosage: " << gv_last_error(dataset.get_ctx()));
     const Screen s{job, dataset, ph, N, Mt, sh};
     const bool with_cov = opt.get_cov_file() != "";
     if (with_cov && !read_covariate_cases(s, (int)opt.get_C())) return EXIT_FAILURE;
@@ -803,6 +807,8 @@ int main(int argc, char** argv) {
     const Job job{opt};
     if (job.dmiss && job.type_data == "bed" && job.rank == 0)
         std::cout << "WARNING: --dosage-missing is ignored for --geno-format bed (PLINK rows carry their own missing code)" << std::endl;
+    if (opt.get_screen_dosage() && job.type_data == "bed" && job.rank == 0)
+        std::cout << "WARNING: --screen-dosage is ignored for --geno-format bed (the screen of 2-bit genotypes needs no option)" << std::endl;
     if (job.droute && job.type_data == "bed" && job.rank == 0)
         std::cout << "WARNING: --dosage-kernels is ignored for --geno-format bed (gv_set_kernel_mode selects the bed kernels)" << std::endl;
     if (job.pcd && (job.mode == "infere" || job.mode == "restart" || job.mode == "both") && job.type_data != "dosage8")

@@ -148,6 +148,11 @@ void Options::read_command_line_options(int argc, char** argv) {
             fatal(std::string("FATAL  : option --dosage-missing has to be 0 or 1! (") + a + " was passed)");
         dosage_missing = atoi(a);
     };
+    H["--screen-dosage"] = [&](const char* a) {
+        if (strcmp(a, "0") && strcmp(a, "1"))
+            fatal(std::string("FATAL  : option --screen-dosage has to be 0 or 1! (") + a + " was passed)");
+        screen_dosage = atoi(a);
+    };
     H["--dosage-kernels"] = [&](const char* a) {
         if (strcmp(a, "valu") && strcmp(a, "mfma"))
             fatal(std::string("FATAL  : option --dosage-kernels has to be valu or mfma! (") + a + " was passed)");

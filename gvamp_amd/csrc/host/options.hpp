@@ -78,6 +78,10 @@
        intercept: an individual with a non-finite covariate is masked together with the NA phenotypes, a marker whose     \
        variance-inflation factor given the covariates is above --screen-vif (default 50) gets NaN, and                    \
        <out>_screen_{beta,se}.bin (per copy of the counted allele) are written beside the three files;                    \
+       --screen-dosage 0|1 (default 0): 1 = --run-mode screen also accepts --geno-format dosage8 / dosage16                 \
+       (gv_set_screen_dosage, DESIGN.md section 29: the mean-imputed dosage, beta per unit of scale * code), with          \
+       --dosage-scale, --dosage-missing and --dosage-kernels as in the other modes; ignored with one warning line for     \
+       --geno-format bed;                                                                                                 \
        --run-mode pca (gv_pca_dev) with --pca-k K: the K leading principal components of the       \
        standardised genotypes among the individuals with a phenotype, by block subspace iteration on a block of          \
        --pca-block L vectors (default min(32, K + max(8, K))) to --pca-tol t (default 1e-8) within --pca-max-iter n       \
@@ -106,7 +110,7 @@
     X(double, clump_kb, -1)                                                                                          \
     X(std::string, score_file, "") X(unsigned int, score_cols, 1) X(std::string, score_units, "std")                \
     X(std::string, score_clump_index, "") X(std::string, score_p_file, "") X(unsigned int, screen_cols, 64)   \
-    X(double, screen_vif, 50.0)                                                                                      \
+    X(double, screen_vif, 50.0) X(int, screen_dosage, 0)                                                             \
     X(unsigned int, pca_k, 0) X(unsigned int, pca_block, 0) X(double, pca_tol, 1e-8) X(unsigned int, pca_max_iter, 100)          \
     X(unsigned int, pca_seed, 0) X(unsigned int, pca_allow_unconverged, 0)                                           \
     X(double, king_cutoff, 0.0884) X(std::string, king_marker_file, "")                                              \

@@ -218,6 +218,8 @@ int gv_get_marker_stats(gv_ctx* ctx, double* mave, double* msig); /* M doubles e
  *   gv_set_kernel_mode, gv_set_dosage_route   | nothing: read by every product; the marker statistics | -- (people statistics of kernel
  *                                             | are the same exact counts in every kernel family      | mode 0 / 1: gv_people_stats again)
  *   gv_set_ld_dosage, gv_set_cg_precond       | window Grams and inverses (rebuilt on demand)         | --
+ *   gv_set_screen_dosage                      | nothing: read by every screen call; no product and no | --
+ *                                             | statistic depends on it                               |
  *   gv_set_dosage_missing                     | refused while codes uploaded with the other setting   | gv_set_dims or an upload of another
  *                                             | are resident                                          | kind first, then the upload
  *   gv_set_dims                               | everything above, the mask (everyone present again)   | gv_set_mask, upload, gv_marker_stats;
@@ -232,7 +234,7 @@ int gv_get_marker_stats(gv_ctx* ctx, double* mave, double* msig); /* M doubles e
  * gv_screen_cov_dev refuses, naming gv_screen_cov_set, until that call has run after the LAST gv_marker_stats
  * (tests/test_gpu_screen_cov_reuse.py holds this row as the other file holds the rows above).
  * What survives a data set (and gv_set_dims): the options "that outlive the data set" -- kernel mode, layout request, dosage route,
- * gv_set_dosage_missing, gv_set_ld_dosage, the preconditioner kind and window, gv_set_expected_passes, the communicator, timing -- and
+ * gv_set_dosage_missing, gv_set_ld_dosage, gv_set_screen_dosage, the preconditioner kind and window, gv_set_expected_passes, the communicator, timing -- and
  * the ticket counter of the streaming kernels.  The tuner's decomposition picks are made again per resident layout (and change no
  * bit); the run-ahead hints of the device-resident CG go with the data set (they change no bit either).
  * Vectors: a gv_vec belongs to the context that allocated it and to the dimensions it was allocated under.  Every entry point checks
@@ -878,6 +880,14 @@ int gv_score_info(const gv_ctx* ctx, gv_score_stats* out);
  * and dosage data, an empty shard, fewer columns -- the dispatcher behind gv_atx_dev / gv_atx2_dev runs, in pairs where a two-vector
  * pass exists and singly otherwise (GV_ATXM_PATH_FALLBACK).  min_cols is 4, measured.  GV_ATXM_KERNEL=1 / 0
  * (development, read by gv_create per context) makes min_cols 1 / unreachable.
+ * 8-bit dosage codes while the fixed-point route is in force (gv_get_dosage_route reports in_force == 1: requested, 8-bit codes, the
+ * plain kernels) with M > 0 have a kernel of their own: GV_ATXM_PATH_KERNEL with cols_per_pass 4 or 8
+ * (GV_ATXM_COLS pins it; the default is GV_ATXM_DENSE_COLS_DEFAULT), ksegs the int32 segments of the one-vector product, and a min_cols
+ * of its own, 3, which GV_ATXM_KERNEL sets the same way.  The contract is the one above: every sum of that route is an exact integer,
+ * a column is quantised and rounded by the functions gv_atx_dev runs, and it is bit-identical to gv_atx_dev of that column alone.  Its
+ * scratch is the context's (the formula: gv_dense_atxm_plan.h); the digit and partial-sum buffers of gv_atx_dev / gv_ax_dev on that route
+ * are not touched.  Route 0, 16-bit codes, a shard with reserved codes under gv_set_dosage_missing, GV_DOSAGE_NA_KERNELS=1 and
+ * methylation data keep the fallback.
  * Edge rules.  C == 0 succeeds and does nothing.  Refused with a message: C < 0; NULL arrays or handles; a p that is not N-space or an
  * out that is not M-space; two outputs that are the same vector; an output that is also an input; marker statistics missing (the
  * message of gv_atx_dev).  Inputs may repeat.
@@ -908,7 +918,26 @@ int gv_score_info(const gv_ctx* ctx, gv_score_stats* out);
  * of one marker, so a rank may call them alone and the outputs of the ranks, put side by side in marker order, are the output of one
  * context on all markers bit for bit -- PROVIDED every rank has set the same mask (gv_set_mask with the same bytes and nonas: the
  * statistics of a marker and n depend on it) and passes the same columns.  On a rank without markers the calls succeed and write
- * nothing. */
+ * nothing.
+ *
+ * Screens on dosage data (additions only).  gv_set_screen_dosage(ctx, 1): gv_screen_dev, gv_screen_cov_set and
+ * gv_screen_cov_dev accept a context whose resident data are dosage codes -- 8 or 16 bits, with or without missing entries
+ * (gv_set_dosage_missing), on either route.  The default is 0: every call and message is what it was.  The setting outlives the dataset
+ * and is read by every call; nothing is derived from it, so nothing goes stale.  Methylation data stay refused either way.
+ * Definition.  With b the code, na = 1 at a present entry (0 at a reserved code), mu' the mean code over the phenotyped present entries
+ * and q = sum_n ((b - mu') na)^2 over the phenotyped individuals, the marker statistics give msig^2 scale^2 q = n - 1 (alpha_scale = 1):
+ * the column (b - mu') msig scale na has squared norm n - 1, the identity the bed screens rest on.  So the formulas above and those of
+ * gv_screen_cov_dev hold unchanged, with the same order of roundings: r = fl(z a) is the Pearson correlation of the mean-imputed dosage
+ * (a missing entry counts as the marker's mean) with the phenotype, nu = n - 2 (n - 2 - K adjusted), and in the adjusted screen
+ * sxx_j = fl(fl(scale scale) q_j) takes the place of fl((n - 1) / msig^2): beta and se are per unit of the value scale * code, per allele
+ * copy at the default scales.  A marker with q == 0 -- constant over the phenotyped present entries, or all missing; exact in code units
+ * whatever the scale -- gives NaN in every output.  q is the sum the statistics pass forms for msig, kept per marker beside mu'
+ * (the decision is taken from q itself, never from msig == 1); it goes stale and is restored with the marker statistics.
+ * The products run on whatever path gv_atxm_dev takes for the context, so column independence on the bits holds as above.
+ * Refused as on bed data, by the same messages: alpha_scale != 1, n < 3 or nu < 1, every vector and handle check. */
+int gv_set_screen_dosage(gv_ctx* ctx, int on);
+int gv_get_screen_dosage(const gv_ctx* ctx, int* on);
+#define GV_ATXM_DENSE_COLS_DEFAULT 8
 #define GV_ATXM_PATH_KERNEL 1
 #define GV_ATXM_PATH_FALLBACK 2
 #define GV_ATXM_COLS_DEFAULT 8
