@@ -38,7 +38,7 @@ EXPORTS = [
     "gv_atxm_dev", "gv_atxm", "gv_atxm_info", "gv_screen_dev",
     "gv_pca_dev", "gv_pca_loadings_dev", "gv_pca_info",
     "gv_king_block", "gv_king_pairs", "gv_king_info",
-    "gv_grm_weights", "gv_grm_block", "gv_grm_pairs", "gv_grm_info",
+    "gv_grm_weights", "gv_grm_block", "gv_grm_pairs", "gv_grm_info", "gv_grm_apply", "gv_grm_he",
     "gv_screen_cov_set", "gv_screen_cov_dev", "gv_screen_cov_info",
     "gv_set_screen_dosage", "gv_get_screen_dosage",
 ]
@@ -94,7 +94,20 @@ class KingStats(C.Structure):          # gv_king_stats
 
 class GrmStats(C.Structure):           # gv_grm_stats
     _fields_ = [("seconds", C.c_double), ("block_pairs", C.c_int64), ("counting_markers", C.c_int64), ("dropped_markers", C.c_int64),
-                ("pairs", C.c_int64), ("useful_macs", C.c_double), ("scratch_bytes", C.c_double)]
+                ("pairs", C.c_int64), ("useful_macs", C.c_double), ("scratch_bytes", C.c_double), ("passes", C.c_int64),
+                ("blocks_computed", C.c_int64)]
+
+
+GRM_APPLY_MAX_COLS = 32
+
+
+class HeResult(C.Structure):           # gv_he_result
+    _fields_ = [("n_ind", C.c_int64), ("n_pairs", C.c_int64), ("sum_a", C.c_double), ("sum_aa", C.c_double), ("h2", C.c_double),
+                ("intercept", C.c_double), ("se_ols", C.c_double), ("se_jack", C.c_double)]
+
+
+HE_DTYPE = np.dtype([("n_ind", np.int64), ("n_pairs", np.int64), ("sum_a", np.float64), ("sum_aa", np.float64), ("h2", np.float64),
+                     ("intercept", np.float64), ("se_ols", np.float64), ("se_jack", np.float64)])
 
 
 class ScreenCovStats(C.Structure):     # gv_screen_cov_stats
@@ -260,6 +273,8 @@ def load():
     L.gv_grm_block.argtypes = [vp, up, i64, i64, i64, i64, dp, i32p]
     L.gv_grm_pairs.argtypes = [vp, up, C.c_double, i64, i32p, i32p, dp, i32p, dp, i32p, C.POINTER(i64)]
     L.gv_grm_info.argtypes = [vp, C.POINTER(GrmStats)]
+    L.gv_grm_apply.argtypes = [vp, up, C.c_int, dp, dp, dp, dp]
+    L.gv_grm_he.argtypes = [vp, up, i64, dp, C.POINTER(HeResult)]
     L.gv_ld_scores_pos.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), C.c_int, dp, C.c_int, dp, dp]
     L.gv_ld_last_passes.argtypes = [vp, C.POINTER(C.c_int)]
     L.gv_ld_clump.argtypes = [vp, dp, C.c_double, C.POINTER(C.c_int), dp, C.c_double, C.c_double, C.c_double, C.POINTER(i64), C.POINTER(i64)]
@@ -1020,7 +1035,36 @@ class Shard:
         st = GrmStats()
         self._ck(self.L.gv_grm_info(self.h, C.byref(st)))
         return dict(seconds=st.seconds, block_pairs=st.block_pairs, counting_markers=st.counting_markers,
-                    dropped_markers=st.dropped_markers, pairs=st.pairs, useful_macs=st.useful_macs, scratch_bytes=st.scratch_bytes)
+                    dropped_markers=st.dropped_markers, pairs=st.pairs, useful_macs=st.useful_macs, scratch_bytes=st.scratch_bytes,
+                    passes=st.passes, blocks_computed=st.blocks_computed)
+
+    # ---- GRM-times-panel product and Haseman-Elston regression (gv_grm_apply / gv_grm_he) ----
+    def grm_apply(self, w, use=None, want=(True, True, True)):
+        """gv_grm_apply: (g0, g1, g2), each N x C float64 (None where `want` is false), of the panel w (N x C, or N values: one
+        column): gp = Gp w with G0 = 1, G1 = A, G2 = fl(A^2) off the diagonal and where M_ij > 0, 0 elsewhere"""
+        w_ = np.ascontiguousarray(w, dtype=np.float64)
+        if w_.ndim == 1:
+            w_ = w_.reshape(-1, 1)
+        if w_.ndim != 2 or w_.shape[0] != self.N:
+            raise GvError("grm_apply: w must be N x C (N = %d), not %s" % (self.N, w_.shape))
+        ncol = w_.shape[1]
+        out = [np.zeros((self.N, max(ncol, 1))) if k else None for k in want]
+        u, upt = self._use(use)
+        self._ck(self.L.gv_grm_apply(self.h, upt, ncol, _dp(w_), *[_dp(o) if o is not None else None for o in out]))
+        return tuple(out)
+
+    def grm_he(self, y, use=None):
+        """gv_grm_he: a record array (HE_DTYPE), one record per column of y (N x C, or N values: one trait; NaN = missing)"""
+        y_ = np.ascontiguousarray(y, dtype=np.float64)
+        if y_.ndim == 1:
+            y_ = y_.reshape(-1, 1)
+        if y_.ndim != 2 or y_.shape[0] != self.N:
+            raise GvError("grm_he: y must be N x C (N = %d), not %s" % (self.N, y_.shape))
+        ncol = y_.shape[1]
+        res = (HeResult * max(ncol, 1))()
+        u, upt = self._use(use)
+        self._ck(self.L.gv_grm_he(self.h, upt, ncol, _dp(y_), res))
+        return np.frombuffer(res, dtype=HE_DTYPE, count=ncol).copy()
 
     def pca_info(self):
         """gv_pca_info of the last pca_dev / pca as a dict"""

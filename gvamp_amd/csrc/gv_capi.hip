@@ -422,6 +422,18 @@ int gv_create(int device, gv_ctx** out) {
         }
         c->ld_part_bytes = mb * 1048576.0;
     }
+    // GV_GRM_PART_MB=<x> (development, read per context): the budget of gv_grm_apply for the block terms of one pass, in MiB (fractions
+    // allowed; default 2048).  It changes no bit, only the number of passes; a call whose single block does not fit refuses.
+    if (const char* pm = getenv("GV_GRM_PART_MB")) {
+        char* end = nullptr;
+        const double mb = strtod(pm, &end);
+        if (end == pm || *end != 0 || !(mb > 0.0) || !std::isfinite(mb)) {
+            g_create_err = "gv_create: GV_GRM_PART_MB=" + std::string(pm) + ": the budget of the GRM block terms is a positive number of MiB";
+            gv_destroy_locked(c);
+            return 1;
+        }
+        c->grm_part_bytes = mb * 1048576.0;
+    }
     // GV_SCORE_COLS=<4|8|16>, GV_SCORE_KS=<k>, GV_SCORE_KERNEL=1|0 and GV_ATXM_COLS=<4|8>, GV_ATXM_KS=<k>, GV_ATXM_KERNEL=1|0 (development,
     // read per context).  None changes a bit.  A GV_SCORE_KS that breaks the int32 bound on a shard is refused by the call; a
     // GV_ATXM_KS is clipped to the K-steps there are.

@@ -126,9 +126,60 @@ struct GrmArgs {
     int* pm;
     double* diag;                   // EP_PAIRS: N or NULL
     int* diag_m;                    // EP_PAIRS: N or NULL
+    int C;                          // EP_APPLY: columns of the panel, 1 .. GV_GRM_APPLY_MAX_COLS
+    const double* w;                // EP_APPLY: the panel, nG * 64 rows of C, zero from row N on
+    int64_t a0, ga, b0, gb;         // EP_APPLY: the pass's tile of the block triangle, I in [a0, a0 + ga), J in [b0, b0 + gb)
+    double* px;                     // EP_APPLY: block terms (rows of I, source J): [3][gb][ga * 64][C]
+    double* py;                     // EP_APPLY: block terms (rows of J, source I): [3][ga][gb * 64][C]; a tile on the diagonal: px
 };
 
-enum { EP_RECT, EP_PAIRS };
+enum { EP_RECT, EP_PAIRS, EP_APPLY };
+
+// EP_APPLY: the block's A as an LDS image, NaN where G0 = G1 = G2 = 0 (the diagonal, M_ij = 0, an individual >= N).  A pitch of 65
+// doubles = 130 dwords: lane r of a row read (ds_read_b64, banks (a / 4) % 64, two halves of 32 lanes) sits on banks 2 r, 2 r + 1, and a
+// transposed read has consecutive lanes on consecutive doubles -- both without a conflict.
+constexpr int APPLY_PITCH = 65;
+
+// One block term of gv_grm_apply: lane r is a row of the term, the wave takes the columns wave + 4 k.  Entry (r, j) of the operator's
+// block is img[r * sr + j * sj] (sr = pitch, sj = 1: as computed; swapped: the mirror block).  The chain of the contract, literally:
+// from +0.0, j ascending, acc = acc + Gp * w with both operations rounded -- written with the plain operators under contract(off): the
+// __dadd_rn / __dmul_rn of the headers inherit the translation unit's contraction and would fuse.  A column slot past C runs on column 0
+// and is not stored.  Term p of (r, c) goes to dst[p * pstride + r * C + c].
+__device__ __forceinline__ void grm_apply_side(const double* img, int sr, int sj, const double* W, int C, int r, int wave, double* dst,
+                                               int64_t pstride) {
+#pragma clang fp contract(off)
+    double t0[8], t1[8], t2[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) t0[k] = t1[k] = t2[k] = 0.0;
+    const double* e = img + r * sr;
+    for (int j = 0; j < 64; j++) {
+        const double x = e[j * sj];
+        const bool ok = x == x;
+        const double g0 = ok ? 1.0 : 0.0, g1 = ok ? x : 0.0;
+        const double g2 = g1 * g1;
+        const double* wj = W + j * C;
+        double wv[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) wv[k] = wj[wave + 4 * k < C ? wave + 4 * k : 0];      // (uniform over the wave: scalar loads)
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const double m0 = g0 * wv[k], m1 = g1 * wv[k], m2 = g2 * wv[k];
+            t0[k] = t0[k] + m0;
+            t1[k] = t1[k] + m1;
+            t2[k] = t2[k] + m2;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int c = wave + 4 * k;
+        if (c < C) {
+            double* d = dst + (int64_t)r * C + c;
+            d[0] = t0[k];
+            d[pstride] = t1[k];
+            d[2 * pstride] = t2[k];
+        }
+    }
+}
 
 // block b of the upper triangle of nG x nG in row-major order (gv_king.hip): row I holds J = I .. nG - 1 and starts at
 // I nG - I (I - 1) / 2.  The fp64 estimate of the root is corrected in exact integers.
@@ -151,7 +202,12 @@ struct GrmStage {
 
 template <int EP>
 __global__ __launch_bounds__(256, 2) void k_grm_block(const GrmArgs a) {
-    __shared__ GrmStage stage[2];
+    // EP_APPLY reuses the staging buffers for the block's image once the K loop is over: 33 KiB a workgroup, so that four workgroups still
+    // share a CU's LDS as they do under the other epilogues (the 64 x C slices of the panel are read through the scalar cache instead)
+    constexpr size_t kLds = EP == EP_APPLY ? sizeof(double) * 64 * APPLY_PITCH : 2 * sizeof(GrmStage);
+    static_assert(kLds >= 2 * sizeof(GrmStage), "the image must cover the staging buffers it replaces");
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kLds];
+    GrmStage* const stage = reinterpret_cast<GrmStage*>(lds);
     // Workgroups are dealt to the eight XCDs round-robin by block index: XCD x takes a contiguous eighth of the block list, so the
     // workgroups that run side by side on one L2 share their I side (gv_king.hip)
     int64_t b;
@@ -160,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void k_grm_block(const GrmArgs a) {
         b = x * q + (x < r ? x : r) + k;
     }
     int64_t I, J;
-    if constexpr (EP == EP_RECT) {
+    if constexpr (EP != EP_PAIRS) {
         I = a.blocks[2 * b];
         J = a.blocks[2 * b + 1];
     } else grm_block_of(b, a.nG, I, J);
@@ -250,6 +306,38 @@ __global__ __launch_bounds__(256, 2) void k_grm_block(const GrmArgs a) {
     // Epilogue.  Register v of tile (i, j) of this lane is the pair of individual 16 (2 wr + i) + lk + 4 v of group I and individual
     // 16 (2 wc + j) + lr of group J.  Nothing is emitted for a pad individual (>= N).
     const double nan = __builtin_nan("");
+    if constexpr (EP == EP_APPLY) {
+        // The block never leaves the workgroup: its image goes to LDS, and every wave then runs the chains of its columns, one lane per
+        // row: the term for (rows of I, source J), and off the diagonal the one for (rows of J, source I) from the same image read
+        // transposed.  The panel's entry w[j][c] is the same for every lane of a wave: a scalar load.
+        double* const img = reinterpret_cast<double*>(lds);
+        if (I < a.a0 || I >= a.a0 + a.ga || J < a.b0 || J >= a.b0 + a.gb) return;      // (never true for a list built by the host)
+        __syncthreads();                            // every wave is done reading the last row group's staging
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int i = 0; i < 2; i++)
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    const int row = 16 * (2 * wr + i) + lk + 4 * v, col = 16 * (2 * wc + j) + lr;
+                    const int64_t gi = I * 64 + row, gj = J * 64 + col;
+                    const int mij = cnt[i][j][v];
+                    const bool ok = gi < a.N && gj < a.N && gi != gj && mij > 0;
+                    img[row * APPLY_PITCH + col] = ok ? __ddiv_rn(acc[i][j][v], (double)mij) : nan;
+                }
+        __syncthreads();
+        const int64_t nw = 64 * a.C, ra = a.ga * 64, rb = a.gb * 64;
+        const double *wI = a.w + I * nw, *wJ = a.w + J * nw;
+        const int wv = __builtin_amdgcn_readfirstlane(wave);
+        grm_apply_side(img, APPLY_PITCH, 1, wJ, a.C, lane, wv, a.px + ((J - a.b0) * ra + (I - a.a0) * 64) * a.C, a.gb * ra * a.C);
+        if (I < J) {
+            if (a.a0 == a.b0)
+                grm_apply_side(img, 1, APPLY_PITCH, wI, a.C, lane, wv, a.px + ((I - a.a0) * ra + (J - a.a0) * 64) * a.C, a.gb * ra * a.C);
+            else
+                grm_apply_side(img, 1, APPLY_PITCH, wI, a.C, lane, wv, a.py + ((I - a.a0) * rb + (J - a.b0) * 64) * a.C, a.ga * rb * a.C);
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const int64_t gj = J * 64 + 16 * (2 * wc + j) + lr;
@@ -288,6 +376,27 @@ __global__ __launch_bounds__(256, 2) void k_grm_block(const GrmArgs a) {
                     }
                 }
             }
+    }
+}
+
+struct ApplyFinishArgs {
+    const double* part;             // [3][nsrc][rows][C]: the block terms of one side of a pass
+    double* out;                    // [3][nG * 64][C]: the running chains
+    int64_t rows, row0, nsrc, N, ostride;
+    int C;
+};
+
+// extends the chain of every (row, column) of a pass's rows by the pass's source groups in ascending order
+__global__ __launch_bounds__(256) void k_grm_apply_finish(const ApplyFinishArgs a) {
+#pragma clang fp contract(off)
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, per = a.rows * a.C;
+    if (idx >= per || a.row0 + idx / a.C >= a.N) return;
+    for (int p = 0; p < 3; p++) {
+        double* o = a.out + p * a.ostride + a.row0 * a.C + idx;
+        double acc = *o;
+        const double* src = a.part + p * a.nsrc * per + idx;
+        for (int64_t s = 0; s < a.nsrc; s++) acc = acc + src[s * per];
+        *o = acc;
     }
 }
 
@@ -390,6 +499,8 @@ static void grm_report(gv_ctx* c, std::chrono::steady_clock::time_point t0, int6
     s.counting_markers = (int64_t)tally[0];
     s.dropped_markers = (int64_t)tally[1];
     s.pairs = pairs;
+    s.passes = block_pairs > 0;
+    s.blocks_computed = block_pairs;
     s.useful_macs = (double)s.counting_markers * (double)pairs;
     s.scratch_bytes = (double)w.bytes;
 }
@@ -535,6 +646,217 @@ int gv_grm_pairs(gv_ctx* c, const uint8_t* use, double cutoff, int64_t cap, int3
     if (diag_m) std::copy(hdm.begin(), hdm.end(), diag_m);
     *n_found = (int64_t)found;
     grm_report(c, t0, a.nblocks, tally, c->N * (c->N - 1) / 2, w);
+    return 0;
+}
+
+// The passes of gv_grm_apply are square tiles of the block triangle, g groups on a side: tile (a, b), a <= b, holds the blocks I in
+// group range a, J in range b, and leaves the terms (rows of a, sources of b) and, off the diagonal, (rows of b, sources of a).  Run in
+// the order b = 0, 1, ..; a = 0 .. b, the tiles meet every row's sources in ascending order -- (0, a), .., (a, a), (a, a + 1), .. for a row
+// of range a -- so the finishing kernel extends the chains pass by pass, and no block is computed twice.
+int gv_grm_apply(gv_ctx* c, const uint8_t* use, int C, const double* wh, double* g0, double* g1, double* g2) {
+    if (!c) return 1;
+    const char* who = "gv_grm_apply";
+    if (grm_check(c, who)) return 1;
+    if (C < 1 || C > GV_GRM_APPLY_MAX_COLS)
+        return fail(c, "%s: C = %d columns is outside 1 .. %d", who, C, GV_GRM_APPLY_MAX_COLS);
+    NEED(c, wh, "gv_grm_apply: w is NULL");
+    NEED(c, g0 || g1 || g2, "gv_grm_apply: g0, g1 and g2 are all NULL");
+    const int64_t N = c->N, nG = (N + 63) / 64, npad = nG * 64;
+    for (int64_t t = 0; t < N * C; t++)
+        if (!std::isfinite(wh[t]))
+            return fail(c, "%s: w[%lld][%lld] is not finite: an absent pair takes part in every sum as 0 * w", who, (long long)(t / C), (long long)(t % C));
+    const double unit = 2.0 * 3.0 * 64.0 * (double)C * 8.0;      // both terms of one block
+    if (c->grm_part_bytes < unit)
+        return fail(c, "%s: the budget of the partial sums, %.0f bytes (GV_GRM_PART_MB), cannot hold the terms of one row group against one "
+                       "source group: 2 sides x 3 operators x 64 rows x %d columns x 8 bytes = %.0f bytes", who, c->grm_part_bytes, C, unit);
+    if (nG * (nG + 1) / 2 > GRM_BLOCKS_MAX)
+        return fail(c, "%s: N = %lld has more than %lld block pairs", who, (long long)N, (long long)GRM_BLOCKS_MAX);
+    int64_t g = (int64_t)std::floor(std::sqrt(c->grm_part_bytes / unit));
+    while (g > 1 && (double)g * (double)g * unit > c->grm_part_bytes) g--;
+    g = std::max<int64_t>(1, std::min(g, nG));
+    const int64_t P = (nG + g - 1) / g;
+    const auto t0 = std::chrono::steady_clock::now();
+    Scratch w;
+    GrmArgs a{};
+    Weights wt;
+    if (grm_prepare(c, who, use, w, a, wt)) return 1;
+    // the block lists of all passes, back to back
+    std::vector<int> blocks;
+    std::vector<int64_t> first;
+    blocks.reserve((size_t)(nG * (nG + 1)));
+    for (int64_t tb = 0; tb < P; tb++)
+        for (int64_t ta = 0; ta <= tb; ta++) {
+            first.push_back((int64_t)blocks.size() / 2);
+            for (int64_t I = ta * g; I < std::min(nG, (ta + 1) * g); I++)
+                for (int64_t J = std::max(I, tb * g); J < std::min(nG, (tb + 1) * g); J++) {
+                    blocks.push_back((int)I);
+                    blocks.push_back((int)J);
+                }
+        }
+    first.push_back((int64_t)blocks.size() / 2);
+    const size_t no = (size_t)npad * (size_t)C, np = 3 * (size_t)(g * g) * 64 * (size_t)C;
+    int* dblocks = nullptr;
+    double *dw = nullptr, *dout = nullptr;
+    GGALLOC(dblocks, blocks.size());
+    GGALLOC(dw, no);
+    GGALLOC(dout, 3 * no);
+    GGALLOC(a.px, np);
+    if (P > 1) GGALLOC(a.py, np);
+    HIPCHK(c, hipMemcpyAsync(dblocks, blocks.data(), sizeof(int) * blocks.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dw, 0, sizeof(double) * no, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dw, wh, sizeof(double) * (size_t)N * (size_t)C, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(dout, 0, sizeof(double) * 3 * no, c->stream));
+    a.C = C;
+    a.w = dw;
+    int64_t pass = 0;
+    for (int64_t tb = 0; tb < P; tb++)
+        for (int64_t ta = 0; ta <= tb; ta++, pass++) {
+            a.a0 = ta * g;
+            a.ga = std::min(nG, (ta + 1) * g) - a.a0;
+            a.b0 = tb * g;
+            a.gb = std::min(nG, (tb + 1) * g) - a.b0;
+            a.blocks = dblocks + 2 * first[(size_t)pass];
+            a.nblocks = first[(size_t)pass + 1] - first[(size_t)pass];
+            hipLaunchKernelGGL(k_grm_block<EP_APPLY>, dim3((unsigned)a.nblocks), dim3(256), 0, c->stream, a);
+            KCHK(c);
+            for (int side = 0; side < (ta == tb ? 1 : 2); side++) {
+                ApplyFinishArgs f{};
+                f.part = side ? a.py : a.px;
+                f.out = dout;
+                f.rows = (side ? a.gb : a.ga) * 64;
+                f.row0 = (side ? a.b0 : a.a0) * 64;
+                f.nsrc = side ? a.ga : a.gb;
+                f.N = N;
+                f.ostride = (int64_t)no;
+                f.C = C;
+                hipLaunchKernelGGL(k_grm_apply_finish, dim3((unsigned)((f.rows * C + 255) / 256)), dim3(256), 0, c->stream, f);
+                KCHK(c);
+            }
+        }
+    // every transfer that can fail comes before the first byte written to the caller
+    unsigned long long tally[2] = {0, 0};
+    std::vector<double> h(3 * no);
+    HIPCHK(c, hipMemcpyAsync(tally, wt.tally, sizeof(tally), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h.data(), dout, sizeof(double) * 3 * no, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double* outs[3] = {g0, g1, g2};
+    for (int p = 0; p < 3; p++)
+        if (outs[p]) std::copy(h.begin() + (size_t)p * no, h.begin() + (size_t)p * no + (size_t)N * (size_t)C, outs[p]);
+    grm_report(c, t0, nG * (nG + 1) / 2, tally, N * (N - 1) / 2, w);
+    c->grm_last.passes = pass;
+    c->grm_last.blocks_computed = (int64_t)blocks.size() / 2;
+    return 0;
+}
+
+namespace {
+
+// the six sums of the regression and what follows from them; NaN in the derived values when n < 3 or D <= 0
+struct HeSums {
+    double n, sx, sxx, sz, szz, sxz;
+    double h2() const {
+        const double D = n * sxx - sx * sx;
+        return n >= 3.0 && D > 0.0 ? (n * sxz - sx * sz) / D : std::nan("");
+    }
+};
+
+}  // namespace
+
+int gv_grm_he(gv_ctx* c, const uint8_t* use, int64_t C, const double* y, gv_he_result* res) {
+    if (!c) return 1;
+    const char* who = "gv_grm_he";
+    if (grm_check(c, who)) return 1;
+    if (C < 1) return fail(c, "%s: C = %lld traits: at least one is needed", who, (long long)C);
+    NEED(c, y, "gv_grm_he: y is NULL");
+    NEED(c, res, "gv_grm_he: res is NULL");
+    const int64_t N = c->N;
+    for (int64_t t = 0; t < N * C; t++)
+        if (std::isinf(y[t]))
+            return fail(c, "%s: y[%lld][%lld] is infinite (NaN marks a missing phenotype)", who, (long long)(t / C), (long long)(t % C));
+    constexpr int64_t PER = 10;                    // traits of one gv_grm_apply: 3 columns each
+    std::vector<gv_he_result> out((size_t)C);
+    gv_grm_stats total{};
+    for (int64_t c0 = 0; c0 < C; c0 += PER) {
+        const int64_t nt = std::min(PER, C - c0), W = 3 * nt;
+        std::vector<double> w((size_t)(N * W), 0.0), g[3];
+        std::vector<char> usable((size_t)nt, 0);
+        for (int64_t t = 0; t < nt; t++) {
+            // K, the mean and the variance over it, and the columns k, yt, yt^2
+            int64_t nk = 0;
+            double sum = 0.0, ss = 0.0;
+            for (int64_t i = 0; i < N; i++)
+                if (!std::isnan(y[i * C + c0 + t])) {
+                    nk++;
+                    sum += y[i * C + c0 + t];
+                }
+            const double m = nk ? sum / (double)nk : 0.0;
+            for (int64_t i = 0; i < N; i++)
+                if (!std::isnan(y[i * C + c0 + t])) ss += (y[i * C + c0 + t] - m) * (y[i * C + c0 + t] - m);
+            const double v = nk > 1 ? ss / (double)(nk - 1) : 0.0, sd = std::sqrt(v);
+            usable[(size_t)t] = v > 0.0 && std::isfinite(v) && std::isfinite(1.0 / sd);
+            out[(size_t)(c0 + t)].n_ind = nk;
+            for (int64_t i = 0; i < N; i++)
+                if (!std::isnan(y[i * C + c0 + t])) {
+                    const double yt = usable[(size_t)t] ? (y[i * C + c0 + t] - m) / sd : 0.0;      // (a constant trait: k alone)
+                    double* row = &w[(size_t)(i * W + 3 * t)];
+                    row[0] = 1.0;
+                    row[1] = yt;
+                    row[2] = yt * yt;
+                }
+        }
+        for (auto& v : g) v.assign((size_t)(N * W), 0.0);
+        if (gv_grm_apply(c, use, (int)W, w.data(), g[0].data(), g[1].data(), g[2].data())) return 1;
+        total.seconds += c->grm_last.seconds;
+        total.passes += c->grm_last.passes;
+        total.blocks_computed += c->grm_last.blocks_computed;
+        total.useful_macs += c->grm_last.useful_macs;
+        total.scratch_bytes = std::max(total.scratch_bytes, c->grm_last.scratch_bytes);
+        total.block_pairs = c->grm_last.block_pairs;
+        total.counting_markers = c->grm_last.counting_markers;
+        total.dropped_markers = c->grm_last.dropped_markers;
+        total.pairs = c->grm_last.pairs;
+        for (int64_t t = 0; t < nt; t++) {
+            gv_he_result& r = out[(size_t)(c0 + t)];
+            // row i's share of every sum: u_i (G v)_i; a pair is in two rows, hence the halves
+            std::vector<HeSums> row((size_t)N);
+            HeSums s{0, 0, 0, 0, 0, 0};
+            for (int64_t i = 0; i < N; i++) {
+                const size_t o = (size_t)(i * W + 3 * t);
+                const double k = w[o], yt = w[o + 1], y2 = w[o + 2];
+                HeSums& q = row[(size_t)i];
+                q = HeSums{k * g[0][o], k * g[1][o], k * g[2][o], yt * g[0][o + 1], y2 * g[0][o + 2], yt * g[1][o + 1]};
+                s.n += q.n;
+                s.sx += q.sx;
+                s.sxx += q.sxx;
+                s.sz += q.sz;
+                s.szz += q.szz;
+                s.sxz += q.sxz;
+            }
+            s = HeSums{0.5 * s.n, 0.5 * s.sx, 0.5 * s.sxx, 0.5 * s.sz, 0.5 * s.szz, 0.5 * s.sxz};
+            r.n_pairs = (int64_t)s.n;
+            r.sum_a = s.sx;
+            r.sum_aa = s.sxx;
+            r.h2 = usable[(size_t)t] ? s.h2() : std::nan("");
+            const double D = s.n * s.sxx - s.sx * s.sx;
+            r.intercept = (s.sz - r.h2 * s.sx) / s.n;
+            const double rss = s.szz - r.intercept * s.sz - r.h2 * s.sxz;
+            r.se_ols = std::sqrt(rss / (s.n - 2.0) * s.n / D);
+            if (std::isnan(r.h2)) r.intercept = r.se_ols = std::nan("");
+            // the delete-one jackknife: individual i takes its row's terms out of every sum
+            double mean = 0.0, dev = 0.0;
+            std::vector<double> hj;
+            for (int64_t i = 0; i < N; i++)
+                if (w[(size_t)(i * W + 3 * t)] != 0.0) {
+                    const HeSums& q = row[(size_t)i];
+                    hj.push_back(HeSums{s.n - q.n, s.sx - q.sx, s.sxx - q.sxx, s.sz - q.sz, s.szz - q.szz, s.sxz - q.sxz}.h2());
+                    mean += hj.back();
+                }
+            mean /= (double)hj.size();
+            for (double v : hj) dev += (v - mean) * (v - mean);
+            r.se_jack = std::isnan(r.h2) || hj.empty() ? std::nan("") : std::sqrt((double)(hj.size() - 1) / (double)hj.size() * dev);
+        }
+    }
+    std::copy(out.begin(), out.end(), res);
+    c->grm_last = total;
     return 0;
 }
 

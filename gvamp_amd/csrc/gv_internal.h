@@ -225,6 +225,8 @@ struct gv_ctx {
     // per context; a memory budget, not a tuned number) and the passes the last LD call took (gv_ld_last_passes)
     double ld_part_bytes = 2147483648.0;
     int ld_last_passes = 0;
+    // gv_grm_apply: the most bytes of block terms one pass may hold (GV_GRM_PART_MB, development, per context)
+    double grm_part_bytes = 2147483648.0;
     // gv_ld_clump: the rounds of the selection, |E1| and |E2| of the last call (gv_ld_clump_last), and the
     // seconds of its block pass and of its selection (gv_ld_clump_seconds)
     int clump_rounds = 0;

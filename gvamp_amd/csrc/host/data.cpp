@@ -503,6 +503,28 @@ data::grm_result data::grm_block(int64_t i0, int64_t ni, int64_t j0, int64_t nj,
     return out;
 }
 
+data::grm_apply_result data::grm_apply(int C, const std::vector<double>& w, const std::vector<unsigned char>& use) {
+    if (!use.empty() && use.size() != (size_t)(M > 0 ? M : 0)) die("FATAL: data::grm_apply: the marker selection must hold M bytes");
+    if (C < 1 || w.size() != (size_t)N * (size_t)C) die("FATAL: data::grm_apply: the panel must hold N x C values");
+    grm_apply_result out;
+    out.g0.assign(w.size(), 0.0);
+    out.g1.assign(w.size(), 0.0);
+    out.g2.assign(w.size(), 0.0);
+    ck(ctx, gv_grm_apply(ctx, use.empty() ? nullptr : use.data(), C, w.data(), out.g0.data(), out.g1.data(), out.g2.data()), "gv_grm_apply");
+    gv_grm_info(ctx, &out.info);
+    return out;
+}
+
+data::grm_he_result data::grm_he(int64_t C, const std::vector<double>& y, const std::vector<unsigned char>& use) {
+    if (!use.empty() && use.size() != (size_t)(M > 0 ? M : 0)) die("FATAL: data::grm_he: the marker selection must hold M bytes");
+    if (C < 1 || y.size() != (size_t)N * (size_t)C) die("FATAL: data::grm_he: the phenotypes must hold N x C values");
+    grm_he_result out;
+    out.traits.assign((size_t)C, gv_he_result{});
+    ck(ctx, gv_grm_he(ctx, use.empty() ? nullptr : use.data(), C, y.data(), out.traits.data()), "gv_grm_he");
+    gv_grm_info(ctx, &out.info);
+    return out;
+}
+
 void data::set_mask(const std::vector<unsigned char>& m4, int nonas_) {
     if (m4.size() != mbytes) {
         std::cout << "FATAL: data::set_mask: " << m4.size() << " mask bytes, not mbytes = " << mbytes << std::endl;

@@ -122,6 +122,18 @@ public:
     };
     grm_result grm_pairs(double cutoff, const std::vector<unsigned char>& use = std::vector<unsigned char>());
     grm_result grm_block(int64_t i0, int64_t ni, int64_t j0, int64_t nj, const std::vector<unsigned char>& use = std::vector<unsigned char>());
+    // [ext] the GRM-times-panel product and Haseman-Elston regression on it (gv_grm_apply / gv_grm_he).  w and y
+    // are N x C row-major (a NaN in y: the phenotype is missing); grm_apply returns g0, g1, g2, N x C each
+    struct grm_apply_result {
+        std::vector<double> g0, g1, g2;
+        gv_grm_stats info;
+    };
+    struct grm_he_result {
+        std::vector<gv_he_result> traits;
+        gv_grm_stats info;
+    };
+    grm_apply_result grm_apply(int C, const std::vector<double>& w, const std::vector<unsigned char>& use = std::vector<unsigned char>());
+    grm_he_result grm_he(int64_t C, const std::vector<double>& y, const std::vector<unsigned char>& use = std::vector<unsigned char>());
     // [ext] replace the mask (bit n & 3 of byte n >> 2 set: individual n has a phenotype) and recompute the marker statistics
     void set_mask(const std::vector<unsigned char>& m4, int nonas_);
     std::vector<double> Ax(double* __restrict__ phen);    // data.cpp:848 : M doubles -> 4*mbytes, reduced + scaled

@@ -2,7 +2,8 @@
 // the run mode up in MODES; every mode is one function run_<mode>(const Job&) that returns the process's exit status:
 //   infere / restart (:34-128, :369-385), test (:129-213), both (:214-283), pvals-calc (:284-368), predict / predict_single (:386-594);
 //   [ext] ldscore (gv_ld_scores), clump (gv_ld_clump, section 20), score (section 21), screen (section 23 and,
-//   with --cov-file, 26), pca (gv_pca_dev, section 24), king (gv_king_pairs, section 25), grm (gv_grm_pairs / gv_grm_block, section 28).
+//   with --cov-file, 26), pca (gv_pca_dev, section 24), king (gv_king_pairs, section 25), grm (gv_grm_pairs / gv_grm_block, section 28),
+//   he (gv_grm_he, section 30).
 // A new mode is one such function and one entry of MODES.  What the modes share sits above them: Job (the options every mode reads
 // and the two ways to build a `data` from them), require_bed / require_one_rank, read_f64_file and Window (an LD window by kb, cM or
 // marker count); driver_common.hpp holds what main_real_probit.cpp needs too.  Every mode is "load data, maybe run vamp::infere, one
@@ -751,6 +752,50 @@ int run_grm(const Job& job) {                                                   
     return opt.get_grm_has_cutoff() ? grm_sparse(job, dataset, use, N, Mt) : grm_dense(job, dataset, use, N, Mt);
 }
 
+int run_he(const Job& job) {                                                           // [ext] DESIGN.md section 30
+    // Haseman-Elston regression of every phenotype file on the relationship matrix, which is never stored
+    const Options& opt = job.opt;
+    if (!require_bed(job)) return EXIT_FAILURE;
+    if (!require_one_rank(job, "S and the common-marker count of a pair are sums over the markers of all ranks, and the all-reduce that "
+                               "would add them is not built"))
+        return EXIT_FAILURE;
+    const int Mt = (int)opt.get_Mt(), N = (int)opt.get_N();
+    need_phen(opt.get_phen_files(), "--phen-files");
+    const std::vector<std::string>& files = opt.get_phen_files();
+    Phenotypes ph;                                  // (every trait keeps its own missing set: the complete cases are not used)
+    if (!read_phenotypes(files, N, ph)) return EXIT_FAILURE;
+    std::vector<unsigned char> use;
+    if (opt.get_grm_marker_file() != "") {
+        std::ifstream in(opt.get_grm_marker_file(), std::ios::binary);
+        use.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+        if (!in.is_open() || use.size() != (size_t)Mt)
+            return refuse(std::cout << "FATAL: --grm-marker-file " << opt.get_grm_marker_file() << " must hold Mt = " << Mt << " bytes of 0 / 1 ("
+                                    << (in.is_open() ? std::to_string(use.size()) + " bytes read" : std::string("cannot open it")) << ")");
+    }
+    const size_t C = files.size();
+    std::vector<double> y((size_t)N * C);
+    for (size_t c = 0; c < C; c++)
+        for (int n = 0; n < N; n++) y[(size_t)n * C + c] = ph.Y[c][(size_t)n];
+    setenv("GVAMP_RESIDENT_LAYOUT", "2", 0);      // the kernel reads the tile layout (a --resident-layout given on the command line stands)
+    data dataset = job.load(std::vector<double>(N, 0.0), opt.get_bed_file(), N, Mt, Mt, 0);      // (bed data: the dosage arguments are unused)
+    const data::grm_he_result res = dataset.grm_he((int64_t)C, y, use);
+    const std::string path = job.out() + ".HEreg";
+    FILE* f = fopen(path.c_str(), "w");
+    bool ok = f != nullptr && fprintf(f, "trait n_ind n_pairs mean_a var_a h2 intercept se_ols se_jack\n") > 0;
+    for (size_t c = 0; c < C && ok; c++) {
+        const gv_he_result& r = res.traits[c];
+        const double mean = r.sum_a / (double)r.n_pairs, var = r.sum_aa / (double)r.n_pairs - mean * mean;
+        ok = fprintf(f, "%s %lld %lld %.17g %.17g %.17g %.17g %.17g %.17g\n", files[c].c_str(), (long long)r.n_ind, (long long)r.n_pairs, mean,
+                     var, r.h2, r.intercept, r.se_ols, r.se_jack) > 0;
+    }
+    if (f) ok = fclose(f) == 0 && ok;
+    if (!ok) return refuse(std::cout << "FATAL: cannot write " << path);
+    std::cout << "he: " << N << " individuals x " << res.info.counting_markers << " counting of " << Mt << " markers, " << C << " traits, "
+              << res.info.passes << " passes, " << res.info.blocks_computed << " blocks, " << res.info.seconds << " seconds -> " << path
+              << std::endl;
+    return 0;
+}
+
 int run_predict(const Job& job) {                                                      // predict and predict_single (:386-594)
     const Options& opt = job.opt;
     const int N_test = (int)opt.get_N_test(), Mt_test = (int)opt.get_Mt_test();
@@ -798,7 +843,7 @@ const struct {
     int (*run)(const Job&);
 } MODES[] = {{"infere", run_infere}, {"restart", run_infere}, {"test", run_test}, {"both", run_both}, {"pvals-calc", run_pvals_calc},
              {"predict", run_predict}, {"predict_single", run_predict}, {"ldscore", run_ldscore}, {"clump", run_clump},
-             {"score", run_score}, {"screen", run_screen}, {"pca", run_pca}, {"king", run_king}, {"grm", run_grm}};
+             {"score", run_score}, {"screen", run_screen}, {"pca", run_pca}, {"king", run_king}, {"grm", run_grm}, {"he", run_he}};
 
 }  // namespace
 

@@ -98,7 +98,11 @@
        default: every marker).  With --grm-cutoff x: <out>.grm.sp, GCTA's sparse text, "i j value" with 0-based          \
        indices, the N diagonal entries first and then every pair with A_ij >= x in ascending (i, j).  Without it:        \
        <out>.grm.bin (the lower triangle with the diagonal, row by row, float32) and <out>.grm.N.bin (the common-marker  \
-       counts in the same order, float32), GCTA's dense format */                                                        \
+       counts in the same order, float32), GCTA's dense format;                                                          \
+       --run-mode he (gv_grm_he) with --phen-files f0,f1,... [--grm-marker-file F]: Haseman-Elston   \
+       regression (GCTA --HEreg) of every phenotype file on that matrix, which is never stored; every trait keeps its     \
+       own missing (NA) individuals: <out>.HEreg, a header line and one line per file, "trait n_ind n_pairs mean_a var_a  \
+       h2 intercept se_ols se_jack" */                                                       \
     X(int, device, -1) X(int, kernel_mode, 1) X(long, synth_seed, -1) X(unsigned int, synth_miss_ppm, 5000)          \
     X(int, diagnostics, 0) X(int, store_iterates, 1) X(int, fuse_solves, 4) X(int, resident_layout, 3)              \
     X(int, reanchor_every, 10) X(std::string, huber_delta_schedule, "deferred") X(std::string, cg_precond, "scalar")    \

@@ -1097,6 +1097,8 @@ typedef struct gv_grm_stats {
     int64_t pairs;               /* pairs delivered: ni * nj of a rectangle, the N (N - 1) / 2 pairs gv_grm_pairs decided, 0 of the weights */
     double useful_macs;          /* counting_markers x pairs */
     double scratch_bytes;        /* device scratch it allocated and released */
+    int64_t passes;              /* launches of the block kernel: 1 for a rectangle or a pair list, the tiles of gv_grm_apply (below) */
+    int64_t blocks_computed;     /* blocks those launches computed; gv_grm_apply computes no block twice: always block_pairs */
 } gv_grm_stats;
 int gv_grm_weights(gv_ctx* ctx, const uint8_t* use /* M or NULL */, double* mu /* M or NULL */, double* rs /* M or NULL */, int64_t* n_used);
 int gv_grm_block(gv_ctx* ctx, const uint8_t* use /* M or NULL */, int64_t i0, int64_t ni, int64_t j0, int64_t nj,
@@ -1104,6 +1106,48 @@ int gv_grm_block(gv_ctx* ctx, const uint8_t* use /* M or NULL */, int64_t i0, in
 int gv_grm_pairs(gv_ctx* ctx, const uint8_t* use /* M or NULL */, double cutoff, int64_t cap, int32_t* pi, int32_t* pj, double* a,
                  int32_t* m_common /* cap each */, double* diag /* N or NULL */, int32_t* diag_m /* N or NULL */, int64_t* n_found);
 int gv_grm_info(gv_ctx* ctx, gv_grm_stats* info);
+
+/* ---- GRM-times-panel product and Haseman-Elston regression, the matrix never stored (additions only: GV_ABI_VERSION stays 4; DESIGN.md
+ * section 30) ------------------------------------------------------------------------------------------------------------------------
+ * Data, `use`, weights, S_ij, M_ij and A_ij are exactly gv_grm_block's, to the bit.  Three symmetric N x N operators, none ever stored,
+ * each with a zero diagonal and zero for a pair with M_ij = 0 (a NaN never enters a sum):
+ *   G0_ij = 1        G1_ij = A_ij        G2_ij = __dmul_rn(A_ij, A_ij)   (the square is rounded before anything is multiplied into it)
+ * gv_grm_apply(ctx, use, C, w, g0, g1, g2), 1 <= C <= GV_GRM_APPLY_MAX_COLS, w N x C row-major on the host and finite:
+ *   gp[i][c] = sum_j Gp_ij w[j][c]        (each of g0, g1, g2 N x C row-major on the host, or NULL)
+ * The order of the sum is part of the contract and a function of N alone.  With S a group of 64 consecutive individuals (64 S ..):
+ *   b_S      = the chain over j ascending in S, from +0.0, of acc = __dadd_rn(acc, __dmul_rn(Gp_ij, w_jc)), never contracted;
+ *              an absent pair and j == i take part with Gp = 0 like any other term
+ *   gp[i][c] = the chain over S = 0, 1, .. ascending, from +0.0, of acc = __dadd_rn(acc, b_S)
+ * So the bits of a column do not depend on C, on the column's place in the batch, on the passes, the scheduling or the kernel mode,
+ * and two calls give the same bytes.
+ * The block terms b_S wait in device memory for the finishing kernel; they are bounded by a budget (2 GiB; GV_GRM_PART_MB, read by
+ * gv_create).  The budget decides the edge g of the square tiles of g x g blocks the call walks the block triangle in, one pass per
+ * tile: 2 sides x 3 operators x g^2 x 64 x C x 8 bytes fit in it.  Passes change no bit and compute no block twice; gv_grm_info
+ * reports them.  A budget below the terms of one block (g = 1) is refused.
+ *
+ * gv_grm_he(ctx, use, C, y, res): Haseman-Elston regression (GCTA --HEreg) of C >= 1 traits, y N x C row-major on the host, NaN = missing.
+ * Per trait: K = the individuals with a finite phenotype, n_K = |K|, m = sum y / n_K, v = sum (y - m)^2 / (n_K - 1),
+ * yt = (y - m) / sqrt(v) on K and 0 elsewhere; the columns k (the indicator of K), yt and yt^2 go through gv_grm_apply, ten traits a
+ * call.  The OLS regression of z = yt_i yt_j on x = A_ij over the pairs {i < j in K, M_ij > 0} follows from
+ *   n = k'G0 k / 2   Sx = k'G1 k / 2   Sxx = k'G2 k / 2   Sz = yt'G0 yt / 2   Szz = (yt^2)'G0 (yt^2) / 2   Sxz = yt'G1 yt / 2
+ *   D = n Sxx - Sx^2    h2 = (n Sxz - Sx Sz) / D    intercept = (Sz - h2 Sx) / n    RSS = Szz - intercept Sz - h2 Sxz
+ *   se_ols = sqrt(RSS / (n - 2) * n / D)
+ * all in fp64 on the host, O(N) per trait.  The delete-one-individual jackknife takes row i's terms u_i (G v)_i out of every sum for
+ * i in K, keeps the standardisation of the full K, and gives se_jack = sqrt((n_K - 1) / n_K * sum (h2_(-i) - mean)^2).
+ * h2, intercept, se_ols and se_jack are NaN when n < 3, D <= 0 or v is not a positive number (a constant trait, n_K < 2); the call
+ * still returns 0.  A trait's result does not depend on the traits beside it.
+ * Refused with a message, nothing written: everything gv_grm_block refuses; C out of range; NULL w, y or res; g0, g1 and g2 all NULL; a
+ * w that is not finite; an infinite y; the budget case above. */
+#define GV_GRM_APPLY_MAX_COLS 32
+typedef struct gv_he_result {
+    int64_t n_ind;               /* n_K */
+    int64_t n_pairs;             /* n: the pairs of the regression */
+    double sum_a, sum_aa;        /* Sx, Sxx over those pairs */
+    double h2, intercept, se_ols, se_jack;
+} gv_he_result;
+int gv_grm_apply(gv_ctx* ctx, const uint8_t* use /* M or NULL */, int C, const double* w /* N x C */, double* g0, double* g1,
+                 double* g2 /* N x C each, or NULL */);
+int gv_grm_he(gv_ctx* ctx, const uint8_t* use /* M or NULL */, int64_t C, const double* y /* N x C */, gv_he_result* res /* C */);
 
 /* ---- covariate-adjusted association screen: partial regression on the batch product (additions only: GV_ABI_VERSION stays 4; DESIGN.md
  * section 26) ------------------------------------------------------------------------------------------------------------------------
